@@ -7,18 +7,24 @@ One "step" = one pass of the hot path over one batch: x_T (Philox, on device) ->
 (text embeddings, weights) are resident in HBM before the timed region.
 
     python bench.py --gpus 1 --steps 3 --warmup 1
+    python bench.py --gpus 1 --steps 3 --warmup 1 --full --dump-outputs bench_outputs
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Multi-GPU: `value` is WEAK scaling -- every rank samples its own 256-series shard (global rows [256*rank, 256*rank+256) of
 the Philox stream); no data-path collective, RCCL only for the barrier and the max-over-ranks time.  BASELINE's metric read
-literally is STRONG scaling (256 series at 1/2/4/8 GPUs), so the line also carries
+literally is STRONG scaling (256 series at 1/2/4/8 GPUs), so the line of a `--full` run also carries
   * at N = 1: `strong_shards` -- the per-GPU share of that job (128 / 64 / 32 series) timed on this GPU, with the predicted
     strong efficiency rate(256/N) / rate(256) (no collective: N x rate(256/N) is the N-GPU rate);
   * at N > 1: `strong` -- the same 256 series split over the ranks (their union equals the one-GPU batch bit for bit).
 
-The same JSON line carries, as extra keys: `roofline` (dominant kernel, in-situ HIP-event timing), `roofline_rows` (the three
-row-chain kernel instances, same timing), `cpu_baseline` (the oracle on the host cores, N=1 only: 3 warm + 10 measured CFG steps),
+A plain run only sets up, warms up, times the --steps batches and prints the result line (`value`, `ms_per_step`,
+`whole_path_tflops`, ...).  `--dump-outputs DIR` also writes what the last timed batch returned: DIR/latent.npy (B,64,30) and
+DIR/series.npy (B,L), float32, rank 0's rows at N > 1 (the first rows only, should the two exceed 64 MB); every input is
+seeded, so two builds can be compared file for file.
+
+With `--full` the same JSON line carries, as extra keys: `roofline` (dominant kernel, in-situ HIP-event timing), `roofline_rows`
+(the three row-chain kernel instances, same timing), `cpu_baseline` (the oracle on the host cores, N=1 only: 3 warm + 10 measured CFG steps),
 `config3` / `config5` (BASELINE configs[2] and configs[4] under this clock, N=1 only), `alt_math` (the bf16x3 arithmetic with its
 own roofline against the bf16 peak / 6 and an in-run `accuracy_vs_fp64` block, N=1 only),
 `train` (BASELINE configs[3] shape: the bf16 DiT training step of train.py at B=1152 per GPU with the gradient all-reduce at
@@ -806,6 +812,20 @@ def _pmc_of(pm, part, counter):
     return None
 
 
+DUMP_BYTES_MAX = 64 * 10**6
+
+
+def dump_outputs(path, **arrays):
+    """`--dump-outputs DIR`: each (rows, ...) tensor as DIR/<name>.npy in float32.  Should they exceed DUMP_BYTES_MAX
+    together (B above ~8000 at L = 96), only the first rows of each are written -- the same rows in every run."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    row_bytes = sum(4 * t[0].numel() for t in arrays.values())
+    rows = min(min(t.shape[0] for t in arrays.values()), DUMP_BYTES_MAX // row_bytes)
+    for name, t in arrays.items():
+        np.save(os.path.join(path, name + ".npy"), t[:rows].detach().float().cpu().numpy())
+
+
 def spawn_ranks(n_gpus, argv=None):
     """`python bench.py --gpus N` without a torchrun environment: start the N ranks ourselves, one FRESH process per
     GPU (`python -m torch.distributed.run --nproc-per-node N bench.py <same flags>` as a CHILD -- never an exec: this
@@ -880,8 +900,18 @@ def main():
                     help="matrix arithmetic: f32 MFMA (headline) or fp32-accurate split-bf16 products (include/t2s.h)")
     ap.add_argument("--no-pmc", action="store_true",
                     help="skip the in-run rocprofv3 --pmc passes (roofline.traffic / mfma_busy then come from the committed profiles)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure everything beyond the headline: roofline / per-kernel timing and the PMC passes, strong "
+                         "scaling, the training leg, the driver legs, config3 / config5, alt_math and the CPU baseline (the "
+                         "--no-<part> flags above still skip single parts); a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write what the last timed batch returned (latent, series) as DIR/<name>.npy, float32")
     ap.add_argument("--pmc-probe", action="store_true", help=argparse.SUPPRESS)
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:        # a plain run: nothing beside the timed headline batches
+        args.no_strong = args.no_train = args.no_legs = args.no_configs = args.no_alt_math = args.no_cpu_baseline = True
     if args.pmc_probe:
         torch.cuda.set_device(0)
         pmc_probe(torch.device("cuda", 0))
@@ -920,6 +950,8 @@ def main():
     tdist.barrier(dist, dev)
     elapsed = tdist.max_over_ranks(dist, time.perf_counter() - t0, dev)
     assert bool(torch.isfinite(series).all()) and bool(torch.isfinite(lat).all())
+    if args.dump_outputs and rank == 0:      # before any --full leg reuses the sampler's buffers
+        dump_outputs(args.dump_outputs, latent=lat, series=series)
 
     total_series = args.steps * B * world
     lanes_used = sampler.graph_lanes or args.lanes or 1       # what the library captured for this batch size
@@ -965,7 +997,7 @@ def main():
                 import traceback
                 traceback.print_exc()
                 legs["class_api"] = {"error": f"{type(e).__name__}: {e}"}
-    if rank == 0:
+    if rank == 0 and args.full:
         # roofline of the dominant kernel (fused attention; 48 % of all FLOPs), same shapes as the workload
         kt = time_kernels_in_situ(model, dev, lat.clone(), text)
         t_attn = kt["attn_us"] * 1e-6
@@ -1023,6 +1055,7 @@ def main():
             out["roofline_rows"]["pmc"] = {"instances": rows_pm, "measured_by_this_run": True}
         out["kernel_breakdown_us"] = {"attention_x4": kt["attn_us"], "row_chain_x5": kt["rows_us"],
                                       "other_x1_adaln": kt["other_us"], "forward_total": kt["forward_us"]}
+    if rank == 0:
         # whole-step figure for context: all DiT FLOPs / wall time
         step_flops = FLOP_FORWARD_PER_SEQ * 2 * B * args.diffusion_steps * args.steps
         out["whole_path_tflops"] = step_flops / elapsed / 1e12

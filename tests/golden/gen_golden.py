@@ -3,7 +3,12 @@
 
 Run once, here, with /root/reference mounted:
 
-    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden.py
+    MKL_CBWR=COMPATIBLE,STRICT PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden.py
+
+ddpm.npz, time_emb.npz, init_seeded.npz and vae_long.npz were recorded with MKL_CBWR=COMPATIBLE,STRICT: MKL's
+reproducible branch, which tests/conftest.py pins so that the bit-exact comparisons hold on any x86 host (MKL's
+default branch depends on the CPU vendor).  The other files were recorded on the default branch; their tests
+compare at tolerances that hold on either.
 
 The reference never travels: only the arrays written below are committed.
 Weights/inputs are regenerated from seeds by ``t2ms_amd.synth`` so the

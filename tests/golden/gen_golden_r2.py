@@ -4,7 +4,9 @@ the reference never travels, only the arrays written here are committed; `timm` 
 stand-in, `dtaidistance` -- imported at evaluation.py:7, not installed -- by an import-time stub whose function is
 never called by anything recorded below).
 
-    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden_r2.py
+    MKL_CBWR=COMPATIBLE,STRICT PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden_r2.py
+
+(MKL_CBWR: see gen_golden.py -- init_seeded.npz is compared bit for bit.)
 
 Writes
   init_seeded.npz   Transformer() under torch.manual_seed(k): parameter ORDER and per-tensor statistics + strided

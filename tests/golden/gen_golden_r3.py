@@ -2,7 +2,9 @@
 """Round-3 fixtures, made by RUNNING THE REFERENCE in the build container (rules as in gen_golden.py / gen_golden_r2.py:
 the reference never travels, only the arrays written here are committed).
 
-    PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden_r3.py
+    MKL_CBWR=COMPATIBLE,STRICT PYTHONDONTWRITEBYTECODE=1 MPLBACKEND=Agg python tests/golden/gen_golden_r3.py
+
+(MKL_CBWR: see gen_golden.py -- vae_long.npz is compared at 1e-9 on fp64 row sums.)
 
 Writes
   vae_long.npz   the reference LA-VAE (model/pretrained/vqvae.py:36-105, default hyper-parameters, seeded weights of

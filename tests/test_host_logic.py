@@ -218,6 +218,28 @@ def test_bench_self_spawn_builds_a_fresh_rank_launcher(monkeypatch, capsys):
     assert not [ln for ln in capsys.readouterr().out.splitlines() if ln.startswith("{")]
 
 
+def test_bench_dump_outputs_float32_and_capped_to_the_same_first_rows(tmp_path, monkeypatch):
+    """`--dump-outputs`: float32 .npy files; above the size cap only the first rows of every array, in every run."""
+    import bench
+    lat = torch.randn(10, 4, 3, dtype=torch.float64)
+    series = torch.randn(10, 6, dtype=torch.float64)
+    bench.dump_outputs(str(tmp_path / "all"), latent=lat, series=series)
+    a = np.load(tmp_path / "all" / "latent.npy")
+    assert a.dtype == np.float32 and np.array_equal(a, lat.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BYTES_MAX", 4 * (12 + 6) * 3 + 5)          # room for three rows of the two
+    bench.dump_outputs(str(tmp_path / "cap"), latent=lat, series=series)
+    assert np.array_equal(np.load(tmp_path / "cap" / "latent.npy"), lat[:3].float().numpy())
+    assert np.array_equal(np.load(tmp_path / "cap" / "series.npy"), series[:3].float().numpy())
+
+
+def test_bench_rejects_zero_timed_steps(monkeypatch):
+    import bench
+    monkeypatch.setattr(sys, "argv", ["bench.py", "--steps", "0"])
+    with pytest.raises(SystemExit) as e:
+        bench.main()
+    assert e.value.code == 2
+
+
 def test_shipped_default_math_is_bf16x3_and_the_suite_pins_f32(monkeypatch):
     """Round 5 made the fp32-accurate bf16x3 arithmetic the default of the Sampler and of infer.py (profiles/r05_accuracy.md);
     the bench headline and the class API stay on the exact f32 MFMA.  The suite itself runs with T2S_DEFAULT_MATH=f32."""

@@ -118,7 +118,7 @@ def test_rccl_one_rank_collectives_and_training_step_equal_the_undistributed_run
 def test_bench_distributed_branch_through_rccl_one_rank(tmp_path):
     """bench.py's N > 1 code (NCCL barrier + max-over-ranks around the timed region, the strong leg, the training leg
     with and without the gradient all-reduce) at world size 1 through RCCL."""
-    r = _run([os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--diffusion-steps", "20",
+    r = _run([os.path.join(REPO, "bench.py"), "--gpus", "1", "--steps", "1", "--warmup", "1", "--full", "--diffusion-steps", "20",
               "--batch", "64", "--no-cpu-baseline", "--no-alt-math", "--train-batch", "32", "--train-steps", "3",
               "--legs", "--infer-driver-rows", "300", "--train-driver-rows", "2000", "--train-driver-batch", "96"],
              29563, True, REPO)

@@ -209,7 +209,7 @@ def test_plain_bench_command_starts_its_own_ranks(tmp_path):
     two ranks itself (fresh children, before any GPU call of its own), relay ONE JSON line with n_gpus = 2 and exit 0."""
     env = _env(0, True)
     env.pop("MASTER_ADDR"), env.pop("MASTER_PORT")
-    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1",
+    cmd = [sys.executable, os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full",
            "--diffusion-steps", "10", "--batch", "64", "--no-cpu-baseline", "--no-train", "--no-legs"]
     r = subprocess.run(cmd, env=env, cwd=str(tmp_path), capture_output=True, text=True, timeout=420)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
@@ -220,7 +220,7 @@ def test_plain_bench_command_starts_its_own_ranks(tmp_path):
 
 
 def test_bench_two_ranks_prints_one_json_line(tmp_path):
-    r = _launch([os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--diffusion-steps", "20",
+    r = _launch([os.path.join(REPO, "bench.py"), "--gpus", "2", "--steps", "1", "--warmup", "1", "--full", "--diffusion-steps", "20",
                  "--batch", "64", "--no-cpu-baseline", "--train-batch", "32", "--train-steps", "3",
                  "--legs", "--infer-driver-rows", "300", "--train-driver-rows", "2000", "--train-driver-batch", "96"], 29556, True, REPO)
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{")]

@@ -9,7 +9,7 @@ cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 out=gpurun_out
 mkdir -p $out
 git_rev=$(cat .git_rev 2>/dev/null || echo unknown)
-echo "== bench"; timeout -k 10 600 python bench.py --gpus 1 --steps 3 --warmup 1 > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
+echo "== bench"; timeout -k 10 600 python bench.py --gpus 1 --steps 3 --warmup 1 --full > $out/${tag}_bench.json 2> $out/${tag}_bench.err || exit 1
 tail -c 400 $out/${tag}_bench.json; echo
 # (--no-pmc: a profiled bench must not start profiler children of its own; --no-configs: the profile is of the headline shape)
 S="--gpus 1 --steps 1 --warmup 1 --no-cpu-baseline --no-alt-math --no-train --no-strong --no-legs --no-configs --no-pmc"

@@ -5,7 +5,7 @@ math=${1:-f32}
 cd /tmp && export TMPDIR=/tmp && cd $GRAFT_REPO_ROOT
 for grp in "SQ_VALU_MFMA_COEXEC_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_ACTIVE_INST_VALU SQ_INSTS_VALU" "SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_INSTS_MFMA SQ_WAIT_INST_LDS"; do
   rm -rf /tmp/pmcr
-  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d /tmp/pmcr -- python3 bench.py --gpus 1 --steps 1 --warmup 1 --diffusion-steps 3 --no-cpu-baseline --no-alt-math --math $math > /dev/null 2> /tmp/pmcr.err || { echo "pass failed: $grp"; tail -3 /tmp/pmcr.err; continue; }
+  timeout -k 10 300 rocprofv3 --pmc $grp --output-format csv -d /tmp/pmcr -- python3 bench.py --gpus 1 --steps 1 --warmup 1 --full --diffusion-steps 3 --no-cpu-baseline --no-alt-math --math $math > /dev/null 2> /tmp/pmcr.err || { echo "pass failed: $grp"; tail -3 /tmp/pmcr.err; continue; }
   python3 - <<'PY'
 import csv, glob, collections
 f = sorted(glob.glob('/tmp/pmcr/*/*counter_collection.csv'))[-1]

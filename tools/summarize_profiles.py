@@ -66,7 +66,7 @@ json.dump({"kernel": "attn_fwd_persistent_kernel", "hbm_bytes_per_launch": attn_
 
 lines = [f"# {tag}: MI355X, collected by `tools/collect_profiles.sh {tag}` in one gpurun call", "",
          "## Headline: sampling (BASELINE configs[1]), f32 MFMA",
-         f"`python bench.py --gpus 1 --steps 3 --warmup 1` (`profiles/{tag}_bench.json`): **{b['value']:.1f} series/s**, "
+         f"`python bench.py --gpus 1 --steps 3 --warmup 1 --full` (`profiles/{tag}_bench.json`): **{b['value']:.1f} series/s**, "
          f"{b['ms_per_step']:.0f} ms per 256-series batch, sampler lanes = {b['config'].get('sampler_lanes')}; whole path "
          f"{b['whole_path_tflops']:.1f} TFLOP/s = {b['whole_path_frac_of_fp32_mfma_peak']:.3f} of the fp32 MFMA peak."]
 if cb:

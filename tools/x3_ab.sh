@@ -4,6 +4,6 @@ cd "$(dirname "$0")/.."
 other=$1; rounds=${2:-2}
 for r in $(seq $rounds); do for lib in "" "$other"; do
   if [ -n "$lib" ]; then export T2S_LIB=$lib; else unset T2S_LIB; fi
-  python bench.py --math bf16x3 --steps 2 --warmup 1 --no-train --no-legs --no-strong --no-alt-math --no-cpu-baseline --no-configs --no-pmc 2>/dev/null | python -c "
+  python bench.py --math bf16x3 --steps 2 --warmup 1 --full --no-train --no-legs --no-strong --no-alt-math --no-cpu-baseline --no-configs --no-pmc 2>/dev/null | python -c "
 import json,sys; t=json.loads(sys.stdin.read()); k=t['kernel_breakdown_us']; print('${lib:-in-tree}'.ljust(36), round(t['value'],2), 'series/s | attention', round(k['attention_x4'],1), 'rows avg', round(k['row_chain_x5'],1), 'us')"
 done; done
