@@ -311,6 +311,12 @@ int t2s_rf_create_flow(const float* x1, const float* x0, const float* t, float* 
  * DDPM.py:35 / infer.py:75 in perf mode; parity mode injects noise instead.) */
 int t2s_philox_normal(float* out, uint64_t seed, uint32_t stream_id, uint32_t row0, int n_rows,
                       int row_elems, void* stream);
+/* The same draws with a key and a key row PER ROW: row r of out = row key_rows[r] of stream `stream_id` under key seeds[r],
+ * bit for bit what t2s_philox_normal(out + r * row_elems, seeds[r], stream_id, key_rows[r], 1, row_elems) writes.
+ * seeds (n_rows) u64 and key_rows (n_rows) u32 are DEVICE arrays.  With stream_id 0xFFFFFFFF it is the x_T draw of a
+ * sampler whose rows come from different runs (t2s_sampler_set_rows). */
+int t2s_philox_normal_rows(float* out, const uint64_t* seeds, const uint32_t* key_rows, uint32_t stream_id,
+                           int n_rows, int row_elems, void* stream);
 /* U[0,1) draws of the same stream: element e of GLOBAL row r = lane e % 4 of counter (e/4, r, stream_id, 0), key = seed,
  * as the 24-bit uniform (x >> 8) * 2^-24 (exact in fp32, never 1.0).  out: (n_rows,row_elems), any row_elems >= 1.
  * (replaces torch.rand at train.py:109,113: the per-row diffusion time of a training step, drawn on the device as a
@@ -473,6 +479,16 @@ int t2s_sampler_set_loop_graph(t2s_sampler* s, int whole_loop);
  * row0 + r).  Takes effect at the next t2s_sampler_run; the captured hipGraphs are kept (the kernels read the
  * value from device memory next to the step counter).  infer.py:66 loops over batches with one sampler. */
 int t2s_sampler_set_row0(t2s_sampler* s, uint32_t row0);
+/* Per-row noise keys and guidance scale: row r of the batch draws its per-step noise as row key_rows[r] of the Philox
+ * stream keyed by seeds[r] and combines pred = u + cfg[r] * (c - u), so one run may hold the rows of several runs
+ * (seeds), positions (key rows) and guidance scales -- rows never interact, so each row comes out bit for bit as in a
+ * uniform sampler of its own seed / row0 / cfg_scale.  HOST arrays of n == batch entries, copied at the call; any of them
+ * NULL = uniform (config seed, row0 + r, cfg_scale respectively); all three NULL restores the uniform sampler.  Takes
+ * effect at the next t2s_sampler_run, the captured hipGraphs are kept (the kernels read the tables and which of them are
+ * in use from device memory).  The run uploads the tables stream-ordered from a pinned buffer the sampler owns; no
+ * synchronous copy.  x_T is the caller's: draw it with t2s_philox_normal_rows (stream_id 0xFFFFFFFF).
+ * T2S_E_INVALID when n != batch or a cfg value is not finite. */
+int t2s_sampler_set_rows(t2s_sampler* s, const uint64_t* seeds, const uint32_t* key_rows, const float* cfg, int n);
 /* Number of lanes the sampler currently holds an instantiated hipGraph for (0: the last run was eager / nothing run
  * yet).  Lets a caller (and tests/test_hip_parity.py) check that use_graph = 1 really replays a graph. */
 int t2s_sampler_graph_lanes(const t2s_sampler* s);

@@ -17,9 +17,16 @@ Differences from the reference, all additive:
     split, its embeddings and every output stay in HBM; the host touches no row inside the loop;
   * under torchrun every rank samples rows [lo,hi) of each launch and keeps them in HBM; the ranks
     meet in ONE gather at the end (a rank without rows joins empty-handed), rank 0 writes;
-  * the per-step decode of the first batch (infer.py:90-93, GIF only) is `--trace`, off by default.
+  * the per-step decode of the first batch (infer.py:90-93, GIF only) is `--trace`, off by default;
+  * `--dataset_name` and `--cfg_scale` take comma-separated lists: ONE job samples the grid datasets x cfg scales (each
+    with `--run_multi`'s 1 + 10 runs) and writes exactly the directories the separate invocations write.  The rows of
+    every (cell, run) share the launches (per-row Philox key and guidance scale, t2s_sampler_set_rows).
+
+    python infer.py --dataset_name ETTh1_24,ETTh1_48,ETTh1_96 --cfg_scale 9 --total_step 10 --run_multi True
 """
 import argparse
+import copy
+import math
 import os
 import sys
 import time
@@ -117,7 +124,158 @@ def launch_plan(n_rows, loader_batch, launch_batch, world):
     return [(s0, min(s0 + per, n_rows)) for s0 in range(0, n_rows, per)]
 
 
+# ------------------------------------------------------------------ the grid: datasets x cfg scales x runs in one job
+class Cell(types.SimpleNamespace):
+    """One (dataset, cfg scale) of the grid: `cfg` the guidance scale, `path` the directory its base run writes."""
+
+
+_CFG_MAX = 3.4028234663852886e38        # the largest finite fp32: the kernels combine in fp32
+
+
+def _cfg_values(value):
+    """--cfg_scale -> [(value as the directory name formats it, float)].  A number passes as it is (argparse leaves a
+    non-string default unconverted: the default 7 names `..._7_...`), a string is a comma-separated list of floats."""
+    if isinstance(value, (int, float)) and not isinstance(value, bool):
+        vals = [value]
+    else:
+        vals = []
+        for part in str(value).split(","):
+            try:
+                vals.append(float(part.strip()))
+            except ValueError:
+                raise ValueError(f"--cfg_scale: {part.strip()!r} is not a number") from None
+    for v in vals:
+        if not (math.isfinite(float(v)) and abs(float(v)) <= _CFG_MAX):
+            raise ValueError(f"--cfg_scale: {v!r} is not a finite fp32 value")
+    return [(v, float(v)) for v in vals]
+
+
+def parse_cells(args):
+    """The cells of the job, datasets x cfg scales in the order given, each with the generation directory the separate
+    invocation `infer.py --dataset_name D --cfg_scale C` computes (infer.py:297-299 of the parent layout).  Refused: datasets
+    of different roots (checkpoint and LA-VAE paths are per root), a list with `--denoiser MLP` (its loop is the per-batch
+    config-1 loop, not the sampler), malformed or non-finite cfg values, a cell named twice."""
+    names = [n.strip() for n in str(args.dataset_name).split(",")]
+    if not all(names):
+        raise ValueError(f"--dataset_name: empty entry in {args.dataset_name!r}")
+    cfgs = _cfg_values(args.cfg_scale)
+    roots = sorted({n.split("_")[0] for n in names})
+    if len(roots) > 1:
+        raise ValueError(f"--dataset_name: all datasets of one job must share one root (checkpoint and LA-VAE), got {roots}")
+    if args.denoiser == "MLP" and len(names) * len(cfgs) > 1:
+        raise ValueError("--denoiser MLP samples one dataset at one cfg scale per job (lists are for the DiT sampler)")
+    cells = []
+    for name in names:
+        for shown, cfg in cfgs:
+            path = os.path.join(args.save_path, "generation",
+                                "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, name, shown, args.total_step))
+            cells.append(Cell(dataset_name=name, cfg=cfg, cfg_shown=shown, path=path))
+    if len({c.path for c in cells}) != len(cells):
+        raise ValueError("the grid names the same (dataset, cfg scale) twice")
+    return cells
+
+
+def grid_units(cells, n_runs, seed):
+    """The (cell, run) pairs of a job, cell-major: run 0 is the base run (seed S, the cell's directory), run r >= 1 is the
+    `--run_multi` run `run_{r-1}` with seed S + r (infer.py:303-307 of the parent: the seed advances by one per run)."""
+    units = []
+    for ci, c in enumerate(cells):
+        for r in range(n_runs):
+            units.append(types.SimpleNamespace(cell=ci, run=r, seed=seed + r, dataset_name=c.dataset_name, cfg=c.cfg,
+                                               path=c.path if r == 0 else os.path.join(c.path, f"run_{r - 1}")))
+    return units
+
+
+def _constructor_draws(args):
+    """Build and drop the modules _load_models constructs, for their initialisation draws from the global CPU generator:
+    the `vqvae(...)` constructor under --random_init (else the LA-VAE is unpickled: no draws), then the denoiser's."""
+    if args.random_init:
+        from model.pretrained.vqvae import vqvae
+        vqvae(types.SimpleNamespace(block_hidden_size=128, num_residual_layers=2, res_hidden_size=256, embedding_dim=64))
+    if args.denoiser == "MLP":
+        from model.denoiser.mlp import MLP
+        MLP()
+    else:
+        Transformer()
+
+
+_DRAWS_AFTER = {}     # (random_init, denoiser, generator state before the constructors) -> state after them
+
+
+def loader_order(args, dataset_name, seed, build_models=None):
+    """-> (dataset, index batches (n_batches, B), what build_models() returned) of the test loader of `dataset_name` in a
+    run seeded with `seed`.  THE order of every run, single or grid: the parent's infer() drew it as
+        torch.manual_seed(seed); loader_provider(...); _load_models(...) (the constructors' initialisation draws from the
+        global CPU generator); epoch_index_batches(loader)
+    and this helper replays exactly that sequence.  With build_models (the one-run MLP path) the real models are built in
+    the constructors' place; without, the generator state the constructors leave is replayed from a cache keyed by the
+    state before them (their draws are a function of that state alone)."""
+    torch.manual_seed(seed)
+    a = copy.copy(args)
+    a.dataset_name, a.seed = dataset_name, seed
+    dataset, loader = loader_provider(a, period="test")
+    models = None
+    if build_models is not None:
+        models = build_models()
+    else:
+        key = (bool(args.random_init), args.denoiser, torch.get_rng_state().numpy().tobytes())
+        after = _DRAWS_AFTER.get(key)
+        if after is None:
+            _constructor_draws(args)
+            _DRAWS_AFTER[key] = torch.get_rng_state()
+        else:
+            torch.set_rng_state(after)
+    batches = walk_index_batches(loader) if getattr(args, "loader_batches", False) else epoch_index_batches(loader)
+    return dataset, batches, models
+
+
+def grid_plan(unit_rows, loader_batch, launch_batch, world):
+    """Global row ranges [(s0, s1)] of the launches of a grid over the concatenated rows of its units (cell-major, then
+    run, then the run's loader order).  launch_batch > 0: `launch_batch * world` rows per launch ACROSS unit boundaries (a
+    launch may mix cells, runs and lengths); 0: one launch per loader batch of each unit (the reference's launch shape)."""
+    if launch_batch > 0:
+        return launch_plan(int(sum(unit_rows)), loader_batch, launch_batch, world)
+    plan, off = [], 0
+    for n in unit_rows:
+        plan += [(off + a, off + b) for a, b in launch_plan(int(n), loader_batch, 0, world)]
+        off += int(n)
+    return plan
+
+
+def launch_segments(unit_rows, g0, g1):
+    """Rows [g0, g1) of the concatenation as [(unit, i0, i1)]: rows [i0, i1) of that unit's loader order."""
+    out, off = [], 0
+    for u, n in enumerate(unit_rows):
+        a, b = max(g0, off), min(g1, off + int(n))
+        if a < b:
+            out.append((u, a - off, b - off))
+        off += int(n)
+    return out
+
+
+def row_tables(segments, unit_seeds, unit_cfgs):
+    """Per-row (seed, key row, cfg) of the rows `segments` name: a row of a unit is keyed as that unit's own one-run
+    invocation keys it -- its seed, its position in the run's order (the global row of a 1x1 job), the cell's cfg."""
+    seeds = np.concatenate([np.full(i1 - i0, int(unit_seeds[u]) & 0xFFFFFFFFFFFFFFFF, dtype=np.uint64)
+                            for u, i0, i1 in segments])
+    keys = np.concatenate([np.arange(i0, i1, dtype=np.int64) for u, i0, i1 in segments]).astype(np.uint32)
+    cfgs = np.concatenate([np.full(i1 - i0, unit_cfgs[u], dtype=np.float32) for u, i0, i1 in segments])
+    return seeds, keys, cfgs
+
+
 def infer(args):
+    """ONE run of one (dataset, cfg scale): args.dataset_name, args.cfg_scale, seeded by args.seed, into
+    args.generation_save_path_result.  The DiT path is the 1x1 grid (sample_grid); `--denoiser MLP` keeps its own loop."""
+    if args.denoiser == "DiT":
+        cell = Cell(dataset_name=args.dataset_name, cfg=float(args.cfg_scale), cfg_shown=args.cfg_scale,
+                    path=args.generation_save_path_result)
+        res = sample_grid(args, [cell], 1)
+        return res[0] if res is not None else None
+    return _infer_mlp(args)
+
+
+def _infer_mlp(args):
+    """The MLP denoiser (BASELINE configs[0] plumbing): one sampling loop per loader batch, as the reference."""
     device = torch.device(args.device)
     rank, local_rank, world = tdist.env_world()
     dist = tdist.init("nccl", device)
@@ -131,22 +289,9 @@ def infer(args):
         print(f"Inference config::Step: {args.total_step}\t CFG Scale: {args.cfg_scale}\t "
               f"Use Pretrained VAE: {args.usepretrainedvae}\t GPUs: {world}")
         os.makedirs(args.generation_save_path_result, exist_ok=True)
-    torch.manual_seed(args.seed)          # identical loader shuffle on every rank
-    dataset, dataloader = loader_provider(args, period="test")
-    model, vae = _load_models(args, device)
-    is_mlp = args.denoiser == "MLP"
-    if not is_mlp:
-        from t2ms_amd.sampler import default_math
-        args.math = getattr(args, "math", None) or default_math()
-        model.set_math(args.math)
-        if rank == 0:
-            print(f"matrix arithmetic: {args.math}" + (" (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)" if args.math == "bf16x3" else ""))
-
-    # The loader's ORDER without the loader's per-row work (datafactory.epoch_index_batches draws what one pass over
-    # the DataLoader draws): output row i is dataset row order[i], exactly the concatenation of the reference's batches
-    # (shuffle=True, drop_last=True, infer.py:66; N = floor(test / B) * B rows).  The test split lives in HBM.
-    # (--loader_batches: the same order from a real DataLoader walk over the row numbers -- public torch API only)
-    batches = walk_index_batches(dataloader) if getattr(args, "loader_batches", False) else epoch_index_batches(dataloader)
+    # identical loader shuffle on every rank; the models are built where the constructors drew (loader_order)
+    dataset, batches, (model, vae) = loader_order(args, args.dataset_name, args.seed,
+                                                  build_models=lambda: _load_models(args, device))
     if rank == 0:
         print("dataset length:", batches.shape[0])
     if batches.shape[0] == 0:
@@ -158,15 +303,14 @@ def infer(args):
     L = int(x1_host.shape[1])
     x1_dev = x1_host.to(device)
     emb_dev = torch.as_tensor(emb_tab)[order].float().to(device)
-    # MLP (configs[0] plumbing): one sampling loop per loader batch, as the reference; DiT: coalesced launches
-    plan = launch_plan(n_rows, B, 0 if is_mlp else int(getattr(args, "launch_batch", 256)), world)
+    plan = launch_plan(n_rows, B, 0, world)          # one sampling loop per loader batch, as the reference
     flush_rows = int(os.environ.get("T2S_INFER_FLUSH_ROWS", str(1 << 17)))     # outputs stay in HBM this long (16 KB / row)
 
     out = None
     if rank == 0:
         out = (np.empty((n_rows, L), np.float32), np.empty((n_rows, 64, 30), np.float32),
                np.empty((n_rows, 64, 30), np.float32))
-    held, held_chunks, trace, samplers = [], [], None, {}
+    held, held_chunks, trace = [], [], None
     t_start = time.time()
 
     def flush():
@@ -198,20 +342,8 @@ def infer(args):
             n = hi - lo
             if n > 0:                     # a rank without rows in this launch (fewer rows than GPUs) only joins the flush
                 x_1, embedding = x1_dev[s0 + lo:s0 + hi], emb_dev[s0 + lo:s0 + hi]
-                if is_mlp:
-                    lat, series, z_enc = sample_mlp_config1(model, vae, backbone, x_1, embedding, args, device, s0 + lo)
-                    lat = torch.nn.functional.pad(lat, (0, 30 - lat.shape[2]))      # the .npy layout is (N,64,30): zero-padded
-                else:
-                    z_enc, _ = model.encoder(x_1.contiguous())                      # infer.py:73-74
-                    sampler = samplers.get(n)
-                    if sampler is None:
-                        sampler = samplers[n] = Sampler(model, vae.decoder, backbone, args.total_step, args.cfg_scale, n, L,
-                                                        device, use_graph=True, seed=args.seed, row0=0)
-                    sampler.set_row0(s0 + lo)     # global row index of this shard's first series; the graph is kept
-                    want_trace = bool(args.trace) and k == 0 and rank == 0
-                    lat, series, tr = sampler.run(embedding.contiguous(), decode=True, trace=want_trace)
-                    if want_trace:
-                        trace = tr.cpu().numpy()
+                lat, series, z_enc = sample_mlp_config1(model, vae, backbone, x_1, embedding, args, device, s0 + lo)
+                lat = torch.nn.functional.pad(lat, (0, 30 - lat.shape[2]))      # the .npy layout is (N,64,30): zero-padded
                 held.append(torch.cat([series.reshape(n, L), lat.reshape(n, 1920), z_enc.reshape(n, 1920)], dim=1))
             held_chunks.append((s0, s1))
             if rank == 0:
@@ -232,6 +364,185 @@ def infer(args):
         print(f"saved {x_1.shape[0]} series to {args.generation_save_path_result}")
     tdist.barrier(dist, device)
     return (x_1[:, :, None], x_t[:, :, None], lat_dec, lat_enc) if rank == 0 else None
+
+
+def sample_grid(args, cells, n_runs):
+    """The DiT sampling of every (cell, run) of `cells` x `n_runs` in ONE job; every unit writes exactly the four files
+    (and `--trace`'s x_infer_trace.npy) its own one-run invocation writes.  Models and the DiT handle are built once; the
+    rows of all units are concatenated (cell-major, then run, then the run's loader order) and cut into launches of
+    `--launch_batch` per GPU (grid_plan), sharded over the ranks as one job's rows are; each launch keys its rows by
+    (unit seed, position in the unit's order, cell cfg) through Sampler.set_rows -- rows never interact and the kernels are
+    batch-invariant bit for bit, so a row comes out as in its own invocation.  Encode and decode run per length group (a
+    launch that mixes lengths decodes outside the sampler's graph: the same decode kernel).
+    -> on rank 0 [(x_1, x_t, lat_dec, lat_enc)] per unit, grid order; None elsewhere."""
+    from t2ms_amd.sampler import default_math
+    device = torch.device(args.device)
+    rank, _, world = tdist.env_world()
+    dist = tdist.init("nccl", device)
+    # ONE seed for the whole job: it seeds the loader shuffle (every rank must walk the same batches to take ITS rows
+    # of each) and keys the Philox noise.  A per-rank time-based default would silently mis-pair series across ranks.
+    args.seed = tdist.broadcast_int(dist, args.seed)
+    backbone = {"flowmatching": "flowmatching", "ddpm": "ddpm"}.get(args.backbone)
+    if backbone is None:
+        raise ValueError("No backbone found")
+    if args.denoiser != "DiT":
+        raise ValueError("sample_grid runs the DiT sampler (--denoiser MLP keeps its own loop)")
+    units = grid_units(cells, n_runs, args.seed)
+    if rank == 0:
+        print(f"Inference config::Step: {args.total_step}\t CFG Scale: {', '.join(str(c.cfg_shown) for c in cells)}\t "
+              f"Use Pretrained VAE: {args.usepretrainedvae}\t GPUs: {world}\t cells: {len(cells)} x runs: {n_runs}")
+        for u in units:
+            os.makedirs(u.path, exist_ok=True)
+    first = copy.copy(args)
+    first.dataset_name = cells[0].dataset_name          # every cell shares the root (parse_cells): one checkpoint, one LA-VAE
+    model, vae = _load_models(first, device)
+    args.math = getattr(args, "math", None) or default_math()
+    model.set_math(args.math)
+    if rank == 0:
+        print(f"matrix arithmetic: {args.math}" + (" (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)" if args.math == "bf16x3" else ""))
+
+    # Every unit's rows in its loader order (loader_order: the parent's generator sequence per (dataset, seed)); output
+    # row i of a unit is dataset row order[i] -- the concatenation of the reference's batches (shuffle=True,
+    # drop_last=True, infer.py:66; N = floor(test / B) * B rows).  The test splits live in HBM.
+    x1_host, x1_dev, emb_dev, lens = [], [], [], []
+    B = None
+    for u in units:
+        dataset, batches, _ = loader_order(args, u.dataset_name, u.seed)
+        if batches.shape[0] == 0:
+            raise RuntimeError(f"{u.dataset_name}: the test loader produced no full batch (drop_last=True): lower --batch_size")
+        order = batches.reshape(-1)
+        B = int(batches.shape[1])
+        (series_tab, emb_tab, _), = resident_tables(dataset)
+        xh = torch.as_tensor(series_tab)[order].float()              # (N, L) fp32: what `x_1.float()` gives per batch
+        x1_host.append(xh)
+        x1_dev.append(xh.to(device))
+        emb_dev.append(torch.as_tensor(emb_tab)[order].float().to(device))
+        lens.append(int(xh.shape[1]))
+    unit_rows = [int(x.shape[0]) for x in x1_host]
+    offs = np.cumsum([0] + unit_rows)
+    n_rows, Lmax = int(offs[-1]), max(lens)
+    if rank == 0:
+        print("dataset length:", ", ".join(str(n // B) for n in unit_rows[::n_runs]))
+    launch_batch = int(getattr(args, "launch_batch", 256))
+    plan = grid_plan(unit_rows, B, launch_batch, world)
+    unit_seeds, unit_cfgs = [u.seed for u in units], [u.cfg for u in units]
+    flush_rows = int(os.environ.get("T2S_INFER_FLUSH_ROWS", str(1 << 17)))     # outputs stay in HBM this long (16 KB / row)
+    width = Lmax + 2 * 1920                  # a packed row: series (zero-padded to the longest length), latent, encoding
+
+    out = None
+    if rank == 0:
+        out = (np.empty((n_rows, Lmax), np.float32), np.empty((n_rows, 64, 30), np.float32),
+               np.empty((n_rows, 64, 30), np.float32))
+    held, held_chunks, samplers = [], [], {}
+    mixed = 0
+    t_start = time.time()
+
+    def flush():
+        """Collective: every rank hands over the rows it sampled since the last flush (ONE all_gather of the packed
+        (rows, Lmax + 2 * 1920) tensor; a rank without rows joins with an empty tensor) and rank 0 files them by global row."""
+        if not held_chunks:
+            return
+        counts = [sum(tdist.shard_rows(s1 - s0, r, world)[1] - tdist.shard_rows(s1 - s0, r, world)[0]
+                      for s0, s1 in held_chunks) for r in range(world)]
+        mine = torch.cat(held, dim=0) if held else torch.empty(0, width, device=device)
+        parts = tdist.gather_ragged(dist, mine, counts, rank)
+        if rank == 0:
+            for r, part in enumerate(parts):
+                if counts[r] == 0:
+                    continue
+                dest = torch.cat([torch.arange(s0 + tdist.shard_rows(s1 - s0, r, world)[0],
+                                               s0 + tdist.shard_rows(s1 - s0, r, world)[1]) for s0, s1 in held_chunks])
+                p = part.cpu().numpy()
+                d = dest.numpy()
+                out[0][d] = p[:, :Lmax]
+                out[1][d] = p[:, Lmax:Lmax + 1920].reshape(-1, 64, 30)
+                out[2][d] = p[:, Lmax + 1920:].reshape(-1, 64, 30)
+        held.clear()
+        held_chunks.clear()
+
+    def length_groups(segs):
+        """{L: (row positions in the launch, the segments of that length)} in launch order."""
+        groups, pos = {}, 0
+        for u, i0, i1 in segs:
+            g = groups.setdefault(lens[u], ([], []))
+            g[0].append(torch.arange(pos, pos + i1 - i0, device=device))        # made on the device: no host wait
+            g[1].append((u, i0, i1))
+            pos += i1 - i0
+        return {Lg: (torch.cat(p), s) for Lg, (p, s) in groups.items()}
+
+    with torch.no_grad():
+        for k, (s0, s1) in enumerate(plan):
+            if len(launch_segments(unit_rows, s0, s1)) > 1:
+                mixed += 1
+            lo, hi = tdist.shard_rows(s1 - s0, rank, world)
+            n = hi - lo
+            if n > 0:                     # a rank without rows in this launch (fewer rows than GPUs) only joins the flush
+                segs = launch_segments(unit_rows, s0 + lo, s0 + hi)
+                seeds, keys, cfgs = row_tables(segs, unit_seeds, unit_cfgs)
+                embedding = torch.cat([emb_dev[u][i0:i1] for u, i0, i1 in segs]) if len(segs) > 1 else \
+                    emb_dev[segs[0][0]][segs[0][1]:segs[0][2]]
+                groups = length_groups(segs)
+                if len(groups) == 1:
+                    x_1 = torch.cat([x1_dev[u][i0:i1] for u, i0, i1 in segs])
+                    z_enc, _ = model.encoder(x_1.contiguous())                      # infer.py:73-74
+                else:
+                    z_enc = torch.empty(n, 64, 30, device=device)
+                    for Lg, (pos, gsegs) in groups.items():
+                        z_enc[pos] = model.encoder(torch.cat([x1_dev[u][i0:i1] for u, i0, i1 in gsegs]).contiguous())[0]
+                L0 = lens[segs[0][0]]
+                sampler = samplers.get((n, L0))
+                if sampler is None:
+                    sampler = samplers[(n, L0)] = Sampler(model, vae.decoder, backbone, args.total_step, unit_cfgs[segs[0][0]],
+                                                          n, L0, device, use_graph=True, seed=args.seed, row0=0)
+                sampler.set_rows(seeds, keys, cfgs)       # this launch's (seed, key row, cfg) per row; the graph is kept
+                lat, series, _ = sampler.run(embedding.contiguous(), decode=len(groups) == 1)
+                ser = torch.zeros(n, Lmax, device=device)
+                if len(groups) == 1:
+                    ser[:, :L0] = series.reshape(n, L0)
+                else:
+                    for Lg, (pos, _) in groups.items():
+                        ser[pos, :Lg] = vae.decoder(lat[pos].contiguous(), length=Lg)[0].reshape(-1, Lg)
+                held.append(torch.cat([ser, lat.reshape(n, 1920), z_enc.reshape(n, 1920)], dim=1))
+            held_chunks.append((s0, s1))
+            if rank == 0:
+                print(f"Generating {k}th Batch TS...  (rows {s0}..{s1 - 1} of {n_rows}, {s1 - s0} series per launch)")
+            if sum(b - a for a, b in held_chunks) >= flush_rows:
+                flush()
+        flush()
+        traces = {}
+        if getattr(args, "trace", False) and rank == 0:
+            # the per-step decode of row 0 (infer.py:90-93), from an eager run of exactly the rows the unit's own
+            # invocation holds in its first launch on rank 0
+            for ui, u in enumerate(units):
+                first = min(B if launch_batch <= 0 else launch_batch * world, unit_rows[ui])
+                m = tdist.shard_rows(first, 0, world)[1]
+                ts = samplers.get(("trace", m, lens[ui]))
+                if ts is None:
+                    ts = samplers[("trace", m, lens[ui])] = Sampler(model, vae.decoder, backbone, args.total_step, u.cfg, m,
+                                                                    lens[ui], device, use_graph=True, seed=args.seed, row0=0)
+                ts.set_rows(*row_tables([(ui, 0, m)], unit_seeds, unit_cfgs))
+                traces[ui] = ts.run(emb_dev[ui][:m].contiguous(), decode=True, trace=True)[2].cpu().numpy()
+    tdist.barrier(dist, device)
+    loop_s = time.time() - t_start
+    args.stats = {"series": n_rows, "loop_s": loop_s, "launches": len(plan), "loader_batch": B, "gpus": world,
+                  "series_per_launch_and_gpu": (plan[0][1] - plan[0][0]) // world, "cells": len(cells), "runs": n_runs,
+                  "mixed_launches": mixed}
+    results = None
+    if rank == 0:
+        print(f"{n_rows} series in {loop_s:.2f} s ({n_rows / loop_s:.1f} series/s)")
+        results = []
+        for ui, u in enumerate(units):
+            a, b = int(offs[ui]), int(offs[ui + 1])
+            x_1 = x1_host[ui].numpy()
+            x_t = np.ascontiguousarray(out[0][a:b, :lens[ui]])
+            lat_dec, lat_enc = out[1][a:b], out[2][a:b]
+            np_save_outputs(u.path, x_1, x_t, lat_dec, lat_enc)                    # infer.py:118-123
+            if ui in traces:
+                np.save(os.path.join(u.path, "x_infer_trace.npy"), traces[ui])
+            print(f"saved {x_1.shape[0]} series to {u.path}")
+            results.append((x_1[:, :, None], x_t[:, :, None], lat_dec, lat_enc))
+    tdist.barrier(dist, device)
+    return results
 
 
 def _save_figs(path, x_1, x_t):
@@ -256,10 +567,12 @@ def build_parser():
     p.add_argument("--usepretrainedvae", default=True, help="pretrained vae")
     p.add_argument("--backbone", type=str, default="flowmatching", help="flowmatching or DDPM or EDM")
     p.add_argument("--denoiser", type=str, default="DiT", help="DiT or MLP")
-    p.add_argument("--cfg_scale", type=float, default=7, help="CFG Scale")
+    p.add_argument("--cfg_scale", type=str, default=7,
+                   help="CFG Scale; a comma-separated list samples every dataset at each scale in one job")
     p.add_argument("--total_step", type=int, default=100, help="total step sampled from [0,1]")
     p.add_argument("--checkpoint_id", type=int, default=19999, help="model id")
-    p.add_argument("--dataset_name", type=str, default="exchangerate_24", help="dataset name")
+    p.add_argument("--dataset_name", type=str, default="exchangerate_24",
+                   help="dataset name; a comma-separated list (one root) samples the grid datasets x cfg scales in one job")
     p.add_argument("--run_multi", type=bool, default=False, help="run multi times for CRPS,MAP,MRR,NDCG")
     # additions (see module docstring)
     p.add_argument("--seed", type=int, default=None, help="Philox noise seed (default: time based)")
@@ -291,22 +604,30 @@ def main(argv=None):
     if args.seed is None:
         args.seed = int(time.time()) & 0x7FFFFFFF
     args.weight_seed = args.seed
-    root = args.dataset_name.split("_")[0]
+    cells = parse_cells(args)
+    root = cells[0].dataset_name.split("_")[0]
     args.checkpoint_path = os.path.join(args.save_path, "checkpoints", f"{args.backbone}_{args.denoiser}_{root}",
                                         f"model_{args.checkpoint_id}.pth")
-    args.generation_save_path = os.path.join(
-        args.save_path, "generation",
-        "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, args.dataset_name, args.cfg_scale, args.total_step))
+    args.generation_save_path = cells[0].path
     print("start generate", args.run_multi)
     args.generation_save_path_result = args.generation_save_path
-    out = infer(args)
-    if args.run_multi:                                           # infer.py:148-164: 1 + 10 runs
-        for run_index in range(10):
+    n_runs = 11 if args.run_multi else 1                         # infer.py:148-164: 1 + 10 runs
+    if len(cells) == 1:                                          # a single cell: the args of the parent's one-cell job
+        args.dataset_name, args.cfg_scale = cells[0].dataset_name, cells[0].cfg_shown
+    if args.denoiser != "DiT":                                   # (one cell: parse_cells) the MLP loop, run by run
+        out = infer(args)
+        for run_index in range(n_runs - 1):
             args.generation_save_path_result = os.path.join(args.generation_save_path, f"run_{run_index}")
             args.seed += 1
             out = infer(args)
-    if out is not None and not args.no_figs:
-        _save_figs(args.generation_save_path, out[0], out[1])
+        if out is not None and not args.no_figs:
+            _save_figs(args.generation_save_path, out[0], out[1])
+        return args
+    results = sample_grid(args, cells, n_runs)
+    if results is not None and not args.no_figs:
+        for ci, c in enumerate(cells):                           # each cell's figures from its last run, as before
+            last = results[(ci + 1) * n_runs - 1]
+            _save_figs(c.path, last[0], last[1])
     return args
 
 

@@ -6,6 +6,8 @@
 // into a hipGraph and replayed `steps` times; everything that changes from step to step
 // (time-embedding row, DDPM coefficients, noise stream / injected-noise slice) is looked up on
 // the device through a step counter that the last node of the graph advances.
+#include <cmath>
+#include <cstring>
 #include <mutex>
 #include <stdlib.h>
 #include <vector>
@@ -69,6 +71,16 @@ __global__ void philox_normal_kernel(float* __restrict__ out, uint64_t seed, uin
     reinterpret_cast<f32x4*>(out)[idx] = normal4(seed, stream_id, row0 + (uint32_t)row, (uint32_t)quad);
 }
 
+// the same draws with a key and a key row per row: row r of out = row key_rows[r] of stream `stream_id` under seeds[r]
+__global__ void philox_normal_rows_kernel(float* __restrict__ out, const uint64_t* __restrict__ seeds,
+                                          const uint32_t* __restrict__ key_rows, uint32_t stream_id, int n_rows,
+                                          int quads_per_row) {
+    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= n_rows * quads_per_row) return;
+    const int row = idx / quads_per_row, quad = idx - row * quads_per_row;
+    reinterpret_cast<f32x4*>(out)[idx] = normal4(seeds[row], stream_id, key_rows[row], (uint32_t)quad);
+}
+
 // U[0,1) draws of the same counter layout: element e of global row `row` = lane e % 4 of counter (e / 4, row, stream_id);
 // 24-bit uniforms (exact in fp32, never 1.0)
 __global__ void philox_uniform_kernel(float* __restrict__ out, uint64_t seed, uint32_t stream_id, uint32_t row0, int n_rows,
@@ -100,7 +112,14 @@ struct StepArgs {
     int B;
     int noise_rows;       // rows per step of the injected-noise array (>= B: a lane steps a row range of the batch)
     int* advance;         // sampling loop: device {loop index, row0, arrival counter}; the last workgroup increments the index
+    // per-row tables (t2s_sampler_set_rows), this lane's slice: used where bit ROWS_SEED / ROWS_KEY / ROWS_CFG of step_ptr[3]
+    // is set (read on the device, so a captured graph serves tables and uniform runs alike); NULL outside the sampler
+    const uint64_t* row_seed;
+    const uint32_t* row_key;
+    const float* row_cfg;
 };
+
+constexpr int ROWS_SEED = 1, ROWS_KEY = 2, ROWS_CFG = 4;
 
 // Last workgroup to finish advances the device loop index (step[0]; step[2] is the arrival counter): every
 // workgroup has read step[0] before it arrives, so the increment cannot overtake a reader, and the stand-alone
@@ -124,28 +143,33 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const StepArgs a) {
     int t = a.t_index;
     uint32_t sid = a.stream_id, row0 = a.row0;
     const float* noise = a.noise;
+    int rows = 0;
     if (a.step_ptr) {
         const int j = a.step_ptr[0];
         row0 = (uint32_t)a.step_ptr[1];   // read on the device so a captured graph serves every shard position
+        rows = a.step_ptr[3];             // which per-row tables this run uses (t2s_sampler_set_rows)
         t = a.steps - 1 - j;
         sid = (uint32_t)j;
         if (noise) noise += (size_t)j * a.noise_rows * LAT;
     }
     const float c0 = a.coef[t * 3 + 0], c1 = a.coef[t * 3 + 1], c2 = a.coef[t * 3 + 2];
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {  // one float4 (quad) at a time
+        const int row = idx / QPR;
         const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[idx];
         const f32x4 u = reinterpret_cast<const f32x4*>(a.eps_u)[idx];
         f32x4 pred = u;
         if (a.eps_c) {
             const f32x4 c = reinterpret_cast<const f32x4*>(a.eps_c)[idx];
-            pred = u + a.cfg * (c - u);
+            pred = u + ((rows & ROWS_CFG) ? a.row_cfg[row] : a.cfg) * (c - u);
         }
         f32x4 z;
         if (noise) {
             z = reinterpret_cast<const f32x4*>(noise)[idx];
         } else {
-            const int row = idx / QPR, quad = idx - row * QPR;
-            z = normal4(a.seed, sid, row0 + (uint32_t)row, (uint32_t)quad);
+            const int quad = idx - row * QPR;
+            const uint64_t seed = (rows & ROWS_SEED) ? a.row_seed[row] : a.seed;
+            const uint32_t key = (rows & ROWS_KEY) ? a.row_key[row] : row0 + (uint32_t)row;
+            z = normal4(seed, sid, key, (uint32_t)quad);
         }
         const f32x4 mean = c0 * (x - c1 * pred);
         reinterpret_cast<f32x4*>(a.x)[idx] = mean + c2 * z;
@@ -153,13 +177,15 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const StepArgs a) {
     if (a.advance) advance_step_when_last(a.advance);
 }
 
+// row_cfg: this lane's slice of the per-row guidance table, used when bit ROWS_CFG of advance[3] is set (NULL: never)
 __global__ __launch_bounds__(256) void rf_step_kernel(float* __restrict__ x, const float* __restrict__ vu,
                                                       const float* __restrict__ vc, float cfg, float dt,
-                                                      int n4, int* advance) {
+                                                      int n4, int* advance, const float* __restrict__ row_cfg) {
+    const bool per_row = row_cfg && advance && (advance[3] & ROWS_CFG);
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n4; idx += gridDim.x * blockDim.x) {
         const f32x4 u = reinterpret_cast<const f32x4*>(vu)[idx];
         f32x4 pred = u;
-        if (vc) pred = u + cfg * (reinterpret_cast<const f32x4*>(vc)[idx] - u);
+        if (vc) pred = u + (per_row ? row_cfg[idx / (LAT / 4)] : cfg) * (reinterpret_cast<const f32x4*>(vc)[idx] - u);
         f32x4 xv = reinterpret_cast<f32x4*>(x)[idx];
         reinterpret_cast<f32x4*>(x)[idx] = xv + pred * dt;
     }
@@ -255,12 +281,13 @@ __global__ __launch_bounds__(256) void mse_final_kernel(const float* __restrict_
 }
 
 // step[0] = loop index, step[1] = global row index of the lane's first series (Philox key), step[2] = arrival counter
-// of the update kernel (advance_step_when_last)
-__global__ void set_step_kernel(int* step, int value, uint32_t row0) {
+// of the update kernel (advance_step_when_last), step[3] = the per-row tables in use (ROWS_* bits)
+__global__ void set_step_kernel(int* step, int value, uint32_t row0, int rows) {
     if (threadIdx.x == 0 && blockIdx.x == 0) {
         step[0] = value;
         step[1] = (int)row0;
         step[2] = 0;
+        step[3] = rows;
     }
 }
 
@@ -277,6 +304,17 @@ extern "C" int t2s_philox_normal(float* out, uint64_t seed, uint32_t stream_id, 
                 "t2s_philox_normal: bad argument (n_rows=%d,row_elems=%d; row_elems %% 4 must be 0)", n_rows, row_elems);
     const int q = row_elems / 4, total = n_rows * q;
     philox_normal_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(out, seed, stream_id, row0, n_rows, q);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+extern "C" int t2s_philox_normal_rows(float* out, const uint64_t* seeds, const uint32_t* key_rows, uint32_t stream_id,
+                                      int n_rows, int row_elems, void* stream) {
+    T2S_REQUIRE(out && seeds && key_rows && n_rows > 0 && row_elems > 0 && row_elems % 4 == 0 &&
+                    (long long)n_rows * row_elems < (1ll << 31),
+                "t2s_philox_normal_rows: bad argument (n_rows=%d,row_elems=%d; row_elems %% 4 must be 0)", n_rows, row_elems);
+    const int q = row_elems / 4, total = n_rows * q;
+    philox_normal_rows_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(out, seeds, key_rows, stream_id, n_rows, q);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -308,7 +346,7 @@ extern "C" int t2s_ddpm_step(float* x, const float* eps_u, const float* eps_c, c
 extern "C" int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float dt, int B, void* stream) {
     T2S_REQUIRE(x && v_u && B > 0, "t2s_rf_step: bad argument");
     const int n4 = B * (LAT / 4);
-    rf_step_kernel<<<(n4 + 255) / 256, 256, 0, (hipStream_t)stream>>>(x, v_u, v_c, cfg, dt, n4, nullptr);
+    rf_step_kernel<<<(n4 + 255) / 256, 256, 0, (hipStream_t)stream>>>(x, v_u, v_c, cfg, dt, n4, nullptr, nullptr);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -420,7 +458,24 @@ struct t2s_sampler {
     float* g_x = nullptr;
     const float* g_text = nullptr;
     const float* g_noise = nullptr;
+    // Per-row tables (t2s_sampler_set_rows): `rows` = the ROWS_* bits in use; the host copy `h_rows` (seeds, key rows, cfg
+    // of every batch row, in the device layout) is uploaded at the next run when `rows_dirty`, through the pinned staging
+    // buffer `h_stage` on the run's stream -- which the next upload reuses only after `ev_rows` says the copy has read it
+    int rows = 0;
+    bool rows_dirty = false;
+    std::vector<unsigned char> h_rows;
+    void* h_stage = nullptr;
+    void* d_rows = nullptr;       // (batch) u64 seeds | (batch) u32 key rows | (batch) f32 cfg
+    hipEvent_t ev_rows = nullptr;
+    bool ev_rows_recorded = false;
 };
+
+namespace {
+inline size_t rows_bytes(int batch) { return (size_t)batch * (sizeof(uint64_t) + sizeof(uint32_t) + sizeof(float)); }
+inline uint64_t* rows_seed(void* base, int batch) { (void)batch; return (uint64_t*)base; }
+inline uint32_t* rows_key(void* base, int batch) { return (uint32_t*)((uint64_t*)base + batch); }
+inline float* rows_cfg(void* base, int batch) { return (float*)(rows_key(base, batch) + batch); }
+}  // namespace
 
 namespace {
 
@@ -541,11 +596,15 @@ int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise
         a.x = xl; a.eps_u = eu; a.eps_c = ec; a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
         a.step_ptr = step; a.steps = c.steps; a.cfg = c.cfg_scale; a.seed = c.seed; a.row0 = c.row0 + (uint32_t)r0;
         a.B = n; a.noise_rows = c.batch; a.advance = step;
+        a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
+        a.row_key = rows_key(s->d_rows, c.batch) + r0;
+        a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
         const int total = n * (LAT / 4), wgs = (total + 255) / 256;
         ddpm_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(a);
     } else {
         const int n4 = n * (LAT / 4), wgs = (n4 + 255) / 256;
-        rf_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(xl, eu, ec, c.cfg_scale, 1.0f / (float)c.steps, n4, step);
+        rf_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(xl, eu, ec, c.cfg_scale, 1.0f / (float)c.steps, n4, step,
+                                                                               rows_cfg(s->d_rows, c.batch) + r0);
     }
     T2S_LAUNCH_CHECK();   // (the update kernel's last workgroup advanced the lane's loop index)
     return T2S_OK;
@@ -621,6 +680,10 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     alloc((void**)&s->eps_c, B * LAT * sizeof(float));
     alloc((void**)&s->tvals, T * sizeof(float));
     alloc((void**)&s->step, t2s_sampler::MAX_LANES * 16 * sizeof(int));   // one counter per lane, 64 B apart
+    alloc(&s->d_rows, rows_bytes(cfg->batch));                            // per-row tables (t2s_sampler_set_rows)
+    if (e == hipSuccess) e = hipHostMalloc(&s->h_stage, rows_bytes(cfg->batch), hipHostMallocDefault);
+    if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_rows, hipEventDisableTiming);
+    s->h_rows.assign(rows_bytes(cfg->batch), 0);
     // whole-run adaLN table (dit_adaln_table; 3.2 GB at 256 series x 1000 steps for ~2 % of a step): only while it is a
     // small part of what the device has FREE right now -- at most 1/8 of it and 16 GB -- so that a process holding several
     // samplers, or sharing the GPU with torch's allocator or a training job, does not run dry later for an optimisation;
@@ -686,6 +749,23 @@ extern "C" int t2s_sampler_set_row0(t2s_sampler* s, uint32_t row0) {
     return T2S_OK;
 }
 
+extern "C" int t2s_sampler_set_rows(t2s_sampler* s, const uint64_t* seeds, const uint32_t* key_rows, const float* cfg, int n) {
+    T2S_REQUIRE(s, "t2s_sampler_set_rows: NULL sampler");
+    const int B = s->cfg.batch;
+    T2S_REQUIRE(n == B, "t2s_sampler_set_rows: n=%d, the sampler's batch is %d", n, B);
+    if (cfg)
+        for (int r = 0; r < n; ++r) T2S_REQUIRE(std::isfinite(cfg[r]), "t2s_sampler_set_rows: cfg[%d] is not finite", r);
+    // host work only: the tables reach the device at the next run (no copy here, so no thread-contract question)
+    void* h = s->h_rows.data();
+    int rows = 0;
+    if (seeds) memcpy(rows_seed(h, B), seeds, (size_t)n * sizeof(uint64_t)), rows |= ROWS_SEED;
+    if (key_rows) memcpy(rows_key(h, B), key_rows, (size_t)n * sizeof(uint32_t)), rows |= ROWS_KEY;
+    if (cfg) memcpy(rows_cfg(h, B), cfg, (size_t)n * sizeof(float)), rows |= ROWS_CFG;
+    s->rows = rows;
+    s->rows_dirty = rows != 0;
+    return T2S_OK;
+}
+
 extern "C" int t2s_sampler_lane_pool(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
@@ -707,7 +787,10 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     if (s->ev_fork) (void)hipEventDestroy(s->ev_fork);
     if (s->ev_in) (void)hipEventDestroy(s->ev_in);
     if (s->ev_out) (void)hipEventDestroy(s->ev_out);
-    void* bufs[] = {s->temb_table, s->coef, s->eps_u, s->eps_c, s->tvals, s->step, s->mod_table};
+    if (s->ev_rows && s->ev_rows_recorded) (void)hipEventSynchronize(s->ev_rows);   // the last upload has read h_stage
+    if (s->ev_rows) (void)hipEventDestroy(s->ev_rows);
+    if (s->h_stage) (void)hipHostFree(s->h_stage);
+    void* bufs[] = {s->temb_table, s->coef, s->eps_u, s->eps_c, s->tvals, s->step, s->mod_table, s->d_rows};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete s;
@@ -809,12 +892,22 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
     }
     // the adaLN modulation of every step for this run's text (state-independent: off the loop's critical path)
     if (s->mod_table && (rc = dit_adaln_table(s->dit, s->temb_table, c.steps, text, c.batch, s->mod_table, st)) != T2S_OK) return rc;
+    // per-row tables set since the last run: stream-ordered upload from the sampler's own pinned staging buffer (the
+    // previous upload has read it once ev_rows completes), before the fork so that every lane sees them
+    if (s->rows && s->rows_dirty) {
+        if (s->ev_rows_recorded) T2S_HIP_CHECK(hipEventSynchronize(s->ev_rows));
+        memcpy(s->h_stage, s->h_rows.data(), s->h_rows.size());
+        T2S_HIP_CHECK(hipMemcpyAsync(s->d_rows, s->h_stage, s->h_rows.size(), hipMemcpyHostToDevice, st));
+        T2S_HIP_CHECK(hipEventRecord(s->ev_rows, st));
+        s->ev_rows_recorded = true;
+        s->rows_dirty = false;
+    }
     if (lanes > 1) {    // fork: the other lanes start after everything already queued on the caller's stream
         T2S_HIP_CHECK(hipEventRecord(s->ev_fork, st));
         for (int l = 1; l < lanes; ++l) T2S_HIP_CHECK(hipStreamWaitEvent(s->side[l], s->ev_fork, 0));
     }
     for (int l = 0; l < lanes; ++l) {
-        set_step_kernel<<<1, 64, 0, lst[l]>>>(s->step + 16 * l, 0, c.row0 + (uint32_t)r0[l]);
+        set_step_kernel<<<1, 64, 0, lst[l]>>>(s->step + 16 * l, 0, c.row0 + (uint32_t)r0[l], s->rows);
         T2S_LAUNCH_CHECK();
     }
     if (graph_ok && whole)

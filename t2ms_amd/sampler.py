@@ -87,6 +87,64 @@ def philox_normal(n_rows: int, row_elems: int, seed: int, stream_id: int, row0: 
     return out
 
 
+def _u64_table(seeds, n: int, what: str) -> np.ndarray:
+    a = np.asarray(seeds)
+    if a.shape != (n,) or not (np.issubdtype(a.dtype, np.integer) or a.dtype == object):
+        raise L.T2SError(f"{what}: seeds must be {n} integers, got shape {a.shape} dtype {a.dtype}")
+    vals = [int(v) for v in a.tolist()]
+    if any(v < 0 or v >= 1 << 64 for v in vals):
+        raise L.T2SError(f"{what}: seeds must lie in [0, 2**64)")
+    return np.asarray(vals, dtype=np.uint64)
+
+
+def _u32_table(key_rows, n: int, what: str) -> np.ndarray:
+    a = np.asarray(key_rows)
+    if a.shape != (n,) or not np.issubdtype(a.dtype, np.integer):
+        raise L.T2SError(f"{what}: key_rows must be {n} integers, got shape {a.shape} dtype {a.dtype}")
+    if a.size and (int(a.min()) < 0 or int(a.max()) >= 1 << 32):
+        raise L.T2SError(f"{what}: key_rows must lie in [0, 2**32)")
+    return a.astype(np.uint32)
+
+
+def _cfg_table(cfg, n: int, what: str) -> np.ndarray:
+    a = np.asarray(cfg, dtype=np.float64)
+    if a.shape != (n,):
+        raise L.T2SError(f"{what}: cfg must hold {n} values, got shape {a.shape}")
+    with np.errstate(over="ignore"):
+        f = a.astype(np.float32)
+    if not np.isfinite(f).all():
+        raise L.T2SError(f"{what}: cfg values must be finite (in fp32)")
+    return f
+
+
+def _device_tables(seeds: np.ndarray, key_rows: np.ndarray, device):
+    """(u64 seeds, u32 key rows) as device tensors of the same bits (int64 / int32 storage).  Staged through pinned memory
+    and copied asynchronously on the current stream: a pageable copy would make the host wait for the work queued before
+    it (the previous launch), which the uniform x_T draw never did."""
+    s = torch.from_numpy(np.ascontiguousarray(seeds.astype(np.uint64)).view(np.int64)).pin_memory()
+    k = torch.from_numpy(np.ascontiguousarray(key_rows.astype(np.uint32)).view(np.int32)).pin_memory()
+    return s.to(device, non_blocking=True), k.to(device, non_blocking=True)
+
+
+def philox_normal_rows(seeds, key_rows, row_elems: int, stream_id: int, device, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """(n_rows, row_elems) N(0,1) draws with a key and a key row per row (t2s_philox_normal_rows): row r equals
+    philox_normal(1, row_elems, seeds[r], stream_id, key_rows[r], device) bit for bit."""
+    device = torch.device(device)
+    n = len(seeds)
+    s = _u64_table(seeds, n, "philox_normal_rows")
+    k = _u32_table(key_rows, n, "philox_normal_rows")
+    if out is None:
+        out = torch.empty(n, row_elems, device=device, dtype=torch.float32)
+    if out.numel() != n * row_elems:
+        raise L.T2SError(f"philox_normal_rows: out holds {out.numel()} values, expected {n} x {row_elems}")
+    if n:
+        ds, dk = _device_tables(s, k, device)
+        with torch.cuda.device(device):
+            L.check(L.lib().t2s_philox_normal_rows(L.dev_ptr(out), ds.data_ptr(), dk.data_ptr(), int(stream_id) & 0xFFFFFFFF,
+                                                   n, row_elems, L.stream_ptr(device)), "t2s_philox_normal_rows")
+    return out
+
+
 def philox_uniform(n_rows: int, row_elems: int, seed: int, stream_id: int, row0: int, device) -> torch.Tensor:
     """(n_rows, row_elems) U[0,1) draws of the library's Philox stream (t2s_philox_uniform): 24-bit uniforms keyed like
     philox_normal by (seed, stream_id, GLOBAL row) -- the per-row diffusion time of a training step (train.py:109,113)."""
@@ -152,6 +210,8 @@ class Sampler:
             L.check(L.lib().t2s_sampler_set_lanes(self.ptr, self.lanes), "t2s_sampler_set_lanes")
             L.check(L.lib().t2s_sampler_set_loop_graph(self.ptr, self.loop_graph), "t2s_sampler_set_loop_graph")
         self._fin = weakref.finalize(self, _destroy_locked, str(self.device), self.ptr)
+        if self.__dict__.get("_rows") is not None:      # a re-created C sampler keeps the per-row tables
+            self.set_rows(*self._rows)
         self._keep = (tvals, coef)
 
     def set_row0(self, row0: int):
@@ -160,10 +220,32 @@ class Sampler:
         self.row0 = int(row0)
         L.check(L.lib().t2s_sampler_set_row0(self.ptr, self.row0), "t2s_sampler_set_row0")
 
+    def set_rows(self, seeds=None, key_rows=None, cfg=None):
+        """Per-row noise key, key row and guidance scale for the NEXT runs (t2s_sampler_set_rows): row r draws x_T and its
+        per-step noise as row key_rows[r] of the Philox stream keyed by seeds[r] and combines u + cfg[r] * (c - u) -- what
+        a uniform sampler of that seed / row0 / cfg_scale does for it, so rows of several runs and guidance scales share one
+        launch.  Each argument: `batch` values, or None = uniform (the sampler's seed, row0 + r, cfg_scale).  All None
+        restores the uniform sampler.  The captured hipGraph is kept."""
+        n = self.batch
+        s = None if seeds is None else _u64_table(seeds, n, "Sampler.set_rows")
+        k = None if key_rows is None else _u32_table(key_rows, n, "Sampler.set_rows")
+        c = None if cfg is None else _cfg_table(cfg, n, "Sampler.set_rows")
+        L.check(L.lib().t2s_sampler_set_rows(self.ptr, None if s is None else s.ctypes.data,
+                                             None if k is None else k.ctypes.data,
+                                             None if c is None else c.ctypes.data, n), "t2s_sampler_set_rows")
+        self._rows = (s, k, c)
+
     def draw_xT(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_T ~ N(0,1) from the Philox stream (perf mode), (batch,64,30)."""
+        """x_T ~ N(0,1) from the Philox stream (perf mode), (batch,64,30); per row as set_rows keyed it."""
         if out is None:
             out = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=self.device, dtype=torch.float32)
+        s, k, _ = self.__dict__.get("_rows") or (None, None, None)
+        if s is not None or k is not None:
+            if s is None:
+                s = np.full(self.batch, self.seed, dtype=np.uint64)
+            if k is None:
+                k = (self.row0 + np.arange(self.batch, dtype=np.int64)).astype(np.uint32)
+            return philox_normal_rows(s, k, L.LAT, XT_STREAM, self.device, out=out)
         with torch.cuda.device(self.device):
             L.check(L.lib().t2s_philox_normal(L.dev_ptr(out), self.seed, XT_STREAM, self.row0, self.batch, L.LAT,
                                               L.stream_ptr(self.device)), "t2s_philox_normal")
