@@ -119,9 +119,27 @@ int t2s_dit_max_seqs(const t2s_dit* h);
  *                           Since round 5 the host-side Sampler and infer.py SELECT this mode unless told otherwise
  *                           (its error against fp64 is not larger than the reference's own CPU fp32 arithmetic at any of
  *                           17 table entries, profiles/r05_accuracy.md); the class API and the bench headline stay on F32.
- * Not capturable; a hipGraph captured under one mode keeps replaying that mode's kernels. */
+ *   T2S_MATH_BF16           single-pass bf16 mixed precision (opt-in; NOT fp32-accurate).  The operands of every matrix
+ *                           product of the DiT forward (qkv, QK^T, PV, proj, fc1, fc2) are rounded ONCE to bf16, round to
+ *                           nearest even, and multiplied by one v_mfma_f32_32x32x16_bf16 per k-step with fp32 accumulation.
+ *                           Where the operands are rounded: weights when they are packed; LayerNorm / adaLN-modulated
+ *                           activations, the attention output and GELU(fc1) in registers in front of their product; k and v
+ *                           after their bias, as they leave the qkv epilogue; q AFTER its fp32 multiplication by
+ *                           32^-0.5 * log2(e) (q itself travels in fp32); the exponentiated scores P = exp2(s - ref) in front
+ *                           of PV -- the running row sum adds the unrounded P.
+ *                           Everything else is fp32 exactly as in the other modes: the residual stream (also in memory),
+ *                           LayerNorm and adaLN modulation, the softmax reference / exponent / running sum, GELU, biases,
+ *                           the final layer, patchify, the time embedding, the adaLN table, the CFG combine, the DDPM / RF
+ *                           update, the Philox noise and the LA-VAE.  This is the contract of the training step's
+ *                           T2S_TRAIN_BF16.  Allocates 2 x max_seqs x 122,880 B + 1.0 MB of bf16 weights on first use, on
+ *                           the library's own set-up stream; weights follow t2s_dit_update_weights.  Errors against fp64:
+ *                           rms ~1e-3 on outputs of magnitude ~4.5 per forward, a quarter of what PyTorch's bf16 autocast
+ *                           makes of the same forward (tests/test_math_bf16.py).
+ * Not capturable; a hipGraph captured under one mode keeps replaying that mode's kernels.  Each mode has a workspace of
+ * its own, so a handle may be switched back and forth. */
 #define T2S_MATH_F32 0
 #define T2S_MATH_BF16X3 1
+#define T2S_MATH_BF16 2
 int t2s_dit_set_math(t2s_dit* h, int math);
 
 /* TimeEmbedding.forward, transformer.py:30-40.  t: (B) fp32 (int64 timesteps are
@@ -193,6 +211,12 @@ int t2s_attn_fwd_packed(const float* q, const float* k, const float* vT, float* 
  * products evaluated as six bf16 MFMAs each.  Packs / unpacks its operands internally and
  * synchronises the stream (tests, benchmarking). */
 int t2s_attn_fwd_x3(const float* q, const float* k, const float* v, float* o, int BH, void* stream);
+
+/* The one-plane bf16 attention kernel (T2S_MATH_BF16) on plain tensors, same calling contract as t2s_attn_fwd_x3.
+ * (Not t2s_attn_fwd_bf16: that is the training kernel, with bf16 operands in memory.)  It computes
+ *     O = sum_j rb(P_j) rb(v_j) / sum_j P_j,   P_j = exp2(rb(q * c) . rb(k_j) - ref),   c = 32^-0.5 * log2(e),
+ * rb = round to nearest even bf16, q * c one fp32 multiplication, products exact in fp32 accumulators. */
+int t2s_attn_fwd_bf16p(const float* q, const float* k, const float* v, float* o, int BH, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Training step of the DiT: train.py:101-127 (pred = model(x_t, t, emb); loss.backward();

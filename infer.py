@@ -399,7 +399,9 @@ def sample_grid(args, cells, n_runs):
     args.math = getattr(args, "math", None) or default_math()
     model.set_math(args.math)
     if rank == 0:
-        print(f"matrix arithmetic: {args.math}" + (" (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)" if args.math == "bf16x3" else ""))
+        print(f"matrix arithmetic: {args.math}" + {"bf16x3": " (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)",
+                                                   "bf16": " (single-pass bf16 operands, fp32 accumulate and residual stream: NOT fp32-accurate; "
+                                                           "--math bf16x3 = fp32-accurate)"}.get(args.math, ""))
 
     # Every unit's rows in its loader order (loader_order: the parent's generator sequence per (dataset, seed)); output
     # row i of a unit is dataset row order[i] -- the concatenation of the reference's batches (shuffle=True,
@@ -586,10 +588,11 @@ def build_parser():
     p.add_argument("--loader_batches", action="store_true",
                    help="take the row order from a real DataLoader walk (public torch API) instead of the emulated draws of "
                         "datafactory.epoch_index_batches -- same order, same files; the cross-check after a torch upgrade")
-    p.add_argument("--math", default=None, choices=["f32", "bf16x3"],
+    p.add_argument("--math", default=None, choices=["f32", "bf16x3", "bf16"],
                    help="matrix arithmetic of the DiT: bf16x3 (default; fp32-ACCURATE split-bf16 products on the bf16 matrix cores, "
                         "+35 %%; its error against fp64 is not larger than the reference's PyTorch-CPU fp32 arithmetic, "
-                        "profiles/r05_accuracy.md) or f32 (exact f32 MFMA)")
+                        "profiles/r05_accuracy.md), f32 (exact f32 MFMA) or bf16 (opt-in mixed precision: operands rounded "
+                        "once to bf16, fp32 accumulate; 2.5x bf16x3, rms error ~1e-3 on outputs of ~4.5 per forward, DESIGN.md 4.4)")
     return p
 
 

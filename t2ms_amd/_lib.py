@@ -18,7 +18,8 @@ N_BLOCKS = 4
 LAT_C, LAT_W, LAT = 64, 30, 1920
 D_MODEL, N_TOK = 128, 480
 TRAIN_F32, TRAIN_BF16 = 0, 1   # t2s.h: T2S_TRAIN_F32 / T2S_TRAIN_BF16
-MATH_F32, MATH_BF16X3 = 0, 1    # t2s.h: T2S_MATH_F32 / T2S_MATH_BF16X3
+MATH_F32, MATH_BF16X3, MATH_BF16 = 0, 1, 2    # t2s.h: T2S_MATH_F32 / T2S_MATH_BF16X3 / T2S_MATH_BF16
+MATH_CODES = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "bf16": MATH_BF16}
 DIT_N_TENSORS = 10 + 10 * N_BLOCKS   # t2s.h: T2S_DIT_N_TENSORS (pointers of t2s_dit_weights, declaration order)
 MSE_SCRATCH_FLOATS = 1024       # t2s.h: T2S_MSE_SCRATCH_FLOATS
 
@@ -139,6 +140,7 @@ SYMBOLS = {
     "t2s_mlp_forward": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_mlp_backward": (_I, [C.POINTER(MlpWeights), _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(MlpGrads), _VP, _U64, _I, _VP]),
     "t2s_attn_fwd_x3": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
+    "t2s_attn_fwd_bf16p": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_attn_fwd_bf16": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_dit_train_forward": (_I, [_VP, C.POINTER(DitWeights), _VP, _VP, _I, _VP, _VP, _I, _VP]),
     "t2s_dit_train_backward": (_I, [_VP, _VP, C.POINTER(DitGrads), _I, _VP]),

@@ -9,6 +9,10 @@
 // k, v^T pre-split bf16 planes written by the row-chain kernel (t2s_x3.h: X3_TILE_UNITS); the
 // exponentiated tile P^T is split in registers.  Per 32-key block and query tile: 12 + 12 MFMAs of
 // 32 cycles (768) instead of 16 + 16 of 64 (2048).
+//
+// The same body instantiated on one bf16 plane (Split1, t2s_x3.h) is the attention of the single-pass "bf16" arithmetic
+// (T2S_MATH_BF16, attn_fwd_bf16p_kernel): q, k, v^T and P^T each rounded once, 2 + 2 MFMAs per key block and query tile (128
+// cycles), a ring slot of 4 KiB.  Not fp32-accurate; the softmax reference, exponent and running sum stay fp32.
 #include <stdlib.h>
 #include "t2s_x3.h"
 
@@ -22,6 +26,9 @@ constexpr int X3_SLOTS = 4;
 constexpr int X3_SLOT_UNITS = 2 * X3_TILE_UNITS;                 // K planes + V^T planes = 12 KiB
 constexpr int X3_LDS_BYTES = X3_SLOTS * X3_SLOT_UNITS * 16;      // 48 KiB
 constexpr int X3_THREADS = 512;
+// the one-plane form ("bf16" arithmetic, t2s_x3.h): same ring, a third of the bytes per slot
+constexpr int P1_SLOT_UNITS = 2 * XN_TILE_UNITS<1>;              // K plane + V^T plane = 4 KiB
+constexpr int P1_LDS_BYTES = X3_SLOTS * P1_SLOT_UNITS * 16;      // 16 KiB
 
 __device__ __forceinline__ float pair_max(float v) {
     const auto r = __builtin_amdgcn_permlane32_swap(__float_as_uint(v), __float_as_uint(v), false, false);
@@ -52,7 +59,8 @@ __device__ __forceinline__ void glds16u(const bf16x8* gsrc_lane, bf16x8* lds_wav
 }
 
 // S^T tile (+ c) = K Q^T over the head dimension (two 16-deep steps), fp32-accurate
-__device__ __forceinline__ f32x16 scores(const Split3 (&kf)[2], const Split3 (&q)[2], f32x16 c) {
+template <class SP>
+__device__ __forceinline__ f32x16 scores(const SP (&kf)[2], const SP (&q)[2], f32x16 c) {
     c = mfma_x3(kf[0], q[0], c);
     return mfma_x3(kf[1], q[1], c);
 }
@@ -69,9 +77,15 @@ __device__ __forceinline__ f32x16 scores_from(const Split3 (&kf)[2], const Split
     acc = mfma16(kf[0].h, q[0].h, acc);
     return mfma_x3(kf[1], q[1], acc);
 }
+__device__ __forceinline__ f32x16 scores_from(const Split1 (&kf)[2], const Split1 (&q)[2], const f32x16& c) {
+    f32x16 acc;
+    asm volatile("v_mfma_f32_32x32x16_bf16 %0, %1, %2, %3" : "=&v"(acc) : "v"(kf[0].h), "v"(q[0].h), "v"(c));
+    return mfma16(kf[1].h, q[1].h, acc);
+}
 
 // rare path: raw scores (C = 0) -> new reference, rescale the running sum / output, P^T in st
-__device__ __forceinline__ float rereference(const Split3 (&kf)[2], const Split3 (&q)[2], f32x16& st, f32x16& ot,
+template <class SP>
+__device__ __forceinline__ float rereference(const SP (&kf)[2], const SP (&q)[2], f32x16& st, f32x16& ot,
                                              TileState& t) {
     f32x16 z;
 #pragma unroll
@@ -94,13 +108,15 @@ __device__ __forceinline__ float rereference(const Split3 (&kf)[2], const Split3
     return exp_sum(st);
 }
 
-// scaled + split Q^T operand of one query tile from its four fp32 fragments (k-step s = fragments 2s, 2s+1)
-__device__ __forceinline__ void load_q(const f32x4 (&raw)[4], Split3 (&q)[2]) {
+// scaled + split Q^T operand of one query tile from its four fp32 fragments (k-step s = fragments 2s, 2s+1).
+// One-plane form: q is rounded to bf16 HERE, after the fp32 multiplication by 32^-0.5 log2(e) (the contract of t2s.h).
+template <class SP>
+__device__ __forceinline__ void load_q(const f32x4 (&raw)[4], SP (&q)[2]) {
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
         const f32x4 a = raw[2 * s] * QSCALE, b = raw[2 * s + 1] * QSCALE;
         const f32x8 v = {a.x, a.y, a.z, a.w, b.x, b.y, b.z, b.w};
-        q[s] = split3(v);
+        q[s] = splitp<SP>(v);
     }
 }
 
@@ -116,15 +132,22 @@ __device__ __forceinline__ void load_q(const f32x4 (&raw)[4], Split3 (&q)[2]) {
 //   * block j+1 has landed (every DMA-issuing wave waited until only its youngest block is in flight),
 //   * every wave is done with block j-1 (both variants finish PV(j-1) before QK(j)),
 // so after it a wave may read K(j+1) and refill slot (j+3) & 3 == (j-1) & 3 with block j+3.
-template <int NT, int STAG>
+//
+// SP = Split3 (bf16x3) or Split1 (one plane): NP planes make 2 NP pieces of K and 2 NP of V^T per key block, and the counted
+// waits below are in units of that piece count -- 12 for bf16x3, 4 for the one-plane form.
+template <int NT, int STAG, class SP>
 __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, const bf16x8* kall, const bf16x8* vall,
                                              f32x4* og, int BH, int lane, int wave) {
     const int stride = gridDim.x;
     const int t0 = wave * 2;
-    // 12 pieces of 1 KiB per key block (6 K planes/steps, 6 V^T)
+    constexpr int NP = planes_of<SP>::n;
+    constexpr int PK = 2 * NP;                       // pieces of K (and of V^T) per key block
+    constexpr int SLOT_UNITS = 2 * XN_TILE_UNITS<NP>;
+    static_assert(NP == 1 || SLOT_UNITS == X3_SLOT_UNITS, "bf16x3 ring geometry");
+    // 2 PK pieces of 1 KiB per key block (bf16x3: 6 K planes/steps, 6 V^T)
     auto issue_piece = [&](int bh, int jb, int gslot, int p) {
-        const bf16x8* src = (p < 6 ? kall : vall) + ((size_t)(bh * NKB + jb) * 6 + (p < 6 ? p : p - 6)) * 64 + lane;
-        glds16u(src, ring + (gslot & (X3_SLOTS - 1)) * X3_SLOT_UNITS + p * 64);
+        const bf16x8* src = (p < PK ? kall : vall) + ((size_t)(bh * NKB + jb) * PK + (p < PK ? p : p - PK)) * 64 + lane;
+        glds16u(src, ring + (gslot & (X3_SLOTS - 1)) * SLOT_UNITS + p * 64);
     };
     // The one-tile wave (NT == 1: wave 7, whose SIMD carries 3 tiles where the others carry 4) issues all 12 pieces of a block,
     // the two-tile waves none (round 5, as t2s_attn.hip: attention 350 against 360 us per launch, sampler +0.9 %,
@@ -134,31 +157,39 @@ __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, co
             if (jb >= NKB) { jb -= NKB; bh += stride; }
             if (bh >= BH) { bh -= stride; jb = NKB - 1; }   // past the end: harmless re-fetch
 #pragma unroll
-            for (int p = 0; p < 12; ++p) issue_piece(bh, jb, gslot, p);
+            for (int p = 0; p < 2 * PK; ++p) issue_piece(bh, jb, gslot, p);
         }
     };
-    // counted waits of the issuing wave: everything but the 12-piece DMAs of the youngest one / two blocks has landed
+    // counted waits of the issuing wave: everything but the 2 PK-piece DMAs of the youngest one / two blocks has landed
+    // (12 / 24 for bf16x3; one plane: 4 pieces per block, so 4 / 8.  Whatever else the wave has in flight behind them -- the
+    // Q prefetch, the O stores -- only makes a wait stricter: "all but the N youngest" still covers every older piece)
     auto wait_but = [&](int blocks) {
-        if constexpr (NT == 1) {
+        if constexpr (NT == 1 && NP == 3) {
             if (blocks == 2) asm volatile("s_waitcnt vmcnt(24)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(12)" ::: "memory");
         }
-    };
-    auto load_k = [&](Split3 (&kf)[2], int gslot) {
-        const bf16x8* slot = ring + (gslot & (X3_SLOTS - 1)) * X3_SLOT_UNITS + lane;
-#pragma unroll
-        for (int s = 0; s < 2; ++s) {
-            kf[s].h = slot[(0 + s) * 64];
-            kf[s].m = slot[(2 + s) * 64];
-            kf[s].l = slot[(4 + s) * 64];
+        if constexpr (NT == 1 && NP == 1) {
+            if (blocks == 2) asm volatile("s_waitcnt vmcnt(8)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
         }
     };
+    // operand fragments of the two k-steps from PK pieces at `base` ([plane * 2 + s])
+    auto load_op = [&](SP (&f)[2], const bf16x8* base) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            f[s].h = base[(0 + s) * 64];
+            if constexpr (NP == 3) {
+                f[s].m = base[(2 + s) * 64];
+                f[s].l = base[(4 + s) * 64];
+            }
+        }
+    };
+    auto load_k = [&](SP (&kf)[2], int gslot) { load_op(kf, ring + (gslot & (X3_SLOTS - 1)) * SLOT_UNITS + lane); };
     int bh = blockIdx.x;
     int gb = 0;                                      // global block counter -> ring slot
     issue_block(bh, 0, 0);
     issue_block(bh, 1, 1);
     issue_block(bh, 2, 2);
 
-    Split3 qa[2], qb[2];
+    SP qa[2], qb[2];
     f32x4 qna[4], qnb[4];
     {
         const f32x4* qg = qall + (size_t)bh * NKB * 256;
@@ -172,7 +203,7 @@ __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, co
     }
     wait_but(2);                                     // block 0 landed
     __builtin_amdgcn_s_barrier();
-    Split3 kf[2];
+    SP kf[2];
     load_k(kf, 0);
 
 #pragma unroll 1
@@ -202,14 +233,8 @@ __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, co
                 __builtin_amdgcn_s_barrier();
                 issue_block(bh, jb + 3, gb + 3);
             }
-            const bf16x8* slot = ring + (gb & (X3_SLOTS - 1)) * X3_SLOT_UNITS + lane;
-            Split3 vf[2];
-#pragma unroll
-            for (int s = 0; s < 2; ++s) {
-                vf[s].h = slot[(6 + 0 + s) * 64];
-                vf[s].m = slot[(6 + 2 + s) * 64];
-                vf[s].l = slot[(6 + 4 + s) * 64];
-            }
+            SP vf[2];
+            load_op(vf, ring + (gb & (X3_SLOTS - 1)) * SLOT_UNITS + PK * 64 + lane);
             // ---- softmax + split of P^T (VALU)
             float psa = 0.f, psb = 0.f;
             bool redo = first;
@@ -225,9 +250,10 @@ __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, co
             }
             ta.l_lane += psa;
             tb.l_lane += psb;
-            const Split3 pa0 = split3_acc(sta, 0), pa1 = split3_acc(sta, 1);
-            Split3 pb0 = pa0, pb1 = pa1;
-            if (NT == 2) { pb0 = split3_acc(stb, 0); pb1 = split3_acc(stb, 1); }
+            // (one plane: P is rounded to bf16 here, for PV only -- the running sum above took the unrounded P)
+            const SP pa0 = splitp_acc<SP>(sta, 0), pa1 = splitp_acc<SP>(sta, 1);
+            SP pb0 = pa0, pb1 = pa1;
+            if (NT == 2) { pb0 = splitp_acc<SP>(stb, 0); pb1 = splitp_acc<SP>(stb, 1); }
             if (!STAG) {
                 wait_but(1);
                 __builtin_amdgcn_s_barrier();
@@ -276,12 +302,9 @@ __device__ __forceinline__ void attn_x3_body(bf16x8* ring, const f32x4* qall, co
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the trailing (unused) DMAs
 }
 
-// k3 / vT3: split planes (BH*15 tiles x 6 KiB each); q, o: fp32 fragment-major as in t2s_attn_fwd_packed
-__global__ __launch_bounds__(X3_THREADS, 2) T2S_X3_KERNEL void attn_fwd_x3_kernel(const float* __restrict__ q,
-                                                                    const __bf16* __restrict__ k3,
-                                                                    const __bf16* __restrict__ vT3,
-                                                                    float* __restrict__ o, int BH) {
-    extern __shared__ __attribute__((aligned(16))) bf16x8 ring3[];
+template <class SP>
+__device__ __forceinline__ void attn_fwd_xn(bf16x8* ring3, const float* __restrict__ q, const __bf16* __restrict__ k3,
+                                            const __bf16* __restrict__ vT3, float* __restrict__ o, int BH) {
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const f32x4* qg = reinterpret_cast<const f32x4*>(q);
@@ -289,18 +312,42 @@ __global__ __launch_bounds__(X3_THREADS, 2) T2S_X3_KERNEL void attn_fwd_x3_kerne
     const bf16x8* vg = reinterpret_cast<const bf16x8*>(vT3);
     f32x4* og = reinterpret_cast<f32x4*>(o);
     // (measured: without the stagger 324 us, with 313 us; s_setprio 1 for waves 4-7 on top: 320 us)
+#if defined(T2S_P1_NO_STAG)   // A/B build: the one-plane kernel without the half-period stagger (profiles/EXPERIMENTS.md)
+    constexpr int SG = planes_of<SP>::n == 1 ? 0 : 1;
+#else
     constexpr int SG = 1;
+#endif
     if (wave < 4)
-        attn_x3_body<2, 0>(ring3, qg, kg, vg, og, BH, lane, wave);
+        attn_x3_body<2, 0, SP>(ring3, qg, kg, vg, og, BH, lane, wave);
     else if (wave < 7)
-        attn_x3_body<2, SG>(ring3, qg, kg, vg, og, BH, lane, wave);
+        attn_x3_body<2, SG, SP>(ring3, qg, kg, vg, og, BH, lane, wave);
     else
-        attn_x3_body<1, SG>(ring3, qg, kg, vg, og, BH, lane, wave);   // tile 14 only (15 is void)
+        attn_x3_body<1, SG, SP>(ring3, qg, kg, vg, og, BH, lane, wave);   // tile 14 only (15 is void)
+}
+
+// k3 / vT3: split planes (BH*15 tiles x 6 KiB each); q, o: fp32 fragment-major as in t2s_attn_fwd_packed
+__global__ __launch_bounds__(X3_THREADS, 2) T2S_X3_KERNEL void attn_fwd_x3_kernel(const float* __restrict__ q,
+                                                                    const __bf16* __restrict__ k3,
+                                                                    const __bf16* __restrict__ vT3,
+                                                                    float* __restrict__ o, int BH) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 ring3[];
+    attn_fwd_xn<Split3>(ring3, q, k3, vT3, o, BH);
+}
+
+// the one-plane form (T2S_MATH_BF16): k1 / vT1 one bf16 plane (BH*15 tiles x 2 KiB each), 2 + 2 MFMAs per key block and
+// query tile; a separate instantiation of the same body, not a run-time branch inside it
+__global__ __launch_bounds__(X3_THREADS, 2) T2S_P1_KERNEL void attn_fwd_bf16p_kernel(const float* __restrict__ q,
+                                                                       const __bf16* __restrict__ k1,
+                                                                       const __bf16* __restrict__ vT1,
+                                                                       float* __restrict__ o, int BH) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 ring1[];
+    attn_fwd_xn<Split1>(ring1, q, k1, vT1, o, BH);
 }
 
 // plain (BH,480,32) fp32 k or v -> split planes: k as the A operand with the key on the lane
 // (transpose = 0), v as V^T with the feature on the lane (transpose = 1)
-__global__ void pack_x3_kernel(const float* __restrict__ src, bf16x8* __restrict__ dst, int BH, int transpose) {
+template <int NP>
+__global__ void pack_xn_kernel(const float* __restrict__ src, bf16x8* __restrict__ dst, int BH, int transpose) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one (bh, tile, s, lane)
     if (idx >= BH * NKB * 2 * 64) return;
     const int lane = idx & 63, s = (idx >> 6) & 1, tile = (idx >> 7) % NKB, bh = idx / (NKB * 128);
@@ -312,11 +359,13 @@ __global__ void pack_x3_kernel(const float* __restrict__ src, bf16x8* __restrict
         v[j] = transpose ? src[((size_t)bh * NTOK + tile * 32 + kk) * DH + i]     // V^T[d = i][key = kk]
                          : src[((size_t)bh * NTOK + tile * 32 + i) * DH + kk];    // K[key = i][d = kk]
     }
-    const Split3 sp = split3(v);
-    bf16x8* d = dst + ((size_t)(bh * NKB + tile) * 6 + s) * 64 + lane;
+    const Split3 sp = split3(v);   // (the one-plane form keeps h = rn_bf16(v))
+    bf16x8* d = dst + ((size_t)(bh * NKB + tile) * 2 * NP + s) * 64 + lane;
     d[0] = sp.h;
-    d[2 * 64] = sp.m;
-    d[4 * 64] = sp.l;
+    if constexpr (NP == 3) {
+        d[2 * 64] = sp.m;
+        d[4 * 64] = sp.l;
+    }
 }
 }  // namespace
 
@@ -330,7 +379,17 @@ int attn_x3_init() {   // once, outside any stream capture
     return T2S_OK;
 }
 
-int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o, int BH, hipStream_t st) {
+int attn_bf16p_init() {   // (16 KiB of LDS needs no opt-in; kept for symmetry and for a ring that grows)
+    static bool done = false;
+    if (!done) {
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_bf16p_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, P1_LDS_BYTES));
+        done = true;
+    }
+    return T2S_OK;
+}
+
+static int attn_xn_grid(int BH) {
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;
@@ -347,15 +406,31 @@ int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o
         if (wg_per_cu < 1 || wg_per_cu > 2) wg_per_cu = 1;
     }
     const int slots = n_cu * wg_per_cu;
-    const int grid = BH < slots ? BH : slots;
-    attn_fwd_x3_kernel<<<grid, X3_THREADS, X3_LDS_BYTES, st>>>(q, k3, vT3, o, BH);
+    return BH < slots ? BH : slots;
+}
+
+int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o, int BH, hipStream_t st) {
+    attn_fwd_x3_kernel<<<attn_xn_grid(BH), X3_THREADS, X3_LDS_BYTES, st>>>(q, k3, vT3, o, BH);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+int launch_attn_bf16p(const float* q, const __bf16* k1, const __bf16* vT1, float* o, int BH, hipStream_t st) {
+    attn_fwd_bf16p_kernel<<<attn_xn_grid(BH), X3_THREADS, P1_LDS_BYTES, st>>>(q, k1, vT1, o, BH);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
 int pack_x3(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
     const int n = BH * NKB * 2 * 64;
-    pack_x3_kernel<<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
+    pack_xn_kernel<3><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+int pack_bf16p(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
+    const int n = BH * NKB * 2 * 64;
+    pack_xn_kernel<1><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -383,24 +458,28 @@ __global__ void o_from_frag_kernel(const f32x4* __restrict__ of, float* __restri
 }
 }  // namespace
 
-extern "C" int t2s_attn_fwd_x3(const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
-    T2S_REQUIRE(q && k && v && o && BH > 0 && BH % NH == 0, "t2s_attn_fwd_x3: bad argument (BH=%d must be a multiple of 4)", BH);
+// NP = 3: bf16x3, NP = 1: the one-plane form
+template <int NP>
+static int attn_fwd_plain(const char* who, const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
+    T2S_REQUIRE(q && k && v && o && BH > 0 && BH % NH == 0, "%s: bad argument (BH=%d must be a multiple of 4)", who, BH);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = attn_x3_init()) return rc;
+    if (int rc = NP == 3 ? attn_x3_init() : attn_bf16p_init()) return rc;
     const size_t n = (size_t)BH * NTOK * DH;
     float* f32buf = nullptr;
     __bf16* planes = nullptr;
     T2S_HIP_CHECK(hipMalloc(&f32buf, 2 * n * sizeof(float)));
-    if (hipMalloc(&planes, 2 * 3 * n * sizeof(__bf16)) != hipSuccess) {
+    if (hipMalloc(&planes, 2 * NP * n * sizeof(__bf16)) != hipSuccess) {
         (void)hipFree(f32buf);
-        set_error("t2s_attn_fwd_x3: hipMalloc failed");
+        set_error("%s: hipMalloc failed", who);
         return T2S_E_HIP;
     }
     const int nf = BH * 15 * 4 * 64;
     q_to_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(q, reinterpret_cast<f32x4*>(f32buf), BH);
-    int rc = pack_x3(k, planes, BH, 0, st);
-    if (rc == T2S_OK) rc = pack_x3(v, planes + 3 * n, BH, 1, st);
-    if (rc == T2S_OK) rc = launch_attn_x3(f32buf, planes, planes + 3 * n, f32buf + n, BH, st);
+    int rc = NP == 3 ? pack_x3(k, planes, BH, 0, st) : pack_bf16p(k, planes, BH, 0, st);
+    if (rc == T2S_OK) rc = NP == 3 ? pack_x3(v, planes + NP * n, BH, 1, st) : pack_bf16p(v, planes + NP * n, BH, 1, st);
+    if (rc == T2S_OK)
+        rc = NP == 3 ? launch_attn_x3(f32buf, planes, planes + NP * n, f32buf + n, BH, st)
+                     : launch_attn_bf16p(f32buf, planes, planes + NP * n, f32buf + n, BH, st);
     if (rc == T2S_OK) {
         o_from_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(reinterpret_cast<const f32x4*>(f32buf + n), o, BH);
         if (hipGetLastError() != hipSuccess) rc = T2S_E_HIP;
@@ -411,3 +490,10 @@ extern "C" int t2s_attn_fwd_x3(const float* q, const float* k, const float* v, f
     return rc;
 }
 
+extern "C" int t2s_attn_fwd_x3(const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
+    return attn_fwd_plain<3>("t2s_attn_fwd_x3", q, k, v, o, BH, stream);
+}
+
+extern "C" int t2s_attn_fwd_bf16p(const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
+    return attn_fwd_plain<1>("t2s_attn_fwd_bf16p", q, k, v, o, BH, stream);
+}

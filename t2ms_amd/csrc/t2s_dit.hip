@@ -7,6 +7,7 @@
 // Between kernels the residual stream, the attention output and q/k/v stay in the
 // fragment-major layout (t2s_common.h: frag_index).
 #include <stdlib.h>
+#include <mutex>
 #include <vector>
 
 #include "t2s_gemm.h"
@@ -28,6 +29,11 @@ int launch_attn_packed(const float* q, const float* k, const float* vT, float* o
 int attn_init();
 int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o, int BH, hipStream_t st);
 int attn_x3_init();
+int launch_attn_bf16p(const float* q, const __bf16* k1, const __bf16* vT1, float* o, int BH, hipStream_t st);
+int attn_bf16p_init();
+// the library's non-blocking set-up stream and per-device run lock (t2s_sampler.hip: t2s_sampler_create)
+hipStream_t lib_setup_stream(int dev);
+std::recursive_mutex* lib_pool_lock(int dev);
 void train_free(t2s_dit* h);
 
 // ------------------------------------------------------------------ small kernels
@@ -222,6 +228,19 @@ int pack_x3_weights(t2s_dit* h, hipStream_t st) {
     return T2S_OK;
 }
 
+// the h plane alone (T2S_MATH_BF16), same chunk order
+int pack_bf16p_weights(t2s_dit* h, hipStream_t st) {
+    int rc;
+    for (int i = 0; i < NBLK; ++i) {
+        if ((rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->qkv_p[i]), reinterpret_cast<bf16x8*>(h->qkv1[i]), 3 * D, D, 0, st)) ||
+            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->proj_p[i]), reinterpret_cast<bf16x8*>(h->proj1[i]), D, D, 0, st)) ||
+            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->fc1_p[i]), reinterpret_cast<bf16x8*>(h->fc11[i]), 2 * D, D, 0, st)) ||
+            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->fc2_c[i]), reinterpret_cast<bf16x8*>(h->fc2c1[i]), D, 2 * D, 1, st)))
+            return rc;
+    }
+    return T2S_OK;
+}
+
 // Floats the kernels read behind every pointer of t2s_dit_weights, in declaration order (10 top-level, then 10 per block)
 struct WeightNeed {
     const char* name;
@@ -309,7 +328,10 @@ int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
     T2S_LAUNCH_CHECK();
     pack_weight_multi_kernel<<<dim3((max_pack + 255) / 256, np), 256, 0, st>>>(pt);
     T2S_LAUNCH_CHECK();
-    if (h->w3 != nullptr) return pack_x3_weights(h, st);
+    if (h->w3 != nullptr)
+        if (int rc = pack_x3_weights(h, st)) return rc;
+    if (h->w1 != nullptr)
+        if (int rc = pack_bf16p_weights(h, st)) return rc;
     return T2S_OK;
 }
 
@@ -333,9 +355,11 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     float* const w_ao = h->ao + tok0;
     float* const w_h0 = h->h0 + tok0 / 2;                      // one slot per PAIR of sequences (CFG pass)
     float* const w_mod = h->mod + (size_t)ws_seq0 * MODROW;
-    __bf16* const w_k3 = h->k3 ? h->k3 + tok0 * 3 : nullptr;
-    __bf16* const w_v3 = h->v3 ? h->v3 + tok0 * 3 : nullptr;
+    __bf16* w_k3 = h->k3 ? h->k3 + tok0 * 3 : nullptr;
+    __bf16* w_v3 = h->v3 ? h->v3 + tok0 * 3 : nullptr;
+    const bool p1 = h->math == T2S_MATH_BF16;   // one bf16 plane (k1 / v1 / w1), the bf16x3 kernels' one-plane instances
     const bool x3 = h->math == T2S_MATH_BF16X3;
+    if (p1) { w_k3 = h->k1 + tok0; w_v3 = h->v1 + tok0; }
     const bool use_table = mt.base != nullptr && step_ptr != nullptr;
     if (!use_table) {   // adaLN for all 4 blocks at once: mod = silu(c) @ W_ada^T + b, c = t_emb (+ text)
         TimeScope ts(h, TC_OTHER, st);
@@ -401,11 +425,12 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
             a.out0 = out0; a.out1 = out1; a.split = split; a.keep_x = keep_stream;
         }
         if (blk >= 0) {
-            a.Wp = reinterpret_cast<const bf16x8*>(h->proj3[blk]); a.W1 = reinterpret_cast<const bf16x8*>(h->fc13[blk]);
-            a.W2c = reinterpret_cast<const bf16x8*>(h->fc2c3[blk]);
+            a.Wp = reinterpret_cast<const bf16x8*>(p1 ? h->proj1[blk] : h->proj3[blk]);
+            a.W1 = reinterpret_cast<const bf16x8*>(p1 ? h->fc11[blk] : h->fc13[blk]);
+            a.W2c = reinterpret_cast<const bf16x8*>(p1 ? h->fc2c1[blk] : h->fc2c3[blk]);
             a.bp = h->proj_b[blk]; a.b1 = h->fc1_b[blk]; a.b2 = h->fc2_b[blk];
         }
-        if (qkv_blk >= 0) { a.Wq = reinterpret_cast<const bf16x8*>(h->qkv3[qkv_blk]); a.bq = h->qkv_b[qkv_blk]; }
+        if (qkv_blk >= 0) { a.Wq = reinterpret_cast<const bf16x8*>(p1 ? h->qkv1[qkv_blk] : h->qkv3[qkv_blk]); a.bq = h->qkv_b[qkv_blk]; }
         a.q = w_q; a.k3 = w_k3; a.v3 = w_v3;
         return a;
     };
@@ -415,7 +440,7 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     // (profiles/r03_rows16_ab.txt; measured with the last block's kernel still on 32-token tiles).
     // T2S_ROWS16_MAX_SEQS moves the switch point (A/B runs; 0 = never).
     static const int rows16_max = getenv("T2S_ROWS16_MAX_SEQS") ? atoi(getenv("T2S_ROWS16_MAX_SEQS")) : 100;
-    const bool use16 = !x3 && S <= rows16_max;
+    const bool use16 = !x3 && !p1 && S <= rows16_max;
     auto rows_args16 = [&](int blk, int qkv_blk) {
         RowArgs a = rows_args(blk, qkv_blk);
         if (blk >= 0) { a.Wp = h->proj_p16[blk]; a.W1 = h->fc1_p16[blk]; a.W2c = h->fc2_c16[blk]; }
@@ -424,23 +449,27 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     };
     {
         TimeScope ts(h, TC_ROWS_FIRST, st);
-        rc = x3 ? launch_dit_rows_x3<false, true>(rows_args_x3(-1, 0), st)
+        rc = p1 ? launch_dit_rows_bf16p<false, true>(rows_args_x3(-1, 0), st)
+           : x3 ? launch_dit_rows_x3<false, true>(rows_args_x3(-1, 0), st)
                 : (use16 ? launch_dit_rows16<false, true>(rows_args16(-1, 0), st) : launch_dit_rows<false, true>(rows_args(-1, 0), st));
         if (rc != T2S_OK) return rc;
     }
     for (int i = 0; i < NBLK; ++i) {
         {
             TimeScope ts(h, TC_ATTN, st);
-            rc = x3 ? launch_attn_x3(w_q, w_k3, w_v3, w_ao, S * NH, st)
+            rc = p1 ? launch_attn_bf16p(w_q, w_k3, w_v3, w_ao, S * NH, st)
+               : x3 ? launch_attn_x3(w_q, w_k3, w_v3, w_ao, S * NH, st)
                     : launch_attn_packed(w_q, w_k, w_v, w_ao, S * NH, st);
             if (rc != T2S_OK) return rc;
         }
         TimeScope ts(h, i + 1 < NBLK ? TC_ROWS : TC_ROWS_LAST, st);
         if (i + 1 < NBLK)
-            rc = x3 ? launch_dit_rows_x3<true, true>(rows_args_x3(i, i + 1), st)
+            rc = p1 ? launch_dit_rows_bf16p<true, true>(rows_args_x3(i, i + 1), st)
+               : x3 ? launch_dit_rows_x3<true, true>(rows_args_x3(i, i + 1), st)
                     : (use16 ? launch_dit_rows16<true, true>(rows_args16(i, i + 1), st) : launch_dit_rows<true, true>(rows_args(i, i + 1), st));
         else
-            rc = x3 ? launch_dit_rows_x3<true, false>(rows_args_x3(i, -1), st)
+            rc = p1 ? launch_dit_rows_bf16p<true, false>(rows_args_x3(i, -1), st)
+               : x3 ? launch_dit_rows_x3<true, false>(rows_args_x3(i, -1), st)
                     : (use16 ? launch_dit_rows16<true, false>(rows_args16(i, -1), st) : launch_dit_rows<true, false>(rows_args(i, -1), st));
         if (rc != T2S_OK) return rc;
     }
@@ -568,12 +597,65 @@ int t2s_dit_update_weights(t2s_dit* h, const t2s_dit_weights* w, void* stream) {
     T2S_REQUIRE(h && w, "t2s_dit_update_weights: NULL argument");
     const int rc_w = check_weights(w, nullptr, /*ranges=*/true);
     if (rc_w != T2S_OK) return rc_w;
-    return upload_weights(h, w, (hipStream_t)stream);
+    const int rc = upload_weights(h, w, (hipStream_t)stream);
+    // a later t2s_dit_set_math(T2S_MATH_BF16) packs from these copies on the set-up stream: leave it something to wait for
+    if (rc == T2S_OK && (h->w_ev != nullptr || hipEventCreateWithFlags(&h->w_ev, hipEventDisableTiming) == hipSuccess))
+        T2S_HIP_CHECK(hipEventRecord(h->w_ev, (hipStream_t)stream));
+    return rc;
 }
+
+namespace {
+// T2S_MATH_BF16, first use: one-plane K / V^T workspace and weight pieces.  Packed on the library's non-blocking set-up
+// stream under the per-device run lock, as t2s_sampler_create does its uploads -- never on the legacy stream, which HIP
+// refuses (and whose use invalidates the capture) while any thread has a capture open on a blocking stream.
+int alloc_bf16p(t2s_dit* h) {
+    int rc, dev = 0;
+    T2S_HIP_CHECK(hipGetDevice(&dev));
+    std::recursive_mutex* mu = lib_pool_lock(dev);
+    T2S_REQUIRE(mu, "t2s_dit_set_math: device %d", dev);
+    std::lock_guard<std::recursive_mutex> lock(*mu);
+    hipStream_t setup = lib_setup_stream(dev);
+    T2S_REQUIRE(setup, "t2s_dit_set_math: no set-up stream on device %d", dev);
+    if ((rc = attn_bf16p_init()) || (rc = dit_rows_bf16p_init<false, true>()) || (rc = dit_rows_bf16p_init<true, true>()) ||
+        (rc = dit_rows_bf16p_init<true, false>()))
+        return rc;
+    const size_t bytes = (size_t)h->max_seqs * NTOK * D * sizeof(__bf16);      // one bf16 plane
+    const size_t wvals = (size_t)NBLK * (3 + 1 + 2 + 2) * D * D;                // qkv, proj, fc1, fc2: the h plane
+    __bf16 *k1 = nullptr, *v1 = nullptr, *w1 = nullptr;
+    if (hipMalloc(&k1, bytes) != hipSuccess || hipMalloc(&v1, bytes) != hipSuccess || hipMalloc(&w1, wvals * sizeof(__bf16)) != hipSuccess) {
+        if (k1) (void)hipFree(k1);
+        if (v1) (void)hipFree(v1);
+        (void)hipGetLastError();
+        set_error("t2s_dit_set_math: hipMalloc(2 x %zu B + weights) failed", bytes);
+        return T2S_E_HIP;
+    }
+    __bf16* p = w1;
+    for (int i = 0; i < NBLK; ++i) {
+        h->qkv1[i] = p; p += (size_t)3 * D * D;
+        h->proj1[i] = p; p += (size_t)D * D;
+        h->fc11[i] = p; p += (size_t)2 * D * D;
+        h->fc2c1[i] = p; p += (size_t)2 * D * D;
+    }
+    h->w1 = w1;
+    hipError_t e = h->w_ev ? hipStreamWaitEvent(setup, h->w_ev, 0) : hipSuccess;   // the last t2s_dit_update_weights
+    rc = e == hipSuccess ? pack_bf16p_weights(h, setup) : T2S_E_HIP;
+    if (rc == T2S_OK && hipStreamSynchronize(setup) != hipSuccess) rc = T2S_E_HIP;
+    if (rc != T2S_OK) {
+        (void)hipFree(k1); (void)hipFree(v1); (void)hipFree(w1);
+        h->w1 = nullptr;
+        if (e != hipSuccess || rc == T2S_E_HIP) set_error("t2s_dit_set_math: packing the bf16 weights failed");
+        return rc;
+    }
+    h->k1 = k1; h->v1 = v1;
+    return T2S_OK;
+}
+}  // namespace
 
 int t2s_dit_set_math(t2s_dit* h, int math) {
     T2S_REQUIRE(h, "t2s_dit_set_math: NULL handle");
-    T2S_REQUIRE(math == T2S_MATH_F32 || math == T2S_MATH_BF16X3, "t2s_dit_set_math: unknown mode %d", math);
+    T2S_REQUIRE(math == T2S_MATH_F32 || math == T2S_MATH_BF16X3 || math == T2S_MATH_BF16, "t2s_dit_set_math: unknown mode %d", math);
+    if (math == T2S_MATH_BF16 && h->k1 == nullptr)
+        if (int rc = alloc_bf16p(h)) return rc;
     if (math == T2S_MATH_BF16X3 && h->k3 == nullptr) {
         int rc;
         if ((rc = attn_x3_init()) || (rc = dit_rows_x3_init<false, true>()) || (rc = dit_rows_x3_init<true, true>()) ||
@@ -609,6 +691,10 @@ void t2s_dit_destroy(t2s_dit* h) {
     if (h->k3) (void)hipFree(h->k3);
     if (h->v3) (void)hipFree(h->v3);
     if (h->w3) (void)hipFree(h->w3);
+    if (h->k1) (void)hipFree(h->k1);
+    if (h->v1) (void)hipFree(h->v1);
+    if (h->w1) (void)hipFree(h->w1);
+    if (h->w_ev) (void)hipEventDestroy(h->w_ev);
     float* bufs[] = {h->arena, h->h, h->q, h->k, h->v, h->ao, h->mod, h->h0};
     for (float* b : bufs)
         if (b) (void)hipFree(b);

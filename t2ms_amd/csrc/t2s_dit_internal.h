@@ -24,6 +24,12 @@ struct t2s_dit {
     __bf16 *k3 = nullptr, *v3 = nullptr;
     __bf16* w3 = nullptr;        // split (3 x bf16) weights of the row chain in chunk order (t2s_rows_x3.h)
     __bf16 *qkv3[t2s::NBLK], *proj3[t2s::NBLK], *fc13[t2s::NBLK], *fc2c3[t2s::NBLK];
+    // T2S_MATH_BF16: the same as ONE bf16 plane each (the h plane of the split), allocated on first use; a workspace of its
+    // own, so that switching between the arithmetics never reads another mode's planes
+    __bf16 *k1 = nullptr, *v1 = nullptr;
+    __bf16* w1 = nullptr;
+    __bf16 *qkv1[t2s::NBLK], *proj1[t2s::NBLK], *fc11[t2s::NBLK], *fc2c1[t2s::NBLK];
+    hipEvent_t w_ev = nullptr;   // recorded behind the last t2s_dit_update_weights (what a first-use pack must wait for)
     // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     t2s_train_ws* train = nullptr;
     int train_dtype = 0;         // T2S_TRAIN_F32 / T2S_TRAIN_BF16 (t2s_dit_set_train_dtype)

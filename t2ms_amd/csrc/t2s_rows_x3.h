@@ -15,7 +15,13 @@
 //     lane (n & 31, h) holds W[n][32 (ks>>1) + 16 (ks&1) + 8 (j>>2) + 4 h + (j&3)], j = 0..7;
 //   fc2 chunk c (the 32 hidden units of fc1 chunk c):  piece (nt, s, p), lane holds
 //     W2[32 nt + (n & 31)][32 c + 16 s + 8 (j>>2) + 4 h + (j&3)].
+//
+// One-plane form ("bf16" arithmetic, T2S_MATH_BF16; dit_rows_bf16p_kernel below): the same body instantiated on Split1
+// (t2s_x3.h).  Weight pieces carry the h plane only -- 8 KiB per chunk = 8 pieces, two per wave -- activation fragments
+// are rounded once, and k / V^T leave as one bf16 plane per tile (2 KiB); 8 MFMAs per chunk instead of 48.
 #pragma once
+#include <type_traits>
+
 #include "t2s_rows.h"
 #include "t2s_x3.h"
 
@@ -56,12 +62,15 @@ __device__ __forceinline__ unsigned long long x3_clk() {
 // last on purpose: it is first needed after the proj chunks).  Not wg_sync(): its release fence waits for vmcnt(0).
 #define X3_SYNC_BUT16() { asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
 #endif
-constexpr int X3_CHUNK_UNITS = 24 * 64;                    // 16-byte units per chunk (24 KiB)
+template <int NP> constexpr int XN_CHUNK_UNITS = 8 * NP * 64;   // 16-byte units per chunk: 8 k-steps x NP planes
+constexpr int X3_CHUNK_UNITS = XN_CHUNK_UNITS<3>;          // 24 KiB
+template <int NP> constexpr int ROWS_XN_LDS_BYTES = 2 * XN_CHUNK_UNITS<NP> * 16 + (ROWS_CB_FLOATS + 4 * ROWS_CM_FLOATS) * 4;
 #ifdef T2S_X3_LONE   // diagnosis (tools/x3_variant.sh x3_lone -DT2S_X3_LONE): pad the allocation so ONE workgroup fits a CU = one wave per SIMD
 constexpr int ROWS_X3_LDS_BYTES = 100 * 1024;
 #else
-constexpr int ROWS_X3_LDS_BYTES = 2 * X3_CHUNK_UNITS * 16 + (ROWS_CB_FLOATS + 4 * ROWS_CM_FLOATS) * 4;
+constexpr int ROWS_X3_LDS_BYTES = ROWS_XN_LDS_BYTES<3>;
 #endif
+constexpr int ROWS_P1_LDS_BYTES = ROWS_XN_LDS_BYTES<1>;
 
 struct RowArgsX3 {
     float* x;          // (M,128) residual stream, fragment-major, in place
@@ -87,7 +96,7 @@ struct RowArgsX3 {
     const bf16x8 *Wp, *W1, *W2c, *Wq;   // split weights in chunk order (see above)
     const float *bp, *b1, *b2, *bq;
     float* q;          // q fragment-major fp32 (the attention scales and splits it once per head)
-    __bf16 *k3, *v3;   // k, V^T split planes (t2s_x3.h)
+    __bf16 *k3, *v3;   // k, V^T split planes (t2s_x3.h); ONE plane each for the one-plane kernels
 #ifdef T2S_X3_STAMP
     unsigned long long* stamp;   // [workgroup < 256][wave][8]: 7 category sums + total
 #endif
@@ -95,7 +104,8 @@ struct RowArgsX3 {
 
 // fp32 packed weights (packed_index order, or the fc2 chunk order of pack_weight_kernel mode 1) ->
 // split planes in the chunk order above.  One thread per (chunk, piece-without-plane, lane).
-static __global__ void pack_rows_x3_kernel(const float* __restrict__ P, bf16x8* __restrict__ dst, int N, int K, int fc2) {
+template <int NP>
+static __global__ void pack_rows_xn_kernel(const float* __restrict__ P, bf16x8* __restrict__ dst, int N, int K, int fc2) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
     const int n_chunks = fc2 ? K / 32 : N / 32;
     if (idx >= n_chunks * 8 * 64) return;
@@ -117,26 +127,40 @@ static __global__ void pack_rows_x3_kernel(const float* __restrict__ P, bf16x8* 
             v[j] = P[((((size_t)(c * (N >> 5) + (n >> 5)) * 4 + g) * 64) + (hh * 32 + (n & 31))) * 4 + e];
         }
     }
-    const Split3 sp = split3(v);
-    bf16x8* d = dst + ((size_t)(chunk * 8 + piece) * 3) * 64 + lane;
+    const Split3 sp = split3(v);   // (NP == 1 keeps h = rn_bf16(v) only)
+    bf16x8* d = dst + ((size_t)(chunk * 8 + piece) * NP) * 64 + lane;
     d[0] = sp.h;
-    d[64] = sp.m;
-    d[128] = sp.l;
+    if constexpr (NP == 3) {
+        d[64] = sp.m;
+        d[128] = sp.l;
+    }
 }
 
 inline int pack_rows_x3(const float* P, bf16x8* dst, int N, int K, int fc2, hipStream_t st) {
     const int n = (fc2 ? K / 32 : N / 32) * 8 * 64;
-    pack_rows_x3_kernel<<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
+    pack_rows_xn_kernel<3><<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
-// the three planes of weight piece `pc` of the chunk in ring slot `wb` (wb already offset by lane)
-__device__ __forceinline__ Split3 ldw3(const bf16x8* wb, int pc) {
-    Split3 w;
-    w.h = wb[(pc * 3 + 0) * 64];
-    w.m = wb[(pc * 3 + 1) * 64];
-    w.l = wb[(pc * 3 + 2) * 64];
+// the h plane alone, in the same chunk order (a third of the bytes)
+inline int pack_rows_bf16p(const float* P, bf16x8* dst, int N, int K, int fc2, hipStream_t st) {
+    const int n = (fc2 ? K / 32 : N / 32) * 8 * 64;
+    pack_rows_xn_kernel<1><<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+// the planes of weight piece `pc` of the chunk in ring slot `wb` (wb already offset by lane)
+template <class SP>
+__device__ __forceinline__ SP ldwp(const bf16x8* wb, int pc) {
+    constexpr int NP = planes_of<SP>::n;
+    SP w;
+    w.h = wb[(pc * NP + 0) * 64];
+    if constexpr (NP == 3) {
+        w.m = wb[(pc * 3 + 1) * 64];
+        w.l = wb[(pc * 3 + 2) * 64];
+    }
     return w;
 }
 
@@ -144,13 +168,13 @@ __device__ __forceinline__ Split3 ldw3(const bf16x8* wb, int pc) {
 // (sched_barrier pins that order; the waitcnt pass then emits counted lgkmcnt waits instead of `3 ds_read, lgkmcnt(0), 6 MFMA`
 // per k-step): rows -1.5 %, sampler +1.1 % in a same-box A/B (profiles/r05_x3_pingpong_ab.txt).  `hook(ks)` runs between the
 // k-steps (the LDS-DMA piece of the next chunk).
-template <bool SWAP, typename BOP, typename HOOK>
+template <bool SWAP, class SP, typename BOP, typename HOOK>
 __device__ __forceinline__ void ktile_x3(const bf16x8* wb, BOP&& bop, f32x16& acc, HOOK&& hook) {
-    Split3 w = ldw3(wb, 0);
+    SP w = ldwp<SP>(wb, 0);
 #pragma unroll
     for (int ks = 0; ks < 8; ++ks) {
-        Split3 wn = w;
-        if (ks + 1 < 8) wn = ldw3(wb, ks + 1);
+        SP wn = w;
+        if (ks + 1 < 8) wn = ldwp<SP>(wb, ks + 1);
         __builtin_amdgcn_sched_barrier(0);
         acc = SWAP ? mfma_x3(bop(ks), w, acc) : mfma_x3(w, bop(ks), acc);
         hook(ks);
@@ -159,9 +183,12 @@ __device__ __forceinline__ void ktile_x3(const bf16x8* wb, BOP&& bop, f32x16& ac
     }
 }
 
-template <bool DO_MLP, bool DO_QKV>
-__global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const RowArgsX3 a) {
-    extern __shared__ __attribute__((aligned(16))) bf16x8 wring3[];  // [2][X3_CHUNK_UNITS]
+// SP = Split3 (bf16x3) or Split1 (one plane); wring3 = the kernel's dynamic LDS, [2][CHUNK_UNITS] + constants
+template <bool DO_MLP, bool DO_QKV, class SP>
+__device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wring3) {
+    constexpr int NP = planes_of<SP>::n;
+    constexpr int CHUNK_UNITS = XN_CHUNK_UNITS<NP>;
+    constexpr int WAVE_PIECES = 2 * NP;           // LDS-DMA pieces per wave and chunk: 8 NP pieces over four waves
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
     const int half = lane >> 5;
@@ -177,21 +204,21 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
     constexpr int N_CHUNKS = (DO_MLP ? 20 : 0) + (DO_QKV ? 12 : 0);
     auto chunk_src = [&](int ci) T2S_X3_KERNEL -> const bf16x8* {
         if constexpr (DO_MLP) {
-            if (ci < 4) return a.Wp + (size_t)ci * X3_CHUNK_UNITS;
+            if (ci < 4) return a.Wp + (size_t)ci * CHUNK_UNITS;
             if (ci < 20) {
                 const int j = ci - 4;
-                return ((j & 1) ? a.W2c : a.W1) + (size_t)(j >> 1) * X3_CHUNK_UNITS;
+                return ((j & 1) ? a.W2c : a.W1) + (size_t)(j >> 1) * CHUNK_UNITS;
             }
             ci -= 20;
         }
-        return a.Wq + (size_t)ci * X3_CHUNK_UNITS;
+        return a.Wq + (size_t)ci * CHUNK_UNITS;
     };
-    // each wave DMAs pieces {wave, wave+4, ..., wave+20} of the chunk
+    // each wave DMAs pieces {wave, wave+4, ..., wave+20} of the chunk (one plane: {wave, wave+4})
     auto fill = [&](int ci) T2S_X3_KERNEL {
         const bf16x8* src = chunk_src(ci) + lane;
-        bf16x8* dst = wring3 + (ci & 1) * X3_CHUNK_UNITS;
+        bf16x8* dst = wring3 + (ci & 1) * CHUNK_UNITS;
 #pragma unroll
-        for (int p = 0; p < 6; ++p)      // untracked (glds16_asm), like the pieces below: with a TRACKED LDS-DMA pending hipcc turns
+        for (int p = 0; p < WAVE_PIECES; ++p)      // untracked (glds16_asm), like the pieces below: with a TRACKED LDS-DMA pending hipcc turns
             glds16_asm(reinterpret_cast<const f32x4*>(src + (wave + 4 * p) * 64),      // every wait of the prologue into vmcnt(0) --
                        reinterpret_cast<f32x4*>(dst + (wave + 4 * p) * 64));           // one full round trip per constant load
     };
@@ -205,10 +232,10 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
     // explicit vmcnt wait in front of its barrier.
     auto fill_piece = [&](int ci, int p) T2S_X3_KERNEL {
         const bf16x8* src = chunk_src(ci) + lane + (wave + 4 * p) * 64;
-        bf16x8* dst = wring3 + (ci & 1) * X3_CHUNK_UNITS + (wave + 4 * p) * 64;
+        bf16x8* dst = wring3 + (ci & 1) * CHUNK_UNITS + (wave + 4 * p) * 64;
         glds16_asm(reinterpret_cast<const f32x4*>(src), reinterpret_cast<f32x4*>(dst));
     };
-#define X3_FILL_MIX(ci, step) if ((step) >= 1 && (step) <= 6) fill_piece(ci, (step) - 1);
+#define X3_FILL_MIX(ci, step) if ((step) >= 1 && (step) <= WAVE_PIECES) fill_piece(ci, (step) - 1);
 #define X3_DMA_LANDED() asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     fill(0);
     // The attention output of the tile is requested FIRST, in front of the constants below (whose loads the compiler waits for
@@ -229,7 +256,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
     }
 
     // ---- per-feature constants in LDS (visible after the first barrier), as in t2s_rows.h ----
-    float* cb = reinterpret_cast<float*>(wring3 + 2 * X3_CHUNK_UNITS);
+    float* cb = reinterpret_cast<float*>(wring3 + 2 * CHUNK_UNITS);
     float* cm = cb + ROWS_CB_FLOATS + wave * ROWS_CM_FLOATS;
     {   // every load first, then every ds_write: written as load -> store pairs each pair cost its own L2 round trip
         const int t0 = threadIdx.x, t1 = t0 + 256;
@@ -325,7 +352,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
         const float* mb = cm;   // [shift_msa, scale_msa, gate_msa, shift_mlp, scale_mlp, gate_mlp] of a.blk
         // ---------------- x += gate_msa * (proj(ao) + b): ao planes resident ----------------
         {
-            Split3 aop[8];      // k-step ks = features 16 ks .. 16 ks + 15 in the permuted order
+            SP aop[8];      // k-step ks = features 16 ks .. 16 ks + 15 in the permuted order
             // Order of the prologue's vector-memory operations: chunk 0's DMA, the attention output (top of the kernel), the
             // constants, and LAST the 16 loads of the residual stream -- it is first needed after the four proj chunks, so the
             // first barrier does not wait for it (X3_SYNC_BUT16) and the split of ao runs while it is in flight.  A timing-only
@@ -337,7 +364,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
             for (int ks = 0; ks < 8; ++ks) {
                 const f32x4 lo = araw[2 * ks], hi = araw[2 * ks + 1];
                 const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
-                aop[ks] = split3(v);
+                aop[ks] = splitp<SP>(v);
             }
             X3_STAMP(0)
 #ifdef T2S_X3_NOPROLOGUE
@@ -348,11 +375,11 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
                 X3_STAMP(5)
-                const bf16x8* wb = wring3 + (ci & 1) * X3_CHUNK_UNITS + lane;
+                const bf16x8* wb = wring3 + (ci & 1) * CHUNK_UNITS + lane;
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
-                ktile_x3<false>(wb, [&](int ks) T2S_X3_KERNEL -> const Split3& { return aop[ks]; }, acc,
+                ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return aop[ks]; }, acc,
                                 [&](int ks) T2S_X3_KERNEL { X3_FILL_MIX(ci + 1, ks) });
                 X3_STAMP(1)
 #pragma unroll
@@ -371,13 +398,13 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
         // ---------------- x += gate_mlp * (fc2(gelu(fc1(mod(LN(x))))) + b2) ----------------
         f32x4* xw = reinterpret_cast<f32x4*>(a.x) + (size_t)tile * 16 * 64 + lane;
         {
-            Split3 xmp[8];      // LayerNorm + modulate output as resident planes (the fp32 copy dies here)
+            SP xmp[8];      // LayerNorm + modulate output as resident planes (the fp32 copy dies here)
             X3_PRIO(2)
             {
                 f32x16 xm[4];
                 ln_modulate(x, xm, mb + 3 * D, mb + 4 * D, half, 1e-6f);
 #pragma unroll
-                for (int ks = 0; ks < 8; ++ks) xmp[ks] = split3_acc(xm[ks >> 1], ks & 1);
+                for (int ks = 0; ks < 8; ++ks) xmp[ks] = splitp_acc<SP>(xm[ks >> 1], ks & 1);
             }
             X3_STAMP(2)
             // park the post-attention residual in HBM for the MLP loop (t2s_rows.h)
@@ -405,7 +432,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
                     const bf16x8* wb = wring3 + lane;  // ci even -> ring slot 0
 #pragma unroll
                     for (int r = 0; r < 16; ++r) hT[r] = 0.f;
-                    ktile_x3<false>(wb, [&](int ks) T2S_X3_KERNEL -> const Split3& { return xmp[ks]; }, hT,
+                    ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, hT,
                                     [&](int ks) T2S_X3_KERNEL { X3_FILL_MIX(ci + 1, ks) });
                     X3_STAMP(1)
                     X3_PRIO(2)   // GELU + split: let this wave's VALU win the issue arbitration over the partner's MFMA stream
@@ -422,15 +449,15 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
                 ++ci;
                 X3_STAMP(5)
                 {   // fc2 partial over the 32 hidden units of this chunk: pieces (nt, s)
-                    const bf16x8* wb = wring3 + X3_CHUNK_UNITS + lane;  // ci odd -> ring slot 1
-                    const Split3 h0 = split3_acc(hT, 0), h1 = split3_acc(hT, 1);
+                    const bf16x8* wb = wring3 + CHUNK_UNITS + lane;  // ci odd -> ring slot 1
+                    const SP h0 = splitp_acc<SP>(hT, 0), h1 = splitp_acc<SP>(hT, 1);
                     X3_PRIO(0)
                     X3_STAMP(2)
 #pragma unroll
                     for (int nt = 0; nt < 4; ++nt) {
-                        acc[nt] = mfma_x3(ldw3(wb, nt * 2 + 0), h0, acc[nt]);
+                        acc[nt] = mfma_x3(ldwp<SP>(wb, nt * 2 + 0), h0, acc[nt]);
                         if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, 2 * nt) }
-                        acc[nt] = mfma_x3(ldw3(wb, nt * 2 + 1), h1, acc[nt]);
+                        acc[nt] = mfma_x3(ldwp<SP>(wb, nt * 2 + 1), h1, acc[nt]);
                         if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, 2 * nt + 1) }
                     }
                     X3_STAMP(1)
@@ -486,7 +513,9 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
                 }
             s2 += xhalf(s2);
             const float rstd = rsqrtf(s2 * (1.0f / 128.0f) + 1e-5f);
-            float fa[4] = {0.f, 0.f, 0.f, 0.f};
+            // (one plane: a vector, not an array -- `half ? fa[2 + q2] : fa[q2]` below goes through 32 B of scratch with the array.
+            // The bf16x3 instance keeps the array it was measured and pinned with, tests/test_isa_pins.py.)
+            std::conditional_t<NP == 3, float[4], f32x4> fa = {0.f, 0.f, 0.f, 0.f};
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt)
 #pragma unroll
@@ -518,13 +547,13 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
         }
     }
     if constexpr (DO_QKV) {
-        Split3 xmp[8];      // LayerNorm + modulate output as resident planes
+        SP xmp[8];      // LayerNorm + modulate output as resident planes
         X3_PRIO(2)
         {
             f32x16 xm[4];
             ln_modulate(x, xm, cm + 768, cm + 768 + D, half, 1e-6f);
 #pragma unroll
-            for (int ks = 0; ks < 8; ++ks) xmp[ks] = split3_acc(xm[ks >> 1], ks & 1);
+            for (int ks = 0; ks < 8; ++ks) xmp[ks] = splitp_acc<SP>(xm[ks >> 1], ks & 1);
         }
         const int tile_in_seq = tile - seq * (NTOK / 32);
         X3_PRIO(0)
@@ -532,7 +561,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
 #pragma unroll 1
         for (int t = 0; t < 12; ++t) {  // output tile t = which*4 + head
             X3_STAMP(5)
-            const bf16x8* wb = wring3 + (ci & 1) * X3_CHUNK_UNITS + lane;
+            const bf16x8* wb = wring3 + (ci & 1) * CHUNK_UNITS + lane;
             const int which = t >> 2, head = t & 3;
             const size_t head_tile = ((size_t)seq * NH + head) * (NTOK / 32) + tile_in_seq;
             f32x16 acc;
@@ -540,7 +569,7 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             if (which < 2) {
                 // q / k tile, transposed product: lane = token, registers = features d
-                ktile_x3<false>(wb, [&](int ks) T2S_X3_KERNEL -> const Split3& { return xmp[ks]; }, acc,
+                ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, acc,
                                 [&](int ks) T2S_X3_KERNEL { if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, ks) } });
                 X3_STAMP(1)
 #pragma unroll
@@ -558,42 +587,48 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
                             dst[g * 64] = o;
                         }
                     } else {
-                        bf16x8* d3 = reinterpret_cast<bf16x8*>(a.k3) + head_tile * X3_TILE_UNITS + lane;
+                        bf16x8* d3 = reinterpret_cast<bf16x8*>(a.k3) + head_tile * XN_TILE_UNITS<NP> + lane;
 #pragma unroll
                         for (int s2 = 0; s2 < 2; ++s2) {
-                            const Split3 sp = split3_acc(acc, s2);
+                            const SP sp = splitp_acc<SP>(acc, s2);
                             d3[(0 + s2) * 64] = sp.h;
-                            d3[(2 + s2) * 64] = sp.m;
-                            d3[(4 + s2) * 64] = sp.l;
+                            if constexpr (NP == 3) {
+                                d3[(2 + s2) * 64] = sp.m;
+                                d3[(4 + s2) * 64] = sp.l;
+                            }
                         }
                     }
                 }
             } else {
                 // v tile with the MFMA operands swapped: lane = feature d, registers = keys
                 const float bias = c_bq[32 * t + (lane & 31)];
-                ktile_x3<true>(wb, [&](int ks) T2S_X3_KERNEL -> const Split3& { return xmp[ks]; }, acc,
+                ktile_x3<true, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, acc,
                                [&](int ks) T2S_X3_KERNEL { if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, ks) } });
                 X3_STAMP(1)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] += bias;
                 if (active) {
-                    bf16x8* d3 = reinterpret_cast<bf16x8*>(a.v3) + head_tile * X3_TILE_UNITS + lane;
+                    bf16x8* d3 = reinterpret_cast<bf16x8*>(a.v3) + head_tile * XN_TILE_UNITS<NP> + lane;
 #pragma unroll
                     for (int s2 = 0; s2 < 2; ++s2) {
-                        const Split3 sp = split3_acc(acc, s2);
+                        const SP sp = splitp_acc<SP>(acc, s2);
                         d3[(0 + s2) * 64] = sp.h;
-                        d3[(2 + s2) * 64] = sp.m;
-                        d3[(4 + s2) * 64] = sp.l;
+                        if constexpr (NP == 3) {
+                            d3[(2 + s2) * 64] = sp.m;
+                            d3[(4 + s2) * 64] = sp.l;
+                        }
                     }
                 }
             }
-            // counted wait + raw barrier: the next chunk's 6 DMA pieces must have landed; the q (4) or
-            // k / v plane (6) stores issued after them stay in flight.  Tail waves store nothing.
+            // counted wait + raw barrier: the next chunk's 6 DMA pieces (one plane: 2) must have landed; the q (4) or
+            // k / v plane (6; one plane: 2) stores issued after them stay in flight.  Tail waves store nothing.
             X3_STAMP(2)
             if (!active)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            else if (which >= 1)
+            else if (which >= 1 && NP == 3)
                 asm volatile("s_waitcnt vmcnt(6)" ::: "memory");
+            else if (which >= 1)
+                asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
             X3_STAMP(3)
@@ -610,6 +645,19 @@ __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const
         d[7] = st_last - st_t0;
     }
 #endif
+}
+
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const RowArgsX3 a) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 wring3[];  // [2][X3_CHUNK_UNITS]
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split3>(a, wring3);
+}
+
+// T2S_MATH_BF16: the one-plane instantiation (a kernel of its own, no run-time branch in the bf16x3 one)
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) T2S_P1_KERNEL void dit_rows_bf16p_kernel(const RowArgsX3 a) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 wring1[];  // [2][XN_CHUNK_UNITS<1>]
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split1>(a, wring1);
 }
 
 template <bool DO_MLP, bool DO_QKV>
@@ -655,6 +703,25 @@ inline int launch_dit_rows_x3(const RowArgsX3& a, hipStream_t st) {
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 #endif
+}
+
+template <bool DO_MLP, bool DO_QKV>
+inline int dit_rows_bf16p_init() {
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_bf16p_kernel<DO_MLP, DO_QKV>),
+                                      hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_P1_LDS_BYTES));
+    return T2S_OK;
+}
+
+template <bool DO_MLP, bool DO_QKV>
+inline int launch_dit_rows_bf16p(const RowArgsX3& a, hipStream_t st) {
+    if (a.M <= 0 || a.M % 32 != 0) {
+        set_error("dit_rows_bf16p: M=%d must be a positive multiple of 32", a.M);
+        return T2S_E_INVALID;
+    }
+    const int tiles = a.M / 32;
+    dit_rows_bf16p_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_P1_LDS_BYTES, st>>>(a);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
 }
 
 }  // namespace t2s

@@ -648,6 +648,12 @@ int pick_lanes(const t2s_sampler* s, bool trace) {
 
 }  // namespace
 
+// for the other translation units' set-up work (t2s_dit_set_math): the same stream, the same lock
+namespace t2s {
+hipStream_t lib_setup_stream(int dev) { return setup_stream(dev); }
+std::recursive_mutex* lib_pool_lock(int dev) { return dev >= 0 && dev < 16 ? &g_pool_use[dev] : nullptr; }
+}  // namespace t2s
+
 extern "C" int t2s_dit_max_seqs(const t2s_dit* h);
 
 extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, t2s_sampler** out) {

@@ -8,6 +8,9 @@
 // <= 3 * 2^-24 |a.b|, i.e. the rounding level of an fp32 multiply.  Six v_mfma_f32_32x32x16_bf16
 // (32 cycles, 16-deep) replace eight v_mfma_f32_32x32x2_f32 (64 cycles, 2-deep): 2.67x fewer matrix
 // cycles at the same accuracy, and bf16 MFMAs co-issue with VALU work, which the f32 form does not.
+//
+// The kernels built on this header are written against the operand type: Split3 gives bf16x3, Split1 (below) the single-pass
+// "bf16" arithmetic of T2S_MATH_BF16 -- one plane, one MFMA per k-step, NOT fp32-accurate.
 #pragma once
 #include "t2s_bf16.h"
 
@@ -80,10 +83,44 @@ __device__ __forceinline__ f32x16 mfma_x3(const Split3& a, const Split3& b, f32x
     return acc;
 }
 
+// ---- one-plane form ("bf16" arithmetic, T2S_MATH_BF16, include/t2s.h): an operand is rounded ONCE to bf16 (the h plane
+// of split3) and a product is ONE MFMA per k-step, fp32 accumulate.  The kernels are written against the operand type
+// (Split3 / Split1), so both arithmetics share one source; the Split3 instantiations are what they were.
+struct Split1 {
+    bf16x8 h;
+};
+template <class SP> struct planes_of;
+template <> struct planes_of<Split3> { static constexpr int n = 3; };
+template <> struct planes_of<Split1> { static constexpr int n = 1; };
+
+template <class SP> __device__ __forceinline__ SP splitp(f32x8 v);
+template <> __device__ __forceinline__ Split3 splitp<Split3>(f32x8 v) { return split3(v); }
+template <> __device__ __forceinline__ Split1 splitp<Split1>(f32x8 v) {
+    Split1 s;
+    s.h = __builtin_convertvector(v, bf16x8);   // round to nearest even
+    return s;
+}
+template <class SP> __device__ __forceinline__ SP splitp_acc(const f32x16& c, int s) {
+    const f32x8 v = {c[8 * s + 0], c[8 * s + 1], c[8 * s + 2], c[8 * s + 3],
+                     c[8 * s + 4], c[8 * s + 5], c[8 * s + 6], c[8 * s + 7]};
+    return splitp<SP>(v);
+}
+__device__ __forceinline__ f32x16 mfma_x3(const Split1& a, const Split1& b, f32x16 acc) { return mfma16(a.h, b.h, acc); }
+
+// The one-plane kernels have little MFMA time to hide VALU work behind, so whether they should give up packed fp32 like the
+// bf16x3 kernels is a separate question: -DT2S_P1_PACKED_FP32 builds them WITH packed fp32 (A/B in profiles/EXPERIMENTS.md).
+#if defined(T2S_P1_PACKED_FP32)
+#define T2S_P1_KERNEL
+#else
+#define T2S_P1_KERNEL T2S_X3_KERNEL
+#endif
+
 // Split K / V^T operand planes of one (sequence, head), written by the row-chain kernel's qkv
 // epilogue and consumed by attn_fwd_x3_kernel, in units of 16 bytes (one lane's 8 bf16):
 //     [(bh * 15 + tile) * 6 + plane * 2 + s][lane]         plane 0/1/2 = h/m/l, s = k-step
 // i.e. 6 KiB per 32-token tile, each 1 KiB piece one LDS-DMA instruction.
-constexpr int X3_TILE_UNITS = 6 * 64;
+// With NP planes a tile is 2 NP pieces ([plane * 2 + s]): 6 KiB for bf16x3, 2 KiB for the one-plane form.
+template <int NP> constexpr int XN_TILE_UNITS = 2 * NP * 64;
+constexpr int X3_TILE_UNITS = XN_TILE_UNITS<3>;
 
 }  // namespace t2s

@@ -274,9 +274,8 @@ class Transformer(nn.Module):
             self.__dict__["_t2s_stamp"] = stamp
         math = self.__dict__.get("_t2s_math", "f32")
         if self.__dict__.get("_t2s_math_applied") != math:
-            with L.device_lock(device), torch.cuda.device(device):       # (first bf16x3 use allocates and synchronises)
-                L.check(L.lib().t2s_dit_set_math(h.ptr, L.MATH_BF16X3 if math == "bf16x3" else L.MATH_F32),
-                        "t2s_dit_set_math")
+            with L.device_lock(device), torch.cuda.device(device):       # (first bf16x3 / bf16 use allocates and synchronises)
+                L.check(L.lib().t2s_dit_set_math(h.ptr, L.MATH_CODES[math]), "t2s_dit_set_math")
             self.__dict__["_t2s_math_applied"] = math
         return h.ptr
 
@@ -288,9 +287,11 @@ class Transformer(nn.Module):
     def set_math(self, math: str):
         """Matrix arithmetic of the (no-grad) forward / the sampler: "f32" (default, f32 MFMA) or "bf16x3"
         (fp32-accurate split-bf16 products on the bf16 matrix cores for the attention and the row chain,
-        include/t2s.h T2S_MATH_BF16X3).  Set it before building a Sampler: a captured hipGraph keeps its kernels."""
-        if math not in ("f32", "bf16x3"):
-            raise ValueError(f"math must be 'f32' or 'bf16x3', got {math!r}")
+        include/t2s.h T2S_MATH_BF16X3) or "bf16" (single-pass mixed precision: every matrix operand rounded once to bf16, one
+        MFMA per k-step, fp32 accumulate, fp32 residual stream and statistics; NOT fp32-accurate, T2S_MATH_BF16).
+        Set it before building a Sampler: a captured hipGraph keeps its kernels."""
+        if math not in L.MATH_CODES:
+            raise ValueError(f"math must be 'f32', 'bf16x3' or 'bf16', got {math!r}")
         self.__dict__["_t2s_math"] = math
         return self
 

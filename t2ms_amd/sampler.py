@@ -26,13 +26,15 @@ XT_STREAM = 0xFFFFFFFF  # Philox stream id reserved for x_T
 # an fp64 run of the oracle (profiles/r05_accuracy.md: its error is not larger than that of the reference's own PyTorch-CPU
 # fp32 arithmetic at any of the 17 entries); "f32" = the exact v_mfma_f32 path, which stays the bench headline and the
 # class-API default.  T2S_DEFAULT_MATH overrides (the test-suite pins f32 so the headline kernels stay covered).
+# "bf16" (T2S_MATH_BF16: operands rounded once to bf16, fp32 accumulate; 2.5x bf16x3, NOT fp32-accurate) is never a default:
+# a caller asks for it by name.
 DEFAULT_MATH = "bf16x3"
 
 
 def default_math() -> str:
     m = os.environ.get("T2S_DEFAULT_MATH", "") or DEFAULT_MATH
-    if m not in ("f32", "bf16x3"):
-        raise ValueError(f"T2S_DEFAULT_MATH must be 'f32' or 'bf16x3', got {m!r}")
+    if m not in ("f32", "bf16x3", "bf16"):
+        raise ValueError(f"T2S_DEFAULT_MATH must be 'f32', 'bf16x3' or 'bf16', got {m!r}")
     return m
 
 
@@ -163,7 +165,7 @@ class Sampler:
                  math: Optional[str] = None):
         """lanes: 0 = automatic (equal part-batch chains on own streams: two when the batch is a multiple of 64 or 32 series, three for 96), 1 .. 4 -- see
         t2s_sampler_set_lanes; a scheduling choice only, the results are bitwise the same.
-        math: "f32" | "bf16x3" selects the model's matrix arithmetic (Transformer.set_math) for this sampler and everything else
+        math: "f32" | "bf16x3" | "bf16" (single-pass bf16 mixed precision: opt-in, not fp32-accurate) selects the model's matrix arithmetic (Transformer.set_math) for this sampler and everything else
         that runs the model afterwards; None = what the model's owner chose with set_math, else default_math() (bf16x3)."""
         self.device = torch.device(device)
         if self.device.type != "cuda":

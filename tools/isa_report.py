@@ -7,6 +7,7 @@ compiler puts NO vector-memory instruction of its own (a spill reload, a sunk gl
 wait that counts it; tests/test_isa_pins.py pins exactly that against a toolchain upgrade.
 
     python tools/isa_report.py [stem ...]        # e.g. t2s_attn t2s_dit
+    python tools/isa_report.py --bf16            # the one-plane (T2S_MATH_BF16) kernels next to their bf16x3 forms
 """
 import os
 import re
@@ -105,11 +106,22 @@ def demangled(name):
         return name
 
 
+# the one-plane bf16 kernels (T2S_MATH_BF16) and the bf16x3 kernels they share their source with: (stem, name fragment)
+BF16_KERNELS = [("t2s_attn_x3", "attn_fwd_bf16p_kernel"), ("t2s_attn_x3", "attn_fwd_x3_kernel"),
+                ("t2s_dit", "dit_rows_bf16p_kernel"), ("t2s_dit", "dit_rows_x3_kernel")]
+
+
 if __name__ == "__main__":
-    stems = sys.argv[1:] or ["t2s_attn", "t2s_dit"]
+    only = None
+    if sys.argv[1:] == ["--bf16"]:
+        stems, only = ["t2s_attn_x3", "t2s_dit"], BF16_KERNELS
+    else:
+        stems = sys.argv[1:] or ["t2s_attn", "t2s_attn_x3", "t2s_dit"]
     with tempfile.TemporaryDirectory() as wd:
         for stem in stems:
             for name, r in report(stem, wd).items():
+                if only is not None and not any(st == stem and frag in name for st, frag in only):
+                    continue
                 m = r["meta"]
                 print(f"{stem}: {demangled(name)}\n    vgpr {m.get('vgpr_count')} agpr {m.get('agpr_count')} sgpr {m.get('sgpr_count')} "
                       f"scratch {m.get('private_segment_fixed_size')} B lds {m.get('group_segment_fixed_size')} B; "
