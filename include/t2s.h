@@ -115,7 +115,10 @@ int t2s_dit_max_seqs(const t2s_dit* h);
  *                           accuracy as an fp32 product (dropped terms <= 3 * 2^-24 relative; measured
  *                           against fp64 the attention kernel is as close as the f32 one) at 2.67x
  *                           fewer matrix cycles.  Allocates 2 x max_seqs x 368,640 B + 3.1 MB of split
- *                           weights on first use; weights follow t2s_dit_update_weights.
+ *                           weights on first use and packs them on the library's own set-up stream, under the per-device
+ *                           lock of t2s_sampler_run ("Threads") and behind the last t2s_dit_update_weights, whatever
+ *                           stream that ran on; a first use that fails leaves the handle as it was.  Weights follow
+ *                           t2s_dit_update_weights.
  *                           Since round 5 the host-side Sampler and infer.py SELECT this mode unless told otherwise
  *                           (its error against fp64 is not larger than the reference's own CPU fp32 arithmetic at any of
  *                           17 table entries, profiles/r05_accuracy.md); the class API and the bench headline stay on F32.
@@ -131,8 +134,8 @@ int t2s_dit_max_seqs(const t2s_dit* h);
  *                           LayerNorm and adaLN modulation, the softmax reference / exponent / running sum, GELU, biases,
  *                           the final layer, patchify, the time embedding, the adaLN table, the CFG combine, the DDPM / RF
  *                           update, the Philox noise and the LA-VAE.  This is the contract of the training step's
- *                           T2S_TRAIN_BF16.  Allocates 2 x max_seqs x 122,880 B + 1.0 MB of bf16 weights on first use, on
- *                           the library's own set-up stream; weights follow t2s_dit_update_weights.  Errors against fp64:
+ *                           T2S_TRAIN_BF16.  Allocates 2 x max_seqs x 122,880 B + 1.0 MB of bf16 weights on first use, by
+ *                           the same path as T2S_MATH_BF16X3; weights follow t2s_dit_update_weights.  Errors against fp64:
  *                           rms ~1e-3 on outputs of magnitude ~4.5 per forward, a quarter of what PyTorch's bf16 autocast
  *                           makes of the same forward (tests/test_math_bf16.py).
  * Not capturable; a hipGraph captured under one mode keeps replaying that mode's kernels.  Each mode has a workspace of

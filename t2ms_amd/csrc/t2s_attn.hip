@@ -23,7 +23,7 @@
 // attn_fwd_plain_kernel: same math on plain (BH,480,32) tensors for the standalone C-ABI entry.
 #include <stdlib.h>
 
-#include "t2s_common.h"
+#include "t2s_dit_internal.h"
 
 namespace t2s {
 

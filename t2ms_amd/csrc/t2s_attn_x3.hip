@@ -14,6 +14,7 @@
 // (T2S_MATH_BF16, attn_fwd_bf16p_kernel): q, k, v^T and P^T each rounded once, 2 + 2 MFMAs per key block and query tile (128
 // cycles), a ring slot of 4 KiB.  Not fp32-accurate; the softmax reference, exponent and running sum stay fp32.
 #include <stdlib.h>
+#include "t2s_dit_internal.h"
 #include "t2s_x3.h"
 
 namespace t2s {
@@ -369,22 +370,21 @@ __global__ void pack_xn_kernel(const float* __restrict__ src, bf16x8* __restrict
 }
 }  // namespace
 
-int attn_x3_init() {   // once, outside any stream capture
-    static bool done = false;
-    if (!done) {
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_x3_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, X3_LDS_BYTES));
-        done = true;
-    }
-    return T2S_OK;
+// host side: one set of helpers for both plane counts (np = 3: bf16x3, np = 1: the one-plane form)
+struct AttnXn {
+    void (*kernel)(const float*, const __bf16*, const __bf16*, float*, int);
+    int lds_bytes;
+};
+static AttnXn attn_xn(int np) {
+    return np == 3 ? AttnXn{attn_fwd_x3_kernel, X3_LDS_BYTES} : AttnXn{attn_fwd_bf16p_kernel, P1_LDS_BYTES};
 }
 
-int attn_bf16p_init() {   // (16 KiB of LDS needs no opt-in; kept for symmetry and for a ring that grows)
-    static bool done = false;
-    if (!done) {
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_bf16p_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, P1_LDS_BYTES));
-        done = true;
+int attn_xn_init(int np) {   // once per kernel, outside any stream capture (16 KiB of LDS needs no opt-in; a ring may grow)
+    static bool done[4] = {};
+    if (!done[np]) {
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_xn(np).kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, attn_xn(np).lds_bytes));
+        done[np] = true;
     }
     return T2S_OK;
 }
@@ -409,28 +409,17 @@ static int attn_xn_grid(int BH) {
     return BH < slots ? BH : slots;
 }
 
-int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o, int BH, hipStream_t st) {
-    attn_fwd_x3_kernel<<<attn_xn_grid(BH), X3_THREADS, X3_LDS_BYTES, st>>>(q, k3, vT3, o, BH);
+int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st) {
+    const AttnXn x = attn_xn(np);
+    x.kernel<<<attn_xn_grid(BH), X3_THREADS, x.lds_bytes, st>>>(q, k, vT, o, BH);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
-int launch_attn_bf16p(const float* q, const __bf16* k1, const __bf16* vT1, float* o, int BH, hipStream_t st) {
-    attn_fwd_bf16p_kernel<<<attn_xn_grid(BH), X3_THREADS, P1_LDS_BYTES, st>>>(q, k1, vT1, o, BH);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-int pack_x3(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
+template <int NP>
+static int pack_xn(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
     const int n = BH * NKB * 2 * 64;
-    pack_xn_kernel<3><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-int pack_bf16p(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
-    const int n = BH * NKB * 2 * 64;
-    pack_xn_kernel<1><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
+    pack_xn_kernel<NP><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -463,7 +452,7 @@ template <int NP>
 static int attn_fwd_plain(const char* who, const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
     T2S_REQUIRE(q && k && v && o && BH > 0 && BH % NH == 0, "%s: bad argument (BH=%d must be a multiple of 4)", who, BH);
     hipStream_t st = (hipStream_t)stream;
-    if (int rc = NP == 3 ? attn_x3_init() : attn_bf16p_init()) return rc;
+    if (int rc = attn_xn_init(NP)) return rc;
     const size_t n = (size_t)BH * NTOK * DH;
     float* f32buf = nullptr;
     __bf16* planes = nullptr;
@@ -475,11 +464,9 @@ static int attn_fwd_plain(const char* who, const float* q, const float* k, const
     }
     const int nf = BH * 15 * 4 * 64;
     q_to_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(q, reinterpret_cast<f32x4*>(f32buf), BH);
-    int rc = NP == 3 ? pack_x3(k, planes, BH, 0, st) : pack_bf16p(k, planes, BH, 0, st);
-    if (rc == T2S_OK) rc = NP == 3 ? pack_x3(v, planes + NP * n, BH, 1, st) : pack_bf16p(v, planes + NP * n, BH, 1, st);
-    if (rc == T2S_OK)
-        rc = NP == 3 ? launch_attn_x3(f32buf, planes, planes + NP * n, f32buf + n, BH, st)
-                     : launch_attn_bf16p(f32buf, planes, planes + NP * n, f32buf + n, BH, st);
+    int rc = pack_xn<NP>(k, planes, BH, 0, st);
+    if (rc == T2S_OK) rc = pack_xn<NP>(v, planes + NP * n, BH, 1, st);
+    if (rc == T2S_OK) rc = launch_attn_xn(NP, f32buf, planes, planes + NP * n, f32buf + n, BH, st);
     if (rc == T2S_OK) {
         o_from_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(reinterpret_cast<const f32x4*>(f32buf + n), o, BH);
         if (hipGetLastError() != hipSuccess) rc = T2S_E_HIP;

@@ -7,12 +7,11 @@
 // Between kernels the residual stream, the attention output and q/k/v stay in the
 // fragment-major layout (t2s_common.h: frag_index).
 #include <stdlib.h>
-#include <mutex>
-#include <vector>
 
+#include "t2s_dit_internal.h"
 #include "t2s_gemm.h"
-#include "t2s_rows_x3.h"
-#include "t2s_rows16.h"
+#include "t2s_rows16.h"    // (in front of t2s_rows_x3.h: kernels are emitted in the order the headers ask for them, and the
+#include "t2s_rows_x3.h"   //  one-plane sampler is 0.4 % slower with the plane kernels placed first, profiles/EXPERIMENTS.md 0.16)
 
 namespace t2s {
 
@@ -24,17 +23,6 @@ void set_error(const char* fmt, ...) {
     vsnprintf(g_err, sizeof(g_err), fmt, ap);
     va_end(ap);
 }
-
-int launch_attn_packed(const float* q, const float* k, const float* vT, float* o, int BH, hipStream_t st);
-int attn_init();
-int launch_attn_x3(const float* q, const __bf16* k3, const __bf16* vT3, float* o, int BH, hipStream_t st);
-int attn_x3_init();
-int launch_attn_bf16p(const float* q, const __bf16* k1, const __bf16* vT1, float* o, int BH, hipStream_t st);
-int attn_bf16p_init();
-// the library's non-blocking set-up stream and per-device run lock (t2s_sampler.hip: t2s_sampler_create)
-hipStream_t lib_setup_stream(int dev);
-std::recursive_mutex* lib_pool_lock(int dev);
-void train_free(t2s_dit* h);
 
 // ------------------------------------------------------------------ small kernels
 // W (N,K) row-major -> MFMA-fragment order.  mode 0: packed_index (tile-major: [nt][G][lane][e]);
@@ -201,8 +189,7 @@ __global__ void unfrag128_kernel(const float* __restrict__ src, float* __restric
 }  // namespace t2s
 
 using namespace t2s;
-
-#include "t2s_dit_internal.h"
+using BfPlanes = t2s_dit::BfPlanes;
 
 namespace {
 
@@ -215,27 +202,15 @@ struct ArenaPlan {
     }
 };
 
-// split planes of the row-chain weights from the handle's packed fp32 copies (T2S_MATH_BF16X3)
-int pack_x3_weights(t2s_dit* h, hipStream_t st) {
+// the planes of the row-chain weights from the handle's packed fp32 copies (bf16x3: the three-way split, bf16: its h plane)
+int pack_bf_weights(const t2s_dit* h, const BfPlanes& pl, hipStream_t st) {
+    auto pack = [&](const f32x4* P, __bf16* dst, int N, int K, int fc2) {
+        return pack_rows_xn(pl.np, reinterpret_cast<const float*>(P), reinterpret_cast<bf16x8*>(dst), N, K, fc2, st);
+    };
     int rc;
     for (int i = 0; i < NBLK; ++i) {
-        if ((rc = pack_rows_x3(reinterpret_cast<const float*>(h->qkv_p[i]), reinterpret_cast<bf16x8*>(h->qkv3[i]), 3 * D, D, 0, st)) ||
-            (rc = pack_rows_x3(reinterpret_cast<const float*>(h->proj_p[i]), reinterpret_cast<bf16x8*>(h->proj3[i]), D, D, 0, st)) ||
-            (rc = pack_rows_x3(reinterpret_cast<const float*>(h->fc1_p[i]), reinterpret_cast<bf16x8*>(h->fc13[i]), 2 * D, D, 0, st)) ||
-            (rc = pack_rows_x3(reinterpret_cast<const float*>(h->fc2_c[i]), reinterpret_cast<bf16x8*>(h->fc2c3[i]), D, 2 * D, 1, st)))
-            return rc;
-    }
-    return T2S_OK;
-}
-
-// the h plane alone (T2S_MATH_BF16), same chunk order
-int pack_bf16p_weights(t2s_dit* h, hipStream_t st) {
-    int rc;
-    for (int i = 0; i < NBLK; ++i) {
-        if ((rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->qkv_p[i]), reinterpret_cast<bf16x8*>(h->qkv1[i]), 3 * D, D, 0, st)) ||
-            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->proj_p[i]), reinterpret_cast<bf16x8*>(h->proj1[i]), D, D, 0, st)) ||
-            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->fc1_p[i]), reinterpret_cast<bf16x8*>(h->fc11[i]), 2 * D, D, 0, st)) ||
-            (rc = pack_rows_bf16p(reinterpret_cast<const float*>(h->fc2_c[i]), reinterpret_cast<bf16x8*>(h->fc2c1[i]), D, 2 * D, 1, st)))
+        if ((rc = pack(h->qkv_p[i], pl.qkv[i], 3 * D, D, 0)) || (rc = pack(h->proj_p[i], pl.proj[i], D, D, 0)) ||
+            (rc = pack(h->fc1_p[i], pl.fc1[i], 2 * D, D, 0)) || (rc = pack(h->fc2_c[i], pl.fc2c[i], D, 2 * D, 1)))
             return rc;
     }
     return T2S_OK;
@@ -281,10 +256,8 @@ int check_weights(const t2s_dit_weights* w, const uint64_t* n_floats, bool range
     return T2S_OK;
 }
 
+// (both callers have just run check_weights: no pointer is NULL)
 int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
-    T2S_REQUIRE(w->conv_w && w->conv_b && w->patch_w && w->patch_b && w->pos_embed && w->ln_w &&
-                    w->ln_b && w->out_w && w->out_b && w->time_freqs,
-                "t2s_dit weights: NULL top-level pointer");
     CopyTable ct{};
     PackTable pt{};
     int nc = 0, np = 0, max_pack = 0;
@@ -305,9 +278,6 @@ int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
     cp(h->freqs, w->time_freqs, 64);
     for (int i = 0; i < NBLK; ++i) {
         const t2s_dit_block_weights& b = w->blk[i];
-        T2S_REQUIRE(b.qkv_w && b.qkv_b && b.proj_w && b.proj_b && b.fc1_w && b.fc1_b && b.fc2_w &&
-                        b.fc2_b && b.ada_w && b.ada_b,
-                    "t2s_dit weights: NULL pointer in block %d", i);
         cp(h->qkv_b[i], b.qkv_b, 3 * D);
         cp(h->proj_b[i], b.proj_b, D);
         cp(h->fc1_b[i], b.fc1_b, 2 * D);
@@ -328,10 +298,9 @@ int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
     T2S_LAUNCH_CHECK();
     pack_weight_multi_kernel<<<dim3((max_pack + 255) / 256, np), 256, 0, st>>>(pt);
     T2S_LAUNCH_CHECK();
-    if (h->w3 != nullptr)
-        if (int rc = pack_x3_weights(h, st)) return rc;
-    if (h->w1 != nullptr)
-        if (int rc = pack_bf16p_weights(h, st)) return rc;
+    for (const BfPlanes& pl : h->bf)
+        if (pl.w != nullptr)
+            if (int rc = pack_bf_weights(h, pl, st)) return rc;
     return T2S_OK;
 }
 
@@ -355,11 +324,11 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     float* const w_ao = h->ao + tok0;
     float* const w_h0 = h->h0 + tok0 / 2;                      // one slot per PAIR of sequences (CFG pass)
     float* const w_mod = h->mod + (size_t)ws_seq0 * MODROW;
-    __bf16* w_k3 = h->k3 ? h->k3 + tok0 * 3 : nullptr;
-    __bf16* w_v3 = h->v3 ? h->v3 + tok0 * 3 : nullptr;
-    const bool p1 = h->math == T2S_MATH_BF16;   // one bf16 plane (k1 / v1 / w1), the bf16x3 kernels' one-plane instances
-    const bool x3 = h->math == T2S_MATH_BF16X3;
-    if (p1) { w_k3 = h->k1 + tok0; w_v3 = h->v1 + tok0; }
+    // T2S_MATH_BF16X3 / T2S_MATH_BF16: every product of the row chain and of the attention is evaluated as six bf16 MFMAs
+    // (fp32-accurate, t2s_x3.h) / as one; k / V^T travel as the mode's bf16 planes.  NULL: f32
+    const BfPlanes* const pl = h->math == T2S_MATH_F32 ? nullptr : &h->bf[h->math - T2S_MATH_BF16X3];
+    __bf16* const w_kp = pl ? pl->k + tok0 * pl->np : nullptr;
+    __bf16* const w_vp = pl ? pl->v + tok0 * pl->np : nullptr;
     const bool use_table = mt.base != nullptr && step_ptr != nullptr;
     if (!use_table) {   // adaLN for all 4 blocks at once: mod = silu(c) @ W_ada^T + b, c = t_emb (+ text)
         TimeScope ts(h, TC_OTHER, st);
@@ -388,8 +357,15 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     const int M = S * NTOK;
     // Row-local chain as one register-resident kernel per block (t2s_rows.h):
     //   rows<qkv only>(block 0) ; { attention(i) ; rows<proj+MLP of i, qkv of i+1> } x 4
-    auto rows_args = [&](int blk, int qkv_blk) {
-        RowArgs a{};
+    // Small launches run the row chain on 16-token tiles (t2s_rows16.h; bit-identical results): up to 100 sequences, i.e.
+    // where the 32-token kernel has fewer than ~1.5 waves per SIMD.  Same-box series/s, 16- vs 32-token tiles: 8 series
+    // (16 sequences) +27 %, 16 +25 %, 24 +1 %, 32 (the 8-GPU strong-scaling shard) +1.2 %, 40 +7.5 %, 48 +7.7 %, 64 -2 %
+    // (profiles/r03_rows16_ab.txt; measured with the last block's kernel still on 32-token tiles).
+    // T2S_ROWS16_MAX_SEQS moves the switch point (A/B runs; 0 = never).
+    static const int rows16_max = getenv("T2S_ROWS16_MAX_SEQS") ? atoi(getenv("T2S_ROWS16_MAX_SEQS")) : 100;
+    const bool use16 = !pl && S <= rows16_max;
+    // what RowArgs and RowArgsX3 share: everything but the weight matrices and k / v
+    auto fill_shared = [&](auto& a, int blk, int qkv_blk) {
         a.x = w_h; a.ao = w_ao; a.mod = w_mod; a.M = M; a.blk = blk; a.qkv_blk = qkv_blk;
         if (use_table) { a.mod = mt.base; a.mod_step = step_ptr; a.mod_rows = mt.rows; a.mod_uncond = uncond_rows; a.mod_row0 = mt.row0; }
         if (blk < 0 && patch_fused) {
@@ -401,77 +377,47 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
             a.f_lnw = h->ln_w; a.f_lnb = h->ln_b; a.f_ow = h->out_w; a.f_ob = h->out_b;
             a.out0 = out0; a.out1 = out1; a.split = split; a.keep_x = keep_stream;
         }
-        if (blk >= 0) {
-            a.Wp = h->proj_p[blk]; a.W1 = h->fc1_p[blk]; a.W2c = h->fc2_c[blk];
-            a.bp = h->proj_b[blk]; a.b1 = h->fc1_b[blk]; a.b2 = h->fc2_b[blk];
-        }
-        if (qkv_blk >= 0) { a.Wq = h->qkv_p[qkv_blk]; a.bq = h->qkv_b[qkv_blk]; }
-        a.q = w_q; a.k = w_k; a.v = w_v;
-        return a;
+        if (blk >= 0) { a.bp = h->proj_b[blk]; a.b1 = h->fc1_b[blk]; a.b2 = h->fc2_b[blk]; }
+        if (qkv_blk >= 0) a.bq = h->qkv_b[qkv_blk];
+        a.q = w_q;
     };
-    // T2S_MATH_BF16X3: every product of the row chain and of the attention is evaluated as six bf16 MFMAs
-    // (fp32-accurate, t2s_x3.h); k / V^T travel as split bf16 planes
-    auto rows_args_x3 = [&](int blk, int qkv_blk) {
-        RowArgsX3 a{};
-        a.x = w_h; a.ao = w_ao; a.mod = w_mod; a.M = M; a.blk = blk; a.qkv_blk = qkv_blk;
-        if (use_table) { a.mod = mt.base; a.mod_step = step_ptr; a.mod_rows = mt.rows; a.mod_uncond = uncond_rows; a.mod_row0 = mt.row0; }
-        if (blk < 0 && patch_fused) {
-            a.p_lat = x; a.p_B = B; a.p_cw = h->conv_w; a.p_cb = h->conv_b; a.p_pw = h->patch_w; a.p_pb = h->patch_b; a.p_pos = h->pos;
+    auto launch_rows = [&](auto do_mlp, auto do_qkv, int blk, int qkv_blk) {   // (std::bool_constant: the kernel instance)
+        constexpr bool DO_MLP = decltype(do_mlp)::value, DO_QKV = decltype(do_qkv)::value;
+        if (pl) {
+            auto w8 = [](const __bf16* p) { return reinterpret_cast<const bf16x8*>(p); };
+            RowArgsX3 a{};
+            fill_shared(a, blk, qkv_blk);
+            if (blk >= 0) { a.Wp = w8(pl->proj[blk]); a.W1 = w8(pl->fc1[blk]); a.W2c = w8(pl->fc2c[blk]); }
+            if (qkv_blk >= 0) a.Wq = w8(pl->qkv[qkv_blk]);
+            a.k3 = w_kp; a.v3 = w_vp;
+            return launch_dit_rows_xn<DO_MLP, DO_QKV>(pl->np, a, st);
         }
-        const bool first = blk <= 0 && qkv_blk <= 1;
-        a.x_in = first ? tokens : w_h; a.in_seqs = first ? in_seqs : S;
-        if (blk == NBLK - 1) {
-            a.f_lnw = h->ln_w; a.f_lnb = h->ln_b; a.f_ow = h->out_w; a.f_ob = h->out_b;
-            a.out0 = out0; a.out1 = out1; a.split = split; a.keep_x = keep_stream;
-        }
-        if (blk >= 0) {
-            a.Wp = reinterpret_cast<const bf16x8*>(p1 ? h->proj1[blk] : h->proj3[blk]);
-            a.W1 = reinterpret_cast<const bf16x8*>(p1 ? h->fc11[blk] : h->fc13[blk]);
-            a.W2c = reinterpret_cast<const bf16x8*>(p1 ? h->fc2c1[blk] : h->fc2c3[blk]);
-            a.bp = h->proj_b[blk]; a.b1 = h->fc1_b[blk]; a.b2 = h->fc2_b[blk];
-        }
-        if (qkv_blk >= 0) { a.Wq = reinterpret_cast<const bf16x8*>(p1 ? h->qkv1[qkv_blk] : h->qkv3[qkv_blk]); a.bq = h->qkv_b[qkv_blk]; }
-        a.q = w_q; a.k3 = w_k3; a.v3 = w_v3;
-        return a;
-    };
-    // Small launches run the row chain on 16-token tiles (t2s_rows16.h; bit-identical results): up to 100 sequences, i.e.
-    // where the 32-token kernel has fewer than ~1.5 waves per SIMD.  Same-box series/s, 16- vs 32-token tiles: 8 series
-    // (16 sequences) +27 %, 16 +25 %, 24 +1 %, 32 (the 8-GPU strong-scaling shard) +1.2 %, 40 +7.5 %, 48 +7.7 %, 64 -2 %
-    // (profiles/r03_rows16_ab.txt; measured with the last block's kernel still on 32-token tiles).
-    // T2S_ROWS16_MAX_SEQS moves the switch point (A/B runs; 0 = never).
-    static const int rows16_max = getenv("T2S_ROWS16_MAX_SEQS") ? atoi(getenv("T2S_ROWS16_MAX_SEQS")) : 100;
-    const bool use16 = !x3 && !p1 && S <= rows16_max;
-    auto rows_args16 = [&](int blk, int qkv_blk) {
-        RowArgs a = rows_args(blk, qkv_blk);
+        RowArgs a{};
+        fill_shared(a, blk, qkv_blk);
+        if (blk >= 0) { a.Wp = h->proj_p[blk]; a.W1 = h->fc1_p[blk]; a.W2c = h->fc2_c[blk]; }
+        if (qkv_blk >= 0) a.Wq = h->qkv_p[qkv_blk];
+        a.k = w_k; a.v = w_v;
+        if (!use16) return launch_dit_rows<DO_MLP, DO_QKV>(a, st);
         if (blk >= 0) { a.Wp = h->proj_p16[blk]; a.W1 = h->fc1_p16[blk]; a.W2c = h->fc2_c16[blk]; }
         if (qkv_blk >= 0) a.Wq = h->qkv_p16[qkv_blk];
-        return a;
+        return launch_dit_rows16<DO_MLP, DO_QKV>(a, st);
     };
+    auto launch_attention = [&] {
+        return pl ? launch_attn_xn(pl->np, w_q, w_kp, w_vp, w_ao, S * NH, st) : launch_attn_packed(w_q, w_k, w_v, w_ao, S * NH, st);
+    };
+    constexpr std::true_type yes{};
+    constexpr std::false_type no{};
     {
         TimeScope ts(h, TC_ROWS_FIRST, st);
-        rc = p1 ? launch_dit_rows_bf16p<false, true>(rows_args_x3(-1, 0), st)
-           : x3 ? launch_dit_rows_x3<false, true>(rows_args_x3(-1, 0), st)
-                : (use16 ? launch_dit_rows16<false, true>(rows_args16(-1, 0), st) : launch_dit_rows<false, true>(rows_args(-1, 0), st));
-        if (rc != T2S_OK) return rc;
+        if ((rc = launch_rows(no, yes, -1, 0))) return rc;
     }
     for (int i = 0; i < NBLK; ++i) {
         {
             TimeScope ts(h, TC_ATTN, st);
-            rc = p1 ? launch_attn_bf16p(w_q, w_k3, w_v3, w_ao, S * NH, st)
-               : x3 ? launch_attn_x3(w_q, w_k3, w_v3, w_ao, S * NH, st)
-                    : launch_attn_packed(w_q, w_k, w_v, w_ao, S * NH, st);
-            if (rc != T2S_OK) return rc;
+            if ((rc = launch_attention())) return rc;
         }
         TimeScope ts(h, i + 1 < NBLK ? TC_ROWS : TC_ROWS_LAST, st);
-        if (i + 1 < NBLK)
-            rc = p1 ? launch_dit_rows_bf16p<true, true>(rows_args_x3(i, i + 1), st)
-               : x3 ? launch_dit_rows_x3<true, true>(rows_args_x3(i, i + 1), st)
-                    : (use16 ? launch_dit_rows16<true, true>(rows_args16(i, i + 1), st) : launch_dit_rows<true, true>(rows_args(i, i + 1), st));
-        else
-            rc = p1 ? launch_dit_rows_bf16p<true, false>(rows_args_x3(i, -1), st)
-               : x3 ? launch_dit_rows_x3<true, false>(rows_args_x3(i, -1), st)
-                    : (use16 ? launch_dit_rows16<true, false>(rows_args16(i, -1), st) : launch_dit_rows<true, false>(rows_args(i, -1), st));
-        if (rc != T2S_OK) return rc;
+        if ((rc = i + 1 < NBLK ? launch_rows(yes, yes, i, i + 1) : launch_rows(yes, no, i, -1))) return rc;
     }
     // (the final layer -- LayerNorm, Linear 128 -> 4, unpatchify -- ran inside the last row kernel)
     return T2S_OK;
@@ -598,17 +544,18 @@ int t2s_dit_update_weights(t2s_dit* h, const t2s_dit_weights* w, void* stream) {
     const int rc_w = check_weights(w, nullptr, /*ranges=*/true);
     if (rc_w != T2S_OK) return rc_w;
     const int rc = upload_weights(h, w, (hipStream_t)stream);
-    // a later t2s_dit_set_math(T2S_MATH_BF16) packs from these copies on the set-up stream: leave it something to wait for
+    // a later first t2s_dit_set_math(T2S_MATH_BF16X3 / _BF16) packs from these copies on the set-up stream: leave it something to wait for
     if (rc == T2S_OK && (h->w_ev != nullptr || hipEventCreateWithFlags(&h->w_ev, hipEventDisableTiming) == hipSuccess))
         T2S_HIP_CHECK(hipEventRecord(h->w_ev, (hipStream_t)stream));
     return rc;
 }
 
 namespace {
-// T2S_MATH_BF16, first use: one-plane K / V^T workspace and weight pieces.  Packed on the library's non-blocking set-up
-// stream under the per-device run lock, as t2s_sampler_create does its uploads -- never on the legacy stream, which HIP
-// refuses (and whose use invalidates the capture) while any thread has a capture open on a blocking stream.
-int alloc_bf16p(t2s_dit* h) {
+// A bf16 mode's first use: its K / V^T workspace and weight pieces (pl.np planes each).  Packed on the library's non-blocking
+// set-up stream under the per-device run lock, as t2s_sampler_create does its uploads -- never on the legacy stream, which HIP
+// refuses (and whose use invalidates the capture) while any thread has a capture open on a blocking stream.  The handle's
+// record is written once everything has succeeded.
+int alloc_bf_planes(t2s_dit* h, BfPlanes& out) {
     int rc, dev = 0;
     T2S_HIP_CHECK(hipGetDevice(&dev));
     std::recursive_mutex* mu = lib_pool_lock(dev);
@@ -616,37 +563,33 @@ int alloc_bf16p(t2s_dit* h) {
     std::lock_guard<std::recursive_mutex> lock(*mu);
     hipStream_t setup = lib_setup_stream(dev);
     T2S_REQUIRE(setup, "t2s_dit_set_math: no set-up stream on device %d", dev);
-    if ((rc = attn_bf16p_init()) || (rc = dit_rows_bf16p_init<false, true>()) || (rc = dit_rows_bf16p_init<true, true>()) ||
-        (rc = dit_rows_bf16p_init<true, false>()))
-        return rc;
-    const size_t bytes = (size_t)h->max_seqs * NTOK * D * sizeof(__bf16);      // one bf16 plane
-    const size_t wvals = (size_t)NBLK * (3 + 1 + 2 + 2) * D * D;                // qkv, proj, fc1, fc2: the h plane
-    __bf16 *k1 = nullptr, *v1 = nullptr, *w1 = nullptr;
-    if (hipMalloc(&k1, bytes) != hipSuccess || hipMalloc(&v1, bytes) != hipSuccess || hipMalloc(&w1, wvals * sizeof(__bf16)) != hipSuccess) {
-        if (k1) (void)hipFree(k1);
-        if (v1) (void)hipFree(v1);
-        (void)hipGetLastError();
+    BfPlanes pl = out;
+    if ((rc = attn_xn_init(pl.np)) || (rc = dit_rows_xn_init(pl.np))) return rc;
+    const size_t bytes = (size_t)h->max_seqs * NTOK * D * pl.np * sizeof(__bf16);
+    const size_t wvals = (size_t)NBLK * (3 + 1 + 2 + 2) * D * D * pl.np;          // qkv, proj, fc1, fc2
+    if (hipMalloc(&pl.k, bytes) != hipSuccess || hipMalloc(&pl.v, bytes) != hipSuccess || hipMalloc(&pl.w, wvals * sizeof(__bf16)) != hipSuccess) {
+        rc = T2S_E_HIP;
         set_error("t2s_dit_set_math: hipMalloc(2 x %zu B + weights) failed", bytes);
-        return T2S_E_HIP;
+    } else {
+        __bf16* p = pl.w;
+        for (int i = 0; i < NBLK; ++i) {
+            pl.qkv[i] = p; p += (size_t)3 * D * D * pl.np;
+            pl.proj[i] = p; p += (size_t)D * D * pl.np;
+            pl.fc1[i] = p; p += (size_t)2 * D * D * pl.np;
+            pl.fc2c[i] = p; p += (size_t)2 * D * D * pl.np;
+        }
+        const hipError_t e = h->w_ev ? hipStreamWaitEvent(setup, h->w_ev, 0) : hipSuccess;   // the last t2s_dit_update_weights
+        rc = e == hipSuccess ? pack_bf_weights(h, pl, setup) : T2S_E_HIP;
+        if (rc == T2S_OK && hipStreamSynchronize(setup) != hipSuccess) rc = T2S_E_HIP;
+        if (rc == T2S_E_HIP) set_error("t2s_dit_set_math: packing the %d-plane weights failed", pl.np);
     }
-    __bf16* p = w1;
-    for (int i = 0; i < NBLK; ++i) {
-        h->qkv1[i] = p; p += (size_t)3 * D * D;
-        h->proj1[i] = p; p += (size_t)D * D;
-        h->fc11[i] = p; p += (size_t)2 * D * D;
-        h->fc2c1[i] = p; p += (size_t)2 * D * D;
-    }
-    h->w1 = w1;
-    hipError_t e = h->w_ev ? hipStreamWaitEvent(setup, h->w_ev, 0) : hipSuccess;   // the last t2s_dit_update_weights
-    rc = e == hipSuccess ? pack_bf16p_weights(h, setup) : T2S_E_HIP;
-    if (rc == T2S_OK && hipStreamSynchronize(setup) != hipSuccess) rc = T2S_E_HIP;
     if (rc != T2S_OK) {
-        (void)hipFree(k1); (void)hipFree(v1); (void)hipFree(w1);
-        h->w1 = nullptr;
-        if (e != hipSuccess || rc == T2S_E_HIP) set_error("t2s_dit_set_math: packing the bf16 weights failed");
+        for (__bf16* b : {pl.k, pl.v, pl.w})
+            if (b) (void)hipFree(b);
+        (void)hipGetLastError();
         return rc;
     }
-    h->k1 = k1; h->v1 = v1;
+    out = pl;
     return T2S_OK;
 }
 }  // namespace
@@ -654,33 +597,8 @@ int alloc_bf16p(t2s_dit* h) {
 int t2s_dit_set_math(t2s_dit* h, int math) {
     T2S_REQUIRE(h, "t2s_dit_set_math: NULL handle");
     T2S_REQUIRE(math == T2S_MATH_F32 || math == T2S_MATH_BF16X3 || math == T2S_MATH_BF16, "t2s_dit_set_math: unknown mode %d", math);
-    if (math == T2S_MATH_BF16 && h->k1 == nullptr)
-        if (int rc = alloc_bf16p(h)) return rc;
-    if (math == T2S_MATH_BF16X3 && h->k3 == nullptr) {
-        int rc;
-        if ((rc = attn_x3_init()) || (rc = dit_rows_x3_init<false, true>()) || (rc = dit_rows_x3_init<true, true>()) ||
-            (rc = dit_rows_x3_init<true, false>()))
-            return rc;
-        const size_t bytes = (size_t)h->max_seqs * NTOK * D * 3 * sizeof(__bf16);   // three bf16 planes
-        const size_t wvals = (size_t)NBLK * (3 + 1 + 2 + 2) * D * D * 3;              // qkv, proj, fc1, fc2: 3 planes
-        if (hipMalloc(&h->k3, bytes) != hipSuccess || hipMalloc(&h->v3, bytes) != hipSuccess ||
-            hipMalloc(&h->w3, wvals * sizeof(__bf16)) != hipSuccess) {
-            if (h->k3) (void)hipFree(h->k3);
-            if (h->v3) (void)hipFree(h->v3);
-            h->k3 = h->v3 = h->w3 = nullptr;
-            set_error("t2s_dit_set_math: hipMalloc(2 x %zu B + weights) failed", bytes);
-            return T2S_E_HIP;
-        }
-        __bf16* p = h->w3;
-        for (int i = 0; i < NBLK; ++i) {
-            h->qkv3[i] = p; p += (size_t)3 * D * D * 3;
-            h->proj3[i] = p; p += (size_t)D * D * 3;
-            h->fc13[i] = p; p += (size_t)2 * D * D * 3;
-            h->fc2c3[i] = p; p += (size_t)2 * D * D * 3;
-        }
-        if ((rc = pack_x3_weights(h, nullptr))) return rc;
-        T2S_HIP_CHECK(hipStreamSynchronize(nullptr));
-    }
+    if (math != T2S_MATH_F32 && h->bf[math - T2S_MATH_BF16X3].w == nullptr)
+        if (int rc = alloc_bf_planes(h, h->bf[math - T2S_MATH_BF16X3])) return rc;
     h->math = math;
     return T2S_OK;
 }
@@ -688,13 +606,10 @@ int t2s_dit_set_math(t2s_dit* h, int math) {
 void t2s_dit_destroy(t2s_dit* h) {
     if (!h) return;
     t2s::train_free(h);
-    if (h->k3) (void)hipFree(h->k3);
-    if (h->v3) (void)hipFree(h->v3);
-    if (h->w3) (void)hipFree(h->w3);
-    if (h->k1) (void)hipFree(h->k1);
-    if (h->v1) (void)hipFree(h->v1);
-    if (h->w1) (void)hipFree(h->w1);
     if (h->w_ev) (void)hipEventDestroy(h->w_ev);
+    for (const BfPlanes& pl : h->bf)
+        for (__bf16* b : {pl.k, pl.v, pl.w})
+            if (b) (void)hipFree(b);
     float* bufs[] = {h->arena, h->h, h->q, h->k, h->v, h->ao, h->mod, h->h0};
     for (float* b : bufs)
         if (b) (void)hipFree(b);

@@ -1,5 +1,7 @@
-// Internal definition of the t2s_dit handle, shared by t2s_dit.hip (inference) and t2s_train.hip.
+// Internal definition of the t2s_dit handle, shared by t2s_dit.hip (inference) and t2s_train.hip, and the functions the
+// translation units of the DiT call across their borders.
 #pragma once
+#include <mutex>
 #include <vector>
 
 #include "t2s_common.h"
@@ -19,16 +21,17 @@ struct t2s_dit {
     float *h = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *ao = nullptr;
     float* h0 = nullptr;         // patchified tokens of the B distinct sequences of a CFG pass (both branches share them)
     float* mod = nullptr;        // (S, MODROW) adaLN modulation of all blocks (adaln_kernel)
-    // T2S_MATH_BF16X3: k and V^T of the running block as split bf16 planes (t2s_x3.h), allocated on first use
     int math = 0;
-    __bf16 *k3 = nullptr, *v3 = nullptr;
-    __bf16* w3 = nullptr;        // split (3 x bf16) weights of the row chain in chunk order (t2s_rows_x3.h)
-    __bf16 *qkv3[t2s::NBLK], *proj3[t2s::NBLK], *fc13[t2s::NBLK], *fc2c3[t2s::NBLK];
-    // T2S_MATH_BF16: the same as ONE bf16 plane each (the h plane of the split), allocated on first use; a workspace of its
-    // own, so that switching between the arithmetics never reads another mode's planes
-    __bf16 *k1 = nullptr, *v1 = nullptr;
-    __bf16* w1 = nullptr;
-    __bf16 *qkv1[t2s::NBLK], *proj1[t2s::NBLK], *fc11[t2s::NBLK], *fc2c1[t2s::NBLK];
+    // T2S_MATH_BF16X3 / T2S_MATH_BF16: k and V^T of the running block as np split bf16 planes (t2s_x3.h; bf16 keeps the h plane
+    // of the split alone) and the row chain's weights as np planes in chunk order (t2s_rows_x3.h).  Allocated on the mode's
+    // first use (w != NULL: ready); a workspace per mode, so that switching between the arithmetics never reads another
+    // mode's planes
+    struct BfPlanes {
+        int np;
+        __bf16 *k = nullptr, *v = nullptr, *w = nullptr;
+        __bf16 *qkv[t2s::NBLK], *proj[t2s::NBLK], *fc1[t2s::NBLK], *fc2c[t2s::NBLK];   // pieces of w
+    };
+    BfPlanes bf[2] = {{3}, {1}};   // [math - T2S_MATH_BF16X3]
     hipEvent_t w_ev = nullptr;   // recorded behind the last t2s_dit_update_weights (what a first-use pack must wait for)
     // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     t2s_train_ws* train = nullptr;
@@ -56,4 +59,21 @@ struct TimeScope {   // records an event pair around the launches issued in its 
     }
     ~TimeScope() { if (on) (void)hipEventRecord(h->ev_pool.back(), st); }
 };
+
+// t2s_attn.hip
+int attn_init();
+int launch_attn_packed(const float* q, const float* k, const float* vT, float* o, int BH, hipStream_t st);
+// t2s_attn_x3.hip; np = 3: bf16x3, np = 1: bf16 (k / vT: np planes)
+int attn_xn_init(int np);
+int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st);
+// t2s_dit.hip
+int dit_forward_cfg_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr,
+                         const float* text, float* out_u, float* out_c, int B, hipStream_t st, int ws_seq0,
+                         const float* mod_table, int mod_rows, int mod_row0);
+int dit_adaln_table(t2s_dit* h, const float* temb_table, int steps, const float* text, int B, float* table, hipStream_t st);
+// t2s_sampler.hip: the library's non-blocking set-up stream and per-device run lock (t2s_sampler_create)
+hipStream_t lib_setup_stream(int dev);
+std::recursive_mutex* lib_pool_lock(int dev);
+// t2s_train.hip
+void train_free(t2s_dit* h);
 }  // namespace t2s

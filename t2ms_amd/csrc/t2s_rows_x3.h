@@ -136,17 +136,10 @@ static __global__ void pack_rows_xn_kernel(const float* __restrict__ P, bf16x8* 
     }
 }
 
-inline int pack_rows_x3(const float* P, bf16x8* dst, int N, int K, int fc2, hipStream_t st) {
+// np = 3: all three planes; np = 1: the h plane alone, in the same chunk order (a third of the bytes)
+inline int pack_rows_xn(int np, const float* P, bf16x8* dst, int N, int K, int fc2, hipStream_t st) {
     const int n = (fc2 ? K / 32 : N / 32) * 8 * 64;
-    pack_rows_xn_kernel<3><<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-// the h plane alone, in the same chunk order (a third of the bytes)
-inline int pack_rows_bf16p(const float* P, bf16x8* dst, int N, int K, int fc2, hipStream_t st) {
-    const int n = (fc2 ? K / 32 : N / 32) * 8 * 64;
-    pack_rows_xn_kernel<1><<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
+    (np == 3 ? pack_rows_xn_kernel<3> : pack_rows_xn_kernel<1>)<<<(n + 255) / 256, 256, 0, st>>>(P, dst, N, K, fc2);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -660,66 +653,56 @@ __global__ __launch_bounds__(256, 2) T2S_P1_KERNEL void dit_rows_bf16p_kernel(co
     dit_rows_xn_body<DO_MLP, DO_QKV, Split1>(a, wring1);
 }
 
+// host side: one set of helpers for both plane counts (np = 3: bf16x3, np = 1: the one-plane kernels, named first: their
+// place in the code object, profiles/EXPERIMENTS.md 0.16)
 template <bool DO_MLP, bool DO_QKV>
-inline int dit_rows_x3_init() {
-    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_x3_kernel<DO_MLP, DO_QKV>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_X3_LDS_BYTES));
+inline auto dit_rows_xn_kernel(int np) { return np == 1 ? dit_rows_bf16p_kernel<DO_MLP, DO_QKV> : dit_rows_x3_kernel<DO_MLP, DO_QKV>; }
+inline int rows_xn_lds_bytes(int np) { return np == 3 ? ROWS_X3_LDS_BYTES : ROWS_P1_LDS_BYTES; }
+
+inline int dit_rows_xn_init(int np) {   // all three instances of a mode
+    const void* const kernels[3] = {reinterpret_cast<const void*>(dit_rows_xn_kernel<false, true>(np)),
+                                    reinterpret_cast<const void*>(dit_rows_xn_kernel<true, true>(np)),
+                                    reinterpret_cast<const void*>(dit_rows_xn_kernel<true, false>(np))};
+    for (const void* k : kernels)
+        T2S_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, rows_xn_lds_bytes(np)));
     return T2S_OK;
 }
 
 template <bool DO_MLP, bool DO_QKV>
-inline int launch_dit_rows_x3(const RowArgsX3& a, hipStream_t st) {
+inline int launch_dit_rows_xn(int np, const RowArgsX3& a, hipStream_t st) {
     if (a.M <= 0 || a.M % 32 != 0) {
-        set_error("dit_rows_x3: M=%d must be a positive multiple of 32", a.M);
+        set_error("dit_rows_xn (%d planes): M=%d must be a positive multiple of 32", np, a.M);
         return T2S_E_INVALID;
     }
     const int tiles = a.M / 32;
 #ifdef T2S_X3_STAMP
-    static unsigned long long* buf = nullptr;
-    static int calls = 0;
-    if (!buf) {
-        T2S_HIP_CHECK(hipMalloc((void**)&buf, 256 * 4 * 8 * sizeof(unsigned long long)));
-        T2S_HIP_CHECK(hipMemset(buf, 0, 256 * 4 * 8 * sizeof(unsigned long long)));
+    if (np == 3) {
+        static unsigned long long* buf = nullptr;
+        static int calls = 0;
+        if (!buf) {
+            T2S_HIP_CHECK(hipMalloc((void**)&buf, 256 * 4 * 8 * sizeof(unsigned long long)));
+            T2S_HIP_CHECK(hipMemset(buf, 0, 256 * 4 * 8 * sizeof(unsigned long long)));
+        }
+        RowArgsX3 a2 = a;
+        a2.stamp = buf;
+        dit_rows_x3_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_X3_LDS_BYTES, st>>>(a2);
+        T2S_LAUNCH_CHECK();
+        if (++calls == 40 && tiles >= 4096) {      // one dump per instance, well after warm-up, at a chip-filling launch
+            static unsigned long long host[256 * 4 * 8];
+            T2S_HIP_CHECK(hipStreamSynchronize(st));
+            T2S_HIP_CHECK(hipMemcpy(host, buf, sizeof(host), hipMemcpyDeviceToHost));
+            double sum[8] = {};
+            const int n = (tiles + 3) / 4 < 256 ? (tiles + 3) / 4 : 256;
+            for (int i = 0; i < n * 4; ++i)
+                for (int k = 0; k < 8; ++k) sum[k] += (double)host[i * 8 + k];
+            fprintf(stderr, "x3_stamp <%d,%d> tiles %d: cycles per wave (s_memtime, 100 MHz ticks x? see tools/x3_stamp.sh) total %.0f | prologue %.0f mfma %.0f valu %.0f "
+                            "vmcnt %.0f barrier %.0f issue %.0f epilogue %.0f\n", (int)DO_MLP, (int)DO_QKV, tiles, sum[7] / (n * 4), sum[0] / (n * 4),
+                    sum[1] / (n * 4), sum[2] / (n * 4), sum[3] / (n * 4), sum[4] / (n * 4), sum[5] / (n * 4), sum[6] / (n * 4));
+        }
+        return T2S_OK;
     }
-    RowArgsX3 a2 = a;
-    a2.stamp = buf;
-    dit_rows_x3_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_X3_LDS_BYTES, st>>>(a2);
-    T2S_LAUNCH_CHECK();
-    if (++calls == 40 && tiles >= 4096) {      // one dump per instance, well after warm-up, at a chip-filling launch
-        static unsigned long long host[256 * 4 * 8];
-        T2S_HIP_CHECK(hipStreamSynchronize(st));
-        T2S_HIP_CHECK(hipMemcpy(host, buf, sizeof(host), hipMemcpyDeviceToHost));
-        double sum[8] = {};
-        const int n = (tiles + 3) / 4 < 256 ? (tiles + 3) / 4 : 256;
-        for (int i = 0; i < n * 4; ++i)
-            for (int k = 0; k < 8; ++k) sum[k] += (double)host[i * 8 + k];
-        fprintf(stderr, "x3_stamp <%d,%d> tiles %d: cycles per wave (s_memtime, 100 MHz ticks x? see tools/x3_stamp.sh) total %.0f | prologue %.0f mfma %.0f valu %.0f "
-                        "vmcnt %.0f barrier %.0f issue %.0f epilogue %.0f\n", (int)DO_MLP, (int)DO_QKV, tiles, sum[7] / (n * 4), sum[0] / (n * 4),
-                sum[1] / (n * 4), sum[2] / (n * 4), sum[3] / (n * 4), sum[4] / (n * 4), sum[5] / (n * 4), sum[6] / (n * 4));
-    }
-    return T2S_OK;
-#else
-    dit_rows_x3_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_X3_LDS_BYTES, st>>>(a);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
 #endif
-}
-
-template <bool DO_MLP, bool DO_QKV>
-inline int dit_rows_bf16p_init() {
-    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_bf16p_kernel<DO_MLP, DO_QKV>),
-                                      hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_P1_LDS_BYTES));
-    return T2S_OK;
-}
-
-template <bool DO_MLP, bool DO_QKV>
-inline int launch_dit_rows_bf16p(const RowArgsX3& a, hipStream_t st) {
-    if (a.M <= 0 || a.M % 32 != 0) {
-        set_error("dit_rows_bf16p: M=%d must be a positive multiple of 32", a.M);
-        return T2S_E_INVALID;
-    }
-    const int tiles = a.M / 32;
-    dit_rows_bf16p_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_P1_LDS_BYTES, st>>>(a);
+    dit_rows_xn_kernel<DO_MLP, DO_QKV>(np)<<<(tiles + 3) / 4, 256, rows_xn_lds_bytes(np), st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

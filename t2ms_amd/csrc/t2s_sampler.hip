@@ -12,16 +12,11 @@
 #include <stdlib.h>
 #include <vector>
 
-#include "t2s_common.h"
+#include "t2s_dit_internal.h"
 
-struct t2s_dit;
 struct t2s_vae;
 
 namespace t2s {
-int dit_forward_cfg_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr,
-                         const float* text, float* out_u, float* out_c, int B, hipStream_t st, int ws_seq0,
-                         const float* mod_table, int mod_rows, int mod_row0);
-int dit_adaln_table(t2s_dit* h, const float* temb_table, int steps, const float* text, int B, float* table, hipStream_t st);
 
 // ---------------------------------------------------------------- Philox4x32-10 + Box-Muller
 struct u32x4 { uint32_t x, y, z, w; };

@@ -26,7 +26,6 @@ int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* 
                          hipStream_t st);
 int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows, const float* do_rows,
              const float* lse, float* dsum, float* dqkv_rows, int BH, hipStream_t st);
-void train_free(t2s_dit* h);
 int attn16_train_fwd(const __bf16* q, const __bf16* k, const __bf16* v, __bf16* o_rows, float* lse, int BH, hipStream_t st);
 int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* o_rows, const __bf16* do_rows,
                const float* lse, float* dsum, __bf16* dqkv_rows, int BH, hipStream_t st);

@@ -431,6 +431,35 @@ def test_switching_between_the_three_arithmetics_on_one_handle(dev):
     assert not torch.equal(want["bf16"], want["bf16x3"]) and not torch.equal(want["bf16"], want["f32"])
 
 
+@gpu
+@pytest.mark.parametrize("mode", ["bf16x3", "bf16"])
+def test_first_use_packs_behind_a_weight_update_on_a_side_stream(dev, mode):
+    """A bf16 mode's FIRST use right behind a t2s_dit_update_weights that was enqueued on a non-default (non-blocking) stream:
+    the planes are packed on the library's set-up stream, which nothing but the handle's event orders after that update.
+    The side stream is kept busy first (elementwise passes over 512 MiB, some tens of ms), so that the update is still
+    PENDING when set_math packs: a pack that does not wait reads the seed-2025 weights and the comparison fails."""
+    B = 3
+    x = synth.make_latents(5, B).to(dev)
+    t = torch.tensor([3, 500, 999], device=dev)
+    text = synth.make_text_embeddings(5, B).to(dev)
+    busy = torch.zeros(1 << 27, device=dev)
+    side = torch.cuda.Stream(dev)
+    with torch.no_grad():
+        want = _dit(dev, 7, math=mode)(input=x, t=t, text_input=text)
+        m = _dit(dev, 2025, math="f32")
+        m(input=x, t=t, text_input=text)                                   # the handle exists, no plane is allocated
+        hid = m.t2s_handle_id()
+        torch.cuda.synchronize(dev)
+        with torch.cuda.stream(side):
+            m.load_state_dict(synth.make_dit_state_dict(7), strict=True)
+            for _ in range(64):
+                busy.add_(1.0)
+            m(input=x, t=t, text_input=text)                               # t2s_dit_update_weights, on the side stream
+            y = m.set_math(mode)(input=x, t=t, text_input=text)            # first use: allocate and pack
+        side.synchronize()
+    assert m.t2s_handle_id() == hid and torch.equal(y, want), mode
+
+
 # ---------------------------------------------------------------------------------------------- 9. the driver
 @gpu
 def test_infer_driver_math_bf16(dev, tmp_path, monkeypatch, capsys):
