@@ -11,7 +11,8 @@ files each metric reads (evaluation.py:285-314: `x_1` of run_0 against the base 
 Additions: `ED` and `DTW` may be named in --method_list (the reference defines both, evaluation.py:137-163, and never
 calls them); `--align_runs` re-orders every run's rows to run_0's ground-truth order first -- each `infer()` call shuffles
 its test loader independently (dataloader.py:111; the reference never seeds), so WITHOUT it row i of one file is not row i of
-another, here exactly as in the reference.
+another, here exactly as in the reference; `--cfid_engine {torch,hip}` names what trains C-FID's TS2Vec encoder
+(t2ms_amd.ts2vec; left unset it is T2S_TS2VEC_FIT from the environment, else torch autograd as before).
 """
 import argparse
 import datetime
@@ -66,7 +67,7 @@ def evaluate_data(args, ori_data, gen_data):
     result = {}
     if "C-FID" in methods:
         from t2ms_amd.ts2vec import initialize_ts2vec            # evaluation.py:238-243: TS2Vec trained on the originals
-        model = initialize_ts2vec(ori, device=args.device)
+        model = initialize_ts2vec(ori, device=args.device, engine=getattr(args, "cfid_engine", None))
         result["C-FID"] = M.fid(model.encode(ori, encoding_window="full_series"), model.encode(gen, encoding_window="full_series"))
     if "MSE" in methods or "WAPE" in methods:
         mse, wape, _ = M.mse_wape(ori, gen, device=args.device)
@@ -117,6 +118,8 @@ def build_parser():
     p.add_argument("--denoiser", type=str, default="DiT", help="DiT or MLP")
     p.add_argument("--cfg_scale", type=float, default=9.0, help="CFG Scale")
     p.add_argument("--total_step", type=int, default=10, help="total step sampled from [0,1]")
+    p.add_argument("--cfid_engine", choices=("torch", "hip"), default=None,
+                   help="what trains the C-FID encoder: torch autograd or the fused HIP step (unset: T2S_TS2VEC_FIT, else torch)")
     p.add_argument("--align_runs", action="store_true",
                    help="re-order every run's rows to one ground-truth order before comparing (see the module docstring)")
     return p

@@ -578,6 +578,55 @@ typedef struct t2s_ts2vec_weights {
  * output_dims) * T * 4 bytes must fit in 160 KB of LDS (T <= 128 at the evaluation's 64 / 100 channels). */
 int t2s_ts2vec_encode(const t2s_ts2vec_weights* w, const float* x, float* rep, float* full, int B, int T, void* stream);
 
+/* One training step of TS2Vec.fit (evaluate/ts2vec.py:113-140): the TRAINING forward of both cropped views (binomial
+ * time mask after input_fc, dropout on the representations), hierarchical_contrastive_loss (:451-497) of their overlap,
+ * and the backward down to every parameter.  fp32 throughout, exact erf GELU and its exact derivative.  The entries below
+ * never allocate, copy synchronously or synchronise: the caller owns the workspace, the calls are capturable and need no
+ * per-device lock.  Bit-reproducible: every weight gradient is summed over (view, series, time) in that order by one
+ * thread, the loss terms in (level, kind, task) order; no floating-point atomics. */
+#define T2S_TS2VEC_TRAIN_MAX_T 128
+#define T2S_TS2VEC_TRAIN_MAX_B 16
+/* The gradient of every tensor of t2s_ts2vec_weights, in its own layout; every entry is OVERWRITTEN. */
+typedef struct t2s_ts2vec_grads {
+    float *fc_w, *fc_b;
+    float* conv1_w[T2S_TS2VEC_MAX_BLOCKS];
+    float* conv1_b[T2S_TS2VEC_MAX_BLOCKS];
+    float* conv2_w[T2S_TS2VEC_MAX_BLOCKS];
+    float* conv2_b[T2S_TS2VEC_MAX_BLOCKS];
+    float *proj_w, *proj_b;
+} t2s_ts2vec_grads;
+/* View row b is x[b, start[b] : start[b]+length] (start is clamped into [0, T-length] on the device). */
+typedef struct t2s_ts2vec_view {
+    const int32_t* start;   /* (B) device */
+    const uint8_t* mask;    /* (B, length) device; 0 = the time step is hidden after input_fc */
+    const uint8_t* keep;    /* (B, output_dims, length) device; the dropout draw: 0 = dropped, else multiplied by keep_scale */
+    int length;             /* crop_l <= length <= T */
+    int pad_;
+} t2s_ts2vec_view;
+typedef struct t2s_ts2vec_step {
+    const float* x;         /* (B, T, input_dims) device */
+    int B, T, crop_l;       /* the loss compares view 0's last crop_l steps with view 1's first crop_l */
+    int temporal_unit;
+    float alpha;            /* weight of the instance loss (the reference: 0.5) */
+    float keep_scale;       /* 1 / (1 - p_dropout) as the caller's dropout evaluates it in fp32 */
+    int x_nan_count;        /* NaNs the caller counted in x on the host; anything but 0 is refused (x is never read here) */
+    int pad_;
+    t2s_ts2vec_view view[2];
+} t2s_ts2vec_step;
+/* Bytes of workspace a step of up to max_B series x max_T time steps needs (0 and an error message if unsupported). */
+uint64_t t2s_ts2vec_train_workspace_bytes(const t2s_ts2vec_weights* w, int max_B, int max_T);
+/* Supported: what t2s_ts2vec_encode supports (equal hidden widths, depth < T2S_TS2VEC_MAX_BLOCKS, its LDS bound),
+ * T <= 128, 1 <= B <= 16, NaN-free x; anything else is T2S_E_INVALID before any launch.  loss_out: device scalar.
+ * A block whose dilation is >= a view's length contributes through its centre tap only: its outer-tap gradients are
+ * exact zeros (no work is done for them).  A max-pool tie sends the gradient to the lower index (torch's rule). */
+int t2s_ts2vec_train_step(const t2s_ts2vec_weights* w, const t2s_ts2vec_grads* grads, const t2s_ts2vec_step* step,
+                          float* loss_out, void* workspace, uint64_t ws_bytes, void* stream);
+/* torch.optim.swa_utils.AveragedModel.update_parameters for a whole parameter list in one launch:
+ * avg += (p - avg) / (n_averaged + 1).  table_dev as for t2s_adamw_step_multi with `param` = the average and `grad` = the
+ * current weights (exp_avg / exp_avg_sq unused); n_averaged >= 1 (the first update is a copy the host does). */
+int t2s_swa_update_multi(const t2s_adamw_tensor* table_dev, int n_tensors, uint64_t total_chunks, int64_t n_averaged,
+                         void* stream);
+
 /* ------------------------------------------------------------------------ *
  * MLP denoiser of BASELINE configs[0]: model/denoiser/mlp.py:49-94 (MLPlayer x 8 on a
  * (64, 6) latent; forward, and the backward for train.py --denoiser MLP).

@@ -78,6 +78,28 @@ class Ts2vecWeights(C.Structure):
                 ("proj_w", C.c_void_p), ("proj_b", C.c_void_p)]
 
 
+TS2VEC_TRAIN_MAX_T, TS2VEC_TRAIN_MAX_B = 128, 16   # t2s.h: T2S_TS2VEC_TRAIN_MAX_T / _MAX_B
+
+
+class Ts2vecGrads(C.Structure):          # t2s_ts2vec_grads: the pointer fields of Ts2vecWeights, writable
+    _fields_ = [f for f in Ts2vecWeights._fields_ if f[1] is not C.c_int]
+
+
+class Ts2vecView(C.Structure):
+    _fields_ = [("start", C.c_void_p), ("mask", C.c_void_p), ("keep", C.c_void_p), ("length", C.c_int), ("pad_", C.c_int)]
+
+
+class Ts2vecStep(C.Structure):
+    _fields_ = [("x", C.c_void_p), ("B", C.c_int), ("T", C.c_int), ("crop_l", C.c_int), ("temporal_unit", C.c_int),
+                ("alpha", C.c_float), ("keep_scale", C.c_float), ("x_nan_count", C.c_int), ("pad_", C.c_int),
+                ("view", Ts2vecView * 2)]
+
+
+class AdamwTensor(C.Structure):          # t2s_adamw_tensor
+    _fields_ = [("param", C.c_void_p), ("grad", C.c_void_p), ("exp_avg", C.c_void_p), ("exp_avg_sq", C.c_void_p),
+                ("n", C.c_uint64)]
+
+
 MLP_LAYERS, MLP_PACKED_FLOATS = 8, 397888   # t2s.h: T2S_MLP_LAYERS, T2S_MLP_PACKED_FLOATS
 MLP_LAYER_FIELDS = (("value_w", "cross_attn.value.weight"), ("value_b", "cross_attn.value.bias"),
                     ("proj_w", "cross_attn.proj.weight"), ("proj_b", "cross_attn.proj.bias"),
@@ -136,6 +158,9 @@ SYMBOLS = {
     "t2s_eval_crps": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "t2s_eval_dtw": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_ts2vec_encode": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP]),
+    "t2s_ts2vec_train_workspace_bytes": (_U64, [C.POINTER(Ts2vecWeights), _I, _I]),
+    "t2s_ts2vec_train_step": (_I, [C.POINTER(Ts2vecWeights), C.POINTER(Ts2vecGrads), C.POINTER(Ts2vecStep), _VP, _VP, _U64, _VP]),
+    "t2s_swa_update_multi": (_I, [_VP, _I, _U64, C.c_int64, _VP]),
     "t2s_mlp_pack": (_I, [C.POINTER(MlpWeights), _VP, _VP]),
     "t2s_mlp_forward": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_mlp_backward": (_I, [C.POINTER(MlpWeights), _VP, _VP, _VP, _VP, _VP, _VP, _VP, C.POINTER(MlpGrads), _VP, _U64, _I, _VP]),

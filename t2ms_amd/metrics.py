@@ -222,7 +222,7 @@ def main(argv=None):
             g3 = gen if gen.ndim == 3 else gen[:, :, None]
             model = initialize_ts2vec(o3.astype(np.float32), device="cuda")
             print(f"samples {ori.shape[0]}  C-FID {fid(model.encode(o3, encoding_window='full_series'), model.encode(g3, encoding_window='full_series')):.6f}"
-                  f"  (TS2Vec trained {model.n_iters} iterations on the original series)")
+                  f"  (TS2Vec trained {model.n_iters} iterations on the original series, engine {model.engine}: T2S_TS2VEC_FIT)")
     runs = sorted((r for r in os.listdir(d) if r.startswith("run_") and r[4:].isdigit()), key=lambda r: int(r[4:]))
     if runs:
         ori = np.load(os.path.join(d, runs[-1], "x_1.npy"))                                  # evaluation.py:304-314
