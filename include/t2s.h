@@ -558,6 +558,34 @@ int t2s_eval_crps(const float* ori, const float* gen, float* per_sample, float* 
 int t2s_eval_dtw(const float* ori, const float* gen, float* per_sample, float* out, int n, int L, int n_series,
                  void* stream);
 
+/* Feature-based measures of evaluate/feature_based_measures.py: calculate_mdd (:30-94), calculate_acd (:98-161),
+ * calculate_sd (:165-191), calculate_kd (:195-223).  They compare the SET ori ("real") with the SET gen ("fake"), both
+ * (n, L, n_series) fp32 contiguous on the device; no row of one is paired with a row of the other, so a common
+ * permutation of the rows changes nothing.  n >= 2, 1 <= L <= 4096, n_series >= 1 (L * n_series <= 2^24); anything else,
+ * a NULL array or a workspace smaller than t2s_eval_features_workspace_bytes is T2S_E_INVALID before any launch.  The
+ * entries never allocate, copy or synchronise and keep no state: the caller owns the workspace (its contents are
+ * scratch; the two entries use disjoint parts of it).  The same input gives the same bits on every call, whatever the
+ * device: sums run in fp64 over chunks of samples that depend on n alone, MDD's counts are integers. */
+#define T2S_EVAL_MAX_LAG 64  /* ACFLoss(max_lag=64): K = min(64, L) lags */
+#define T2S_EVAL_MDD_BINS 50 /* calculate_mdd: n_bins=50 */
+/* Bytes of workspace t2s_eval_moments / t2s_eval_mdd need at this shape (0 and an error message if unsupported). */
+uint64_t t2s_eval_features_workspace_bytes(int n, int L, int n_series);
+/* ACD, SD, KD from one statistics pass.  Per channel, over its n*L values centred by the channel mean: acf_k = mean of
+ * x[i,t] x[i,t-k] over (i, t >= k) / population variance for k < K (acf_torch, :98-109); skewness = mean x^3 / unbiased
+ * std^3 (skew_torch, :165-172); excess kurtosis = mean x^4 / population variance^2 - 3 (kurtosis_torch, :195-204).
+ * out[3] = [ACD, SD, KD] = the means over channels of [sqrt(sum_k (acf_k(gen) - acf_k(ori))^2), |skew(gen) - skew(ori)|,
+ * |kurt(gen) - kurt(ori)|].  stats (may be NULL): (2, n_series, 4 + K), set 0 = ori, 1 = gen, each row
+ * [mean, population variance, skewness, excess kurtosis, acf_0 .. acf_{K-1}]. */
+int t2s_eval_moments(const float* ori, const float* gen, float* stats, float* out, int n, int L, int n_series,
+                     void* workspace, uint64_t workspace_bytes, void* stream);
+/* MDD (HistoLoss + histogram_torch, :30-94).  Per column (t, c): 50 equal bins between the min and the max of the n real
+ * values (max = min + 1e-5 for a constant column), real and fake values counted per bin (torch.histc's binning, the max
+ * in the last bin; a fake value outside [min, max] counts nowhere), loss = mean over bins of |fake density - real
+ * density|, density = count / (n * bin width).  per_column (may be NULL): (L, n_series) column losses -- the reference
+ * lists them channel-major; out[0] = their mean. */
+int t2s_eval_mdd(const float* ori, const float* gen, float* per_column, float* out, int n, int L, int n_series,
+                 void* workspace, uint64_t workspace_bytes, void* stream);
+
 /* TS2Vec encoder of the C-FID metric: evaluate/ts2vec.py:352-399 (TSEncoder.forward, eval mode, mask 'all_true') followed
  * by the 'full_series' pooling of TS2Vec.encode (:236-245).  Device pointers to the state-dict tensors:
  * input_fc.{weight (hidden,input_dims),bias}; block i in [0,depth]: feature_extractor.net.i.conv{1,2}.conv.{weight

@@ -22,6 +22,7 @@ MATH_F32, MATH_BF16X3, MATH_BF16 = 0, 1, 2    # t2s.h: T2S_MATH_F32 / T2S_MATH_B
 MATH_CODES = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "bf16": MATH_BF16}
 DIT_N_TENSORS = 10 + 10 * N_BLOCKS   # t2s.h: T2S_DIT_N_TENSORS (pointers of t2s_dit_weights, declaration order)
 MSE_SCRATCH_FLOATS = 1024       # t2s.h: T2S_MSE_SCRATCH_FLOATS
+EVAL_MAX_LAG, EVAL_MDD_BINS = 64, 50   # t2s.h: T2S_EVAL_MAX_LAG / T2S_EVAL_MDD_BINS
 
 c_float_p = C.c_void_p  # device pointers travel as opaque addresses
 
@@ -157,6 +158,9 @@ SYMBOLS = {
     "t2s_eval_ed": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_eval_crps": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "t2s_eval_dtw": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "t2s_eval_features_workspace_bytes": (_U64, [_I, _I, _I]),
+    "t2s_eval_moments": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
+    "t2s_eval_mdd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
     "t2s_ts2vec_encode": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_ts2vec_train_workspace_bytes": (_U64, [C.POINTER(Ts2vecWeights), _I, _I]),
     "t2s_ts2vec_train_step": (_I, [C.POINTER(Ts2vecWeights), C.POINTER(Ts2vecGrads), C.POINTER(Ts2vecStep), _VP, _VP, _U64, _VP]),

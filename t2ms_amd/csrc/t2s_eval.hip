@@ -11,6 +11,24 @@
 //   best run can: score_i = 1 / (g* + 1) if sim_{g*} > threshold else 0, where g* is the RUN INDEX of the best
 //   run (evaluation.py:37-41 take `idx + 1` of the argsort entry, not its position); ties go to the largest
 //   index (reversed stable argsort).  MRR = mean_i score_i.
+//
+// Feature-based measures of evaluate/feature_based_measures.py on two SETS ori ("real") and gen ("fake") of shape
+// (n, L, n_series); none of them pairs row i with row i.  Per channel c, over all n*L values x of the channel, centred by
+// the channel mean (two passes: the mean first, then centred sums, fp64 throughout), N = n*L, K = min(64, L):
+//   lag_k  = sum_{i, t >= k} x[i,t] x[i,t-k]            acf_k = (lag_k / (n (L-k))) / var_pop,  var_pop = lag_0 / N  (:98-109)
+//   ACD    = mean_c sqrt(sum_k (acf_k(gen) - acf_k(ori))^2)                                                        (:155-161)
+//   skew   = (sum x^3 / N) / std^3,  std^2 = lag_0 / (N-1)       SD = mean_c |skew(gen) - skew(ori)|     (:165-172,183-191)
+//   kurt   = (sum x^4 / N) / var_pop^2 - 3                       KD = mean_c |kurt(gen) - kurt(ori)|     (:195-204,215-223)
+// The samples are cut into P = min(n, 1024) chunks (a function of n alone); a workgroup sums one chunk in a fixed order
+// and a fold kernel adds the P partials in index order: the grid never changes a bit of the result.
+// MDD (HistoLoss + histogram_torch, :30-94), per column (t, c) = the n values ori[:, t, c]:
+//   a = min, b = max of the real column (b = a + 1e-5 when b == a); 50 equal bins on [a, b], delta = (b - a) / 50 (fp64
+//   here); real count: bin floor((x - a) / (b - a) 50), x == b in the last bin (torch.histc);
+//   fake count of bin k: the fake values with delta/2 - |x - centre_k| > 0, which off a bin edge is the real side's
+//   binning restricted to [a, b] -- the kernel bins both sides with that one rule (ON an edge the reference's own answer
+//   hangs on the rounding of its fp32 centres; here the value goes to the upper bin, and b to the last);
+//   loss(t, c) = mean_k |count_gen[k] - count_ori[k]| / (n delta);  MDD = mean over the L*n_series columns.
+// Counts are integers added with LDS / global integer atomics: exact under any split of n over workgroups.
 #include "t2s_common.h"
 
 namespace t2s {
@@ -210,6 +228,288 @@ __global__ __launch_bounds__(256) void eval_dtw_kernel(const float* __restrict__
     if (threadIdx.x == 0) per_sample[smp] = (float)sqrt(diag[((2 * L - 2) % 3) * L + (L - 1)]);
 }
 
+// ---- feature-based measures (evaluate/feature_based_measures.py): see the head of this file
+constexpr int FEAT_MAX_LAG = T2S_EVAL_MAX_LAG;     // 64: ACFLoss(max_lag=64)
+constexpr int FEAT_BINS = T2S_EVAL_MDD_BINS;       // 50: calculate_mdd's n_bins
+constexpr int FEAT_MAX_CHUNKS = 1024;
+constexpr int FEAT_TILE = 64;                      // columns per MDD workgroup: one wave along the contiguous (t, c) axis
+
+struct FeatLayout {          // byte offsets into the caller's workspace; a function of (n, L, n_series) alone
+    int P, K;
+    size_t cols;
+    size_t mean_part, stat_part, chan, minmax, counts, col_loss, total;
+};
+
+__host__ __device__ inline int feat_lags(int L) { return L < FEAT_MAX_LAG ? L : FEAT_MAX_LAG; }
+
+inline FeatLayout feat_layout(int n, int L, int S) {
+    FeatLayout w{};
+    w.P = n < FEAT_MAX_CHUNKS ? n : FEAT_MAX_CHUNKS;
+    w.K = feat_lags(L);
+    w.cols = (size_t)L * S;
+    size_t o = 0;
+    w.mean_part = o; o += (size_t)2 * w.P * S * sizeof(double);
+    w.stat_part = o; o += (size_t)2 * w.P * S * (2 + w.K) * sizeof(double);
+    w.chan = o;      o += (((size_t)3 * S * sizeof(float)) + 15) / 16 * 16;
+    w.minmax = o;    o += (size_t)2 * w.cols * sizeof(unsigned);
+    w.counts = o;    o += (size_t)2 * FEAT_BINS * w.cols * sizeof(unsigned);
+    w.col_loss = o;  o += w.cols * sizeof(float);
+    w.total = (o + 255) / 256 * 256;
+    return w;
+}
+
+// sum of one double per thread of a 256-thread workgroup, the same tree on every call; every thread gets the sum
+__device__ __forceinline__ double feat_block_sum(double v, double* red) {
+    red[threadIdx.x] = v;
+    __syncthreads();
+    for (int o = 128; o >= 1; o >>= 1) {
+        if ((int)threadIdx.x < o) red[threadIdx.x] += red[threadIdx.x + o];
+        __syncthreads();
+    }
+    const double r = red[0];
+    __syncthreads();
+    return r;
+}
+
+// the channel mean from the P chunk sums, folded the same way by whoever needs it
+__device__ __forceinline__ double feat_mean(const double* __restrict__ part, int P, int S, int c, double count, double* red) {
+    double s = 0.0;
+    for (int p = threadIdx.x; p < P; p += 256) s += part[(size_t)p * S + c];
+    return feat_block_sum(s, red) / count;
+}
+
+// grid (P, 2): chunk p of set blockIdx.y -> mean_part[set][p][c] = sum of the chunk's values of channel c
+__global__ __launch_bounds__(256) void feat_sum_kernel(const float* __restrict__ ori, const float* __restrict__ gen,
+                                                       double* __restrict__ mean_part, int n, int L, int S) {
+    __shared__ double red[256];
+    const int P = gridDim.x, p = blockIdx.x, set = blockIdx.y;
+    const size_t s0 = (size_t)p * n / P, s1 = (size_t)(p + 1) * n / P;
+    const float* x = (set ? gen : ori) + s0 * L * S;
+    const size_t cnt = (s1 - s0) * L;
+    for (int c = 0; c < S; ++c) {
+        double s = 0.0;
+        for (size_t j = threadIdx.x; j < cnt; j += 256) s += (double)x[j * S + c];
+        s = feat_block_sum(s, red);
+        if (threadIdx.x == 0) mean_part[((size_t)set * P + p) * S + c] = s;
+    }
+}
+
+// grid (P, 2), dynamic LDS = L doubles: per channel the chunk's centred sums [sum x^3, sum x^4, lag_0 .. lag_{K-1}].
+// A series of one channel is staged centred in LDS; lane k of wave w adds x[t] x[t-k] for t = w, w+4, ...: x[t] is a
+// broadcast and x[t-k] 64 consecutive doubles, so neither read conflicts.
+__global__ __launch_bounds__(256) void feat_stats_kernel(const float* __restrict__ ori, const float* __restrict__ gen,
+                                                         const double* __restrict__ mean_part, double* __restrict__ stat_part,
+                                                         int n, int L, int S) {
+    extern __shared__ double xs[];
+    __shared__ double red[256];
+    const int P = gridDim.x, p = blockIdx.x, set = blockIdx.y, K = feat_lags(L);
+    const size_t s0 = (size_t)p * n / P, s1 = (size_t)(p + 1) * n / P;
+    const float* x = set ? gen : ori;
+    const int k = threadIdx.x & 63, w = threadIdx.x >> 6;
+    for (int c = 0; c < S; ++c) {
+        const double mean = feat_mean(mean_part + (size_t)set * P * S, P, S, c, (double)n * (double)L, red);
+        double lag = 0.0, m3 = 0.0, m4 = 0.0;
+        for (size_t i = s0; i < s1; ++i) {
+            const float* row = x + i * L * S + c;
+            for (int t = threadIdx.x; t < L; t += 256) {
+                const double d = (double)row[(size_t)t * S] - mean, d2 = d * d;
+                xs[t] = d;
+                m3 += d2 * d;
+                m4 += d2 * d2;
+            }
+            __syncthreads();
+            if (k < K)
+                for (int t = w; t < L; t += 4)
+                    if (t >= k) lag += xs[t] * xs[t - k];
+            __syncthreads();
+        }
+        double* dst = stat_part + (((size_t)set * P + p) * S + c) * (2 + K);
+        m3 = feat_block_sum(m3, red);
+        m4 = feat_block_sum(m4, red);
+        red[threadIdx.x] = lag;                       // [wave][lag]
+        __syncthreads();
+        if ((int)threadIdx.x < K) dst[2 + k] = ((red[k] + red[64 + k]) + red[128 + k]) + red[192 + k];
+        if (threadIdx.x == 0) { dst[0] = m3; dst[1] = m4; }
+        __syncthreads();
+    }
+}
+
+// grid (n_series): folds the P partials of channel c in index order, derives mean / var / skew / kurt / acf of both
+// sets (-> stats[set][c][4 + K] when asked for) and the channel's three differences -> chan[3][S]
+__global__ __launch_bounds__(256) void feat_fold_kernel(const double* __restrict__ mean_part, const double* __restrict__ stat_part,
+                                                        float* __restrict__ stats, float* __restrict__ chan,
+                                                        int n, int L, int S, int P) {
+    __shared__ double red[256];
+    __shared__ double tot[2][2 + FEAT_MAX_LAG];
+    __shared__ double mean[2];
+    const int c = blockIdx.x, K = feat_lags(L);
+    const double N = (double)n * (double)L;
+    for (int set = 0; set < 2; ++set) {
+        const double m = feat_mean(mean_part + (size_t)set * P * S, P, S, c, N, red);
+        if (threadIdx.x == 0) mean[set] = m;
+    }
+    if ((int)threadIdx.x < 2 * (2 + K)) {
+        const int set = threadIdx.x / (2 + K), j = threadIdx.x - set * (2 + K);
+        double s = 0.0;
+        for (int p = 0; p < P; ++p) s += stat_part[(((size_t)set * P + p) * S + c) * (2 + K) + j];
+        tot[set][j] = s;
+    }
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        double skew[2], kurt[2], var[2];
+        for (int set = 0; set < 2; ++set) {
+            var[set] = tot[set][2] / N;
+            const double sd = sqrt(tot[set][2] / (N - 1.0));
+            skew[set] = (tot[set][0] / N) / (sd * sd * sd);
+            kurt[set] = (tot[set][1] / N) / (var[set] * var[set]) - 3.0;
+        }
+        double acd = 0.0;
+        for (int j = 0; j < K; ++j) {
+            double acf[2];
+            for (int set = 0; set < 2; ++set) {
+                acf[set] = (tot[set][2 + j] / ((double)n * (double)(L - j))) / var[set];
+                if (stats != nullptr) stats[((size_t)set * S + c) * (4 + K) + 4 + j] = (float)acf[set];
+            }
+            acd += (acf[1] - acf[0]) * (acf[1] - acf[0]);
+        }
+        if (stats != nullptr)
+            for (int set = 0; set < 2; ++set) {
+                float* o = stats + ((size_t)set * S + c) * (4 + K);
+                o[0] = (float)mean[set]; o[1] = (float)var[set]; o[2] = (float)skew[set]; o[3] = (float)kurt[set];
+            }
+        chan[c] = (float)sqrt(acd);
+        chan[S + c] = (float)fabs(skew[1] - skew[0]);
+        chan[2 * S + c] = (float)fabs(kurt[1] - kurt[0]);
+    }
+}
+
+// grid (3): out[b] = mean over channels of chan[b][:]
+__global__ __launch_bounds__(256) void feat_chan_mean_kernel(const float* __restrict__ chan, float* __restrict__ out, int S) {
+    __shared__ double red[256];
+    double s = 0.0;
+    for (int c = threadIdx.x; c < S; c += 256) s += (double)chan[(size_t)blockIdx.x * S + c];
+    s = feat_block_sum(s, red);
+    if (threadIdx.x == 0) out[blockIdx.x] = (float)(s / (double)S);
+}
+
+// floats as unsigned keys of the same order, so that min / max across workgroups are integer atomics
+__device__ __forceinline__ unsigned feat_key(float v) {
+    const unsigned u = __float_as_uint(v);
+    return (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+}
+__device__ __forceinline__ float feat_unkey(unsigned k) {
+    return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k);
+}
+
+__global__ __launch_bounds__(256) void feat_mdd_init_kernel(unsigned* __restrict__ minmax, unsigned* __restrict__ counts, size_t cols) {
+    const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (i < cols) { minmax[i] = 0xffffffffu; minmax[cols + i] = 0u; }
+    if (i < 2 * FEAT_BINS * cols) counts[i] = 0u;
+}
+
+// How a workgroup of the two MDD passes walks its tile: the lanes of a wave run along the contiguous column axis (tc
+// columns, 64 in a full tile) and, where the tile is narrower than a wave, along 64 / tc samples as well; the four waves
+// take different samples.  blockIdx.y owns the samples [s0, s1).
+struct FeatWalk {
+    size_t col, s0, s1, first, step;
+    int lc;
+    bool active;
+};
+__device__ __forceinline__ FeatWalk feat_walk(size_t cols, int n) {
+    FeatWalk f;
+    const size_t col0 = (size_t)blockIdx.x * FEAT_TILE;
+    const int tc = cols - col0 < (size_t)FEAT_TILE ? (int)(cols - col0) : FEAT_TILE;
+    const int spw = 64 / tc, lane = threadIdx.x & 63, wave = threadIdx.x >> 6, ls = lane / tc;
+    f.lc = lane - ls * tc;
+    f.active = ls < spw;
+    f.col = col0 + f.lc;
+    f.s0 = (size_t)blockIdx.y * n / gridDim.y;
+    f.s1 = (size_t)(blockIdx.y + 1) * n / gridDim.y;
+    f.first = f.s0 + (size_t)wave * spw + ls;
+    f.step = (size_t)4 * spw;
+    return f;
+}
+
+// grid (ceil(cols / 64), splits of n): min / max of every real column
+__global__ __launch_bounds__(256) void feat_mdd_minmax_kernel(const float* __restrict__ ori, unsigned* __restrict__ minmax,
+                                                              size_t cols, int n) {
+    const FeatWalk f = feat_walk(cols, n);
+    if (!f.active || f.first >= f.s1) return;
+    float lo = ori[f.first * cols + f.col], hi = lo;
+#pragma unroll 4
+    for (size_t i = f.first + f.step; i < f.s1; i += f.step) {
+        const float v = ori[i * cols + f.col];
+        lo = fminf(lo, v);
+        hi = fmaxf(hi, v);
+    }
+    atomicMin(&minmax[f.col], feat_key(lo));
+    atomicMax(&minmax[cols + f.col], feat_key(hi));
+}
+
+// the bin of x on [a, a + width], or -1 outside (and for a NaN)
+__device__ __forceinline__ int feat_bin(float x, float a, float b, double width) {
+    if (!(x >= a && x <= b)) return -1;
+    const int k = (int)(((double)x - (double)a) / width * (double)FEAT_BINS);
+    return k < FEAT_BINS ? k : FEAT_BINS - 1;
+}
+
+// b of a column: its max, or a + 1e-5 when the column is constant (histogram_torch, :32)
+__device__ __forceinline__ void feat_range(const unsigned* __restrict__ minmax, size_t cols, size_t col, float& a, float& b,
+                                           double& width) {
+    a = feat_unkey(minmax[col]);
+    b = feat_unkey(minmax[cols + col]);
+    width = (double)b - (double)a;
+    if (b == a) { width = 1e-5; b = (float)((double)a + 1e-5); if (!(b > a)) b = a; }
+}
+
+// same grid: counts[set][bin][col] += the tile's histogram of this workgroup's samples, gathered in LDS first
+__global__ __launch_bounds__(256) void feat_mdd_count_kernel(const float* __restrict__ ori, const float* __restrict__ gen,
+                                                             const unsigned* __restrict__ minmax, unsigned* __restrict__ counts,
+                                                             size_t cols, int n) {
+    __shared__ unsigned h[2 * FEAT_BINS * FEAT_TILE];            // [set][bin][column of the tile]
+    for (int i = threadIdx.x; i < 2 * FEAT_BINS * FEAT_TILE; i += 256) h[i] = 0u;
+    __syncthreads();
+    const FeatWalk f = feat_walk(cols, n);
+    if (f.active) {
+        float a, b;
+        double width;
+        feat_range(minmax, cols, f.col, a, b, width);
+#pragma unroll 4
+        for (size_t i = f.first; i < f.s1; i += f.step) {
+            const int ko = feat_bin(ori[i * cols + f.col], a, b, width);
+            const int kg = feat_bin(gen[i * cols + f.col], a, b, width);
+            if (ko >= 0) atomicAdd(&h[ko * FEAT_TILE + f.lc], 1u);
+            if (kg >= 0) atomicAdd(&h[(FEAT_BINS + kg) * FEAT_TILE + f.lc], 1u);
+        }
+    }
+    __syncthreads();
+    const size_t col0 = (size_t)blockIdx.x * FEAT_TILE;
+    for (int i = threadIdx.x; i < 2 * FEAT_BINS * FEAT_TILE; i += 256) {
+        const int lc = i & (FEAT_TILE - 1), row = i / FEAT_TILE;      // row = set * 50 + bin
+        if (h[i] != 0u && col0 + lc < cols) atomicAdd(&counts[(size_t)row * cols + col0 + lc], h[i]);
+    }
+}
+
+// one thread per column: loss = mean_k |count_gen - count_ori| / (n delta)
+__global__ __launch_bounds__(256) void feat_mdd_finish_kernel(const unsigned* __restrict__ minmax, const unsigned* __restrict__ counts,
+                                                              float* __restrict__ col_loss, float* __restrict__ per_column,
+                                                              size_t cols, int n) {
+    const size_t col = (size_t)blockIdx.x * 256 + threadIdx.x;
+    if (col >= cols) return;
+    float a, b;
+    double width;
+    feat_range(minmax, cols, col, a, b, width);
+    const double delta = width / (double)FEAT_BINS;
+    double s = 0.0;
+    for (int k = 0; k < FEAT_BINS; ++k) {
+        const double co = (double)counts[(size_t)k * cols + col], cg = (double)counts[(size_t)(FEAT_BINS + k) * cols + col];
+        s += fabs(cg / ((double)n * delta) - co / ((double)n * delta));
+    }
+    const float loss = (float)(s / (double)FEAT_BINS);
+    col_loss[col] = loss;
+    if (per_column != nullptr) per_column[col] = loss;
+}
+
 // ---- TS2Vec encoder forward (evaluate/ts2vec.py:366-399 in eval mode, mask 'all_true'): one workgroup per series, the
 // three (channels x T) activation planes live in LDS; weights (< 1 MB) are read through L1 / L2.
 struct Ts2vecDev {
@@ -368,6 +668,77 @@ extern "C" int t2s_eval_dtw(const float* ori, const float* gen, float* per_sampl
     eval_dtw_kernel<<<n, 256, lds, st>>>(ori, gen, per_sample, L, n_series);
     T2S_LAUNCH_CHECK();
     eval_mean_kernel<<<1, 256, 0, st>>>(per_sample, out, n);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+static int feat_check(const char* who, const void* ori, const void* gen, const void* out, int n, int L, int n_series,
+                      const void* workspace, uint64_t workspace_bytes) {
+    using namespace t2s;
+    T2S_REQUIRE(ori && gen && out, "%s: ori, gen and out must not be NULL", who);
+    T2S_REQUIRE(n >= 2, "%s: n=%d, the measures need at least 2 samples", who, n);
+    T2S_REQUIRE(L >= 1 && L <= 4096, "%s: L=%d is outside [1, 4096]", who, L);
+    T2S_REQUIRE(n_series >= 1 && (uint64_t)L * (uint64_t)n_series <= (1u << 24), "%s: n_series=%d (L * n_series must be in [1, 2^24])", who, n_series);
+    const uint64_t need = feat_layout(n, L, n_series).total;
+    T2S_REQUIRE(workspace && workspace_bytes >= need, "%s: workspace of %llu bytes, t2s_eval_features_workspace_bytes asks for %llu",
+                who, (unsigned long long)(workspace ? workspace_bytes : 0), (unsigned long long)need);
+    return T2S_OK;
+}
+
+extern "C" uint64_t t2s_eval_features_workspace_bytes(int n, int L, int n_series) {
+    using namespace t2s;
+    if (n < 2 || L < 1 || L > 4096 || n_series < 1 || (uint64_t)L * (uint64_t)n_series > (1u << 24)) {
+        set_error("t2s_eval_features_workspace_bytes: unsupported n=%d, L=%d, n_series=%d (n >= 2, 1 <= L <= 4096, L * n_series <= 2^24)",
+                  n, L, n_series);
+        return 0;
+    }
+    return feat_layout(n, L, n_series).total;
+}
+
+extern "C" int t2s_eval_moments(const float* ori, const float* gen, float* stats, float* out, int n, int L, int n_series,
+                                void* workspace, uint64_t workspace_bytes, void* stream) {
+    using namespace t2s;
+    if (int rc = feat_check("t2s_eval_moments", ori, gen, out, n, L, n_series, workspace, workspace_bytes)) return rc;
+    const FeatLayout w = feat_layout(n, L, n_series);
+    char* ws = (char*)workspace;
+    double* mean_part = (double*)(ws + w.mean_part);
+    double* stat_part = (double*)(ws + w.stat_part);
+    float* chan = (float*)(ws + w.chan);
+    hipStream_t st = (hipStream_t)stream;
+    feat_sum_kernel<<<dim3(w.P, 2), 256, 0, st>>>(ori, gen, mean_part, n, L, n_series);
+    T2S_LAUNCH_CHECK();
+    feat_stats_kernel<<<dim3(w.P, 2), 256, (size_t)L * sizeof(double), st>>>(ori, gen, mean_part, stat_part, n, L, n_series);
+    T2S_LAUNCH_CHECK();
+    feat_fold_kernel<<<n_series, 256, 0, st>>>(mean_part, stat_part, stats, chan, n, L, n_series, w.P);
+    T2S_LAUNCH_CHECK();
+    feat_chan_mean_kernel<<<3, 256, 0, st>>>(chan, out, n_series);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+extern "C" int t2s_eval_mdd(const float* ori, const float* gen, float* per_column, float* out, int n, int L, int n_series,
+                            void* workspace, uint64_t workspace_bytes, void* stream) {
+    using namespace t2s;
+    if (int rc = feat_check("t2s_eval_mdd", ori, gen, out, n, L, n_series, workspace, workspace_bytes)) return rc;
+    const FeatLayout w = feat_layout(n, L, n_series);
+    char* ws = (char*)workspace;
+    unsigned* minmax = (unsigned*)(ws + w.minmax);
+    unsigned* counts = (unsigned*)(ws + w.counts);
+    float* col_loss = (float*)(ws + w.col_loss);
+    hipStream_t st = (hipStream_t)stream;
+    const unsigned tiles = (unsigned)((w.cols + FEAT_TILE - 1) / FEAT_TILE);
+    // at least 64 samples per workgroup, and about a thousand workgroups when n allows: L * n_series may be 24
+    unsigned splits = 1024u / tiles > 0 ? 1024u / tiles : 1u;
+    if (splits > (unsigned)(n + 63) / 64) splits = (unsigned)(n + 63) / 64;
+    feat_mdd_init_kernel<<<(unsigned)((2 * FEAT_BINS * w.cols + 255) / 256), 256, 0, st>>>(minmax, counts, w.cols);
+    T2S_LAUNCH_CHECK();
+    feat_mdd_minmax_kernel<<<dim3(tiles, splits), 256, 0, st>>>(ori, minmax, w.cols, n);
+    T2S_LAUNCH_CHECK();
+    feat_mdd_count_kernel<<<dim3(tiles, splits), 256, 0, st>>>(ori, gen, minmax, counts, w.cols, n);
+    T2S_LAUNCH_CHECK();
+    feat_mdd_finish_kernel<<<(unsigned)((w.cols + 255) / 256), 256, 0, st>>>(minmax, counts, col_loss, per_column, w.cols, n);
+    T2S_LAUNCH_CHECK();
+    eval_mean_kernel<<<1, 256, 0, st>>>(col_loss, out, (int)w.cols);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

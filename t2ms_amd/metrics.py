@@ -1,7 +1,8 @@
 """Evaluation metrics on the GPU, computed from the arrays infer.py writes exactly as the reference's
 evaluation.py defines them: MSE / WAPE (:166-206), ED (:137-150), DTW (:152-163), MRR (:21-45) and CRPS (:51-83) over
-the run_0..run_k repetitions `--run_multi` writes, and the TS2Vec encoder forward + FID of the C-FID metric
-(:127-135,238-243; evaluate/ts2vec.py:352-399).  `python -m t2ms_amd.metrics <generation dir>` prints them for a
+the run_0..run_k repetitions `--run_multi` writes, the TS2Vec encoder forward + FID of the C-FID metric
+(:127-135,238-243; evaluate/ts2vec.py:352-399), and the set-against-set measures MDD / ACD / SD / KD of
+evaluate/feature_based_measures.py (calculate_mdd :30-94, _acd :98-161, _sd :165-191, _kd :195-223).  `python -m t2ms_amd.metrics <generation dir>` prints them for a
 directory holding x_1.npy and x_t.npy ({save_path}/generation/{backbone}_{denoiser}_{dataset}_{cfg}_{steps}/[run_k/])
 and the run_* sub-directories.
 
@@ -110,6 +111,75 @@ def dtw(ori, gen, device="cuda"):
     return float(out.cpu()[0]), per.cpu()
 
 
+class _Features:
+    """Both sets on the device plus the workspace t2s_eval_moments / t2s_eval_mdd share: one upload serves all four."""
+
+    def __init__(self, ori, gen, device, what):
+        a, b = _pair(ori, gen, what)
+        self.dev = _gpu(device, what)
+        self.a, self.b = a.contiguous().to(self.dev), b.contiguous().to(self.dev)
+        self.shape = tuple(int(v) for v in a.shape)
+        need = L.lib().t2s_eval_features_workspace_bytes(*self.shape)
+        if need == 0:
+            L.check(1, "t2s_eval_features_workspace_bytes")
+        self.ws = torch.empty(need, dtype=torch.uint8, device=self.dev)
+
+    def moments(self):
+        """((ACD, SD, KD), stats): stats holds, per set (0 = ori, 1 = gen) and channel, `mean`, `var` (population),
+        `skew`, `kurt` (excess), each (2, n_series), and `acf` (2, n_series, K), K = min(64, L)."""
+        n, length, s = self.shape
+        k = min(L.EVAL_MAX_LAG, length)
+        stats, out = torch.empty(2, s, 4 + k, device=self.dev), torch.empty(3, device=self.dev)
+        with torch.cuda.device(self.dev):
+            L.check(L.lib().t2s_eval_moments(self.a.data_ptr(), self.b.data_ptr(), stats.data_ptr(), out.data_ptr(), n, length, s,
+                                             self.ws.data_ptr(), self.ws.numel(), L.stream_ptr(self.dev)), "t2s_eval_moments")
+        st = stats.cpu()
+        return tuple(float(v) for v in out.cpu()), {"mean": st[:, :, 0], "var": st[:, :, 1], "skew": st[:, :, 2],
+                                                    "kurt": st[:, :, 3], "acf": st[:, :, 4:]}
+
+    def mdd(self):
+        """(MDD, per_column (L, n_series))."""
+        n, length, s = self.shape
+        per, out = torch.empty(length, s, device=self.dev), torch.empty(1, device=self.dev)
+        with torch.cuda.device(self.dev):
+            L.check(L.lib().t2s_eval_mdd(self.a.data_ptr(), self.b.data_ptr(), per.data_ptr(), out.data_ptr(), n, length, s,
+                                         self.ws.data_ptr(), self.ws.numel(), L.stream_ptr(self.dev)), "t2s_eval_mdd")
+        return float(out.cpu()[0]), per.cpu()
+
+
+def mdd(ori, gen, device="cuda"):
+    """(MDD, per_column (L, n_series)): calculate_mdd, evaluate/feature_based_measures.py:30-94 -- per time step and
+    channel the mean absolute difference of the two sets' 50-bin densities on the real set's range."""
+    return _Features(ori, gen, device, "mdd").mdd()
+
+
+def acd(ori, gen, device="cuda"):
+    """(ACD, stats): calculate_acd, feature_based_measures.py:98-161 -- the distance of the two sets' autocorrelation
+    functions over min(64, L) lags; stats as _Features.moments returns them."""
+    (v, _, _), stats = _Features(ori, gen, device, "acd").moments()
+    return v, stats
+
+
+def sd(ori, gen, device="cuda"):
+    """(SD, stats): calculate_sd, feature_based_measures.py:165-191 -- the difference of the two sets' skewness."""
+    (_, v, _), stats = _Features(ori, gen, device, "sd").moments()
+    return v, stats
+
+
+def kd(ori, gen, device="cuda"):
+    """(KD, stats): calculate_kd, feature_based_measures.py:195-223 -- the difference of the two sets' excess kurtosis."""
+    (_, _, v), stats = _Features(ori, gen, device, "kd").moments()
+    return v, stats
+
+
+def feature_measures(ori, gen, device="cuda"):
+    """({"MDD", "ACD", "SD", "KD"}, {"per_column", "stats"}) from one upload and one statistics pass."""
+    f = _Features(ori, gen, device, "feature_measures")
+    (a, s, k), stats = f.moments()
+    m, per = f.mdd()
+    return {"MDD": m, "ACD": a, "SD": s, "KD": k}, {"per_column": per, "stats": stats}
+
+
 def _runs_first(ori, gens, what):
     a = torch.as_tensor(np.asarray(ori) if not torch.is_tensor(ori) else ori).float()
     if torch.is_tensor(gens) or isinstance(gens, np.ndarray):
@@ -213,6 +283,10 @@ def main(argv=None):
         gen = np.load(os.path.join(d, "x_t.npy"))
         mse, wape, _ = mse_wape(ori, gen)
         print(f"samples {ori.shape[0]}  MSE {mse:.6f}  WAPE {wape:.6f}  ED {ed(ori, gen)[0]:.6f}  DTW {dtw(ori, gen)[0]:.6f}")
+        o3 = ori if ori.ndim == 3 else ori[:, :, None]
+        if o3.shape[0] >= 2 and o3.shape[1] <= 4096:
+            fm, _ = feature_measures(o3, gen if gen.ndim == 3 else gen[:, :, None])
+            print(f"samples {ori.shape[0]}  MDD {fm['MDD']:.6f}  ACD {fm['ACD']:.6f}  SD {fm['SD']:.6f}  KD {fm['KD']:.6f}")
         if ori.shape[0] >= 8 and os.environ.get("T2S_METRICS_CFID", "1") not in ("", "0"):
             # evaluation.py:238-243: train TS2Vec on the original series (200 contrastive iterations), encode both sets
             # with it, FID of the representations.  The encoder is trained per call from a random initialisation, as in
