@@ -266,9 +266,9 @@ def device_lock(device) -> "threading.RLock":
     the DEVICE -- building / growing / destroying a handle, a Sampler's create / stage / run / destroy -- so that none of it
     runs while another thread's sampler run has a stream capture open.  HIP answers a device-wide synchronous call from ANY
     thread (hipDeviceSynchronize = torch.cuda.synchronize(), a synchronous hipMemcpy) with an error while a capture is open
-    on the device, thread-local capture mode notwithstanding, and that error invalidates the capture (reproduced in round 5:
-    tools/stress_threads.py --unserialised).  The caller's OWN device-wide calls in other threads are not
-    covered: see include/t2s.h "Threads"."""
+    on the device, thread-local capture mode notwithstanding, and that error invalidates the capture (reproduced in round 5 by
+    a diagnosis build without this serialisation, last carried by commit f0cbfbc).  The caller's OWN
+    device-wide calls in other threads are not covered: see include/t2s.h "Threads"."""
     import threading
     return _DEVICE_LOCKS.setdefault(str(torch.device(device)), threading.RLock())
 

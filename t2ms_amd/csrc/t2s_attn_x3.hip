@@ -13,7 +13,6 @@
 // The same body instantiated on one bf16 plane (Split1, t2s_x3.h) is the attention of the single-pass "bf16" arithmetic
 // (T2S_MATH_BF16, attn_fwd_bf16p_kernel): q, k, v^T and P^T each rounded once, 2 + 2 MFMAs per key block and query tile (128
 // cycles), a ring slot of 4 KiB.  Not fp32-accurate; the softmax reference, exponent and running sum stay fp32.
-#include <stdlib.h>
 #include "t2s_dit_internal.h"
 #include "t2s_x3.h"
 
@@ -313,11 +312,7 @@ __device__ __forceinline__ void attn_fwd_xn(bf16x8* ring3, const float* __restri
     const bf16x8* vg = reinterpret_cast<const bf16x8*>(vT3);
     f32x4* og = reinterpret_cast<f32x4*>(o);
     // (measured: without the stagger 324 us, with 313 us; s_setprio 1 for waves 4-7 on top: 320 us)
-#if defined(T2S_P1_NO_STAG)   // A/B build: the one-plane kernel without the half-period stagger (profiles/EXPERIMENTS.md)
-    constexpr int SG = planes_of<SP>::n == 1 ? 0 : 1;
-#else
     constexpr int SG = 1;
-#endif
     if (wave < 4)
         attn_x3_body<2, 0, SP>(ring3, qg, kg, vg, og, BH, lane, wave);
     else if (wave < 7)
@@ -399,14 +394,7 @@ static int attn_xn_grid(int BH) {
         else
             n_cu = 256;
     }
-    static int wg_per_cu = 0;
-    if (wg_per_cu == 0) {
-        const char* e = getenv("T2S_X3_WGS_PER_CU");
-        wg_per_cu = e ? atoi(e) : 1;
-        if (wg_per_cu < 1 || wg_per_cu > 2) wg_per_cu = 1;
-    }
-    const int slots = n_cu * wg_per_cu;
-    return BH < slots ? BH : slots;
+    return BH < n_cu ? BH : n_cu;   // one persistent workgroup per CU
 }
 
 int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st) {

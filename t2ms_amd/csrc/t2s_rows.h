@@ -26,7 +26,6 @@
 // Per 32-token tile: 256 (proj) + 512 (fc1) + 512 (fc2) + 768 (qkv) MFMAs of 32x32x2.
 #pragma once
 #include "t2s_common.h"
-#include <stdlib.h>
 
 namespace t2s {
 
@@ -38,9 +37,10 @@ constexpr int ROWS_CHUNK_F4 = 1024;                       // float4 per chunk (1
 // weight DMA and all stores, once per 64 MFMAs (seen in the ISA; cost ~15 %).
 constexpr int ROWS_CB_FLOATS = 896;
 constexpr int ROWS_CM_FLOATS = 1024;                      // per wave (bf16x3 kernel, t2s_rows_x3.h)
-#ifndef T2S_ROWS_NW
-#define T2S_ROWS_NW 4
-#endif
+// NW = waves per workgroup: 4 (two workgroups per CU) rather than 8 (one; each wave then issues half the
+// weight DMA pieces and the weights cross L2 -> LDS once per 256 tokens).  Measured: 8 is slower, 510 vs 480 us
+// average per launch -- one barrier domain of 8 waves loses more than the halved DMA issue gains.
+constexpr int ROWS_NW = 4;
 // f32 kernel: a THREE-slot ring, the DMA ROWS_DIST = 2 chunks ahead behind COUNTED vmcnt waits, and 768 adaLN floats
 // per wave (the MLP phase never reads shift_msa / scale_msa of its block: those two slots hold the qkv block's shift /
 // scale) -- 49,152 + 3,584 + 12,288 = 65,024 B.  With the two-slot ring every chunk ended in `vmcnt(0)`: a weight chunk
@@ -48,17 +48,11 @@ constexpr int ROWS_CM_FLOATS = 1024;                      // per wave (bf16x3 ke
 // run: 960 tiles for 1024 SIMDs) cannot hide.  Same-box A/B (tools/ab_sample.sh, series/s at B = 256 / 128, two sampler
 // lanes): two slots 61.6 / 61.0, three slots 62.2 / 61.9, FOUR slots (81,408 B) 61.4 / 58.2 -- the larger footprint
 // keeps the other lane's kernels off the CU, so the ring stays as small as the distance allows.
-#ifndef T2S_ROWS_SLOTS
-#define T2S_ROWS_SLOTS 3
-#endif
-constexpr int ROWS_SLOTS = T2S_ROWS_SLOTS;
-#ifndef T2S_ROWS_DIST
-#define T2S_ROWS_DIST 2
-#endif
-constexpr int ROWS_DIST = T2S_ROWS_DIST;                  // chunks the DMA runs ahead (< ROWS_SLOTS)
+constexpr int ROWS_SLOTS = 3;
+constexpr int ROWS_DIST = 2;                              // chunks the DMA runs ahead (< ROWS_SLOTS)
 static_assert(ROWS_DIST >= 1 && ROWS_DIST < ROWS_SLOTS, "the DMA may run at most ROWS_SLOTS - 1 chunks ahead");
 constexpr int ROWS_CMF = 768;                             // per-wave adaLN floats of the f32 kernel
-constexpr int ROWS_LDS_BYTES = ROWS_SLOTS * ROWS_CHUNK_F4 * 16 + (ROWS_CB_FLOATS + T2S_ROWS_NW * ROWS_CMF) * 4;
+constexpr int ROWS_LDS_BYTES = ROWS_SLOTS * ROWS_CHUNK_F4 * 16 + (ROWS_CB_FLOATS + ROWS_NW * ROWS_CMF) * 4;
 
 struct RowArgs {
     float* x;          // (M,128) residual stream, fragment-major, in place
@@ -219,13 +213,9 @@ __device__ __forceinline__ void ln_modulate(const f32x16 (&x)[4], f32x16 (&y)[4]
 // trip was already covered by the dependent 64-cycle MFMA chain -- timing-only builds without the fragment reads, without the
 // DMA or without the chunk barriers are all within 3 % of the real kernel (profiles/r03_rows_ablations.txt); what a tile
 // pays beyond its MFMA + VALU time is its prologue (x / attention-output rows from HBM), launch and tail.
-#ifndef T2S_ROWS_PIPE
-#define T2S_ROWS_PIPE 1
-#endif
 #define T2S_SCHED_FENCE() __builtin_amdgcn_sched_barrier(0)
 template <bool SWAP, typename BOP>
 __device__ __forceinline__ void ktile_mfma(const f32x4* __restrict__ wb, BOP&& bop, f32x16& acc) {
-#if T2S_ROWS_PIPE
     f32x4 w = wb[0];
 #pragma unroll
     for (int G = 0; G < 16; ++G) {
@@ -237,24 +227,9 @@ __device__ __forceinline__ void ktile_mfma(const f32x4* __restrict__ wb, BOP&& b
         T2S_SCHED_FENCE();
         w = wn;
     }
-#else
-#pragma unroll
-    for (int G = 0; G < 16; ++G) {
-        const f32x4 w = wb[G * 64];
-#pragma unroll
-        for (int e = 0; e < 4; ++e) acc = SWAP ? mfma32(bop(G, e), w[e], acc) : mfma32(w[e], bop(G, e), acc);
-    }
-#endif
 }
 
 
-// NW = waves per workgroup: 4 (two workgroups per CU; the default) or 8 (one; each wave then issues half the
-// weight DMA pieces and the weights cross L2 -> LDS once per 256 tokens).  Measured: 8 is slower, 510 vs 480 us
-// average per launch -- one barrier domain of 8 waves loses more than the halved DMA issue gains.
-#ifndef T2S_ROWS_NW
-#define T2S_ROWS_NW 4
-#endif
-constexpr int ROWS_NW = T2S_ROWS_NW;
 // chunk barrier of the row kernels: the weight DMA is issued by inline asm (glds16_asm: invisible to hipcc's waitcnt
 // pass, so that the ds_read -> MFMA pipelines keep their counted lgkmcnt waits), hence the explicit vmcnt(0) in front of
 // __syncthreads(), which by itself only covers what the compiler tracks
@@ -502,7 +477,6 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
                 prefetch(ci);
                 {   // fc2 partial over k-groups 4c..4c+3 of K=256; fragments ordered [nt][g]
                     const f32x4* wb = wring + (ci % ROWS_SLOTS) * ROWS_CHUNK_F4 + lane;
-#if T2S_ROWS_PIPE
                     f32x4 w = wb[0];
 #pragma unroll
                     for (int i = 0; i < 16; ++i) {      // i = 4 g + nt: same order of additions as before
@@ -515,17 +489,6 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
                         T2S_SCHED_FENCE();
                         w = wn;
                     }
-#else
-#pragma unroll
-                    for (int g = 0; g < 4; ++g) {
-#pragma unroll
-                        for (int nt = 0; nt < 4; ++nt) {
-                            const f32x4 w = wb[(nt * 4 + g) * 64];
-#pragma unroll
-                            for (int e = 0; e < 4; ++e) acc[nt] = mfma32(w[e], hT[4 * g + e], acc[nt]);
-                        }
-                    }
-#endif
                 }
                 chunk_done(ci, 0);
                 ++ci;
@@ -675,9 +638,7 @@ inline int launch_dit_rows(const RowArgs& a, hipStream_t st) {
         return T2S_E_INVALID;
     }
     const int tiles = a.M / 32;
-    static const int extra_lds = getenv("T2S_ROWS_EXTRA_LDS") ? atoi(getenv("T2S_ROWS_EXTRA_LDS")) : 0;  // diagnostic: force fewer workgroups per CU
-    if (extra_lds > 0) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_kernel<DO_MLP, DO_QKV>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES + extra_lds);
-    dit_rows_kernel<DO_MLP, DO_QKV><<<(tiles + ROWS_NW - 1) / ROWS_NW, 64 * ROWS_NW, ROWS_LDS_BYTES + extra_lds, st>>>(a);
+    dit_rows_kernel<DO_MLP, DO_QKV><<<(tiles + ROWS_NW - 1) / ROWS_NW, 64 * ROWS_NW, ROWS_LDS_BYTES, st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

@@ -30,46 +30,18 @@ namespace t2s {
 // Raise the wave's issue priority for its VALU-heavy sections (LayerNorm, GELU, operand splits): the two
 // waves of a SIMD are arbitrated by priority, then age, and a partner in an MFMA section needs the issue
 // port for only 8 of every 32 cycles (measured: 375 -> 364 us average per launch).
-#ifndef T2S_X3_NO_PRIO
 #define X3_PRIO(p) __builtin_amdgcn_s_setprio(p);
-#else
-#define X3_PRIO(p)
-#endif
 
-// -DT2S_X3_STAMP (tools/x3_stamp.sh; diagnosis only): every wave attributes the s_memtime cycles between consecutive stamps to a
-// category -- 0 prologue (first loads / operand split until chunk 0 has landed), 1 MFMA groups, 2 VALU sections (LayerNorm,
-// GELU, splits, gate / residual), 3 `s_waitcnt vmcnt(0)` in front of a chunk barrier, 4 the barrier itself, 5 issuing global
-// loads / stores and LDS-DMA, 6 epilogue -- and the first workgroups write their sums to RowArgsX3::stamp.
-#ifdef T2S_X3_STAMP
-__device__ __forceinline__ unsigned long long x3_clk() {
-    unsigned long long t;
-    __builtin_amdgcn_sched_barrier(0);
-    asm volatile("s_memtime %0\n\ts_waitcnt lgkmcnt(0)" : "=s"(t)::"memory");
-    __builtin_amdgcn_sched_barrier(0);
-    return t;
-}
-#define X3_STAMP_DECL unsigned long long st_last = x3_clk(), st_acc[7] = {0, 0, 0, 0, 0, 0, 0}; const unsigned long long st_t0 = st_last;
-#define X3_STAMP(k) { const unsigned long long n_ = x3_clk(); st_acc[k] += n_ - st_last; st_last = n_; }
-#define X3_SYNC() { asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory"); X3_STAMP(3) __builtin_amdgcn_s_barrier(); X3_STAMP(4) }
-#define X3_SYNC_BUT16() { asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); X3_STAMP(3) __builtin_amdgcn_s_barrier(); X3_STAMP(4) }
-#else
-#define X3_STAMP_DECL
-#define X3_STAMP(k)
 // (explicit vmcnt(0): every weight DMA of this kernel is issued by untracked inline asm, the fence inside wg_sync() only covers
 // what hipcc tracks -- as ROWS_SYNC in t2s_rows.h)
 #define X3_SYNC() { asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); wg_sync(); }
 // the same, but the 16 YOUNGEST vector-memory operations of the wave may still be in flight (the tile's residual stream, issued
 // last on purpose: it is first needed after the proj chunks).  Not wg_sync(): its release fence waits for vmcnt(0).
 #define X3_SYNC_BUT16() { asm volatile("s_waitcnt vmcnt(16) lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_s_barrier(); }
-#endif
 template <int NP> constexpr int XN_CHUNK_UNITS = 8 * NP * 64;   // 16-byte units per chunk: 8 k-steps x NP planes
 constexpr int X3_CHUNK_UNITS = XN_CHUNK_UNITS<3>;          // 24 KiB
 template <int NP> constexpr int ROWS_XN_LDS_BYTES = 2 * XN_CHUNK_UNITS<NP> * 16 + (ROWS_CB_FLOATS + 4 * ROWS_CM_FLOATS) * 4;
-#ifdef T2S_X3_LONE   // diagnosis (tools/x3_variant.sh x3_lone -DT2S_X3_LONE): pad the allocation so ONE workgroup fits a CU = one wave per SIMD
-constexpr int ROWS_X3_LDS_BYTES = 100 * 1024;
-#else
 constexpr int ROWS_X3_LDS_BYTES = ROWS_XN_LDS_BYTES<3>;
-#endif
 constexpr int ROWS_P1_LDS_BYTES = ROWS_XN_LDS_BYTES<1>;
 
 struct RowArgsX3 {
@@ -97,9 +69,6 @@ struct RowArgsX3 {
     const float *bp, *b1, *b2, *bq;
     float* q;          // q fragment-major fp32 (the attention scales and splits it once per head)
     __bf16 *k3, *v3;   // k, V^T split planes (t2s_x3.h); ONE plane each for the one-plane kernels
-#ifdef T2S_X3_STAMP
-    unsigned long long* stamp;   // [workgroup < 256][wave][8]: 7 category sums + total
-#endif
 };
 
 // fp32 packed weights (packed_index order, or the fc2 chunk order of pack_weight_kernel mode 1) ->
@@ -216,10 +185,9 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                        reinterpret_cast<f32x4*>(dst + (wave + 4 * p) * 64));           // one full round trip per constant load
     };
 
-    X3_STAMP_DECL
     // The next chunk's six LDS-DMA pieces are issued BETWEEN the k-steps of the current chunk's MFMA group, one per k-step:
     // an LDS-DMA instruction costs ~100 issue cycles in an MFMA gap against ~150 in front of the group, where nothing covers
-    // the wave's vector-memory issue (-DT2S_X3_STAMP put 14 % of a wave's cycles into the six-instruction burst; spread out
+    // the wave's vector-memory issue (a cycle-stamped build put 14 % of a wave's cycles into the six-instruction burst; spread out
     // they cost 10 %: rows -1.0 %, sampler +0.7 % in a same-box A/B, profiles/r05_x3_dma_mix_ab.txt).  Untracked inline asm
     // (glds16_asm) so hipcc keeps its counted lgkmcnt waits for the fragment reads: every chunk therefore ends with an
     // explicit vmcnt wait in front of its barrier.
@@ -238,12 +206,7 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
         const f32x4* ar = reinterpret_cast<const f32x4*>(a.ao) + (size_t)tile * 16 * 64 + lane;
 #pragma unroll
         for (int g = 0; g < 16; ++g) {
-#ifdef T2S_X3_NOPROLOGUE   // TIMING ONLY (results invalid): the bound of a perfect prefetch of the tile's inputs
-            araw[g] = f32x4{0.01f * lane, 0.3f, 0.1f * g, -0.7f};
-            (void)ar;
-#else
             araw[g] = ar[g * 64];
-#endif
         }
         __builtin_amdgcn_sched_barrier(0);
     }
@@ -328,12 +291,7 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
         const f32x4* xr = reinterpret_cast<const f32x4*>(a.x_in) + (size_t)tile_src * 16 * 64 + lane;
 #pragma unroll
         for (int G = 0; G < 16; ++G) {
-#ifdef T2S_X3_NOPROLOGUE   // TIMING ONLY (results invalid): the bound of a perfect prefetch of the tile's inputs
-            const f32x4 t = {0.25f * lane, 0.5f, -0.125f * G, 1.0f};
-            (void)xr;
-#else
             const f32x4 t = xr[G * 64];
-#endif
 #pragma unroll
             for (int e = 0; e < 4; ++e) x[G >> 2][4 * (G & 3) + e] = t[e];
         }
@@ -359,22 +317,15 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                 const f32x8 v = {lo.x, lo.y, lo.z, lo.w, hi.x, hi.y, hi.z, hi.w};
                 aop[ks] = splitp<SP>(v);
             }
-            X3_STAMP(0)
-#ifdef T2S_X3_NOPROLOGUE
-            X3_SYNC()
-#else
             X3_SYNC_BUT16()  // chunk 0 landed, ao consumed; the residual stream may still be on its way
-#endif
 #pragma unroll
             for (int nt = 0; nt < 4; ++nt) {
-                X3_STAMP(5)
                 const bf16x8* wb = wring3 + (ci & 1) * CHUNK_UNITS + lane;
                 f32x16 acc;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
                 ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return aop[ks]; }, acc,
                                 [&](int ks) T2S_X3_KERNEL { X3_FILL_MIX(ci + 1, ks) });
-                X3_STAMP(1)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 bias = ldc4(c_bp, nt, g, half);
@@ -382,7 +333,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 #pragma unroll
                     for (int e = 0; e < 4; ++e) x[nt][4 * g + e] += gate[e] * (acc[4 * g + e] + bias[e]);
                 }
-                X3_STAMP(2)
                 X3_DMA_LANDED()
                 X3_SYNC()
                 ++ci;
@@ -399,7 +349,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 #pragma unroll
                 for (int ks = 0; ks < 8; ++ks) xmp[ks] = splitp_acc<SP>(xm[ks >> 1], ks & 1);
             }
-            X3_STAMP(2)
             // park the post-attention residual in HBM for the MLP loop (t2s_rows.h)
             if (active) {
 #pragma unroll
@@ -416,10 +365,8 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[nt][r] = 0.f;
             X3_PRIO(0)
-            X3_STAMP(5)
 #pragma unroll 1
             for (int c = 0; c < 8; ++c) {  // 32 hidden units per chunk; ci = 4 + 2c (even) here
-                X3_STAMP(5)
                 f32x16 hT;
                 {
                     const bf16x8* wb = wring3 + lane;  // ci even -> ring slot 0
@@ -427,7 +374,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                     for (int r = 0; r < 16; ++r) hT[r] = 0.f;
                     ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, hT,
                                     [&](int ks) T2S_X3_KERNEL { X3_FILL_MIX(ci + 1, ks) });
-                    X3_STAMP(1)
                     X3_PRIO(2)   // GELU + split: let this wave's VALU win the issue arbitration over the partner's MFMA stream
 #pragma unroll
                     for (int g = 0; g < 4; ++g) {
@@ -436,16 +382,13 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                         for (int e = 0; e < 4; ++e) hT[4 * g + e] = gelu_tanh_f(hT[4 * g + e] + bias[e]);
                     }
                 }
-                X3_STAMP(2)
                 X3_DMA_LANDED()
                 X3_SYNC()
                 ++ci;
-                X3_STAMP(5)
                 {   // fc2 partial over the 32 hidden units of this chunk: pieces (nt, s)
                     const bf16x8* wb = wring3 + CHUNK_UNITS + lane;  // ci odd -> ring slot 1
                     const SP h0 = splitp_acc<SP>(hT, 0), h1 = splitp_acc<SP>(hT, 1);
                     X3_PRIO(0)
-                    X3_STAMP(2)
 #pragma unroll
                     for (int nt = 0; nt < 4; ++nt) {
                         acc[nt] = mfma_x3(ldwp<SP>(wb, nt * 2 + 0), h0, acc[nt]);
@@ -453,7 +396,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                         acc[nt] = mfma_x3(ldwp<SP>(wb, nt * 2 + 1), h1, acc[nt]);
                         if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, 2 * nt + 1) }
                     }
-                    X3_STAMP(1)
                 }
                 X3_DMA_LANDED()
                 X3_SYNC()
@@ -474,10 +416,8 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                     }
                     if (active && (DO_QKV || a.out0 == nullptr || a.keep_x)) xw[(nt * 4 + g) * 64] = t;   // final residual stream of this block
                 }
-            X3_STAMP(2)
         }
     } else {
-        X3_STAMP(0)
         X3_SYNC()  // chunk 0 landed
     }
 
@@ -550,10 +490,8 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
         }
         const int tile_in_seq = tile - seq * (NTOK / 32);
         X3_PRIO(0)
-        X3_STAMP(2)
 #pragma unroll 1
         for (int t = 0; t < 12; ++t) {  // output tile t = which*4 + head
-            X3_STAMP(5)
             const bf16x8* wb = wring3 + (ci & 1) * CHUNK_UNITS + lane;
             const int which = t >> 2, head = t & 3;
             const size_t head_tile = ((size_t)seq * NH + head) * (NTOK / 32) + tile_in_seq;
@@ -564,7 +502,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                 // q / k tile, transposed product: lane = token, registers = features d
                 ktile_x3<false, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, acc,
                                 [&](int ks) T2S_X3_KERNEL { if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, ks) } });
-                X3_STAMP(1)
 #pragma unroll
                 for (int g = 0; g < 4; ++g) {
                     const f32x4 bias = *reinterpret_cast<const f32x4*>(c_bq + 32 * t + 8 * g + 4 * half);
@@ -597,7 +534,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                 const float bias = c_bq[32 * t + (lane & 31)];
                 ktile_x3<true, SP>(wb, [&](int ks) T2S_X3_KERNEL -> const SP& { return xmp[ks]; }, acc,
                                [&](int ks) T2S_X3_KERNEL { if (ci + 1 < N_CHUNKS) { X3_FILL_MIX(ci + 1, ks) } });
-                X3_STAMP(1)
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] += bias;
                 if (active) {
@@ -615,7 +551,6 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
             }
             // counted wait + raw barrier: the next chunk's 6 DMA pieces (one plane: 2) must have landed; the q (4) or
             // k / v plane (6; one plane: 2) stores issued after them stay in flight.  Tail waves store nothing.
-            X3_STAMP(2)
             if (!active)
                 asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             else if (which >= 1 && NP == 3)
@@ -624,20 +559,10 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
                 asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
             else
                 asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-            X3_STAMP(3)
             __builtin_amdgcn_s_barrier();
-            X3_STAMP(4)
             ++ci;
         }
     }
-#ifdef T2S_X3_STAMP
-    X3_STAMP(6)
-    if (a.stamp != nullptr && blockIdx.x < 256 && lane == 0) {
-        unsigned long long* d = a.stamp + ((size_t)blockIdx.x * 4 + wave) * 8;
-        for (int k = 0; k < 7; ++k) d[k] = st_acc[k];
-        d[7] = st_last - st_t0;
-    }
-#endif
 }
 
 template <bool DO_MLP, bool DO_QKV>
@@ -675,33 +600,6 @@ inline int launch_dit_rows_xn(int np, const RowArgsX3& a, hipStream_t st) {
         return T2S_E_INVALID;
     }
     const int tiles = a.M / 32;
-#ifdef T2S_X3_STAMP
-    if (np == 3) {
-        static unsigned long long* buf = nullptr;
-        static int calls = 0;
-        if (!buf) {
-            T2S_HIP_CHECK(hipMalloc((void**)&buf, 256 * 4 * 8 * sizeof(unsigned long long)));
-            T2S_HIP_CHECK(hipMemset(buf, 0, 256 * 4 * 8 * sizeof(unsigned long long)));
-        }
-        RowArgsX3 a2 = a;
-        a2.stamp = buf;
-        dit_rows_x3_kernel<DO_MLP, DO_QKV><<<(tiles + 3) / 4, 256, ROWS_X3_LDS_BYTES, st>>>(a2);
-        T2S_LAUNCH_CHECK();
-        if (++calls == 40 && tiles >= 4096) {      // one dump per instance, well after warm-up, at a chip-filling launch
-            static unsigned long long host[256 * 4 * 8];
-            T2S_HIP_CHECK(hipStreamSynchronize(st));
-            T2S_HIP_CHECK(hipMemcpy(host, buf, sizeof(host), hipMemcpyDeviceToHost));
-            double sum[8] = {};
-            const int n = (tiles + 3) / 4 < 256 ? (tiles + 3) / 4 : 256;
-            for (int i = 0; i < n * 4; ++i)
-                for (int k = 0; k < 8; ++k) sum[k] += (double)host[i * 8 + k];
-            fprintf(stderr, "x3_stamp <%d,%d> tiles %d: cycles per wave (s_memtime, 100 MHz ticks x? see tools/x3_stamp.sh) total %.0f | prologue %.0f mfma %.0f valu %.0f "
-                            "vmcnt %.0f barrier %.0f issue %.0f epilogue %.0f\n", (int)DO_MLP, (int)DO_QKV, tiles, sum[7] / (n * 4), sum[0] / (n * 4),
-                    sum[1] / (n * 4), sum[2] / (n * 4), sum[3] / (n * 4), sum[4] / (n * 4), sum[5] / (n * 4), sum[6] / (n * 4));
-        }
-        return T2S_OK;
-    }
-#endif
     dit_rows_xn_kernel<DO_MLP, DO_QKV>(np)<<<(tiles + 3) / 4, 256, rows_xn_lds_bytes(np), st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;

@@ -581,11 +581,6 @@ int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise
     int rc = dit_forward_cfg_step(s->dit, xl, s->temb_table, step, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
                                   s->mod_table, c.batch + 1, r0);
     if (rc != T2S_OK) return rc;
-    // T2S_SKIP_UPDATE=1 (TIMING ONLY, results invalid: the state and the loop index never advance): the sampler without its
-    // update launch -- the upper bound of what fusing the DDPM / RF update into the last row kernel could save (VERDICT r04
-    // item 7; profiles/EXPERIMENTS.md section 1)
-    static const bool skip_update = getenv("T2S_SKIP_UPDATE") && atoi(getenv("T2S_SKIP_UPDATE")) != 0;
-    if (skip_update) return T2S_OK;
     if (c.mode == T2S_MODE_DDPM) {
         StepArgs a{};
         a.x = xl; a.eps_u = eu; a.eps_c = ec; a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
@@ -666,9 +661,7 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     int cur_dev = 0;
     T2S_HIP_CHECK(hipGetDevice(&cur_dev));
     T2S_REQUIRE(cur_dev >= 0 && cur_dev < 16, "t2s_sampler_create: device %d", cur_dev);
-#ifndef T2S_DIAG_UNSERIALISED   // (diagnosis build of tools/stress_threads.py --unserialised: round 4's locking)
     std::lock_guard<std::recursive_mutex> pool_lock(g_pool_use[cur_dev]);
-#endif
     t2s_sampler* s = new t2s_sampler();
     s->dit = dit; s->vae = vae; s->cfg = *cfg;
     s->cfg.ddpm_coef = nullptr; s->cfg.t_values = nullptr;  // host pointers are not retained
@@ -702,7 +695,7 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     // operation on the legacy stream implicitly joins every blocking stream of the device, and HIP refuses it
     // (hipErrorStreamCaptureImplicit, "operation would make the legacy stream depend on a capturing blocking stream") while
     // ANY thread has a capture open -- invalidating that capture.  That was the round-4 two-thread failure (reproduced in
-    // round 5 with the serialisation taken away, tools/stress_threads.py --unserialised).
+    // round 5 by a diagnosis build with the serialisation taken away, last carried by commit f0cbfbc).
     hipStream_t setup = setup_stream(cur_dev);
     if (e == hipSuccess && !setup) e = hipErrorUnknown;
     if (e == hipSuccess) e = hipMemcpyAsync(s->tvals, cfg->t_values, T * sizeof(float), hipMemcpyHostToDevice, setup);
@@ -779,9 +772,7 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     if (!s) return;
     int cur_dev = 0;
     std::unique_lock<std::recursive_mutex> pool_lock;  // hipFree synchronises the device: not inside another thread's capture
-#ifndef T2S_DIAG_UNSERIALISED
     if (hipGetDevice(&cur_dev) == hipSuccess && cur_dev >= 0 && cur_dev < 16) pool_lock = std::unique_lock<std::recursive_mutex>(g_pool_use[cur_dev]);
-#endif
     drop_graph(s);
     for (int l = 0; l < t2s_sampler::MAX_LANES; ++l)
         if (s->ev_join[l]) (void)hipEventDestroy(s->ev_join[l]);

@@ -15,10 +15,7 @@ namespace t2s {
 constexpr int VAE_TMAX = 32;   // positions after the stride-4 stem: L/4 <= 32  (L <= 128)
 constexpr int VAE_CMAX = 256;  // res_hidden
 constexpr int VAE_THREADS = 256;
-#ifndef T2S_VAE_CP
-#define T2S_VAE_CP 8
-#endif
-constexpr int VAE_CO_PER_THREAD = T2S_VAE_CP;   // output channels per thread in conv1d_lds
+constexpr int VAE_CO_PER_THREAD = 8;   // output channels per thread in conv1d_lds
 
 struct VaeDev {  // device copies in the reference layouts
     int hidden, res_hidden, n_res, emb;

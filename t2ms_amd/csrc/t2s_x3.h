@@ -108,12 +108,8 @@ template <class SP> __device__ __forceinline__ SP splitp_acc(const f32x16& c, in
 __device__ __forceinline__ f32x16 mfma_x3(const Split1& a, const Split1& b, f32x16 acc) { return mfma16(a.h, b.h, acc); }
 
 // The one-plane kernels have little MFMA time to hide VALU work behind, so whether they should give up packed fp32 like the
-// bf16x3 kernels is a separate question: -DT2S_P1_PACKED_FP32 builds them WITH packed fp32 (A/B in profiles/EXPERIMENTS.md).
-#if defined(T2S_P1_PACKED_FP32)
-#define T2S_P1_KERNEL
-#else
+// bf16x3 kernels was a separate question: built WITH packed fp32 they lost 3.2 % of a step (profiles/EXPERIMENTS.md 0.15).
 #define T2S_P1_KERNEL T2S_X3_KERNEL
-#endif
 
 // Split K / V^T operand planes of one (sequence, head), written by the row-chain kernel's qkv
 // epilogue and consumed by attn_fwd_x3_kernel, in units of 16 bytes (one lane's 8 bf16):

@@ -53,13 +53,6 @@ def loop_t_values(backbone: str, steps: int) -> torch.Tensor:
 _STREAMS = {}
 
 
-def _run_lock(device) -> "threading.RLock":
-    """The package's per-device lock (_lib.device_lock): held for EVERYTHING a Sampler does on the GPU -- building its handle
-    and C sampler (allocations, copies, a device synchronize), staging inputs, the run itself.  Foreign GPU work of other
-    threads is not covered."""
-    return L.device_lock(device)
-
-
 def _sampler_stream(device) -> "torch.cuda.Stream":
     """ONE capture stream per device for every Sampler of the process.  HIP maps streams onto a few hardware queues in
     creation order and two streams on one queue run one after the other: with a stream per Sampler, lane 0 (this stream)
@@ -69,12 +62,6 @@ def _sampler_stream(device) -> "torch.cuda.Stream":
     if key not in _STREAMS:
         _STREAMS[key] = torch.cuda.Stream(torch.device(device))
     return _STREAMS[key]
-
-
-def _destroy_locked(device_key, ptr):
-    """t2s_sampler_destroy frees device memory (a device-wide synchronisation): not while another thread's run is capturing."""
-    with L.device_lock(device_key):
-        L.lib().t2s_sampler_destroy(ptr)
 
 
 def philox_normal(n_rows: int, row_elems: int, seed: int, stream_id: int, row0: int, device) -> torch.Tensor:
@@ -184,8 +171,10 @@ class Sampler:
         self._create()
 
     def _create(self):
-        """(Re)build the C sampler against the model's CURRENT t2s_dit handle."""
-        with _run_lock(self.device):
+        """(Re)build the C sampler against the model's CURRENT t2s_dit handle.  The package's per-device lock
+        (_lib.device_lock) is held for EVERYTHING a Sampler does on the GPU -- building its handle and C sampler (allocations,
+        copies, a device synchronize), staging inputs, the run itself.  Foreign GPU work of other threads is not covered."""
+        with L.device_lock(self.device):
             self._create_locked()
 
     def _create_locked(self):
@@ -211,7 +200,7 @@ class Sampler:
             L.check(L.lib().t2s_sampler_create(dit, vae, C.byref(cfg), C.byref(self.ptr)), "t2s_sampler_create")
             L.check(L.lib().t2s_sampler_set_lanes(self.ptr, self.lanes), "t2s_sampler_set_lanes")
             L.check(L.lib().t2s_sampler_set_loop_graph(self.ptr, self.loop_graph), "t2s_sampler_set_loop_graph")
-        self._fin = weakref.finalize(self, _destroy_locked, str(self.device), self.ptr)
+        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_sampler_destroy", str(self.device), self.ptr)
         if self.__dict__.get("_rows") is not None:      # a re-created C sampler keeps the per-row tables
             self.set_rows(*self._rows)
         self._keep = (tvals, coef)
@@ -257,46 +246,43 @@ class Sampler:
             decode: bool = True, trace: bool = False):
         """Returns (latent (B,64,30), series (B,L) or None, trace (steps,L) or None).
         ``noise`` (steps,B,64,30) injects the per-step draws (parity mode)."""
-        with _run_lock(self.device):
-            return self._run_locked(text, x_T, noise, decode, trace)
-
-    def _run_locked(self, text, x_T, noise, decode, trace):
-        dev = self.device
-        text = L.as_f32(text.to(dev))
-        if tuple(text.shape) != (self.batch, L.D_MODEL):
-            raise L.T2SError(f"Sampler.run: text must be ({self.batch},128), got {tuple(text.shape)}")
-        # persistent device buffers: the captured hipGraph is bound to their addresses
-        if self.__dict__.get("_x") is None:
-            self._x = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
-            self._text = torch.empty(self.batch, L.D_MODEL, device=dev, dtype=torch.float32)
-            self._series = torch.empty(self.batch, self.length, device=dev, dtype=torch.float32)
-        self._text.copy_(text)
-        if x_T is None:
-            self.draw_xT(self._x)
-        else:
-            if tuple(x_T.shape) != (self.batch, L.LAT_C, L.LAT_W):
-                raise L.T2SError(f"Sampler.run: x_T must be ({self.batch},64,30), got {tuple(x_T.shape)}")
-            self._x.copy_(x_T)
-        if noise is not None:
-            noise = L.as_f32(noise.to(dev))
-            if tuple(noise.shape) != (self.steps, self.batch, L.LAT_C, L.LAT_W):
-                raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,30)")
-        if (decode or trace) and self.decoder is None:
-            raise L.T2SError("Sampler.run: decode requested but no decoder was given")
-        tr = torch.empty(self.steps, self.length, device=dev, dtype=torch.float32) if trace else None
-        with torch.cuda.device(dev):
-            # weights may have changed since the last run: refresh the packed copy on the caller's stream
-            self.model.t2s_handle(dev, 2 * self.batch)
-            if self.model.t2s_handle_id() != self._dit_uid:
-                self._create()  # the model re-created its handle (capacity grew / device moved): drop the graph
-            cur = torch.cuda.current_stream(dev)
-            self.stream.wait_stream(cur)
-            L.check(L.lib().t2s_sampler_run(self.ptr, L.dev_ptr(self._x), L.dev_ptr(self._text), L.dev_ptr(noise),
-                                            L.dev_ptr(self._series) if decode else None, L.dev_ptr(tr),
-                                            self.stream.cuda_stream), "t2s_sampler_run")
-            cur.wait_stream(self.stream)
-        self._last = (noise, tr)  # keep caller-provided buffers alive until the stream has consumed them
-        return self._x.clone(), (self._series.clone() if decode else None), tr
+        with L.device_lock(self.device):
+            dev = self.device
+            text = L.as_f32(text.to(dev))
+            if tuple(text.shape) != (self.batch, L.D_MODEL):
+                raise L.T2SError(f"Sampler.run: text must be ({self.batch},128), got {tuple(text.shape)}")
+            # persistent device buffers: the captured hipGraph is bound to their addresses
+            if self.__dict__.get("_x") is None:
+                self._x = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
+                self._text = torch.empty(self.batch, L.D_MODEL, device=dev, dtype=torch.float32)
+                self._series = torch.empty(self.batch, self.length, device=dev, dtype=torch.float32)
+            self._text.copy_(text)
+            if x_T is None:
+                self.draw_xT(self._x)
+            else:
+                if tuple(x_T.shape) != (self.batch, L.LAT_C, L.LAT_W):
+                    raise L.T2SError(f"Sampler.run: x_T must be ({self.batch},64,30), got {tuple(x_T.shape)}")
+                self._x.copy_(x_T)
+            if noise is not None:
+                noise = L.as_f32(noise.to(dev))
+                if tuple(noise.shape) != (self.steps, self.batch, L.LAT_C, L.LAT_W):
+                    raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,30)")
+            if (decode or trace) and self.decoder is None:
+                raise L.T2SError("Sampler.run: decode requested but no decoder was given")
+            tr = torch.empty(self.steps, self.length, device=dev, dtype=torch.float32) if trace else None
+            with torch.cuda.device(dev):
+                # weights may have changed since the last run: refresh the packed copy on the caller's stream
+                self.model.t2s_handle(dev, 2 * self.batch)
+                if self.model.t2s_handle_id() != self._dit_uid:
+                    self._create()  # the model re-created its handle (capacity grew / device moved): drop the graph
+                cur = torch.cuda.current_stream(dev)
+                self.stream.wait_stream(cur)
+                L.check(L.lib().t2s_sampler_run(self.ptr, L.dev_ptr(self._x), L.dev_ptr(self._text), L.dev_ptr(noise),
+                                                L.dev_ptr(self._series) if decode else None, L.dev_ptr(tr),
+                                                self.stream.cuda_stream), "t2s_sampler_run")
+                cur.wait_stream(self.stream)
+            self._last = (noise, tr)  # keep caller-provided buffers alive until the stream has consumed them
+            return self._x.clone(), (self._series.clone() if decode else None), tr
 
     @property
     def graph_lanes(self) -> int:
@@ -307,7 +293,7 @@ class Sampler:
         """Benchmark entry: x_T from Philox into the persistent buffers, no output copies.
         Requires one prior run() (buffers + text in place).  Returns (latent, series) views."""
         dev = self.device
-        with _run_lock(dev), torch.cuda.device(dev):
+        with L.device_lock(dev), torch.cuda.device(dev):
             if self.model.t2s_handle_id() != self._dit_uid:
                 self._create()
             self.draw_xT(self._x)

@@ -254,3 +254,31 @@ def test_shipped_default_math_is_bf16x3_and_the_suite_pins_f32(monkeypatch):
     monkeypatch.setenv("T2S_DEFAULT_MATH", "tf32")
     with pytest.raises(ValueError):
         sampler.default_math()
+
+
+def _csrc_sources():
+    import glob
+    paths = sorted(glob.glob(os.path.join(REPO, "t2ms_amd", "csrc", "*.h")) + glob.glob(os.path.join(REPO, "t2ms_amd", "csrc", "*.hip")))
+    assert len(paths) >= 20
+    return [(os.path.basename(p), open(p, encoding="utf-8").read()) for p in paths]
+
+
+def test_csrc_has_no_experiment_build_switches():
+    """The library has ONE build: no preprocessor conditional of csrc/ tests a T2S_ macro (__HIP_DEVICE_COMPILE__ is the only
+    conditional the kernels need).  Experiment builds are made, measured, written down and removed (tools/README.md)."""
+    import re
+    cond = re.compile(r"^\s*#\s*(?:if|ifdef|ifndef|elif)\b(.*)$", re.M)
+    found = [f"{name}: {m.group(0).strip()}" for name, text in _csrc_sources() for m in cond.finditer(text)
+             if re.search(r"\bT2S_\w*", m.group(1))]
+    assert not found, found
+
+
+def test_every_environment_switch_of_the_library_is_documented():
+    """Every T2S_* variable the library reads with getenv is listed in INTEGRATION.md: a switch nobody documents is a switch
+    nobody tests."""
+    import re
+    names = {m for _, text in _csrc_sources() for m in re.findall(r'getenv\(\s*"(T2S_\w+)"', text)}
+    assert len(names) >= 8, names
+    doc = open(os.path.join(REPO, "INTEGRATION.md"), encoding="utf-8").read()
+    missing = sorted(n for n in names if not re.search(r"\b%s\b" % n, doc))
+    assert not missing, missing

@@ -20,11 +20,6 @@ from model.denoiser.transformer import Transformer  # noqa: E402
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=150)
-    ap.add_argument("--unserialised", action="store_true",
-                    help="DIAGNOSIS: round 4's locking -- only Sampler.run takes the per-device lock, creating / staging / destroying "
-                         "samplers run concurrently with the other thread's open capture (use with T2S_LIB = a library built with "
-                         "-DT2S_DIAG_UNSERIALISED: tools/variant.sh t2s_sampler diag_unser -DT2S_DIAG_UNSERIALISED).  Records WHICH "
-                         "call fails with WHICH HIP error when the serialisation of DESIGN 4.5 is taken away.")
     ap.add_argument("--foreign-sync", choices=["global", "relaxed"], default=None,
                     help="a third thread calls torch.cuda.synchronize() in a loop (a caller's own device-wide call, outside every "
                          "lock): in HIP's default capture mode ('global': refused while a capture is open, and the capture dies) or "
@@ -32,17 +27,6 @@ def main():
     ap.add_argument("--fresh-handles", type=int, default=0, metavar="N",
                     help="every N-th round builds a new Transformer and a new LA-VAE (their HIP handles are created inside the loop)")
     a = ap.parse_args()
-    if a.unserialised:
-        import contextlib
-        from t2ms_amd import sampler as S
-        real_lock = S._run_lock
-        S._run_lock = lambda device: contextlib.nullcontext()
-
-        def run_with_lock(self, text, x_T=None, noise=None, decode=True, trace=False):
-            with real_lock(self.device):
-                return self._run_locked(text, x_T, noise, decode, trace)
-        S.Sampler.run = run_with_lock
-        S._destroy_locked = lambda device_key, ptr: S.L.lib().t2s_sampler_destroy(ptr)
     torch.cuda.set_device(0)
     dev = torch.device("cuda", 0)
     _, vae = bench.build_models(dev)
