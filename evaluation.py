@@ -123,11 +123,22 @@ def build_parser():
     p.add_argument("--denoiser", type=str, default="DiT", help="DiT or MLP")
     p.add_argument("--cfg_scale", type=float, default=9.0, help="CFG Scale")
     p.add_argument("--total_step", type=int, default=10, help="total step sampled from [0,1]")
+    p.add_argument("--solver", default=None, choices=["ancestral", "ddim", "dpmpp2m", "euler", "ab2"],
+                   help="the --solver infer.py sampled with: only names the generation directory (suffix _{solver}{S})")
+    p.add_argument("--sample_steps", type=int, default=None, help="the --sample_steps infer.py sampled with (directory name only)")
     p.add_argument("--cfid_engine", choices=("torch", "hip"), default=None,
                    help="what trains the C-FID encoder: torch autograd or the fused HIP step (unset: T2S_TS2VEC_FIT, else torch)")
     p.add_argument("--align_runs", action="store_true",
                    help="re-order every run's rows to one ground-truth order before comparing (see the module docstring)")
     return p
+
+
+def model_name(args):
+    """The directory name infer.py wrote under: the reference's, plus the suffix of a few-step solver (--solver,
+    --sample_steps: `_{solver}{S}`; none for the backbone's own update)."""
+    from t2ms_amd.sampler import resolve_solver
+    suffix = resolve_solver(args.backbone, getattr(args, "solver", None), getattr(args, "sample_steps", None), None, args.total_step)[1]
+    return "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, args.dataset_name, args.cfg_scale, args.total_step) + suffix
 
 
 def main(argv=None):
@@ -136,7 +147,10 @@ def main(argv=None):
         sys.exit("evaluation.py: no GPU visible -- the metrics kernels run on the GPU (no CPU fallback)")
     args.device = "cuda"
     args.data_length = args.dataset_name.split("_")[-1] if args.dataset_name != "SUSHI" else 2048
-    args.model_name = "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, args.dataset_name, args.cfg_scale, args.total_step)
+    try:
+        args.model_name = model_name(args)
+    except ValueError as e:
+        sys.exit(f"evaluation.py: {e}")
     args.generation_save_path = os.path.join(args.save_path, "generation", args.model_name)
     args.evaluation_save_path = os.path.join(args.save_path, "evaluation", args.model_name)
     g = args.generation_save_path

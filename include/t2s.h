@@ -325,6 +325,21 @@ int t2s_mse(const float* a, const float* b, float* out, uint64_t n, void* stream
  *   x <- x + (u + cfg*(c-u)) * dt */
 int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float dt, int B,
                 void* stream);
+/* One table-driven linear multistep update for the few-step solvers (DDIM, DPM-Solver++(2M), Adams-Bashforth 2 -- built on
+ * the host by t2ms_amd.sampler.solver_tables; no counterpart in the reference), fused with the CFG combine.  Per element,
+ *   pred = u + cfg*(c-u)   (pred = u when pred_c is NULL)
+ *   x' = c0*x + c1*pred + c2*h + c3*z        h' = c4*x + c5*pred   (from the OLD x)
+ * coef: DEVICE (S,6), row `index` = {c0..c5}: the row of LOOP INDEX `index` (not S-1-index).  hist: (B,1920) history of the
+ * solver (the previous x0 prediction / velocity), in place like x.  z = noise[n] (B,1920) if noise != NULL, else the Philox
+ * N(0,1) stream (seed, stream_id, row0 + row) exactly as t2s_ddpm_step draws it.
+ * A coefficient that is exactly 0 means its operand is not touched: c2 == 0 -> hist is not read (it may hold NaN or be
+ * uninitialised on the first step); c3 == 0 -> no draw is made (noise may be NULL, no Philox work); c4 == c5 == 0 -> hist
+ * is not written.  Arithmetic, fixed: evaluated in fp64 from the fp32 operands in the order pred, c0*x, + c1*pred, + c2*h,
+ * + c3*z (fused multiply-adds) and rounded to fp32 once -- the x0-prediction history cancels two terms 157 times its size
+ * at t = 999 of a 1000-step schedule; results repeat bit for bit. */
+int t2s_lms_step(float* x, float* hist, const float* pred_u, const float* pred_c /* may be NULL */,
+                 const float* noise /* (B,1920) or NULL */, const float* coef /* DEVICE (S,6) */, int index,
+                 float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B, void* stream);
 /* DDPM.q_sample (DDPM.py:19-27): out = sqrt_ab[t[b]]*x0 + sqrt_1mab[t[b]]*eps.
  * sqrt_ab, sqrt_1mab: (T) host-built tables, T = n_steps; t: (B) int32 (out of range -> NaN row, see p_sample). */
 int t2s_ddpm_q_sample(const float* x0, const float* eps, const int32_t* t, const float* sqrt_ab,
@@ -434,9 +449,10 @@ typedef struct t2s_sampler t2s_sampler;
 
 #define T2S_MODE_DDPM 0
 #define T2S_MODE_RF 1
+#define T2S_MODE_LMS 2   /* table-driven linear multistep update (t2s_lms_step): t2s_sampler_create_lms only */
 
 typedef struct t2s_sample_config {
-    int mode;            /* T2S_MODE_DDPM | T2S_MODE_RF                                  */
+    int mode;            /* T2S_MODE_DDPM | T2S_MODE_RF (| T2S_MODE_LMS: _create_lms)    */
     int steps;           /* infer.py --total_step                                         */
     float cfg_scale;     /* infer.py --cfg_scale                                          */
     int batch;           /* series per call on this GPU (2*batch <= dit max_seqs)         */
@@ -451,6 +467,16 @@ typedef struct t2s_sample_config {
 
 int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae /* may be NULL: no decode */,
                        const t2s_sample_config* cfg, t2s_sampler** out);
+/* The same sampler with the few-step update of t2s_lms_step in place of the ancestral DDPM / Euler update: cfg->mode =
+ * T2S_MODE_LMS, cfg->steps = S (the number of denoiser evaluations), cfg->t_values (S) the t handed to the denoiser at loop
+ * index j (a DDPM solver's grid of TRAINED integer times, or the flow model's j/S), cfg->ddpm_coef NULL; lms_coef HOST
+ * (S,6), row j = the coefficients of loop index j, copied at the call.  The sampler owns the (batch,1920) history buffer
+ * (zeroed here; lanes slice it by rows).  Everything else is t2s_sampler_run's as it is: graphs (one step / whole loop),
+ * lanes, trace0, set_row0 / set_rows, the adaLN table, every matrix arithmetic.  `noise` stays (steps,B,64,30) and is read
+ * only at steps whose c3 != 0.  T2S_E_INVALID -- before any allocation, with a t2s_last_error text -- for a NULL table, a
+ * coefficient that is not finite, steps < 1 or another mode; t2s_sampler_create in turn refuses T2S_MODE_LMS. */
+int t2s_sampler_create_lms(t2s_dit* dit, t2s_vae* vae /* may be NULL: no decode */, const t2s_sample_config* cfg,
+                           const float* lms_coef, t2s_sampler** out);
 void t2s_sampler_destroy(t2s_sampler* s);
 /* Run the whole loop.
  *   x      (B,64,30) in: x_T (perf mode: fill it with t2s_philox_normal, stream_id 0xFFFFFFFF);

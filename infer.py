@@ -22,7 +22,13 @@ Differences from the reference, all additive:
     with `--run_multi`'s 1 + 10 runs) and writes exactly the directories the separate invocations write.  The rows of
     every (cell, run) share the launches (per-row Philox key and guidance scale, t2s_sampler_set_rows).
 
+  * `--solver {ancestral,ddim,dpmpp2m,euler,ab2}`, `--sample_steps S`, `--eta`: few-step solvers (no counterpart in
+    the reference, sample quality on trained checkpoints not assessed).  The default follows the backbone and is the reference's
+    run, byte for byte; `ddim` / `dpmpp2m` sample a `--total_step` DDPM checkpoint in S evaluations, `ab2` is a second-order
+    step for the flow model; a non-default solver writes to `..._{total_step}_{solver}{S}/`.
+
     python infer.py --dataset_name ETTh1_24,ETTh1_48,ETTh1_96 --cfg_scale 9 --total_step 10 --run_multi True
+    python infer.py --dataset_name ETTh1_96 --backbone ddpm --total_step 1000 --solver dpmpp2m --sample_steps 50
 """
 import argparse
 import copy
@@ -45,7 +51,7 @@ from model.backbone.rectified_flow import RectifiedFlow      # noqa: E402,F401
 from model.denoiser.transformer import Transformer            # noqa: E402
 from t2ms_amd import dist as tdist                            # noqa: E402
 from t2ms_amd import synth                                    # noqa: E402
-from t2ms_amd.sampler import Sampler, np_save_outputs         # noqa: E402
+from t2ms_amd.sampler import Sampler, np_save_outputs, resolve_solver   # noqa: E402
 
 
 def _weight_seed(args):
@@ -164,11 +170,17 @@ def parse_cells(args):
         raise ValueError(f"--dataset_name: all datasets of one job must share one root (checkpoint and LA-VAE), got {roots}")
     if args.denoiser == "MLP" and len(names) * len(cfgs) > 1:
         raise ValueError("--denoiser MLP samples one dataset at one cfg scale per job (lists are for the DiT sampler)")
+    # --solver / --sample_steps / --eta: the default follows the backbone and leaves every path as it was; a few-step solver
+    # names its own directory ("..._{steps}_{solver}{S}")
+    args.solver, suffix = resolve_solver(args.backbone, getattr(args, "solver", None), getattr(args, "sample_steps", None),
+                                         getattr(args, "eta", None), args.total_step)
+    if suffix and args.denoiser == "MLP":
+        raise ValueError(f"--solver {args.solver} runs in the DiT sampler (--denoiser MLP keeps the reference's loop)")
     cells = []
     for name in names:
         for shown, cfg in cfgs:
             path = os.path.join(args.save_path, "generation",
-                                "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, name, shown, args.total_step))
+                                "{}_{}_{}_{}_{}".format(args.backbone, args.denoiser, name, shown, args.total_step) + suffix)
             cells.append(Cell(dataset_name=name, cfg=cfg, cfg_shown=shown, path=path))
     if len({c.path for c in cells}) != len(cells):
         raise ValueError("the grid names the same (dataset, cfg scale) twice")
@@ -436,6 +448,9 @@ def sample_grid(args, cells, n_runs):
         out = (np.empty((n_rows, Lmax), np.float32), np.empty((n_rows, 64, 30), np.float32),
                np.empty((n_rows, 64, 30), np.float32))
     held, held_chunks, samplers = [], [], {}
+    # the few-step solver of the job (parse_cells resolved it; absent = the backbone's own update, as before)
+    solver_kw = dict(solver=getattr(args, "solver", None), sample_steps=getattr(args, "sample_steps", None),
+                     eta=getattr(args, "eta", None) or 0.0)
     mixed = 0
     t_start = time.time()
 
@@ -495,7 +510,7 @@ def sample_grid(args, cells, n_runs):
                 sampler = samplers.get((n, L0))
                 if sampler is None:
                     sampler = samplers[(n, L0)] = Sampler(model, vae.decoder, backbone, args.total_step, unit_cfgs[segs[0][0]],
-                                                          n, L0, device, use_graph=True, seed=args.seed, row0=0)
+                                                          n, L0, device, use_graph=True, seed=args.seed, row0=0, **solver_kw)
                 sampler.set_rows(seeds, keys, cfgs)       # this launch's (seed, key row, cfg) per row; the graph is kept
                 lat, series, _ = sampler.run(embedding.contiguous(), decode=len(groups) == 1)
                 ser = torch.zeros(n, Lmax, device=device)
@@ -521,7 +536,8 @@ def sample_grid(args, cells, n_runs):
                 ts = samplers.get(("trace", m, lens[ui]))
                 if ts is None:
                     ts = samplers[("trace", m, lens[ui])] = Sampler(model, vae.decoder, backbone, args.total_step, u.cfg, m,
-                                                                    lens[ui], device, use_graph=True, seed=args.seed, row0=0)
+                                                                    lens[ui], device, use_graph=True, seed=args.seed, row0=0,
+                                                                    **solver_kw)
                 ts.set_rows(*row_tables([(ui, 0, m)], unit_seeds, unit_cfgs))
                 traces[ui] = ts.run(emb_dev[ui][:m].contiguous(), decode=True, trace=True)[2].cpu().numpy()
     tdist.barrier(dist, device)
@@ -593,12 +609,24 @@ def build_parser():
                         "+35 %%; its error against fp64 is not larger than the reference's PyTorch-CPU fp32 arithmetic, "
                         "profiles/r05_accuracy.md), f32 (exact f32 MFMA) or bf16 (opt-in mixed precision: operands rounded "
                         "once to bf16, fp32 accumulate; 2.5x bf16x3, rms error ~1e-3 on outputs of ~4.5 per forward, DESIGN.md 4.4)")
+    p.add_argument("--solver", default=None, choices=["ancestral", "ddim", "dpmpp2m", "euler", "ab2"],
+                   help="sampling update (default: the backbone's own -- ancestral for ddpm, euler for flowmatching: the reference's "
+                        "run).  ddpm: ddim / dpmpp2m sample a --total_step checkpoint in --sample_steps denoiser evaluations; "
+                        "flowmatching: ab2 is a second-order step at the same --total_step evaluations.  No counterpart in the "
+                        "reference; the output directory gets the suffix _{solver}{S}")
+    p.add_argument("--sample_steps", type=int, default=None,
+                   help="denoiser evaluations S <= --total_step of --solver ddim / dpmpp2m (default: --total_step)")
+    p.add_argument("--eta", type=float, default=None, help="--solver ddim: noise scale (0 = deterministic, the default)")
     return p
 
 
 def main(argv=None):
     args = build_parser().parse_args(argv)
     args.mix_train = False
+    try:
+        resolve_solver(args.backbone, args.solver, args.sample_steps, args.eta, args.total_step)
+    except ValueError as e:
+        sys.exit(f"infer.py: {e}")
     if not torch.cuda.is_available():
         sys.exit("infer.py: no GPU visible -- this build runs the HIP path only (no CPU fallback)")
     local_rank = tdist.local_device_index()

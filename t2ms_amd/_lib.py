@@ -130,7 +130,7 @@ class SampleConfig(C.Structure):
                 ("ddpm_coef", C.c_void_p), ("t_values", C.c_void_p)]
 
 
-MODE_DDPM, MODE_RF = 0, 1
+MODE_DDPM, MODE_RF, MODE_LMS = 0, 1, 2   # t2s.h: T2S_MODE_DDPM / T2S_MODE_RF / T2S_MODE_LMS
 
 # every symbol include/t2s.h declares: (name, restype, argtypes)
 _VP, _I, _F, _U64, _U32 = C.c_void_p, C.c_int, C.c_float, C.c_uint64, C.c_uint32
@@ -180,6 +180,7 @@ SYMBOLS = {
     "t2s_attn_fwd": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_attn_fwd_packed": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_ddpm_step": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _F, _U64, _U32, _U32, _I, _VP]),
+    "t2s_lms_step": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _F, _U64, _U32, _U32, _I, _VP]),
     "t2s_ddpm_p_sample": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_ddpm_p_sample_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_ddpm_q_sample_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
@@ -198,6 +199,7 @@ SYMBOLS = {
     "t2s_vae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_vae_encode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_sampler_create": (_I, [_VP, _VP, C.POINTER(SampleConfig), C.POINTER(_VP)]),
+    "t2s_sampler_create_lms": (_I, [_VP, _VP, C.POINTER(SampleConfig), _VP, C.POINTER(_VP)]),
     "t2s_sampler_destroy": (None, [_VP]),
     "t2s_sampler_run": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "t2s_sampler_set_lanes": (_I, [_VP, _I]),

@@ -172,6 +172,97 @@ __global__ __launch_bounds__(256) void ddpm_step_kernel(const StepArgs a) {
     if (a.advance) advance_step_when_last(a.advance);
 }
 
+// ---------------------------------------------------------------- linear multistep update (DDIM, DPM-Solver++(2M), AB2)
+// One table-driven update for every few-step solver: per element, with pred = u + cfg * (c - u) (pred = u without eps_c),
+//   x' = c0 * x + c1 * pred + c2 * h + c3 * z        h' = c4 * x + c5 * pred   (from the OLD x)
+// coef row j = {c0 .. c5} belongs to LOOP INDEX j (not steps-1-j: the solver's grid is in t_values, the table follows the
+// loop).  A coefficient that is exactly 0 means its operand is not touched -- c2 == 0: h is not loaded (NaN / uninitialised
+// history on the first step is fine); c3 == 0: no draw, no Philox work, noise may be NULL; c4 == c5 == 0: h is not
+// written.  The coefficients are launch-uniform, so are the branches.
+// Arithmetic (fixed: results repeat bit for bit): the fp32 operands are widened, the update is evaluated in fp64 in the order
+// pred = fma(cfg, c - u, u); acc = c0 * x; acc = fma(c1, pred, acc); acc = fma(c2, h, acc); acc = fma(c3, z, acc);
+// hn = fma(c5, pred, c4 * x), and acc / hn are rounded to fp32 ONCE.  Why fp64: the x0-prediction history of DPM-Solver++ is
+// (x - s * eps) / a with 1 / a = 157 at t = 999 of the 1000-step schedule -- two large terms that cancel -- and a four-term
+// fp32 sum carries four roundings of partial sums larger than its result; the kernel is bound by its four to seven
+// (B,1920) streams, the ~40 fp64 operations per quad do not show (tools/solver_probe.py).
+struct LmsArgs {
+    float* x;             // (B,1920) in place
+    float* hist;          // (B,1920) in place
+    const float* eps_u;   // (B,1920)
+    const float* eps_c;   // (B,1920) or NULL
+    const float* noise;   // injected draws: (steps,noise_rows,1920) indexed by step (this shard's first row), or (B,1920)
+                          // if step_ptr NULL; NULL: Philox
+    const float* coef;    // DEVICE (S,6)
+    const int* step_ptr;  // device {loop index j, global row of the first series, -, ROWS_* bits}, or NULL (then index /
+                          // stream_id / row0 are immediate)
+    int index;
+    float cfg;
+    uint64_t seed;
+    uint32_t stream_id;
+    uint32_t row0;
+    int B;
+    int noise_rows;
+    int* advance;         // sampling loop: the last workgroup increments the lane's loop index (advance_step_when_last)
+    const uint64_t* row_seed;   // per-row tables as in StepArgs
+    const uint32_t* row_key;
+    const float* row_cfg;
+};
+
+__global__ __launch_bounds__(256) void lms_step_kernel(const LmsArgs a) {
+    constexpr int QPR = LAT / 4;
+    int j = a.index;
+    uint32_t sid = a.stream_id, row0 = a.row0;
+    const float* noise = a.noise;
+    int rows = 0;
+    if (a.step_ptr) {
+        j = a.step_ptr[0];
+        row0 = (uint32_t)a.step_ptr[1];
+        rows = a.step_ptr[3];
+        sid = (uint32_t)j;               // the draw of loop index j is stream j, as ddpm_step_kernel keys it
+        if (noise) noise += (size_t)j * a.noise_rows * LAT;
+    }
+    const float* cj = a.coef + (size_t)j * 6;
+    const float c0 = cj[0], c1 = cj[1], c2 = cj[2], c3 = cj[3], c4 = cj[4], c5 = cj[5];
+    const bool use_h = c2 != 0.0f, use_z = c3 != 0.0f, put_h = c4 != 0.0f || c5 != 0.0f;
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {
+        const int row = idx / QPR;
+        const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[idx];
+        const f32x4 u = reinterpret_cast<const f32x4*>(a.eps_u)[idx];
+        f32x4 c = u, h = x, z = x;                   // (placeholders where the operand is not read)
+        double cfg = 0.0;
+        if (a.eps_c) {
+            c = reinterpret_cast<const f32x4*>(a.eps_c)[idx];
+            cfg = (double)((rows & ROWS_CFG) ? a.row_cfg[row] : a.cfg);
+        }
+        if (use_h) h = reinterpret_cast<const f32x4*>(a.hist)[idx];
+        if (use_z) {
+            if (noise) {
+                z = reinterpret_cast<const f32x4*>(noise)[idx];
+            } else {
+                const int quad = idx - row * QPR;
+                const uint64_t seed = (rows & ROWS_SEED) ? a.row_seed[row] : a.seed;
+                const uint32_t key = (rows & ROWS_KEY) ? a.row_key[row] : row0 + (uint32_t)row;
+                z = normal4(seed, sid, key, (uint32_t)quad);
+            }
+        }
+        f32x4 xn, hn;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            double pred = (double)u[e];
+            if (a.eps_c) pred = fma(cfg, (double)c[e] - (double)u[e], pred);
+            double acc = (double)c0 * (double)x[e];
+            acc = fma((double)c1, pred, acc);
+            if (use_h) acc = fma((double)c2, (double)h[e], acc);
+            if (use_z) acc = fma((double)c3, (double)z[e], acc);
+            xn[e] = (float)acc;
+            hn[e] = (float)fma((double)c5, pred, (double)c4 * (double)x[e]);
+        }
+        if (put_h) reinterpret_cast<f32x4*>(a.hist)[idx] = hn;
+        reinterpret_cast<f32x4*>(a.x)[idx] = xn;
+    }
+    if (a.advance) advance_step_when_last(a.advance);
+}
+
 // row_cfg: this lane's slice of the per-row guidance table, used when bit ROWS_CFG of advance[3] is set (NULL: never)
 __global__ __launch_bounds__(256) void rf_step_kernel(float* __restrict__ x, const float* __restrict__ vu,
                                                       const float* __restrict__ vc, float cfg, float dt,
@@ -338,6 +429,20 @@ extern "C" int t2s_ddpm_step(float* x, const float* eps_u, const float* eps_c, c
     return T2S_OK;
 }
 
+extern "C" int t2s_lms_step(float* x, float* hist, const float* pred_u, const float* pred_c, const float* noise,
+                            const float* coef, int index, float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B,
+                            void* stream) {
+    T2S_REQUIRE(x && hist && pred_u && coef, "t2s_lms_step: NULL argument");
+    T2S_REQUIRE(B > 0 && index >= 0 && (long long)B * LAT < (1ll << 31), "t2s_lms_step: B=%d index=%d", B, index);
+    LmsArgs a{};
+    a.x = x; a.hist = hist; a.eps_u = pred_u; a.eps_c = pred_c; a.noise = noise; a.coef = coef; a.step_ptr = nullptr;
+    a.index = index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
+    const int total = B * (LAT / 4), wgs = (total + 255) / 256;
+    lms_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, (hipStream_t)stream>>>(a);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
 extern "C" int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float dt, int B, void* stream) {
     T2S_REQUIRE(x && v_u && B > 0, "t2s_rf_step: bad argument");
     const int n4 = B * (LAT / 4);
@@ -423,7 +528,8 @@ struct t2s_sampler {
     t2s_vae* vae = nullptr;
     t2s_sample_config cfg{};
     float* temb_table = nullptr;  // (steps,128)
-    float* coef = nullptr;        // (steps,3)  DDPM only
+    float* coef = nullptr;        // (steps,3)  DDPM; (steps,6) by LOOP INDEX in T2S_MODE_LMS
+    float* hist = nullptr;        // (B,1920)   T2S_MODE_LMS: the solver's history (x0_prev / v_prev), sliced by rows per lane
     float* eps_u = nullptr;       // (B,1920)
     float* eps_c = nullptr;
     float* tvals = nullptr;       // (steps)
@@ -591,6 +697,17 @@ int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise
         a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
         const int total = n * (LAT / 4), wgs = (total + 255) / 256;
         ddpm_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(a);
+    } else if (c.mode == T2S_MODE_LMS) {
+        LmsArgs a{};
+        a.x = xl; a.hist = s->hist + (size_t)r0 * LAT; a.eps_u = eu; a.eps_c = ec;
+        a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
+        a.step_ptr = step; a.cfg = c.cfg_scale; a.seed = c.seed; a.row0 = c.row0 + (uint32_t)r0;
+        a.B = n; a.noise_rows = c.batch; a.advance = step;
+        a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
+        a.row_key = rows_key(s->d_rows, c.batch) + r0;
+        a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
+        const int total = n * (LAT / 4), wgs = (total + 255) / 256;
+        lms_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(a);
     } else {
         const int n4 = n * (LAT / 4), wgs = (n4 + 255) / 256;
         rf_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(xl, eu, ec, c.cfg_scale, 1.0f / (float)c.steps, n4, step,
@@ -646,9 +763,8 @@ std::recursive_mutex* lib_pool_lock(int dev) { return dev >= 0 && dev < 16 ? &g_
 
 extern "C" int t2s_dit_max_seqs(const t2s_dit* h);
 
-extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, t2s_sampler** out) {
-    T2S_REQUIRE(dit && cfg && out, "t2s_sampler_create: NULL argument");
-    T2S_REQUIRE(cfg->mode == T2S_MODE_DDPM || cfg->mode == T2S_MODE_RF, "t2s_sampler_create: mode=%d", cfg->mode);
+// t2s_sampler_create (lms_coef NULL; modes DDPM / RF) and t2s_sampler_create_lms (mode LMS, HOST (steps,6) table)
+static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, const float* lms_coef, t2s_sampler** out) {
     T2S_REQUIRE(cfg->steps > 0 && cfg->steps <= 100000, "t2s_sampler_create: steps=%d", cfg->steps);
     T2S_REQUIRE(cfg->batch > 0 && 2 * cfg->batch <= t2s_dit_max_seqs(dit),
                 "t2s_sampler_create: batch=%d needs 2*batch <= dit max_seqs=%d", cfg->batch, t2s_dit_max_seqs(dit));
@@ -669,7 +785,8 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     hipError_t e = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
     alloc((void**)&s->temb_table, T * D * sizeof(float));
-    alloc((void**)&s->coef, T * 3 * sizeof(float));
+    alloc((void**)&s->coef, T * (lms_coef ? 6 : 3) * sizeof(float));
+    if (lms_coef) alloc((void**)&s->hist, B * LAT * sizeof(float));
     alloc((void**)&s->eps_u, B * LAT * sizeof(float));
     alloc((void**)&s->eps_c, B * LAT * sizeof(float));
     alloc((void**)&s->tvals, T * sizeof(float));
@@ -701,6 +818,9 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     if (e == hipSuccess) e = hipMemcpyAsync(s->tvals, cfg->t_values, T * sizeof(float), hipMemcpyHostToDevice, setup);
     if (e == hipSuccess && cfg->mode == T2S_MODE_DDPM)
         e = hipMemcpyAsync(s->coef, cfg->ddpm_coef, T * 3 * sizeof(float), hipMemcpyHostToDevice, setup);
+    if (e == hipSuccess && lms_coef) e = hipMemcpyAsync(s->coef, lms_coef, T * 6 * sizeof(float), hipMemcpyHostToDevice, setup);
+    // a caller's table may read the history at its first step (the solvers of t2ms_amd.sampler.solver_tables never do)
+    if (e == hipSuccess && lms_coef) e = hipMemsetAsync(s->hist, 0, B * LAT * sizeof(float), setup);
     if (e == hipSuccess) e = hipStreamSynchronize(setup);      // the host tables may go away when the call returns
     if (e != hipSuccess) {
         set_error("t2s_sampler_create: allocation/upload failed: %s", hipGetErrorString(e));
@@ -722,6 +842,25 @@ extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_c
     (void)lane_streams();
     *out = s;
     return T2S_OK;
+}
+
+extern "C" int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, t2s_sampler** out) {
+    T2S_REQUIRE(dit && cfg && out, "t2s_sampler_create: NULL argument");
+    T2S_REQUIRE(cfg->mode == T2S_MODE_DDPM || cfg->mode == T2S_MODE_RF, "t2s_sampler_create: mode=%d", cfg->mode);
+    return sampler_create(dit, vae, cfg, nullptr, out);
+}
+
+extern "C" int t2s_sampler_create_lms(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, const float* lms_coef,
+                                      t2s_sampler** out) {
+    // every refusal before any allocation
+    T2S_REQUIRE(dit && cfg && out, "t2s_sampler_create_lms: NULL argument");
+    T2S_REQUIRE(cfg->mode == T2S_MODE_LMS, "t2s_sampler_create_lms: mode=%d (T2S_MODE_LMS = %d)", cfg->mode, T2S_MODE_LMS);
+    T2S_REQUIRE(cfg->steps >= 1, "t2s_sampler_create_lms: steps=%d", cfg->steps);
+    T2S_REQUIRE(lms_coef, "t2s_sampler_create_lms: the coefficient table is NULL");
+    T2S_REQUIRE(cfg->steps <= 100000, "t2s_sampler_create_lms: steps=%d", cfg->steps);
+    for (int i = 0; i < cfg->steps * 6; ++i)
+        T2S_REQUIRE(std::isfinite(lms_coef[i]), "t2s_sampler_create_lms: coefficient %d of step %d is not finite", i % 6, i / 6);
+    return sampler_create(dit, vae, cfg, lms_coef, out);
 }
 
 extern "C" int t2s_sampler_set_lanes(t2s_sampler* s, int lanes) {
@@ -782,7 +921,7 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     if (s->ev_rows && s->ev_rows_recorded) (void)hipEventSynchronize(s->ev_rows);   // the last upload has read h_stage
     if (s->ev_rows) (void)hipEventDestroy(s->ev_rows);
     if (s->h_stage) (void)hipHostFree(s->h_stage);
-    void* bufs[] = {s->temb_table, s->coef, s->eps_u, s->eps_c, s->tvals, s->step, s->mod_table, s->d_rows};
+    void* bufs[] = {s->temb_table, s->coef, s->hist, s->eps_u, s->eps_c, s->tvals, s->step, s->mod_table, s->d_rows};
     for (void* b : bufs)
         if (b) (void)hipFree(b);
     delete s;

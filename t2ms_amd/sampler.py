@@ -50,6 +50,132 @@ def loop_t_values(backbone: str, steps: int) -> torch.Tensor:
     raise ValueError("No backbone found")
 
 
+SOLVERS = {"ddpm": ("ancestral", "ddim", "dpmpp2m"), "flowmatching": ("euler", "ab2")}   # [0] = today's update kernel
+
+
+def default_solver(backbone: str) -> str:
+    if backbone not in SOLVERS:
+        raise ValueError("No backbone found")
+    return SOLVERS[backbone][0]
+
+
+def resolve_solver(backbone: str, solver: Optional[str] = None, sample_steps: Optional[int] = None, eta: Optional[float] = None,
+                   total_step: Optional[int] = None):
+    """The drivers' --solver / --sample_steps / --eta against --backbone -> (solver, directory suffix).  The default
+    follows the backbone (ancestral / euler: today's run, suffix ""); a few-step solver appends "_{solver}{S}" to the
+    generation directory so that runs with different solvers do not overwrite one another.  ValueError with a plain
+    message for a mismatched pair: a solver of the other backbone, --sample_steps with flowmatching or without a few-step
+    solver, --eta without ddim."""
+    if backbone not in SOLVERS:
+        raise ValueError("No backbone found")
+    solver = solver or default_solver(backbone)
+    if solver not in SOLVERS[backbone]:
+        raise ValueError(f"--solver {solver} does not go with --backbone {backbone} (its solvers: {', '.join(SOLVERS[backbone])})")
+    if eta is not None and solver != "ddim":
+        raise ValueError(f"--eta is ddim's noise scale; --solver is {solver}")
+    if sample_steps is not None and backbone == "flowmatching":
+        raise ValueError("--sample_steps is for the ddpm solvers; the flow model's step count is --total_step")
+    if sample_steps is not None and solver == default_solver(backbone):
+        raise ValueError(f"--sample_steps needs --solver ddim or dpmpp2m; {solver} runs all --total_step steps")
+    if solver == default_solver(backbone):
+        return solver, ""
+    if total_step is not None:
+        solver_tables(backbone, solver, total_step, sample_steps, eta or 0.0)      # its refusals (S > T, dpmpp2m with S = 1, ...)
+    S = sample_steps if sample_steps is not None else total_step
+    return solver, f"_{solver}{S}"
+
+
+def solver_grid(total_step: int, sample_steps: int) -> np.ndarray:
+    """The "trailing" grid of S = sample_steps trained DDPM times out of T = total_step: tau_i = round(T - i*T/S) - 1
+    (int64, strictly decreasing, tau_0 = T-1; S = T gives T-1 .. 0).  Integers: the denoiser only sees times it was
+    trained on.  After tau_{S-1} the target level is clean (alpha_bar = 1)."""
+    T, S = int(total_step), int(sample_steps)
+    if not 1 <= S <= T:
+        raise ValueError(f"sample_steps must lie in [1, total_step = {T}], got {S}")
+    tau = np.round(T - np.arange(S, dtype=np.float64) * T / S).astype(np.int64) - 1
+    assert tau[0] == T - 1 and tau[-1] >= 0 and (np.diff(tau) < 0).all()
+    return tau
+
+
+def solver_tables(backbone: str, solver: str, total_step: int, sample_steps: Optional[int] = None, eta: float = 0.0):
+    """-> (t_values (S,) fp32, coef (S,6) fp32) of a few-step solver for the table-driven update of t2s_lms_step,
+        x' = c0*x + c1*pred + c2*h + c3*z        h' = c4*x + c5*pred        (row j = loop index j)
+    All algebra in fp64 from the fp32 alpha_bar of ddpm_host_tables(total_step) (the trained schedule as the reference
+    computes it), rounded to fp32 once at the end.  These solvers have no counterpart in the reference.
+
+    ddpm, on solver_grid(total_step, sample_steps); a = sqrt(ab), s = sqrt(1 - ab) at tau_i, primes at tau_{i+1} (clean
+    after the last: a' = 1, s' = 0, so the last update returns the x0 prediction), x0 = (x - s*eps)/a:
+      "ddim"     x' = a'*x0 + sqrt(1 - ab' - g^2)*eps + g*z,  g = eta*sqrt((1-ab')/(1-ab))*sqrt(1 - ab/ab')
+                 (Song et al. 2021, eq. 12 / 16); eta = 0: c3 == 0 exactly; no history (c2 = c4 = c5 = 0)
+      "dpmpp2m"  DPM-Solver++ multistep, order 2, on eps-prediction (Lu et al. 2022, alg. 2): lam = log(a/s),
+                 h = lam' - lam, r = (lam - lam_prev)/h, D = (1 + 1/(2r))*x0 - 1/(2r)*x0_prev,
+                 x' = (s'/s)*x - a'*expm1(-h)*D; history = x0 (c4 = 1/a, c5 = -s/a); first and last step of order 1
+                 (= ddim with eta 0); S >= 2
+    flowmatching, t_values of loop_t_values, dt = 1/S, S = total_step (sample_steps None or equal):
+      "ab2"      step 0 Euler (c0 = 1, c1 = dt), then x' = x + dt*(1.5*v - 0.5*v_prev); history = v (c5 = 1)
+    The last row writes no history (nothing reads it).  "ancestral" / "euler" are today's update kernels, not tables:
+    ValueError here."""
+    T = int(total_step)
+    if backbone not in SOLVERS:
+        raise ValueError("No backbone found")
+    if solver not in SOLVERS[backbone] or solver == SOLVERS[backbone][0]:
+        raise ValueError(f"solver_tables: no table for solver {solver!r} with backbone {backbone!r} "
+                         f"(tables: {', '.join(SOLVERS[backbone][1:])}; {SOLVERS[backbone][0]!r} is the existing update kernel)")
+    eta = float(eta)
+    if backbone == "flowmatching":
+        if sample_steps is not None and int(sample_steps) != T:
+            raise ValueError(f"{solver}: the flow model's step count is total_step ({T}); sample_steps must be None or equal, "
+                             f"got {sample_steps}")
+        if eta != 0.0:
+            raise ValueError("eta belongs to ddim")
+        if T < 1:
+            raise ValueError(f"total_step must be >= 1, got {T}")
+        S, dt = T, 1.0 / T
+        coef = np.zeros((S, 6), dtype=np.float64)
+        coef[:, 0] = 1.0
+        coef[0, 1] = dt
+        coef[1:, 1], coef[1:, 2] = 1.5 * dt, -0.5 * dt
+        coef[:-1, 5] = 1.0
+        return loop_t_values(backbone, S).contiguous(), torch.from_numpy(coef.astype(np.float32))
+    S = T if sample_steps is None else int(sample_steps)
+    tau = solver_grid(T, S)
+    if solver == "dpmpp2m" and S < 2:
+        raise ValueError("dpmpp2m is a two-step method: sample_steps must be >= 2")
+    if solver != "ddim" and eta != 0.0:
+        raise ValueError("eta belongs to ddim")
+    if not (np.isfinite(eta) and eta >= 0.0):
+        raise ValueError(f"eta must be finite and >= 0, got {eta}")
+    ab_all = ddpm_host_tables(T)["alpha_bar"].numpy().astype(np.float64)
+    ab = ab_all[tau]
+    ab_n = np.append(ab[1:], 1.0)                       # the next level; clean after the last grid point
+    a, s, a_n, s_n = np.sqrt(ab), np.sqrt(1.0 - ab), np.sqrt(ab_n), np.sqrt(1.0 - ab_n)
+    coef = np.zeros((S, 6), dtype=np.float64)
+    if solver == "ddim":
+        g = eta * np.sqrt((1.0 - ab_n) / (1.0 - ab)) * np.sqrt(1.0 - ab / ab_n)
+        if (1.0 - ab_n - g * g < 0.0).any():
+            raise ValueError(f"ddim: eta = {eta} gives a variance above 1 - alpha_bar' on this grid")
+        coef[:, 0] = a_n / a
+        coef[:, 1] = np.sqrt(1.0 - ab_n - g * g) - a_n * s / a
+        coef[:, 3] = g
+    else:
+        lam = np.log(a / s)
+        with np.errstate(divide="ignore"):
+            lam_n = np.append(lam[1:], np.inf)          # clean: h = inf, expm1(-h) = -1
+        h = lam_n - lam
+        E = -a_n * np.expm1(-h)                         # x' = (s'/s)*x + E*D
+        w = np.zeros(S)                                 # 1/(2r); 0 = first order (first and last step)
+        w[1:-1] = 0.5 * h[1:-1] / (lam[1:-1] - lam[:-2])
+        coef[:, 0] = s_n / s + E * (1.0 + w) / a
+        coef[:, 1] = -E * (1.0 + w) * s / a
+        coef[:, 2] = -E * w
+        coef[:-1, 4] = 1.0 / a[:-1]
+        coef[:-1, 5] = -s[:-1] / a[:-1]
+    c32 = (coef + 0.0).astype(np.float32)               # (+ 0.0: a -0.0 coefficient becomes the 0.0 it stands for)
+    if not np.isfinite(c32).all():
+        raise ValueError(f"{solver}: a coefficient is not finite in fp32 on this grid")
+    return torch.from_numpy(tau.astype(np.float32)), torch.from_numpy(c32)
+
+
 _STREAMS = {}
 
 
@@ -146,14 +272,39 @@ def philox_uniform(n_rows: int, row_elems: int, seed: int, stream_id: int, row0:
     return out
 
 
+def lms_step(x: torch.Tensor, hist: torch.Tensor, pred_u: torch.Tensor, pred_c: Optional[torch.Tensor], coef: torch.Tensor,
+             index: int, cfg: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0,
+             row0: int = 0) -> None:
+    """One update of t2s_lms_step, IN PLACE on x and hist ((B,64,30) or (B,1920) fp32 on the GPU):
+    x' = c0*x + c1*pred + c2*h + c3*z, h' = c4*x + c5*pred with {c0..c5} = coef[index] (DEVICE (S,6)), pred = u + cfg*(c-u)
+    (pred = u when pred_c is None), z = `noise` or, when None, the Philox draw (seed, stream_id, row0 + row).  For stepwise
+    loops; the Sampler runs the same kernel from its loop."""
+    B = x.shape[0]
+    for name, v in (("x", x), ("hist", hist), ("pred_u", pred_u), ("pred_c", pred_c), ("noise", noise)):
+        if v is not None and (v.shape[0] != B or v.numel() != B * L.LAT):
+            raise L.T2SError(f"lms_step: {name} must hold ({B},1920) values, got {tuple(v.shape)}")
+    if coef.dim() != 2 or coef.shape[1] != 6 or not 0 <= int(index) < coef.shape[0]:
+        raise L.T2SError(f"lms_step: coef must be (S,6) with 0 <= index < S, got {tuple(coef.shape)}, index {index}")
+    with torch.cuda.device(x.device):
+        L.check(L.lib().t2s_lms_step(L.dev_ptr(x, "x"), L.dev_ptr(hist, "hist"), L.dev_ptr(pred_u, "pred_u"),
+                                     L.dev_ptr(pred_c, "pred_c"), L.dev_ptr(noise, "noise"), L.dev_ptr(coef, "coef"), int(index),
+                                     float(cfg), int(seed), int(stream_id) & 0xFFFFFFFF, int(row0), B, L.stream_ptr(x.device)),
+                "t2s_lms_step")
+
+
 class Sampler:
     def __init__(self, model, decoder, backbone: str, steps: int, cfg_scale: float, batch: int, length: int,
                  device, use_graph: bool = True, seed: int = 2025, row0: int = 0, lanes: int = 0, loop_graph: int = -1,
-                 math: Optional[str] = None):
+                 math: Optional[str] = None, solver: Optional[str] = None, sample_steps: Optional[int] = None, eta: float = 0.0):
         """lanes: 0 = automatic (equal part-batch chains on own streams: two when the batch is a multiple of 64 or 32 series, three for 96), 1 .. 4 -- see
         t2s_sampler_set_lanes; a scheduling choice only, the results are bitwise the same.
         math: "f32" | "bf16x3" | "bf16" (single-pass bf16 mixed precision: opt-in, not fp32-accurate) selects the model's matrix arithmetic (Transformer.set_math) for this sampler and everything else
-        that runs the model afterwards; None = what the model's owner chose with set_math, else default_math() (bf16x3)."""
+        that runs the model afterwards; None = what the model's owner chose with set_math, else default_math() (bf16x3).
+        solver: None / "ancestral" (ddpm) / "euler" (flowmatching) = the reference's update, exactly what was created before
+        the solvers existed; "ddim" / "dpmpp2m" (ddpm) and "ab2" (flowmatching) = the few-step solvers of solver_tables
+        (t2s_sampler_create_lms).  `steps` stays the TRAINED schedule length (--total_step); with a ddpm solver the loop runs
+        sample_steps (default: steps) denoiser evaluations and self.steps becomes that S -- the first dimension of `noise`.
+        eta: ddim's stochasticity (0 = deterministic)."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.T2SError("Sampler needs a GPU device; the HIP path has no CPU fallback")
@@ -162,6 +313,14 @@ class Sampler:
         if hasattr(model, "set_math"):
             model.set_math(self.math)
         self.backbone, self.steps, self.cfg_scale = backbone, int(steps), float(cfg_scale)
+        self.total_step, self.solver, self.eta = int(steps), solver, float(eta)
+        self._lms = None
+        if solver is not None and solver != default_solver(backbone):
+            self._lms = solver_tables(backbone, solver, self.total_step, sample_steps, self.eta)    # raises on a mismatched pair
+            self.steps = int(self._lms[0].numel())
+        elif sample_steps is not None or self.eta != 0.0:
+            raise ValueError(f"sample_steps / eta need a few-step solver ({', '.join(SOLVERS.get(backbone, ('?',))[1:])}); "
+                             f"{default_solver(backbone)!r} runs the trained schedule")
         self.batch, self.length, self.seed, self.row0 = int(batch), int(length), int(seed), int(row0)
         self.use_graph = bool(use_graph)
         self.lanes = int(lanes)
@@ -181,13 +340,16 @@ class Sampler:
         if self.ptr is not None:
             self._fin()
         model, decoder, backbone, use_graph = self.model, self.decoder, self.backbone, self.use_graph
-        tvals = loop_t_values(backbone, self.steps).contiguous()
+        lms = self.__dict__.get("_lms")
+        tvals = loop_t_values(backbone, self.steps).contiguous() if lms is None else lms[0].contiguous()
         cfg = L.SampleConfig()
-        cfg.mode = L.MODE_DDPM if backbone == "ddpm" else L.MODE_RF
+        cfg.mode = L.MODE_LMS if lms is not None else (L.MODE_DDPM if backbone == "ddpm" else L.MODE_RF)
         cfg.steps, cfg.cfg_scale, cfg.batch, cfg.length = self.steps, self.cfg_scale, self.batch, self.length
         cfg.use_graph, cfg.seed, cfg.row0 = int(bool(use_graph)), self.seed, self.row0
         coef = None
-        if backbone == "ddpm":
+        if lms is not None:
+            coef = lms[1].contiguous()                   # host (S,6), copied by the library
+        elif backbone == "ddpm":
             coef = ddpm_host_tables(self.steps)["coef"].contiguous()
             cfg.ddpm_coef = coef.data_ptr()          # host pointers, copied by the library
         cfg.t_values = tvals.data_ptr()
@@ -197,7 +359,11 @@ class Sampler:
             vae = decoder._handle(self.device) if decoder is not None else None
             torch.cuda.synchronize(self.device)
             self.ptr = C.c_void_p()
-            L.check(L.lib().t2s_sampler_create(dit, vae, C.byref(cfg), C.byref(self.ptr)), "t2s_sampler_create")
+            if lms is not None:
+                L.check(L.lib().t2s_sampler_create_lms(dit, vae, C.byref(cfg), coef.data_ptr(), C.byref(self.ptr)),
+                        "t2s_sampler_create_lms")
+            else:
+                L.check(L.lib().t2s_sampler_create(dit, vae, C.byref(cfg), C.byref(self.ptr)), "t2s_sampler_create")
             L.check(L.lib().t2s_sampler_set_lanes(self.ptr, self.lanes), "t2s_sampler_set_lanes")
             L.check(L.lib().t2s_sampler_set_loop_graph(self.ptr, self.loop_graph), "t2s_sampler_set_loop_graph")
         self._fin = weakref.finalize(self, L.destroy_locked, "t2s_sampler_destroy", str(self.device), self.ptr)
