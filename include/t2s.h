@@ -440,6 +440,27 @@ typedef struct t2s_vae_enc_grads {
 int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g, int B,
                             int L, void* stream);
 
+/* Backward of Decoder.forward (vqvae.py:97-105): with the encoder backward above, the MSE pair and t2s_adamw_step_multi this is
+ * one optimisation step of LA-VAE pre-training (pretrained_lavae_unified.py:142-174, vqvae.shared_eval mode 'train').
+ *   z (B,64,latent_w) the forward's input; drecon (B,L) = dLoss/drecon; dafter (B,64,L/4) = dLoss/dafter or NULL;
+ *   g: one gradient tensor per decoder.* parameter, same shapes as t2s_vae_weights' dec_* fields; every one is OVERWRITTEN;
+ *   dz (B,64,latent_w) receives dLoss/dz (decoder part + the transposed interpolation of dafter); NULL: not computed.
+ * The forward is recomputed from z (nothing is saved by t2s_vae_decode[_w]); data gradients run per series in LDS, weight
+ * gradients as exact-fp32 MFMA GEMMs over all (series, position) rows with a fixed two-stage reduction, the 4-tap
+ * _conv_trans_2 and the two small biases as per-series partial rows added in series order: bit-reproducible.
+ * Default LA-VAE shape only (hidden 128, res_hidden 128 / 256, emb 64), 8 <= L <= 128, 1 <= latent_w <= 32; anything else
+ * is T2S_E_INVALID ("unsupported").  Like t2s_vae_encode_backward it allocates its row blocks on first use / when B * L grows
+ * (not capturable then, and a device-wide call: the host mirror takes its per-device lock around a call that grows them). */
+typedef struct t2s_vae_dec_grads {
+    float *conv1_w, *conv1_b;   /* decoder._conv_1 (hidden,emb,3), (hidden) */
+    float* stack_conv3_w[4];    /* decoder._residual_stack._layers.i._block.1.weight (res_hidden,hidden,3) */
+    float* stack_conv1_w[4];    /* decoder._residual_stack._layers.i._block.3.weight (hidden,res_hidden,1) */
+    float *ct1_w, *ct1_b;       /* decoder._conv_trans_1 (hidden,hidden/2,4), (hidden/2) */
+    float *ct2_w, *ct2_b;       /* decoder._conv_trans_2 (hidden/2,1,4), (1) */
+} t2s_vae_dec_grads;
+int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter, const t2s_vae_dec_grads* g,
+                            float* dz, int B, int L, int latent_w, void* stream);
+
 /* ------------------------------------------------------------------------ *
  * Fused sampling loop: infer.py:75-95 (x_T -> steps x [2 DiT forwards + CFG +
  * sampler update] -> LA-VAE decode), one hipGraph per step replayed `steps`

@@ -1,0 +1,148 @@
+#!/usr/bin/env python3
+"""LA-VAE pre-training driver (reference pretrained_lavae_unified.py): same flags and defaults, the epoch loop of
+lines 142-174, the same output paths -- with every optimisation step (vqvae.shared_eval(..., 'train')) on the HIP
+kernels: encoder and decoder forward + backward, both MSE terms, fused AdamW.
+
+    python pretrain_lavae.py --dataset_name ETTh1 --mix_train True
+    python pretrain_lavae.py --dataset_name ETTh1_24 --split_train --synthetic 600
+
+writes results/saved_pretrained_models/dataset{name}_epoch{updates}/final_model.pth, the file train.py:22 and infer.py:39
+start from (they look it up under the dataset's family name, i.e. what a mix-train run on `--dataset_name ETTh1` writes).
+
+Kept from the reference: AdamW(lr, weight_decay 1e-2) as BaseModel.configure_optimizers builds it, and NO scheduler step
+(the reference builds one and never steps it); `epochs = int(updates / len(loader) + 0.5)`; a whole-module checkpoint
+`model_epoch_{e}.pth` whenever `e % (updates / 10) == 0`; afterwards the test split goes through
+shared_eval(..., 'test') and metrics.txt gets MAE and RMSE.
+Different on purpose: `final_model.pth` is ALWAYS the whole module (torch.save(model, ...)) -- the reference's non-mix
+branch writes a bare state dict there, which its own train.py:22 / infer.py:39 cannot use; data comes from this project's
+loader_provider (`--dataset_name`, `--synthetic N`, `--split_train` as in train.py) instead of the fork's bench-press
+loader; MAE / RMSE run over every test series (the reference keeps one length group); the plots are omitted.
+"""
+import argparse
+import os
+import random
+import sys
+
+import numpy as np
+import torch
+
+REPO = os.path.dirname(os.path.abspath(__file__))
+if REPO not in sys.path:
+    sys.path.insert(0, REPO)
+
+
+def seed_everything(seed_value=42):
+    random.seed(seed_value)
+    np.random.seed(seed_value)
+    torch.manual_seed(seed_value)
+    if torch.cuda.is_available():
+        torch.cuda.manual_seed_all(seed_value)
+    print(f"seed: {seed_value}")
+
+
+def save_dir_of(args):
+    """pretrained_lavae_unified.py:130-131."""
+    return os.path.join(args.save_path, "dataset{}_epoch{}".format(args.dataset_name, args.num_training_updates))
+
+
+def pretrain_step(model, opt, batch):
+    """One optimisation step on a (B, L) device batch (pretrained_lavae_unified.py:151-152 / 166-167) -> its loss (device)."""
+    loss, _, _, _ = model.shared_eval(batch, opt, "train")
+    return loss
+
+
+def _series_batches(data, mix):
+    """The series tensors of one loader batch: the non-empty length groups of a mix-train batch, or the one batch."""
+    groups = data if mix else [data]
+    return [g[1] for g in groups if g is not None and g[1] is not None]
+
+
+def inference(model, test_loader, device, save_dir, mix):
+    """pretrained_lavae_unified.py:55-94 without the plots: MAE / RMSE of the reconstruction over the test split."""
+    model.eval()
+    abs_sum = sq_sum = torch.zeros((), device=device, dtype=torch.float64)
+    n = 0
+    for data in test_loader:
+        for batch_x in _series_batches(data, mix):
+            real = batch_x.float().to(device)
+            _, _, recon, _ = model.shared_eval(real, None, "test")
+            diff = (real - recon.reshape(real.shape)).double()
+            abs_sum = abs_sum + diff.abs().sum()
+            sq_sum = sq_sum + (diff * diff).sum()
+            n += diff.numel()
+    mae = float(abs_sum) / max(n, 1)
+    rmse = (float(sq_sum) / max(n, 1)) ** 0.5
+    with open(os.path.join(save_dir, "metrics.txt"), "w") as f:
+        f.write(f"MAE: {mae}\n")
+        f.write(f"RMSE: {rmse}\n")
+    return mae, rmse
+
+
+def pretrain(args):
+    """-> the loss of every optimisation step, in order."""
+    if not torch.cuda.is_available():
+        sys.exit("pretrain_lavae.py: no GPU visible -- this build runs the HIP path only (no CPU fallback)")
+    from datafactory.dataloader import loader_provider
+    from model.pretrained.vqvae import vqvae
+    from t2ms_amd.train import T2SAdamW
+    device = torch.device(getattr(args, "device", None) or f"cuda:{torch.cuda.current_device()}")
+    save_dir = save_dir_of(args)
+    os.makedirs(save_dir, exist_ok=True)
+    seed_everything(args.general_seed)
+    model = vqvae(args).to(device)
+    # BaseModel.configure_optimizers' hyper-parameters on the fused kernel; its scheduler is never stepped by the reference
+    opt = T2SAdamW(model.parameters(), lr=args.learning_rate, weight_decay=1e-2)
+    if args.mix_train:
+        args.data_length = 0
+    _, train_loader = loader_provider(args, period="train")
+    losses, pending = [], []
+    model.train()
+    for epoch in range(int((args.num_training_updates / max(1, len(train_loader))) + 0.5)):
+        i = -1
+        for i, data in enumerate(train_loader):
+            for batch_x in _series_batches(data, args.mix_train):
+                batch = batch_x.clone().detach().float().to(device)
+                pending.append(pretrain_step(model, opt, batch))        # (.item() here would drain the GPU at every step)
+        if pending:
+            ep = torch.stack(pending).tolist()
+            pending.clear()
+            losses.extend(ep)
+            print(f"Epoch: {epoch}, Batch: {i}, Loss: {float(np.mean(ep))}")
+        if epoch % (args.num_training_updates / 10) == 0:
+            torch.save(model, os.path.join(save_dir, f"model_epoch_{epoch}.pth"))
+            print(f"Saved Model from epoch: {epoch}")
+    torch.save(model, os.path.join(save_dir, "final_model.pth"))
+    print("Training complete.")
+    print("Starting inference...")
+    _, test_loader = loader_provider(args, period="test")
+    mae, rmse = inference(model, test_loader, device, save_dir, args.mix_train)
+    print(f"MAE: {mae}  RMSE: {rmse}")
+    return losses
+
+
+def get_args(argv=None):
+    p = argparse.ArgumentParser(description="Pre-train the LA-VAE")
+    p.add_argument("--dataset_name", type=str, default="ETTh1", help="dataset served by loader_provider")
+    p.add_argument("--batch_size", type=int, default=8)
+    p.add_argument("--num_training_updates", type=int, default=2000, help="optimisation steps the epoch count is derived from")
+    p.add_argument("--save_path", type=str, default="results/saved_pretrained_models/", help="root of the checkpoint directories")
+    p.add_argument("--general_seed", type=int, default=42, help="seed of the python / numpy / torch generators")
+    p.add_argument("--learning_rate", type=float, default=1e-3, help="AdamW learning rate")
+    p.add_argument("--block_hidden_size", type=int, default=128, help="channels of the codec (128 for the HIP backward)")
+    p.add_argument("--num_residual_layers", type=int, default=2, help="residual layers per stack (<= 4)")
+    p.add_argument("--res_hidden_size", type=int, default=256, help="channels inside a residual layer (128 / 256 for the HIP backward)")
+    p.add_argument("--embedding_dim", type=int, default=64, help="latent channels (64)")
+    p.add_argument("--num_embeddings", type=int, default=128, help="accepted as in the reference, unused (no quantiser)")
+    p.add_argument("--compression_factor", type=int, default=4, help="accepted as in the reference, unused")
+    p.add_argument("--commitment_cost", type=float, default=0.25, help="accepted as in the reference, unused")
+    p.add_argument("--mix_train", type=bool, default=False, help="train on the 24 / 48 / 96 length groups of one dataset family")
+    p.add_argument("--synthetic", type=int, default=0, help="serve N synthetic rows per length instead of the CSVs")
+    p.add_argument("--split_train", action="store_true", help="mix_train=False (argparse type=bool cannot be switched off)")
+    args = p.parse_args(argv)
+    if args.split_train:
+        args.mix_train = False
+    return args
+
+
+if __name__ == "__main__":
+    pretrain(get_args())

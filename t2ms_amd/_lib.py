@@ -68,6 +68,11 @@ class VaeEncGrads(C.Structure):
                 ("prevq_w", C.c_void_p), ("prevq_b", C.c_void_p)]
 
 
+class VaeDecGrads(C.Structure):          # t2s_vae_dec_grads
+    _fields_ = [("conv1_w", C.c_void_p), ("conv1_b", C.c_void_p), ("stack_conv3_w", C.c_void_p * 4), ("stack_conv1_w", C.c_void_p * 4),
+                ("ct1_w", C.c_void_p), ("ct1_b", C.c_void_p), ("ct2_w", C.c_void_p), ("ct2_b", C.c_void_p)]
+
+
 TS2VEC_MAX_BLOCKS = 16
 
 
@@ -196,6 +201,7 @@ SYMBOLS = {
     "t2s_vae_destroy": (None, [_VP]),
     "t2s_vae_update_weights": (_I, [_VP, C.POINTER(VaeWeights), _VP]),
     "t2s_vae_encode_backward": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeEncGrads), _I, _I, _VP]),
+    "t2s_vae_decode_backward": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeDecGrads), _VP, _I, _I, _I, _VP]),
     "t2s_vae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_vae_encode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_sampler_create": (_I, [_VP, _VP, C.POINTER(SampleConfig), C.POINTER(_VP)]),

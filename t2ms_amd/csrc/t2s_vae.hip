@@ -508,6 +508,181 @@ __global__ __launch_bounds__(256) void vae_part_reduce_kernel(const float* __res
     else db[c - n_w] = v;
 }
 
+// ------------------------------------------------------------------------------------------------ decoder backward
+// Backward of Decoder.forward (vqvae.py:97-105), what LA-VAE pre-training (pretrained_lavae_unified.py) adds to the encoder
+// backward above; the same two stages:
+//   vae_decode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS exactly as
+//                           vae_decode_kernel computes it up to the ReLU behind _conv_trans_1 (the samples themselves are not
+//                           needed), layer inputs leave as row blocks and ReLU patterns stay as bit words; then the data
+//                           gradients walk back from drecon to the latent.  _conv_trans_2 (hidden/2 x 4 = 256 values) and the
+//                           two small biases are reduced per series into partial rows.
+//   launch_wgrad32          dW = dY^T X per layer.  _conv_1: K = emb * 3 = 192, im2col rows padded to 256 columns.
+//                           _conv_trans_1 (Cin, Cout * 4): the layer INPUT rows are the N operand, the gathered rows of the
+//                           output gradient (column co * 4 + kk = d[co][2 i - 1 + kk]) the K operand.
+struct VaeDecBwdBufs {
+    float *Xc1, *dY1, *Xct1, *Gct1, *part2, *partb1;
+    float *Xr3[4], *Xm[4], *dYc1[4], *dYc3[4];
+};
+constexpr int VAE_DBWD_MASK_BYTES = (5 * 128 + 4 * 256 + 128) * 4;   // ReLU bit words of vae_decode_bwd_kernel
+constexpr int VAE_P2 = 257;   // _conv_trans_2 partial row: dW (hidden/2 x 4 = 256) | db (1) at hidden = 128
+constexpr int VAE_PB1 = 64;   // _conv_trans_1 bias partial row (hidden/2)
+
+// din[ci][i] = sum_{co, kk : 0 <= 2 i - 1 + kk < Tout} W[ci][co][kk] * dout[co][2 i - 1 + kk]   -- data gradient of
+// convT1d_k4s2_lds (a stride-2 convolution of the output gradient) -- zeroed where the layer input's ReLU was off.
+__device__ void convT1d_k4s2_dgrad_lds(const float* dout, int Cout, int Tout, float* din, int Cin, int Tin,
+                                       const float* __restrict__ W, int ld_out, int ld_in, const unsigned* mask) {
+    constexpr int CP = VAE_CO_PER_THREAD;
+    for (int o = threadIdx.x; o < (Cin / CP) * Tin; o += VAE_THREADS) {
+        const int ci = (o / Tin) * CP, i = o - (o / Tin) * Tin;
+        float acc[CP];
+#pragma unroll
+        for (int u = 0; u < CP; ++u) acc[u] = 0.f;
+        for (int co = 0; co < Cout; ++co) {
+            const float* w = W + ((size_t)ci * Cout + co) * 4;
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int t = 2 * i - 1 + kk;
+                if (t < 0 || t >= Tout) continue;
+                const float d = dout[co * ld_out + t];
+#pragma unroll
+                for (int u = 0; u < CP; ++u) acc[u] += w[(size_t)u * Cout * 4 + kk] * d;
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < CP; ++u) {
+            const bool on = mask == nullptr || ((mask[ci + u] >> i) & 1u);
+            din[(ci + u) * ld_in + i] = on ? acc[u] : 0.f;
+        }
+    }
+}
+
+__global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDev w, const float* __restrict__ z,
+                                                                     const float* __restrict__ drecon,
+                                                                     const float* __restrict__ dafter, float* __restrict__ dz,
+                                                                     const VaeDecBwdBufs s, int L, int W) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* bufA = smem;
+    float* bufB = smem + VAE_CMAX * LD;
+    float* wide = bufB + VAE_CMAX * LD;                            // [hidden/2][T2]
+    float* dr = wide + 64 * 2 * VAE_TMAX;                          // [L]: this series' drecon
+    unsigned* m_r = reinterpret_cast<unsigned*>(smem + VAE_LDS_FLOATS);    // [5][128]: r_l for l < n_res, then r_final
+    unsigned* m_m = m_r + 5 * 128;                                 // [4][256]
+    unsigned* m_w = m_m + 4 * 256;                                 // [64][2]: the ReLU behind _conv_trans_1
+    const int b = blockIdx.x;
+    const int T2 = L / 2, T = L / 4, H = w.hidden, R = w.res_hidden, half_c = H / 2, E = w.emb;
+    const size_t row0 = (size_t)b * T;
+    // ---------------- forward, recomputed as vae_decode_kernel computes it (one tile)
+    for (int o = threadIdx.x; o < E * W; o += VAE_THREADS) {
+        const int c = o / W, t = o - c * W;
+        bufB[c * LD + t] = z[(size_t)b * E * W + o];
+    }
+    for (int t = threadIdx.x; t < L; t += VAE_THREADS) dr[t] = drecon[(size_t)b * L + t];
+    __syncthreads();
+    interp_linear_ac(bufB, E, W, LD, bufA, T, LD);
+    __syncthreads();
+    // _conv_1's im2col rows, K = emb * 3 = 192 padded to 256 columns
+    for (int o = threadIdx.x; o < T * 256; o += VAE_THREADS) {
+        const int t = o >> 8, col = o & 255;
+        const int ci = col / 3, ti = t + (col - ci * 3) - 1;
+        s.Xc1[(row0 + t) * 256 + col] = (col < E * 3 && ti >= 0 && ti < T) ? bufA[ci * LD + ti] : 0.f;
+    }
+    conv1d_lds<3, 1, false, false>(bufA, E, T, bufB, H, T, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
+    __syncthreads();
+    for (int l = 0; l < w.n_res; ++l) {
+        relu_inplace(bufB, H, T, LD);
+        __syncthreads();
+        relu_mask(bufB, H, T, LD, m_r + l * 128, 1);
+        im2col_rows<3, 1>(bufB, H, T, LD, s.Xr3[l], row0, T, 1);
+        conv1d_lds<3, 1, true, false>(bufB, H, T, bufA, R, T, w.dec_c3[l], nullptr, 1, LD, LD);
+        __syncthreads();
+        relu_mask(bufA, R, T, LD, m_m + l * 256, 1);
+        rows_out(bufA, R, T, LD, s.Xm[l], row0, R);
+        conv1d_lds<1, 1, false, true>(bufA, R, T, bufB, H, T, w.dec_c1[l], nullptr, 0, LD, LD);
+        __syncthreads();
+    }
+    relu_inplace(bufB, H, T, LD);
+    __syncthreads();
+    relu_mask(bufB, H, T, LD, m_r + w.n_res * 128, 1);
+    rows_out(bufB, H, T, LD, s.Xct1, row0, H);
+    convT1d_k4s2_lds<true>(bufB, H, T, wide, half_c, w.dec_ct1_w, w.dec_ct1_b, LD, T2);
+    __syncthreads();
+    relu_mask(wide, half_c, T2, T2, m_w, 2);
+    // ---------------- backward.  _conv_trans_2: recon[t] = b + sum_{ci,kk : t = 2 i - 1 + kk} wide[ci][i] W[ci][kk]
+    // dW[ci][kk] = sum_i wide[ci][i] drecon[2 i - 1 + kk], db = sum_t drecon[t]: one partial row per series
+    for (int o = threadIdx.x; o < half_c * 4 + 1; o += VAE_THREADS) {
+        float acc = 0.f;
+        if (o == half_c * 4) {
+            for (int t = 0; t < L; ++t) acc += dr[t];
+        } else {
+            const int ci = o >> 2, kk = o & 3;
+            for (int i = 0; i < T2; ++i) {
+                const int t = 2 * i - 1 + kk;
+                if (t >= 0 && t < L) acc += wide[ci * T2 + i] * dr[t];
+            }
+        }
+        s.part2[(size_t)b * VAE_P2 + o] = acc;
+    }
+    __syncthreads();
+    // d(_conv_trans_1 pre-ReLU)[ci][i] = sum_kk W[ci][kk] drecon[2 i - 1 + kk], masked, in place of wide
+    for (int o = threadIdx.x; o < half_c * T2; o += VAE_THREADS) {
+        const int ci = o / T2, i = o - ci * T2;
+        float acc = 0.f;
+#pragma unroll
+        for (int kk = 0; kk < 4; ++kk) {
+            const int t = 2 * i - 1 + kk;
+            if (t >= 0 && t < L) acc += w.dec_ct2_w[ci * 4 + kk] * dr[t];
+        }
+        wide[o] = ((m_w[ci * 2 + (i >> 5)] >> (i & 31)) & 1u) ? acc : 0.f;
+    }
+    __syncthreads();
+    for (int co = threadIdx.x; co < half_c; co += VAE_THREADS) {    // _conv_trans_1 bias: column sum of its output gradient
+        float acc = 0.f;
+        for (int t = 0; t < T2; ++t) acc += wide[co * T2 + t];
+        s.partb1[(size_t)b * VAE_PB1 + co] = acc;
+    }
+    im2col_rows<4, 2>(wide, half_c, T2, T2, s.Gct1, row0, T, 1);    // column co * 4 + kk = d[co][2 i - 1 + kk]
+    // d r_final, masked by r_final > 0: the gradient at the stack's output h (r_final itself left as Xct1)
+    convT1d_k4s2_dgrad_lds(wide, half_c, T2, bufB, H, T, w.dec_ct1_w, T2, LD, m_r + w.n_res * 128);
+    __syncthreads();
+    for (int l = w.n_res - 1; l >= 0; --l) {
+        // bufB = dL/dh_out, h_out = r + c1(m), m = relu(c3(r)), r = relu(h_in)
+        rows_out(bufB, H, T, LD, s.dYc1[l], row0, H);
+        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, w.dec_c1[l], 0, LD, LD, m_m + l * 256, 1);
+        __syncthreads();
+        rows_out(bufA, R, T, LD, s.dYc3[l], row0, R);
+        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, w.dec_c3[l], 1, LD, LD, m_r + l * 128, 1);
+        __syncthreads();
+    }
+    rows_out(bufB, H, T, LD, s.dY1, row0, H);                       // dL/d(_conv_1 output)
+    if (dz == nullptr) return;
+    conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, E, T, w.dec_conv1_w, 1, LD, LD, nullptr, 1);   // dL/d(after), decoder part
+    __syncthreads();
+    // dz = interp^T(d after + dafter) with the forward's own index arithmetic (interp_linear_ac)
+    const float scale = T > 1 ? (float)(W - 1) / (float)(T - 1) : 0.f;
+    for (int o = threadIdx.x; o < E * W; o += VAE_THREADS) {
+        const int c = o / W, j = o - c * W;
+        const float* da = dafter != nullptr ? dafter + ((size_t)b * E + c) * T : nullptr;
+        float acc = 0.f;
+        for (int t = 0; t < T; ++t) {
+            const float real = scale * (float)t;
+            const int i0 = (int)real;
+            const int i1 = i0 + (i0 < W - 1 ? 1 : 0);
+            const float l1 = real - (float)i0, l0 = 1.0f - l1;
+            const float d = bufA[c * LD + t] + (da != nullptr ? da[t] : 0.f);
+            if (i0 == j) acc += l0 * d;
+            if (i1 == j) acc += l1 * d;
+        }
+        dz[(size_t)b * E * W + o] = acc;
+    }
+}
+
+// dst (rows, cols) = the first `cols` columns of src (rows, ld)
+__global__ __launch_bounds__(256) void vae_copy_cols_kernel(const float* __restrict__ src, int ld, float* __restrict__ dst, int rows,
+                                                            int cols) {
+    const int o = blockIdx.x * 256 + threadIdx.x;
+    if (o < rows * cols) dst[o] = src[(size_t)(o / cols) * ld + (o % cols)];
+}
+
 }  // namespace t2s
 
 using namespace t2s;
@@ -524,6 +699,10 @@ struct t2s_vae {
     float* wg = nullptr;
     size_t wg_floats = 0;
     int n_cu = 0;
+    // decoder backward (t2s_vae_decode_backward): its own row blocks, grown on demand; `wg` is shared
+    float* dbwd = nullptr;
+    size_t dbwd_rows = 0;
+    int dbwd_series = 0;
 };
 
 namespace {
@@ -636,6 +815,8 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_bwd_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_BWD_MASK_BYTES));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_bwd_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_DBWD_MASK_BYTES));
         attr = true;
     }
     *out = h;
@@ -647,6 +828,7 @@ extern "C" void t2s_vae_destroy(t2s_vae* h) {
     if (h->arena) (void)hipFree(h->arena);
     if (h->bwd) (void)hipFree(h->bwd);
     if (h->wg) (void)hipFree(h->wg);
+    if (h->dbwd) (void)hipFree(h->dbwd);
     delete h;
 }
 
@@ -790,5 +972,86 @@ extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* 
     vae_part_reduce_kernel<<<VAE_P1 / 32, 256, 0, st>>>(s.part1, B, VAE_P1, g->conv1_w, 256, g->conv1_b);
     T2S_LAUNCH_CHECK();
     (void)H;
+    return T2S_OK;
+}
+
+extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter,
+                                       const t2s_vae_dec_grads* g, float* dz, int B, int L, int latent_w, void* stream) {
+    T2S_REQUIRE(h && z && drecon && g, "t2s_vae_decode_backward: NULL argument");
+    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_backward: handle was created without decoder weights");
+    const VaeDev& d = h->dev;
+    T2S_REQUIRE(d.hidden == 128 && d.res_hidden % 128 == 0 && d.emb == 64,
+                "t2s_vae_decode_backward: hidden=%d res_hidden=%d emb=%d unsupported (hidden 128, res_hidden 128 / 256, emb 64)", d.hidden,
+                d.res_hidden, d.emb);
+    T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "t2s_vae_decode_backward: B=%d L=%d unsupported (8 <= L <= 128, a multiple of 4)", B, L);
+    T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_TMAX, "t2s_vae_decode_backward: latent width %d unsupported (1..%d)", latent_w, VAE_TMAX);
+    T2S_REQUIRE(g->conv1_w && g->conv1_b && g->ct1_w && g->ct1_b && g->ct2_w && g->ct2_b, "t2s_vae_decode_backward: NULL gradient pointer");
+    for (int l = 0; l < d.n_res; ++l)
+        T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "t2s_vae_decode_backward: NULL gradient pointer of residual layer %d", l);
+    hipStream_t st = (hipStream_t)stream;
+    const int T = L / 4, R = d.res_hidden, NR = d.n_res;
+    const size_t rows = (size_t)B * T;
+    if (h->n_cu == 0) {
+        int dev = 0;
+        hipDeviceProp_t prop;
+        T2S_HIP_CHECK(hipGetDevice(&dev));
+        T2S_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+        h->n_cu = prop.multiProcessorCount;
+    }
+    // row blocks: floats per row, in the order the pointers are handed out below
+    const size_t per_row = 256 + 128 + 128 + 256 + (size_t)NR * (384 + R + 128 + R);
+    if (rows > h->dbwd_rows || B > h->dbwd_series) {
+        const size_t r2 = rows > h->dbwd_rows ? rows : h->dbwd_rows;
+        const int b2 = B > h->dbwd_series ? B : h->dbwd_series;
+        if (h->dbwd) T2S_HIP_CHECK(hipFree(h->dbwd));
+        h->dbwd = nullptr;
+        h->dbwd_rows = 0;         // (a failed hipMalloc below must not leave sizes that vouch for a NULL buffer)
+        h->dbwd_series = 0;
+        T2S_HIP_CHECK(hipMalloc((void**)&h->dbwd, (r2 * per_row + 128 * 256 + (size_t)b2 * (VAE_P2 + VAE_PB1)) * sizeof(float)));
+        h->dbwd_rows = r2;
+        h->dbwd_series = b2;
+    }
+    {   // weight-gradient partial tiles: the largest of this decoder's shapes
+        size_t need = 0;
+        const int shapes[3][2] = {{128, 256}, {R, 384}, {128, R}};
+        for (auto& sh : shapes) {
+            const int tiles = (sh[0] / 128) * (sh[1] / 128);
+            int per = 3 * h->n_cu / tiles;
+            per = per < 1 ? 1 : per;
+            const size_t n = (size_t)per * tiles * (128 * 128) + (size_t)per * (sh[0] / 128) * 128;
+            need = n > need ? n : need;
+        }
+        if (need > h->wg_floats) {
+            if (h->wg) T2S_HIP_CHECK(hipFree(h->wg));
+            h->wg = nullptr;
+            h->wg_floats = 0;
+            T2S_HIP_CHECK(hipMalloc((void**)&h->wg, need * sizeof(float)));
+            h->wg_floats = need;
+        }
+    }
+    VaeDecBwdBufs s{};
+    float* p = h->dbwd;
+    auto take = [&](size_t cols) { float* q = p; p += h->dbwd_rows * cols; return q; };
+    s.Xc1 = take(256); s.dY1 = take(128); s.Xct1 = take(128); s.Gct1 = take(256);
+    for (int l = 0; l < NR; ++l) { s.Xr3[l] = take(384); s.Xm[l] = take(R); s.dYc1[l] = take(128); s.dYc3[l] = take(R); }
+    float* tmp_w = p;                                              // (128,256): _conv_1 with K padded from 192
+    s.part2 = tmp_w + 128 * 256;
+    s.partb1 = s.part2 + (size_t)h->dbwd_series * VAE_P2;
+    vae_decode_bwd_kernel<<<B, VAE_THREADS, VAE_LDS_FLOATS * 4 + VAE_DBWD_MASK_BYTES, st>>>(d, z, drecon, dafter, dz, s, L, latent_w);
+    T2S_LAUNCH_CHECK();
+    int rc;
+    const int M = (int)rows;
+    if ((rc = launch_wgrad32(s.dY1, s.Xc1, tmp_w, g->conv1_b, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+    vae_copy_cols_kernel<<<(128 * 192 + 255) / 256, 256, 0, st>>>(tmp_w, 256, g->conv1_w, 128, 192);
+    T2S_LAUNCH_CHECK();
+    for (int l = 0; l < NR; ++l) {
+        if ((rc = launch_wgrad32(s.dYc3[l], s.Xr3[l], g->stack_conv3_w[l], nullptr, M, R, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+        if ((rc = launch_wgrad32(s.dYc1[l], s.Xm[l], g->stack_conv1_w[l], nullptr, M, 128, R, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+    }
+    if ((rc = launch_wgrad32(s.Xct1, s.Gct1, g->ct1_w, nullptr, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+    vae_part_reduce_kernel<<<(VAE_P2 + 31) / 32, 256, 0, st>>>(s.part2, B, VAE_P2, g->ct2_w, 256, g->ct2_b);
+    T2S_LAUNCH_CHECK();
+    vae_part_reduce_kernel<<<VAE_PB1 / 32, 256, 0, st>>>(s.partb1, B, VAE_PB1, g->ct1_b, VAE_PB1, nullptr);
+    T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

@@ -6,10 +6,13 @@ resolve to these classes and their tensors are used as-is.  ``Encoder.forward``
 and ``Decoder.forward`` run single-launch HIP kernels (t2s_vae.hip); the
 nn.Conv1d objects only hold weights.  The reference freezes the VAE while training
 the DiT (train.py:31-33); with `usepretrainedvae` false the encoder trains and its
-backward is t2s_vae_encode_backward.  No CPU fallback.
+backward is t2s_vae_encode_backward.  LA-VAE pre-training (pretrained_lavae_unified.py,
+``vqvae.shared_eval(..., "train")``) trains both halves: the decoder's backward is
+t2s_vae_decode_backward (_DecodeFn), the losses are t2s_mse with its backward.  No CPU fallback.
 """
 from __future__ import annotations
 
+import contextlib
 import ctypes as C
 import os
 import weakref
@@ -55,6 +58,7 @@ class _VaeHandle:
         torch.cuda.synchronize(device)
         with torch.cuda.device(device):
             L.check(L.lib().t2s_vae_create(C.byref(w), C.byref(self.ptr)), "t2s_vae_create")
+        self.dbwd_rows = self.dbwd_series = 0     # what t2s_vae_decode_backward's row blocks hold (it grows them on demand)
         self._fin = weakref.finalize(self, L.destroy_locked, "t2s_vae_destroy", str(torch.device(device)), self.ptr)
 
     def close(self):
@@ -264,24 +268,108 @@ class Decoder(_Codec):
             setattr(w, name, c.data_ptr())
         return w, keep
 
+    def _hip_backward_ok(self, Ln, W):
+        """t2s_vae_decode_backward covers what t2s_vae_encode_backward covers (Encoder._hip_backward_ok): the reference's
+        default LA-VAE on the BASELINE lengths, latent width <= 32."""
+        rh = self._residual_stack._layers[0]._block[1].out_channels if len(self._residual_stack._layers) else 128
+        return (self._conv_1.out_channels == 128 and rh % 128 == 0 and self._conv_1.in_channels == 64
+                and len(self._residual_stack._layers) <= 4 and 8 <= Ln <= 128 and Ln % 4 == 0 and 1 <= W <= 32)
+
+    def _grad_params(self):
+        """The 10 decoder tensors in t2s_vae_dec_grads order."""
+        ps = [self._conv_1.weight, self._conv_1.bias]
+        ps += [layer._block[1].weight for layer in self._residual_stack._layers]
+        ps += [layer._block[3].weight for layer in self._residual_stack._layers]
+        return ps + [self._conv_trans_1.weight, self._conv_trans_1.bias, self._conv_trans_2.weight, self._conv_trans_2.bias]
+
+    def _forward_autograd(self, inputs, length):
+        """The same forward as torch ops UNDER AUTOGRAD: only for LA-VAE shapes t2s_vae_decode_backward does not cover
+        (non-default hyper-parameters, L > 128) when the decoder trains -- host-level plumbing like Encoder._forward_autograd,
+        no throughput claim.  The default shape runs forward AND backward in the HIP kernels (_DecodeFn)."""
+        import torch.nn.functional as F
+        after = F.interpolate(inputs.float(), size=int(length / 4), mode="linear", align_corners=True)
+        h = self._conv_1(after)
+        for layer in self._residual_stack._layers:
+            h = F.relu(h)
+            h = h + layer._block[3](F.relu(layer._block[1](h)))
+        h = F.relu(h)
+        h = F.relu(self._conv_trans_1(h))
+        return torch.squeeze(self._conv_trans_2(h)), after
+
     def forward(self, inputs, length):
         """z (B,64,W) -> (recon, after (B,64,L/4)); vqvae.py:97-105 (W = 30 on the DiT path; any W <= 32, e.g. the L/4
         of the MLP-denoiser path, as F.interpolate accepts).  ``recon`` follows torch.squeeze's shape rule: (B,L), or
-        (L,) when B == 1."""
+        (L,) when B == 1.  With grad enabled and a decoder parameter or the latent asking for a gradient (LA-VAE
+        pre-training) the same forward kernel runs behind _DecodeFn, whose backward is t2s_vae_decode_backward; under
+        no_grad or with everything frozen (infer.py, evaluation, the Sampler's C handle) nothing is saved."""
         if not inputs.is_cuda:
             raise L.T2SError("Decoder.forward: input must live on a GPU; the HIP path has no CPU fallback")
-        z = L.as_f32(inputs)
-        if z.dim() != 3 or not 1 <= z.shape[2] <= 32:
-            raise L.T2SError(f"Decoder.forward: latent must be (B,C,W) with W <= 32, got {tuple(z.shape)}")
-        B, dev = z.shape[0], z.device
+        if inputs.dim() != 3 or not 1 <= inputs.shape[2] <= 32:
+            raise L.T2SError(f"Decoder.forward: latent must be (B,C,W) with W <= 32, got {tuple(inputs.shape)}")
         Ln = int(length / 4) * 4
+        if torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if (self._hip_backward_ok(Ln, inputs.shape[2])
+                    and os.environ.get("T2S_DECODER_TORCH_AUTOGRAD", "0") in ("", "0")):
+                recon, after = _DecodeFn.apply(self, L.as_f32(inputs), Ln, *self._grad_params())
+                return torch.squeeze(recon.unsqueeze(1)), after
+            return self._forward_autograd(inputs, length)
+        recon, after = self._forward_hip(L.as_f32(inputs), Ln)
+        return torch.squeeze(recon.unsqueeze(1)), after
+
+    def _forward_hip(self, z, Ln):
+        B, dev = z.shape[0], z.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
             recon = torch.empty(B, Ln, device=dev, dtype=torch.float32)
             after = torch.empty(B, z.shape[1], Ln // 4, device=dev, dtype=torch.float32)
             L.check(L.lib().t2s_vae_decode_w(h, L.dev_ptr(z, "inputs"), L.dev_ptr(recon), L.dev_ptr(after), B, Ln,
                                              z.shape[2], L.stream_ptr(dev)), "t2s_vae_decode")
-        return torch.squeeze(recon.unsqueeze(1)), after
+        return recon, after
+
+
+class _DecodeFn(torch.autograd.Function):
+    """Decoder.forward under autograd, both directions in the HIP kernels: t2s_vae_decode_w now, t2s_vae_decode_backward for
+    the 10 parameter gradients and the latent's (the forward is recomputed from z there; nothing but z is saved)."""
+
+    @staticmethod
+    def forward(ctx, dec, z, Ln, *params):
+        with torch.no_grad():
+            recon, after = dec._forward_hip(z, Ln)
+        ctx.dec, ctx.Ln = dec, Ln
+        ctx.save_for_backward(z)
+        ctx.n_layers = len(dec._residual_stack._layers)
+        ctx.set_materialize_grads(False)      # a loss on `recon` alone: `after` then arrives as None, not as a zero tensor
+        return recon, after
+
+    @staticmethod
+    def backward(ctx, drecon, dafter):
+        (z,) = ctx.saved_tensors
+        dec, n, Ln = ctx.dec, ctx.n_layers, ctx.Ln
+        dev, B, W = z.device, z.shape[0], z.shape[2]
+        params = dec._grad_params()
+        grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in params]
+        g = L.VaeDecGrads()
+        g.conv1_w, g.conv1_b = grads[0].data_ptr(), grads[1].data_ptr()
+        for i in range(n):
+            g.stack_conv3_w[i] = grads[2 + i].data_ptr()
+            g.stack_conv1_w[i] = grads[2 + n + i].data_ptr()
+        for nm, t in zip(("ct1_w", "ct1_b", "ct2_w", "ct2_b"), grads[2 + 2 * n:]):
+            setattr(g, nm, t.data_ptr())
+        drc = L.as_f32(drecon).reshape(B, Ln) if drecon is not None else torch.zeros(B, Ln, device=dev)
+        dac = L.as_f32(dafter) if dafter is not None else None
+        dz = torch.empty_like(z) if ctx.needs_input_grad[1] else None
+        with torch.cuda.device(dev):
+            h = dec._handle(dev)           # (the weights of the forward: no optimizer step happens between the two)
+            hobj = dec.__dict__["_t2s_h"]
+            rows = B * (Ln // 4)
+            grows = rows > hobj.dbwd_rows or B > hobj.dbwd_series
+            # growing the row blocks frees / allocates device memory: under the device's lock, like building the handle
+            with L.device_lock(dev) if grows else contextlib.nullcontext():
+                L.check(L.lib().t2s_vae_decode_backward(h, L.dev_ptr(z), L.dev_ptr(drc), L.dev_ptr(dac), C.byref(g), L.dev_ptr(dz),
+                                                        B, Ln, W, L.stream_ptr(dev)), "t2s_vae_decode_backward")
+            hobj.dbwd_rows, hobj.dbwd_series = max(hobj.dbwd_rows, rows), max(hobj.dbwd_series, B)
+        out = [gr if p.requires_grad else None for gr, p in zip(grads, params)]
+        return (None, dz, None, *out)
 
 
 class vqvae(BaseModel):
@@ -295,11 +383,19 @@ class vqvae(BaseModel):
                                args.res_hidden_size)
 
     def shared_eval(self, batch, optimizer, mode):  # pyright: ignore[reportIncompatibleMethodOverride]
-        """vqvae.py:118-135.  Only the val/test branch exists here: LA-VAE pre-training
-        (pretrained_lavae_unified.py) is outside the accelerated path."""
-        if mode == "train":
-            raise L.T2SError("LA-VAE training is out of scope of the HIP path (frozen codec, train.py:31-33)")
+        """vqvae.py:118-135.  'train' is one optimisation step of LA-VAE pre-training (pretrained_lavae_unified.py:142-174)
+        entirely on the HIP kernels: encoder and decoder forward + backward (_EncodeFn, _DecodeFn), both MSE terms with their
+        backward (_MseFn), and the caller's optimizer -- T2SAdamW in pretrain_lavae.py.  'val' / 'test' run under no_grad."""
         from ...train import mse_loss
+        if mode == "train":
+            optimizer.zero_grad()
+            z, before = self.encoder(batch)
+            data_recon, after = self.decoder(z, length=batch.shape[-1])
+            recon_error = mse_loss(data_recon.reshape(batch.shape), batch)     # (B == 1: recon is (L,), torch.squeeze's rule)
+            loss = recon_error + mse_loss(before, after)
+            loss.backward()
+            optimizer.step()
+            return loss.detach(), recon_error.detach(), data_recon.detach(), z.detach()
         with torch.no_grad():
             z, before = self.encoder(batch)
             data_recon, after = self.decoder(z, length=batch.shape[-1])
