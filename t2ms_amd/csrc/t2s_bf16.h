@@ -696,17 +696,21 @@ inline void wgrad16_plan(int M, int N, int K, int n_cu, int* rows_per_wg, int* g
     *rows_per_wg = rows;
     *gx = (M + rows - 1) / rows;
 }
+// scratch floats of one (N, K) shape, for EVERY M: gx is not monotonic in M (rows_per_wg is rounded up to 64, so a smaller M can
+// need one more slab than a larger one), so a workspace is sized for the plan's bound gx <= per slabs -- one partial tile per
+// slab and (N / 128, K / 128) tile, one 128-wide bias partial per slab and N / 128
+inline size_t wgrad16_shape_scratch_floats(int N, int K, int n_cu) {
+    const int tiles = (N / 128) * (K / 128);
+    int per = 3 * n_cu / tiles;
+    per = per < 1 ? 1 : per;
+    return (size_t)per * tiles * (128 * 128) + (size_t)per * (N / 128) * 128;
+}
 inline size_t wgrad16_scratch_floats(int M, int n_cu) {      // worst case over the DiT's four linears AND over every M' <= M
-    // gx is not monotonic in M (rows_per_wg is rounded up to 64, so a smaller M can need one more slab than a larger one): a
-    // workspace built for cap_seqs sequences serves every smaller batch, so it is sized for the bound gx <= per slabs
     (void)M;
     size_t worst = 0;
     const int shapes[4][2] = {{128, 128}, {256, 128}, {384, 128}, {128, 256}};
     for (auto& sh : shapes) {
-        const int tiles = (sh[0] / 128) * (sh[1] / 128);
-        int per = 3 * n_cu / tiles;
-        per = per < 1 ? 1 : per;
-        const size_t need = (size_t)per * tiles * (128 * 128) + (size_t)per * (sh[0] / 128) * 128;
+        const size_t need = wgrad16_shape_scratch_floats(sh[0], sh[1], n_cu);
         worst = need > worst ? need : worst;
     }
     return worst;

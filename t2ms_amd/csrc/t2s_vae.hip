@@ -111,20 +111,53 @@ __device__ void convT1d_k4s2_lds(const float* in, int Cin, int Tin, float* out, 
     }
 }
 
-// F.interpolate(mode='linear', align_corners=True) along the last axis, [C][Tin] -> [C][Tout]
-// (`out` holds the global output positions [out_g0, out_g0 + Tw) of Tout)
+// F.interpolate(mode='linear', align_corners=True) along the last axis maps Tin positions to Tout: output position t reads
+// l0 * in[i0] + l1 * in[i1].  The ONE copy of that index arithmetic, shared by the forward and its transpose.
+struct InterpTap { int i0, i1; float l0, l1; };
+__device__ inline float interp_scale_ac(int Tin, int Tout) { return Tout > 1 ? (float)(Tin - 1) / (float)(Tout - 1) : 0.f; }
+__device__ inline InterpTap interp_tap_ac(float scale, int t, int Tin) {
+    InterpTap p;
+    const float real = scale * (float)t;
+    p.i0 = (int)real;
+    p.i1 = p.i0 + (p.i0 < Tin - 1 ? 1 : 0);
+    p.l1 = real - (float)p.i0;
+    p.l0 = 1.0f - p.l1;
+    return p;
+}
+
+// [C][Tin] -> [C][Tout] (`out` holds the global output positions [out_g0, out_g0 + Tw) of Tout)
 __device__ void interp_linear_ac(const float* in, int C, int Tin, int ld_in, float* out, int Tout,
                                  int ld_out, int out_g0 = 0, int Tw = -1) {
-    const float scale = Tout > 1 ? (float)(Tin - 1) / (float)(Tout - 1) : 0.f;
+    const float scale = interp_scale_ac(Tin, Tout);
     if (Tw < 0) Tw = Tout;
     for (int o = threadIdx.x; o < C * Tw; o += VAE_THREADS) {
         const int c = o / Tw, t = o - c * Tw;
-        const float real = scale * (float)(out_g0 + t);
-        const int i0 = (int)real;
-        const int i1 = i0 + (i0 < Tin - 1 ? 1 : 0);
-        const float l1 = real - (float)i0;
-        const float l0 = 1.0f - l1;
-        out[c * ld_out + t] = l0 * in[c * ld_in + i0] + l1 * in[c * ld_in + i1];
+        const InterpTap p = interp_tap_ac(scale, out_g0 + t, Tin);
+        out[c * ld_out + t] = p.l0 * in[c * ld_in + p.i0] + p.l1 * in[c * ld_in + p.i1];
+    }
+}
+
+// The transpose of interp_linear_ac: the forward maps Tin to Tout; this gathers the Tout gradients into Tin,
+//   out[c][i] = (INIT ? init[c][i] : 0) + sum over t = 0 .. Tout - 1 of { l0(t) d[c][t] if i0(t) == i } + { l1(t) d[c][t] if i1(t) == i },
+//   d[c][t] = g[c][t] (+ add[c][t] if ADD).
+// Operands may live in LDS or global memory, each with its own row stride.  INIT and ADD are compile-time: an absent operand
+// costs no floating-point operation, so every instantiation keeps one fixed expression (a run-time "+ 0" would not be the
+// same bits as no addition for a negative zero).
+template <bool INIT, bool ADD>
+__device__ void interp_linear_ac_transposed(const float* g, int ld_g, const float* add, int ld_add, const float* init, int ld_init,
+                                            float* out, int ld_out, int C, int Tin, int Tout) {
+    const float scale = interp_scale_ac(Tin, Tout);
+    for (int o = threadIdx.x; o < C * Tin; o += VAE_THREADS) {
+        const int c = o / Tin, i = o - c * Tin;
+        float acc = INIT ? init[c * ld_init + i] : 0.f;
+        for (int t = 0; t < Tout; ++t) {
+            const InterpTap p = interp_tap_ac(scale, t, Tin);
+            float d = g[c * ld_g + t];
+            if (ADD) d += add[c * ld_add + t];
+            if (p.i0 == i) acc += p.l0 * d;
+            if (p.i1 == i) acc += p.l1 * d;
+        }
+        out[c * ld_out + i] = acc;
     }
 }
 
@@ -288,16 +321,12 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w,
 // z = F.interpolate(before, 30, mode='linear', align_corners=True) (vqvae.py:70) from the (B,64,T) rows in global memory
 __global__ __launch_bounds__(VAE_THREADS) void vae_interp_z_kernel(const float* __restrict__ before, float* __restrict__ z,
                                                                    int C, int T) {
-    const float scale = (float)(T - 1) / (float)(LATW - 1);
+    const float scale = interp_scale_ac(T, LATW);
     const float* in = before + (size_t)blockIdx.x * C * T;
     for (int o = threadIdx.x; o < C * LATW; o += VAE_THREADS) {
         const int c = o / LATW, t = o - c * LATW;
-        const float real = scale * (float)t;
-        const int i0 = (int)real;
-        const int i1 = i0 + (i0 < T - 1 ? 1 : 0);
-        const float l1 = real - (float)i0;
-        const float l0 = 1.0f - l1;
-        z[(size_t)blockIdx.x * C * LATW + o] = l0 * in[(size_t)c * T + i0] + l1 * in[(size_t)c * T + i1];
+        const InterpTap p = interp_tap_ac(scale, t, T);
+        z[(size_t)blockIdx.x * C * LATW + o] = p.l0 * in[(size_t)c * T + p.i0] + p.l1 * in[(size_t)c * T + p.i1];
     }
 }
 
@@ -312,9 +341,12 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_interp_z_kernel(const float* 
 //                           per series into one partial row.
 //   launch_wgrad32          dW = dY^T X per layer on the exact-fp32 MFMA (t2s_wgrad.h), deterministic two-stage reduction;
 //                           vae_part_reduce_kernel adds the conv_1 partial rows in series order.
+struct VaeStackBufs {   // per residual layer: the rows of r and m (inputs of c3 / c1), the output gradients of c1 / c3
+    float *Xr3[4], *Xm[4], *dYc1[4], *dYc3[4];
+};
 struct VaeBwdBufs {
     float *Xc2, *Xc3, *Xp, *dYp, *dY3, *dY2, *part1;
-    float *Xr3[4], *Xm[4], *dYc1[4], *dYc3[4];
+    VaeStackBufs st;
 };
 constexpr int VAE_BWD_MASK_BYTES = (128 + 128 + 5 * 128 + 4 * 256) * 4;   // ReLU bit words of vae_encode_bwd_kernel
 constexpr int VAE_P1 = 320;   // conv_1 partial row: dW (hidden/2 x 4 = 256) | db (64) at hidden = 128
@@ -384,6 +416,44 @@ __device__ void rows_out(const float* buf, int C, int T, int ld, float* __restri
     }
 }
 
+// residual_stack for the backward kernels: the same arithmetic on x = bufB (tmp = bufA), and what the backward needs stays
+// behind -- the ReLU patterns m_r [n_res + 1][128] (r_l = relu(h_l), then r_final) and m_m [n_res][256] (m_l), the rows of r_l
+// (im2col'd) and m_l.  Ends behind the final relu_mask: the caller writes r_final's rows where its next layer wants them.
+__device__ void residual_stack_recompute(float* bufB, float* bufA, int H, int R, int n_res, int T, const float* const* c3,
+                                         const float* const* c1, const VaeStackBufs& s, size_t row0, unsigned* m_r, unsigned* m_m) {
+    for (int l = 0; l < n_res; ++l) {
+        relu_inplace(bufB, H, T, LD);
+        __syncthreads();
+        relu_mask(bufB, H, T, LD, m_r + l * 128, 1);               // r_l > 0  <=>  h_l > 0
+        im2col_rows<3, 1>(bufB, H, T, LD, s.Xr3[l], row0, T, 1);
+        conv1d_lds<3, 1, true, false>(bufB, H, T, bufA, R, T, c3[l], nullptr, 1, LD, LD);
+        __syncthreads();
+        relu_mask(bufA, R, T, LD, m_m + l * 256, 1);
+        rows_out(bufA, R, T, LD, s.Xm[l], row0, R);
+        conv1d_lds<1, 1, false, true>(bufA, R, T, bufB, H, T, c1[l], nullptr, 0, LD, LD);
+        __syncthreads();
+    }
+    relu_inplace(bufB, H, T, LD);
+    __syncthreads();
+    relu_mask(bufB, H, T, LD, m_r + n_res * 128, 1);
+}
+
+// The way back through the stack: bufB holds dL/dh_out of the last layer on entry (already masked by r_final > 0) and
+// dL/dh_in of the first on return; every layer's output gradients leave as the row blocks dYc1 / dYc3.
+__device__ void residual_stack_backward(float* bufB, float* bufA, int H, int R, int n_res, int T, const float* const* c3,
+                                        const float* const* c1, const VaeStackBufs& s, size_t row0, const unsigned* m_r,
+                                        const unsigned* m_m) {
+    for (int l = n_res - 1; l >= 0; --l) {
+        // bufB = dL/dh_out, h_out = r + c1(m), m = relu(c3(r)), r = relu(h_in)
+        rows_out(bufB, H, T, LD, s.dYc1[l], row0, H);
+        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, c1[l], 0, LD, LD, m_m + l * 256, 1);       // d(pre-ReLU of m)
+        __syncthreads();
+        rows_out(bufA, R, T, LD, s.dYc3[l], row0, R);
+        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, c3[l], 1, LD, LD, m_r + l * 128, 1);        // + skip, masked: dL/dh_in
+        __syncthreads();
+    }
+}
+
 __global__ __launch_bounds__(VAE_THREADS) void vae_encode_bwd_kernel(const VaeDev w, const float* __restrict__ x,
                                                                      const float* __restrict__ dz,
                                                                      const float* __restrict__ dbefore, const VaeBwdBufs s, int L) {
@@ -418,55 +488,23 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_encode_bwd_kernel(const VaeDe
     im2col_rows<3, 1>(bufA, H, T, LD, s.Xc3, row0, T, 1);
     conv1d_lds<3, 1, false, false>(bufA, H, T, bufB, H, T, w.enc_conv3_w, w.enc_conv3_b, 1, LD, LD);
     __syncthreads();
-    for (int l = 0; l < w.n_res; ++l) {
-        relu_inplace(bufB, H, T, LD);
-        __syncthreads();
-        relu_mask(bufB, H, T, LD, m_r + l * 128, 1);               // r_l > 0  <=>  h_l > 0
-        im2col_rows<3, 1>(bufB, H, T, LD, s.Xr3[l], row0, T, 1);
-        conv1d_lds<3, 1, true, false>(bufB, H, T, bufA, R, T, w.enc_c3[l], nullptr, 1, LD, LD);
-        __syncthreads();
-        relu_mask(bufA, R, T, LD, m_m + l * 256, 1);
-        rows_out(bufA, R, T, LD, s.Xm[l], row0, R);
-        conv1d_lds<1, 1, false, true>(bufA, R, T, bufB, H, T, w.enc_c1[l], nullptr, 0, LD, LD);
-        __syncthreads();
-    }
-    relu_inplace(bufB, H, T, LD);
-    __syncthreads();
-    relu_mask(bufB, H, T, LD, m_r + w.n_res * 128, 1);
+    residual_stack_recompute(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.Xp, row0, H);
     __syncthreads();
     // ---------------- backward.  dbefore_total = dbefore (if given) + interp^T(dz)  -> bufA [emb][T]
     {
-        const float scale = (float)(T - 1) / (float)(LATW - 1);
-        for (int o = threadIdx.x; o < w.emb * T; o += VAE_THREADS) {
-            const int c = o / T, i = o - c * T;
-            float acc = dbefore != nullptr ? dbefore[((size_t)b * w.emb + c) * T + i] : 0.f;
-            const float* g = dz + ((size_t)b * w.emb + c) * LATW;
-            for (int j = 0; j < LATW; ++j) {                       // the forward's own index arithmetic (interp_linear_ac)
-                const float real = scale * (float)j;
-                const int i0 = (int)real;
-                const int i1 = i0 + (i0 < T - 1 ? 1 : 0);
-                const float l1 = real - (float)i0, l0 = 1.0f - l1;
-                if (i0 == i) acc += l0 * g[j];
-                if (i1 == i) acc += l1 * g[j];
-            }
-            bufA[c * LD + i] = acc;
-        }
+        const float* g = dz + (size_t)b * w.emb * LATW;
+        if (dbefore != nullptr)
+            interp_linear_ac_transposed<true, false>(g, LATW, nullptr, 0, dbefore + (size_t)b * w.emb * T, T, bufA, LD, w.emb, T, LATW);
+        else
+            interp_linear_ac_transposed<false, false>(g, LATW, nullptr, 0, nullptr, 0, bufA, LD, w.emb, T, LATW);
     }
     __syncthreads();
     rows_out(bufA, w.emb, T, LD, s.dYp, row0, 128);                // padded to 128 columns for the weight-gradient GEMM
     // d r_final = Wp^T dbefore, masked by r_final > 0: the gradient at the stack's output h
     conv1d_dgrad_lds<1, 1, false>(bufA, w.emb, T, bufB, H, T, w.enc_prevq_w, 0, LD, LD, m_r + w.n_res * 128, 1);
     __syncthreads();
-    for (int l = w.n_res - 1; l >= 0; --l) {
-        // bufB = dL/dh_out, h_out = r + c1(m), m = relu(c3(r)), r = relu(h_in)
-        rows_out(bufB, H, T, LD, s.dYc1[l], row0, H);
-        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, w.enc_c1[l], 0, LD, LD, m_m + l * 256, 1);       // d(pre-ReLU of m)
-        __syncthreads();
-        rows_out(bufA, R, T, LD, s.dYc3[l], row0, R);
-        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, w.enc_c3[l], 1, LD, LD, m_r + l * 128, 1);        // + skip, masked: dL/dh_in
-        __syncthreads();
-    }
+    residual_stack_backward(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.dY3, row0, H);                       // dL/d(conv_3 output)
     conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, H, T, w.enc_conv3_w, 1, LD, LD, m_a, 1);                     // dL/d(conv_2 pre-ReLU)
     __syncthreads();
@@ -521,7 +559,7 @@ __global__ __launch_bounds__(256) void vae_part_reduce_kernel(const float* __res
 //                           output gradient (column co * 4 + kk = d[co][2 i - 1 + kk]) the K operand.
 struct VaeDecBwdBufs {
     float *Xc1, *dY1, *Xct1, *Gct1, *part2, *partb1;
-    float *Xr3[4], *Xm[4], *dYc1[4], *dYc3[4];
+    VaeStackBufs st;
 };
 constexpr int VAE_DBWD_MASK_BYTES = (5 * 128 + 4 * 256 + 128) * 4;   // ReLU bit words of vae_decode_bwd_kernel
 constexpr int VAE_P2 = 257;   // _conv_trans_2 partial row: dW (hidden/2 x 4 = 256) | db (1) at hidden = 128
@@ -588,21 +626,7 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDe
     }
     conv1d_lds<3, 1, false, false>(bufA, E, T, bufB, H, T, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
     __syncthreads();
-    for (int l = 0; l < w.n_res; ++l) {
-        relu_inplace(bufB, H, T, LD);
-        __syncthreads();
-        relu_mask(bufB, H, T, LD, m_r + l * 128, 1);
-        im2col_rows<3, 1>(bufB, H, T, LD, s.Xr3[l], row0, T, 1);
-        conv1d_lds<3, 1, true, false>(bufB, H, T, bufA, R, T, w.dec_c3[l], nullptr, 1, LD, LD);
-        __syncthreads();
-        relu_mask(bufA, R, T, LD, m_m + l * 256, 1);
-        rows_out(bufA, R, T, LD, s.Xm[l], row0, R);
-        conv1d_lds<1, 1, false, true>(bufA, R, T, bufB, H, T, w.dec_c1[l], nullptr, 0, LD, LD);
-        __syncthreads();
-    }
-    relu_inplace(bufB, H, T, LD);
-    __syncthreads();
-    relu_mask(bufB, H, T, LD, m_r + w.n_res * 128, 1);
+    residual_stack_recompute(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.Xct1, row0, H);
     convT1d_k4s2_lds<true>(bufB, H, T, wide, half_c, w.dec_ct1_w, w.dec_ct1_b, LD, T2);
     __syncthreads();
@@ -644,36 +668,17 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDe
     // d r_final, masked by r_final > 0: the gradient at the stack's output h (r_final itself left as Xct1)
     convT1d_k4s2_dgrad_lds(wide, half_c, T2, bufB, H, T, w.dec_ct1_w, T2, LD, m_r + w.n_res * 128);
     __syncthreads();
-    for (int l = w.n_res - 1; l >= 0; --l) {
-        // bufB = dL/dh_out, h_out = r + c1(m), m = relu(c3(r)), r = relu(h_in)
-        rows_out(bufB, H, T, LD, s.dYc1[l], row0, H);
-        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, w.dec_c1[l], 0, LD, LD, m_m + l * 256, 1);
-        __syncthreads();
-        rows_out(bufA, R, T, LD, s.dYc3[l], row0, R);
-        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, w.dec_c3[l], 1, LD, LD, m_r + l * 128, 1);
-        __syncthreads();
-    }
+    residual_stack_backward(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.dY1, row0, H);                       // dL/d(_conv_1 output)
     if (dz == nullptr) return;
     conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, E, T, w.dec_conv1_w, 1, LD, LD, nullptr, 1);   // dL/d(after), decoder part
     __syncthreads();
-    // dz = interp^T(d after + dafter) with the forward's own index arithmetic (interp_linear_ac)
-    const float scale = T > 1 ? (float)(W - 1) / (float)(T - 1) : 0.f;
-    for (int o = threadIdx.x; o < E * W; o += VAE_THREADS) {
-        const int c = o / W, j = o - c * W;
-        const float* da = dafter != nullptr ? dafter + ((size_t)b * E + c) * T : nullptr;
-        float acc = 0.f;
-        for (int t = 0; t < T; ++t) {
-            const float real = scale * (float)t;
-            const int i0 = (int)real;
-            const int i1 = i0 + (i0 < W - 1 ? 1 : 0);
-            const float l1 = real - (float)i0, l0 = 1.0f - l1;
-            const float d = bufA[c * LD + t] + (da != nullptr ? da[t] : 0.f);
-            if (i0 == j) acc += l0 * d;
-            if (i1 == j) acc += l1 * d;
-        }
-        dz[(size_t)b * E * W + o] = acc;
-    }
+    // dz = interp^T(d after + dafter)
+    float* dzb = dz + (size_t)b * E * W;
+    if (dafter != nullptr)
+        interp_linear_ac_transposed<false, true>(bufA, LD, dafter + (size_t)b * E * T, T, nullptr, 0, dzb, W, E, W, T);
+    else
+        interp_linear_ac_transposed<false, false>(bufA, LD, nullptr, 0, nullptr, 0, dzb, W, E, W, T);
 }
 
 // dst (rows, cols) = the first `cols` columns of src (rows, ld)
@@ -692,17 +697,16 @@ struct t2s_vae {
     float* arena = nullptr;
     bool has_encoder = false;
     bool has_decoder = false;
-    // encoder backward (t2s_vae_encode_backward): row blocks + weight-gradient partial tiles, grown on demand
-    float* bwd = nullptr;
-    size_t bwd_rows = 0;          // rows (= B * L / 4) the row blocks hold
-    int bwd_series = 0;           // series the conv_1 partial rows hold
+    // the two backwards (t2s_vae_encode_backward, t2s_vae_decode_backward): each its own row blocks, the weight-gradient
+    // partial tiles `wg` shared; all grown on demand
+    struct RowBuf {
+        float* p = nullptr;
+        size_t rows = 0;          // rows (= B * L / 4) the row blocks hold
+        int series = 0;           // series the per-series partial rows hold
+    } bwd, dbwd;
     float* wg = nullptr;
     size_t wg_floats = 0;
     int n_cu = 0;
-    // decoder backward (t2s_vae_decode_backward): its own row blocks, grown on demand; `wg` is shared
-    float* dbwd = nullptr;
-    size_t dbwd_rows = 0;
-    int dbwd_series = 0;
 };
 
 namespace {
@@ -826,9 +830,9 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
 extern "C" void t2s_vae_destroy(t2s_vae* h) {
     if (!h) return;
     if (h->arena) (void)hipFree(h->arena);
-    if (h->bwd) (void)hipFree(h->bwd);
+    if (h->bwd.p) (void)hipFree(h->bwd.p);
     if (h->wg) (void)hipFree(h->wg);
-    if (h->dbwd) (void)hipFree(h->dbwd);
+    if (h->dbwd.p) (void)hipFree(h->dbwd.p);
     delete h;
 }
 
@@ -893,85 +897,118 @@ extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* befor
     return T2S_OK;
 }
 
+// ------------------------------------------------------------------------ what the two backward entries share on the host
+namespace {
+// the handle's shape and the batch, `who` = the entry's name
+int vae_bwd_check(const char* who, const VaeDev& d, int B, int L) {
+    // the weight-gradient GEMMs work on 128-wide tiles: the reference's default LA-VAE (pretrained_lavae_unified.py:119-122)
+    T2S_REQUIRE(d.hidden == 128 && d.res_hidden % 128 == 0 && d.emb == 64,
+                "%s: hidden=%d res_hidden=%d emb=%d unsupported (hidden 128, res_hidden 128 / 256, emb 64)", who, d.hidden, d.res_hidden, d.emb);
+    T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "%s: B=%d L=%d unsupported (8 <= L <= 128, a multiple of 4)", who, B, L);
+    return T2S_OK;
+}
+
+int vae_cu_count(t2s_vae* h) {
+    if (h->n_cu != 0) return T2S_OK;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    T2S_HIP_CHECK(hipGetDevice(&dev));
+    T2S_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    h->n_cu = prop.multiProcessorCount;
+    return T2S_OK;
+}
+
+// the weight-gradient partial tiles serve the largest of the caller's (N, K) shapes
+template <int n>
+int vae_ensure_wg(t2s_vae* h, const int (&shapes)[n][2]) {
+    size_t need = 0;
+    for (auto& sh : shapes) {
+        const size_t f = wgrad16_shape_scratch_floats(sh[0], sh[1], h->n_cu);
+        need = f > need ? f : need;
+    }
+    if (need <= h->wg_floats) return T2S_OK;
+    if (h->wg) T2S_HIP_CHECK(hipFree(h->wg));
+    h->wg = nullptr;
+    h->wg_floats = 0;              // (a failed hipMalloc below must not leave a size that vouches for a NULL buffer)
+    T2S_HIP_CHECK(hipMalloc((void**)&h->wg, need * sizeof(float)));
+    h->wg_floats = need;
+    return T2S_OK;
+}
+
+// `rb` holds `rows` row-block rows of per_row floats, B partial rows of per_series floats and `fixed` floats.  It grows when
+// rows > rb.rows or B > rb.series, and never shrinks; growing frees and allocates, which the host mirror serialises under its
+// per-device lock -- vqvae.py (_vae_backward) repeats exactly this condition to know when.
+int vae_grow_rows(t2s_vae::RowBuf& rb, size_t rows, int B, size_t per_row, size_t per_series, size_t fixed) {
+    if (rows <= rb.rows && B <= rb.series) return T2S_OK;
+    const size_t r2 = rows > rb.rows ? rows : rb.rows;
+    const int b2 = B > rb.series ? B : rb.series;
+    if (rb.p) T2S_HIP_CHECK(hipFree(rb.p));
+    rb = t2s_vae::RowBuf{};       // (a failed hipMalloc below must not leave sizes that vouch for a NULL buffer)
+    T2S_HIP_CHECK(hipMalloc((void**)&rb.p, (r2 * per_row + (size_t)b2 * per_series + fixed) * sizeof(float)));
+    rb.rows = r2;
+    rb.series = b2;
+    return T2S_OK;
+}
+
+// hands out the row blocks of a RowBuf in order
+struct VaeTake {
+    float* p;
+    size_t rows;
+    float* operator()(size_t cols) { float* q = p; p += rows * cols; return q; }
+};
+
+// the residual stack's share of a row buffer: floats per row and the hand-out in the same order; its weight gradients
+size_t vae_stack_row_floats(int NR, int R) { return (size_t)NR * (384 + R + 128 + R); }
+void vae_stack_take(VaeTake& take, VaeStackBufs& s, int NR, int R) {
+    for (int l = 0; l < NR; ++l) { s.Xr3[l] = take(384); s.Xm[l] = take(R); s.dYc1[l] = take(128); s.dYc3[l] = take(R); }
+}
+int vae_stack_wgrad(t2s_vae* h, const VaeStackBufs& s, float* const* g_c3, float* const* g_c1, int M, hipStream_t st) {
+    const int R = h->dev.res_hidden;
+    int rc;
+    for (int l = 0; l < h->dev.n_res; ++l) {
+        if ((rc = launch_wgrad32(s.dYc3[l], s.Xr3[l], g_c3[l], nullptr, M, R, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+        if ((rc = launch_wgrad32(s.dYc1[l], s.Xm[l], g_c1[l], nullptr, M, 128, R, h->wg, h->wg_floats, h->n_cu, st))) return rc;
+    }
+    return T2S_OK;
+}
+}
+
 extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g,
                                        int B, int L, void* stream) {
     T2S_REQUIRE(h && x && dz && g, "t2s_vae_encode_backward: NULL argument");
     T2S_REQUIRE(h->has_encoder, "t2s_vae_encode_backward: handle was created without encoder weights");
     const VaeDev& d = h->dev;
-    // the weight-gradient GEMMs work on 128-wide tiles: the reference's default LA-VAE (pretrained_lavae_unified.py:119-122)
-    T2S_REQUIRE(d.hidden == 128 && d.res_hidden % 128 == 0 && d.emb == 64,
-                "t2s_vae_encode_backward: hidden=%d res_hidden=%d emb=%d unsupported (hidden 128, res_hidden 128 / 256, emb 64)", d.hidden,
-                d.res_hidden, d.emb);
-    T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "t2s_vae_encode_backward: B=%d L=%d unsupported (L <= 128, a multiple of 4)", B, L);
+    int rc;
+    if ((rc = vae_bwd_check("t2s_vae_encode_backward", d, B, L))) return rc;
     T2S_REQUIRE(g->conv1_w && g->conv1_b && g->conv2_w && g->conv2_b && g->conv3_w && g->conv3_b && g->prevq_w && g->prevq_b,
                 "t2s_vae_encode_backward: NULL gradient pointer");
     for (int l = 0; l < d.n_res; ++l)
         T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "t2s_vae_encode_backward: NULL gradient pointer of residual layer %d", l);
     hipStream_t st = (hipStream_t)stream;
-    const int T = L / 4, H = d.hidden, R = d.res_hidden, NR = d.n_res;
-    const size_t rows = (size_t)B * T;
-    if (h->n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        T2S_HIP_CHECK(hipGetDevice(&dev));
-        T2S_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        h->n_cu = prop.multiProcessorCount;
-    }
-    // row blocks: floats per row, in the order the pointers are handed out below
-    const size_t per_row = 256 + 384 + 128 + 128 + 128 + 128 + (size_t)NR * (384 + R + 128 + R);
-    if (rows > h->bwd_rows || B > h->bwd_series) {
-        const size_t r2 = rows > h->bwd_rows ? rows : h->bwd_rows;
-        const int b2 = B > h->bwd_series ? B : h->bwd_series;
-        if (h->bwd) T2S_HIP_CHECK(hipFree(h->bwd));
-        h->bwd = nullptr;
-        h->bwd_rows = 0;          // (a failed hipMalloc below must not leave sizes that vouch for a NULL buffer)
-        h->bwd_series = 0;
-        T2S_HIP_CHECK(hipMalloc((void**)&h->bwd, (r2 * per_row + (size_t)b2 * VAE_P1 + 128 * 128 + 128) * sizeof(float)));
-        h->bwd_rows = r2;
-        h->bwd_series = b2;
-    }
-    {   // weight-gradient partial tiles: the largest of this encoder's shapes
-        size_t need = 0;
-        const int shapes[5][2] = {{128, 256}, {128, 384}, {R, 384}, {128, R}, {128, 128}};
-        for (auto& sh : shapes) {
-            const int tiles = (sh[0] / 128) * (sh[1] / 128);
-            int per = 3 * h->n_cu / tiles;
-            per = per < 1 ? 1 : per;
-            const size_t n = (size_t)per * tiles * (128 * 128) + (size_t)per * (sh[0] / 128) * 128;
-            need = n > need ? n : need;
-        }
-        if (need > h->wg_floats) {
-            if (h->wg) T2S_HIP_CHECK(hipFree(h->wg));
-            h->wg = nullptr;
-            h->wg_floats = 0;
-            T2S_HIP_CHECK(hipMalloc((void**)&h->wg, need * sizeof(float)));
-            h->wg_floats = need;
-        }
-    }
+    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4);
+    if ((rc = vae_cu_count(h))) return rc;
+    // row blocks: floats per row, in the order the pointers are handed out below; conv_1's partial rows; prevq padded to 128 outputs
+    if ((rc = vae_grow_rows(h->bwd, (size_t)M, B, 256 + 384 + 128 + 128 + 128 + 128 + vae_stack_row_floats(NR, R), VAE_P1, 128 * 128 + 128)))
+        return rc;
+    const int shapes[5][2] = {{128, 256}, {128, 384}, {R, 384}, {128, R}, {128, 128}};
+    if ((rc = vae_ensure_wg(h, shapes))) return rc;
     VaeBwdBufs s{};
-    float* p = h->bwd;
-    auto take = [&](size_t cols) { float* q = p; p += h->bwd_rows * cols; return q; };
+    VaeTake take{h->bwd.p, h->bwd.rows};
     s.Xc2 = take(256); s.Xc3 = take(384); s.Xp = take(128); s.dYp = take(128); s.dY3 = take(128); s.dY2 = take(128);
-    for (int l = 0; l < NR; ++l) { s.Xr3[l] = take(384); s.Xm[l] = take(R); s.dYc1[l] = take(128); s.dYc3[l] = take(R); }
-    s.part1 = p;
-    float* tmp_w = p + (size_t)h->bwd_series * VAE_P1;             // (128,128) + (128): prevq padded to 128 outputs
+    vae_stack_take(take, s.st, NR, R);
+    s.part1 = take.p;
+    float* tmp_w = s.part1 + (size_t)h->bwd.series * VAE_P1;       // (128,128) + (128): prevq padded to 128 outputs
     float* tmp_b = tmp_w + 128 * 128;
     vae_encode_bwd_kernel<<<B, VAE_THREADS, VAE_LDS_FLOATS * 4 + VAE_BWD_MASK_BYTES, st>>>(d, x, dz, dbefore, s, L);
     T2S_LAUNCH_CHECK();
-    int rc;
-    const int M = (int)rows;
     if ((rc = launch_wgrad32(s.dY2, s.Xc2, g->conv2_w, g->conv2_b, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     if ((rc = launch_wgrad32(s.dY3, s.Xc3, g->conv3_w, g->conv3_b, M, 128, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-    for (int l = 0; l < NR; ++l) {
-        if ((rc = launch_wgrad32(s.dYc3[l], s.Xr3[l], g->stack_conv3_w[l], nullptr, M, R, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-        if ((rc = launch_wgrad32(s.dYc1[l], s.Xm[l], g->stack_conv1_w[l], nullptr, M, 128, R, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-    }
+    if ((rc = vae_stack_wgrad(h, s.st, g->stack_conv3_w, g->stack_conv1_w, M, st))) return rc;
     if ((rc = launch_wgrad32(s.dYp, s.Xp, tmp_w, tmp_b, M, 128, 128, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     T2S_HIP_CHECK(hipMemcpyAsync(g->prevq_w, tmp_w, (size_t)64 * 128 * sizeof(float), hipMemcpyDeviceToDevice, st));
     T2S_HIP_CHECK(hipMemcpyAsync(g->prevq_b, tmp_b, (size_t)64 * sizeof(float), hipMemcpyDeviceToDevice, st));
     vae_part_reduce_kernel<<<VAE_P1 / 32, 256, 0, st>>>(s.part1, B, VAE_P1, g->conv1_w, 256, g->conv1_b);
     T2S_LAUNCH_CHECK();
-    (void)H;
     return T2S_OK;
 }
 
@@ -980,74 +1017,32 @@ extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* 
     T2S_REQUIRE(h && z && drecon && g, "t2s_vae_decode_backward: NULL argument");
     T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_backward: handle was created without decoder weights");
     const VaeDev& d = h->dev;
-    T2S_REQUIRE(d.hidden == 128 && d.res_hidden % 128 == 0 && d.emb == 64,
-                "t2s_vae_decode_backward: hidden=%d res_hidden=%d emb=%d unsupported (hidden 128, res_hidden 128 / 256, emb 64)", d.hidden,
-                d.res_hidden, d.emb);
-    T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "t2s_vae_decode_backward: B=%d L=%d unsupported (8 <= L <= 128, a multiple of 4)", B, L);
+    int rc;
+    if ((rc = vae_bwd_check("t2s_vae_decode_backward", d, B, L))) return rc;
     T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_TMAX, "t2s_vae_decode_backward: latent width %d unsupported (1..%d)", latent_w, VAE_TMAX);
     T2S_REQUIRE(g->conv1_w && g->conv1_b && g->ct1_w && g->ct1_b && g->ct2_w && g->ct2_b, "t2s_vae_decode_backward: NULL gradient pointer");
     for (int l = 0; l < d.n_res; ++l)
         T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "t2s_vae_decode_backward: NULL gradient pointer of residual layer %d", l);
     hipStream_t st = (hipStream_t)stream;
-    const int T = L / 4, R = d.res_hidden, NR = d.n_res;
-    const size_t rows = (size_t)B * T;
-    if (h->n_cu == 0) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        T2S_HIP_CHECK(hipGetDevice(&dev));
-        T2S_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
-        h->n_cu = prop.multiProcessorCount;
-    }
-    // row blocks: floats per row, in the order the pointers are handed out below
-    const size_t per_row = 256 + 128 + 128 + 256 + (size_t)NR * (384 + R + 128 + R);
-    if (rows > h->dbwd_rows || B > h->dbwd_series) {
-        const size_t r2 = rows > h->dbwd_rows ? rows : h->dbwd_rows;
-        const int b2 = B > h->dbwd_series ? B : h->dbwd_series;
-        if (h->dbwd) T2S_HIP_CHECK(hipFree(h->dbwd));
-        h->dbwd = nullptr;
-        h->dbwd_rows = 0;         // (a failed hipMalloc below must not leave sizes that vouch for a NULL buffer)
-        h->dbwd_series = 0;
-        T2S_HIP_CHECK(hipMalloc((void**)&h->dbwd, (r2 * per_row + 128 * 256 + (size_t)b2 * (VAE_P2 + VAE_PB1)) * sizeof(float)));
-        h->dbwd_rows = r2;
-        h->dbwd_series = b2;
-    }
-    {   // weight-gradient partial tiles: the largest of this decoder's shapes
-        size_t need = 0;
-        const int shapes[3][2] = {{128, 256}, {R, 384}, {128, R}};
-        for (auto& sh : shapes) {
-            const int tiles = (sh[0] / 128) * (sh[1] / 128);
-            int per = 3 * h->n_cu / tiles;
-            per = per < 1 ? 1 : per;
-            const size_t n = (size_t)per * tiles * (128 * 128) + (size_t)per * (sh[0] / 128) * 128;
-            need = n > need ? n : need;
-        }
-        if (need > h->wg_floats) {
-            if (h->wg) T2S_HIP_CHECK(hipFree(h->wg));
-            h->wg = nullptr;
-            h->wg_floats = 0;
-            T2S_HIP_CHECK(hipMalloc((void**)&h->wg, need * sizeof(float)));
-            h->wg_floats = need;
-        }
-    }
+    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4);
+    if ((rc = vae_cu_count(h))) return rc;
+    // row blocks: floats per row, in the order the pointers are handed out below; the two partial rows; _conv_1 with K padded to 256
+    if ((rc = vae_grow_rows(h->dbwd, (size_t)M, B, 256 + 128 + 128 + 256 + vae_stack_row_floats(NR, R), VAE_P2 + VAE_PB1, 128 * 256))) return rc;
+    const int shapes[3][2] = {{128, 256}, {R, 384}, {128, R}};
+    if ((rc = vae_ensure_wg(h, shapes))) return rc;
     VaeDecBwdBufs s{};
-    float* p = h->dbwd;
-    auto take = [&](size_t cols) { float* q = p; p += h->dbwd_rows * cols; return q; };
+    VaeTake take{h->dbwd.p, h->dbwd.rows};
     s.Xc1 = take(256); s.dY1 = take(128); s.Xct1 = take(128); s.Gct1 = take(256);
-    for (int l = 0; l < NR; ++l) { s.Xr3[l] = take(384); s.Xm[l] = take(R); s.dYc1[l] = take(128); s.dYc3[l] = take(R); }
-    float* tmp_w = p;                                              // (128,256): _conv_1 with K padded from 192
+    vae_stack_take(take, s.st, NR, R);
+    float* tmp_w = take.p;                                         // (128,256): _conv_1 with K padded from 192
     s.part2 = tmp_w + 128 * 256;
-    s.partb1 = s.part2 + (size_t)h->dbwd_series * VAE_P2;
+    s.partb1 = s.part2 + (size_t)h->dbwd.series * VAE_P2;
     vae_decode_bwd_kernel<<<B, VAE_THREADS, VAE_LDS_FLOATS * 4 + VAE_DBWD_MASK_BYTES, st>>>(d, z, drecon, dafter, dz, s, L, latent_w);
     T2S_LAUNCH_CHECK();
-    int rc;
-    const int M = (int)rows;
     if ((rc = launch_wgrad32(s.dY1, s.Xc1, tmp_w, g->conv1_b, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     vae_copy_cols_kernel<<<(128 * 192 + 255) / 256, 256, 0, st>>>(tmp_w, 256, g->conv1_w, 128, 192);
     T2S_LAUNCH_CHECK();
-    for (int l = 0; l < NR; ++l) {
-        if ((rc = launch_wgrad32(s.dYc3[l], s.Xr3[l], g->stack_conv3_w[l], nullptr, M, R, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-        if ((rc = launch_wgrad32(s.dYc1[l], s.Xm[l], g->stack_conv1_w[l], nullptr, M, 128, R, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-    }
+    if ((rc = vae_stack_wgrad(h, s.st, g->stack_conv3_w, g->stack_conv1_w, M, st))) return rc;
     if ((rc = launch_wgrad32(s.Xct1, s.Gct1, g->ct1_w, nullptr, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     vae_part_reduce_kernel<<<(VAE_P2 + 31) / 32, 256, 0, st>>>(s.part2, B, VAE_P2, g->ct2_w, 256, g->ct2_b);
     T2S_LAUNCH_CHECK();

@@ -1,5 +1,5 @@
-// fp32 weight-gradient GEMM shared by the DiT training step (t2s_train.hip, T2S_TRAIN_F32) and the LA-VAE encoder backward
-// (t2s_vae.hip): dW = dY^T X over M rows on v_mfma_f32_32x32x2_f32 (exact fp32), two deterministic stages (one partial tile
+// fp32 weight-gradient GEMM shared by the DiT training step (t2s_train.hip, T2S_TRAIN_F32) and the LA-VAE encoder and decoder
+// backwards (t2s_vae.hip): dW = dY^T X over M rows on v_mfma_f32_32x32x2_f32 (exact fp32), two deterministic stages (one partial tile
 // per row slab, added in slab order by wgrad16_reduce_kernel of t2s_bf16.h).
 #pragma once
 #include "t2s_bf16.h"
@@ -11,8 +11,9 @@ namespace t2s {
 // A operand = dY^T straight from row-major global memory (lane = output feature n: 128-B coalesced
 // segments, two token rows per MFMA); B operand = X rows, staged ONCE per workgroup in LDS
 // (64-row sub-slabs, coalesced float4) and shared by the 4 waves, which own different n-tiles of
-// the same 128-wide k-chunk.  Partial tiles are added to the gradient with fp32 atomics (full
-// 128-B rows per wave instruction).  The bias gradient falls out of the A operand for free.
+// the same 128-wide k-chunk.  Every workgroup stores its partial tile (full 128-B rows per wave
+// instruction); wgrad16_reduce_kernel adds them in slab order: no atomics.  The bias gradient
+// falls out of the A operand for free.
 constexpr int WG_ROWS = 64;   // rows staged per LDS pass
 static __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restrict__ dY, const float* __restrict__ X,
                                                     float* __restrict__ part, float* __restrict__ bpart, int M, int N,
@@ -64,7 +65,7 @@ static __global__ __launch_bounds__(256) void wgrad_kernel(const float* __restri
 }
 
 
-// dW (N,K) = dY^T X, db (N) = column sums of dY (db may be NULL); N % 128 == 0, K % 128 == 0.  scratch: wgrad16_scratch_floats().
+// dW (N,K) = dY^T X, db (N) = column sums of dY (db may be NULL); N % 128 == 0, K % 128 == 0.  scratch: wgrad16_shape_scratch_floats(N, K).
 inline int launch_wgrad32(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, float* scratch,
                           size_t scratch_floats, int n_cu, hipStream_t st) {
     T2S_REQUIRE(N % 128 == 0 && K % 128 == 0 && M > 0, "wgrad: unsupported shape M=%d N=%d K=%d", M, N, K);

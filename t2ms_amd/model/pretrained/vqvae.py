@@ -58,7 +58,9 @@ class _VaeHandle:
         torch.cuda.synchronize(device)
         with torch.cuda.device(device):
             L.check(L.lib().t2s_vae_create(C.byref(w), C.byref(self.ptr)), "t2s_vae_create")
-        self.dbwd_rows = self.dbwd_series = 0     # what t2s_vae_decode_backward's row blocks hold (it grows them on demand)
+        # what the C handle's backward row blocks hold (a mirror handle serves one direction, an encoder's or a decoder's):
+        # vae_grow_rows (t2s_vae.hip) grows them when rows > held rows or B > held series; _vae_backward repeats that condition
+        self.bwd_rows = self.bwd_series = 0
         self._fin = weakref.finalize(self, L.destroy_locked, "t2s_vae_destroy", str(torch.device(device)), self.ptr)
 
     def close(self):
@@ -77,8 +79,45 @@ def _stack_ptrs(stack: ResidualStack, dst: L.VaeStackWeights, keep):
     return n
 
 
+def _vae_backward(codec, struct, B, Ln, call):
+    """What _EncodeFn.backward and _DecodeFn.backward share: fresh gradient tensors for codec._grad_params(), which lists
+    them in the declared field order of `struct` (a residual-stack array takes one per layer), then
+    `call(handle, byref(struct), stream)`; returns the gradients with None for a frozen parameter."""
+    params = codec._grad_params()
+    grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in params]
+    g, ptrs, n = struct(), iter(t.data_ptr() for t in grads), len(codec._residual_stack._layers)
+    for name, ctype in struct._fields_:
+        if ctype is C.c_void_p:
+            setattr(g, name, next(ptrs))
+        else:
+            getattr(g, name)[:n] = [next(ptrs) for _ in range(n)]
+    dev = params[0].device
+    with torch.cuda.device(dev):
+        ptr = codec._handle(dev)           # (the weights of the forward: no optimizer step happens between the two)
+        h, rows = codec.__dict__["_t2s_h"], B * (Ln // 4)
+        grows = rows > h.bwd_rows or B > h.bwd_series          # the C side's condition: vae_grow_rows, t2s_vae.hip
+        # growing the row blocks frees / allocates device memory: under the device's lock, like building the handle
+        with L.device_lock(dev) if grows else contextlib.nullcontext():
+            call(ptr, C.byref(g), L.stream_ptr(dev))
+        h.bwd_rows, h.bwd_series = max(h.bwd_rows, rows), max(h.bwd_series, B)
+    return [gr if p.requires_grad else None for gr, p in zip(grads, params)]
+
+
 class _Codec(nn.Module):
     """Shared handle cache for Encoder / Decoder (keyed on parameter storage + version)."""
+
+    def _res_hidden(self):
+        """num_residual_hiddens as the stack's first layer has it; None for a stack without layers."""
+        layers = self._residual_stack._layers
+        return layers[0]._block[1].out_channels if len(layers) else None
+
+    def _hip_backward_covers(self, hidden, emb, Ln):
+        """t2s_vae_encode_backward / t2s_vae_decode_backward cover the reference's default LA-VAE (pretrained_lavae_unified.py:
+        119-122: hidden 128, res_hidden 128 / 256, emb 64, 1..4 residual layers) on the BASELINE lengths (L <= 128).  A stack
+        without layers has no res_hidden (the library is told 1) and is not covered."""
+        rh = self._res_hidden()
+        return (hidden == 128 and emb == 64 and rh is not None and rh % 128 == 0 and len(self._residual_stack._layers) <= 4
+                and 8 <= Ln <= 128 and Ln % 4 == 0)
 
     def _tensors(self):
         return [p for p in self.parameters()]
@@ -134,7 +173,7 @@ class Encoder(_Codec):
         w, keep = L.VaeWeights(), []
         w.hidden = self._conv_2.out_channels
         w.emb = self._pre_vq_conv.out_channels
-        w.res_hidden = self._residual_stack._layers[0]._block[1].out_channels if len(self._residual_stack._layers) else 1
+        w.res_hidden = self._res_hidden() or 1
         w.n_res_layers = _stack_ptrs(self._residual_stack, w.enc_stack, keep)
         for name, t in (("enc_conv1_w", self._conv_1.weight), ("enc_conv1_b", self._conv_1.bias),
                         ("enc_conv2_w", self._conv_2.weight), ("enc_conv2_b", self._conv_2.bias),
@@ -146,11 +185,7 @@ class Encoder(_Codec):
         return w, keep
 
     def _hip_backward_ok(self, Ln):
-        """t2s_vae_encode_backward covers the reference's default LA-VAE (pretrained_lavae_unified.py:119-122: hidden 128,
-        res_hidden 128 / 256, emb 64) on the BASELINE lengths (L <= 128)."""
-        rh = self._residual_stack._layers[0]._block[1].out_channels if len(self._residual_stack._layers) else 128
-        return (self._conv_2.out_channels == 128 and rh % 128 == 0 and self._pre_vq_conv.out_channels == 64
-                and len(self._residual_stack._layers) <= 4 and 8 <= Ln <= 128 and Ln % 4 == 0)
+        return self._hip_backward_covers(self._conv_2.out_channels, self._pre_vq_conv.out_channels, Ln)
 
     def _grad_params(self):
         """The 12 encoder tensors in t2s_vae_enc_grads order."""
@@ -215,32 +250,17 @@ class _EncodeFn(torch.autograd.Function):
             z, before = enc._forward_hip(inputs)
         ctx.enc = enc
         ctx.save_for_backward(L.as_f32(inputs).reshape(inputs.shape[0], inputs.shape[-1]))
-        ctx.n_layers = len(enc._residual_stack._layers)
         ctx.set_materialize_grads(False)      # train.py uses z only: `before` then arrives as None, not as a zero tensor
         return z, before
 
     @staticmethod
     def backward(ctx, dz, dbefore):
         (x,) = ctx.saved_tensors
-        enc, n = ctx.enc, ctx.n_layers
-        dev = x.device
-        params = enc._grad_params()
-        grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in params]
-        g = L.VaeEncGrads()
-        names = ["conv1_w", "conv1_b", "conv2_w", "conv2_b", "conv3_w", "conv3_b"]
-        for nm, t in zip(names, grads[:6]):
-            setattr(g, nm, t.data_ptr())
-        for i in range(n):
-            g.stack_conv3_w[i] = grads[6 + i].data_ptr()
-            g.stack_conv1_w[i] = grads[6 + n + i].data_ptr()
-        g.prevq_w, g.prevq_b = grads[6 + 2 * n].data_ptr(), grads[7 + 2 * n].data_ptr()
-        dzc = L.as_f32(dz) if dz is not None else torch.zeros(x.shape[0], 64, L.LAT_W, device=dev)
+        B, Ln = x.shape
+        dzc = L.as_f32(dz) if dz is not None else torch.zeros(B, 64, L.LAT_W, device=x.device)
         dbc = L.as_f32(dbefore) if dbefore is not None else None
-        with torch.cuda.device(dev):
-            h = enc._handle(dev)           # (the weights of the forward: no optimizer step happens between the two)
-            L.check(L.lib().t2s_vae_encode_backward(h, L.dev_ptr(x), L.dev_ptr(dzc), L.dev_ptr(dbc), C.byref(g), x.shape[0],
-                                                    x.shape[1], L.stream_ptr(dev)), "t2s_vae_encode_backward")
-        out = [gr if p.requires_grad else None for gr, p in zip(grads, params)]
+        out = _vae_backward(ctx.enc, L.VaeEncGrads, B, Ln, lambda h, g, st: L.check(L.lib().t2s_vae_encode_backward(
+            h, L.dev_ptr(x), L.dev_ptr(dzc), L.dev_ptr(dbc), g, B, Ln, st), "t2s_vae_encode_backward"))
         return (None, None, *out)
 
 
@@ -258,7 +278,7 @@ class Decoder(_Codec):
         w, keep = L.VaeWeights(), []
         w.hidden = self._conv_1.out_channels
         w.emb = self._conv_1.in_channels
-        w.res_hidden = self._residual_stack._layers[0]._block[1].out_channels if len(self._residual_stack._layers) else 1
+        w.res_hidden = self._res_hidden() or 1
         w.n_res_layers = _stack_ptrs(self._residual_stack, w.dec_stack, keep)
         for name, t in (("dec_conv1_w", self._conv_1.weight), ("dec_conv1_b", self._conv_1.bias),
                         ("dec_ct1_w", self._conv_trans_1.weight), ("dec_ct1_b", self._conv_trans_1.bias),
@@ -269,11 +289,7 @@ class Decoder(_Codec):
         return w, keep
 
     def _hip_backward_ok(self, Ln, W):
-        """t2s_vae_decode_backward covers what t2s_vae_encode_backward covers (Encoder._hip_backward_ok): the reference's
-        default LA-VAE on the BASELINE lengths, latent width <= 32."""
-        rh = self._residual_stack._layers[0]._block[1].out_channels if len(self._residual_stack._layers) else 128
-        return (self._conv_1.out_channels == 128 and rh % 128 == 0 and self._conv_1.in_channels == 64
-                and len(self._residual_stack._layers) <= 4 and 8 <= Ln <= 128 and Ln % 4 == 0 and 1 <= W <= 32)
+        return self._hip_backward_covers(self._conv_1.out_channels, self._conv_1.in_channels, Ln) and 1 <= W <= 32
 
     def _grad_params(self):
         """The 10 decoder tensors in t2s_vae_dec_grads order."""
@@ -337,38 +353,18 @@ class _DecodeFn(torch.autograd.Function):
             recon, after = dec._forward_hip(z, Ln)
         ctx.dec, ctx.Ln = dec, Ln
         ctx.save_for_backward(z)
-        ctx.n_layers = len(dec._residual_stack._layers)
         ctx.set_materialize_grads(False)      # a loss on `recon` alone: `after` then arrives as None, not as a zero tensor
         return recon, after
 
     @staticmethod
     def backward(ctx, drecon, dafter):
         (z,) = ctx.saved_tensors
-        dec, n, Ln = ctx.dec, ctx.n_layers, ctx.Ln
-        dev, B, W = z.device, z.shape[0], z.shape[2]
-        params = dec._grad_params()
-        grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in params]
-        g = L.VaeDecGrads()
-        g.conv1_w, g.conv1_b = grads[0].data_ptr(), grads[1].data_ptr()
-        for i in range(n):
-            g.stack_conv3_w[i] = grads[2 + i].data_ptr()
-            g.stack_conv1_w[i] = grads[2 + n + i].data_ptr()
-        for nm, t in zip(("ct1_w", "ct1_b", "ct2_w", "ct2_b"), grads[2 + 2 * n:]):
-            setattr(g, nm, t.data_ptr())
-        drc = L.as_f32(drecon).reshape(B, Ln) if drecon is not None else torch.zeros(B, Ln, device=dev)
+        B, W, Ln = z.shape[0], z.shape[2], ctx.Ln
+        drc = L.as_f32(drecon).reshape(B, Ln) if drecon is not None else torch.zeros(B, Ln, device=z.device)
         dac = L.as_f32(dafter) if dafter is not None else None
         dz = torch.empty_like(z) if ctx.needs_input_grad[1] else None
-        with torch.cuda.device(dev):
-            h = dec._handle(dev)           # (the weights of the forward: no optimizer step happens between the two)
-            hobj = dec.__dict__["_t2s_h"]
-            rows = B * (Ln // 4)
-            grows = rows > hobj.dbwd_rows or B > hobj.dbwd_series
-            # growing the row blocks frees / allocates device memory: under the device's lock, like building the handle
-            with L.device_lock(dev) if grows else contextlib.nullcontext():
-                L.check(L.lib().t2s_vae_decode_backward(h, L.dev_ptr(z), L.dev_ptr(drc), L.dev_ptr(dac), C.byref(g), L.dev_ptr(dz),
-                                                        B, Ln, W, L.stream_ptr(dev)), "t2s_vae_decode_backward")
-            hobj.dbwd_rows, hobj.dbwd_series = max(hobj.dbwd_rows, rows), max(hobj.dbwd_series, B)
-        out = [gr if p.requires_grad else None for gr, p in zip(grads, params)]
+        out = _vae_backward(ctx.dec, L.VaeDecGrads, B, Ln, lambda h, g, st: L.check(L.lib().t2s_vae_decode_backward(
+            h, L.dev_ptr(z), L.dev_ptr(drc), L.dev_ptr(dac), g, L.dev_ptr(dz), B, Ln, W, st), "t2s_vae_decode_backward"))
         return (None, dz, None, *out)
 
 

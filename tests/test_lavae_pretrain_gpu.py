@@ -301,3 +301,62 @@ def test_decoder_backward_refuses_what_it_does_not_cover(dev):
     for Lbad, Wbad in ((4, 30), (132, 30), (26, 30), (24, 33), (24, 0)):
         rc = L.lib().t2s_vae_decode_backward(hd, z.detach().data_ptr(), drecon.data_ptr(), None, C.byref(g), None, 2, Lbad, Wbad, None)
         assert rc == -1 and "unsupported" in L.lib().t2s_last_error().decode(), (Lbad, Wbad)
+
+
+@pytest.mark.parametrize("side", ["encoder", "decoder"])
+def test_backward_grows_its_row_blocks_under_the_device_lock(dev, side, monkeypatch):
+    """Both backwards free / allocate their row blocks when B * L/4 or B exceeds what the handle holds (vae_grow_rows), which
+    must not run inside another thread's stream capture: the mirror takes the device's lock around exactly those calls, in
+    both directions.  Counted: the entries of L.device_lock during backward() alone (the forward has built the handle
+    before).  Shapes: rows 4 / series 2 first, the same again, series 3 (rows 6), then rows 4 <= 6 with series 1 <= 3."""
+    import gc
+    from t2ms_amd import _lib as L
+    gc.collect()                       # no finalizer of an earlier test's handle (destroy_locked) inside the counts
+    entries, real = [0], L.device_lock
+
+    def counting(device):
+        entries[0] += 1
+        return real(device)
+
+    monkeypatch.setattr(L, "device_lock", counting)
+    v = _vae(dev)
+    codec = getattr(v, side)
+
+    def backward_entries(B, Ls):
+        codec.zero_grad(set_to_none=True)
+        if side == "encoder":
+            z, before = codec(synth.make_series(40 + B + Ls, B, Ls).to(dev))
+            loss, node = z.sum() + before.sum(), z
+        else:
+            rec, after = codec(synth.make_latents(40 + B + Ls, B).to(dev), length=Ls)
+            loss, node = rec.sum() + after.sum(), after
+        assert type(node.grad_fn).__name__ == ("_EncodeFnBackward" if side == "encoder" else "_DecodeFnBackward")
+        n0 = entries[0]
+        loss.backward()
+        n1 = entries[0]
+        assert all(p.grad is not None and torch.isfinite(p.grad).all() for p in codec.parameters())
+        return n1 - n0
+
+    assert backward_entries(2, 8) >= 1
+    assert backward_entries(2, 8) == 0
+    assert backward_entries(3, 8) == 1
+    assert backward_entries(1, 16) == 0
+
+
+def test_zero_residual_layers_take_the_torch_op_path(dev):
+    """A residual stack without layers has no res_hidden; the library is told 1, which the backward entries refuse
+    ("unsupported").  The mirror must therefore not choose the HIP pair for it: the labelled torch-op forwards run under
+    autograd, as for every other shape the kernels do not cover, and backward() gives finite, non-zero gradients."""
+    from model.pretrained.vqvae import vqvae
+    torch.manual_seed(5)
+    v = vqvae(types.SimpleNamespace(block_hidden_size=128, num_residual_layers=0, res_hidden_size=256, embedding_dim=64)).to(dev)
+    x = synth.make_series(77, 1, 8).to(dev)
+    z, before = v.encoder(x)
+    rec, after = v.decoder(z, length=8)
+    assert z.requires_grad and type(z.grad_fn).__name__ != "_EncodeFnBackward"
+    assert after.requires_grad and type(after.grad_fn).__name__ != "_DecodeFnBackward"
+    (rec.sum() + after.sum() + before.sum()).backward()
+    ps = dict(v.named_parameters())
+    assert len(ps) == 14
+    for n, p in ps.items():
+        assert p.grad is not None and torch.isfinite(p.grad).all() and float(p.grad.abs().max()) > 0, n
