@@ -421,6 +421,26 @@ int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* before, int B, i
  * step does after the optimizer changed encoder.* (train.py:31-33 with usepretrainedvae false) -- no allocation, stream-ordered. */
 int t2s_vae_update_weights(t2s_vae* h, const t2s_vae_weights* w, void* stream);
 
+/* Multichannel LA-VAE codec: model/pretrained/myvqvae.py:32-86 (Encoder, Decoder) of the T2MS motion models -- C-channel
+ * series (7 deadlift, 10 bench press), latent width flow_dim.  t2s_vae_weights is the same struct; three tensors carry the
+ * channel count: enc_conv1_w (hidden/2,channels,4), dec_ct2_w (hidden/2,channels,4), dec_ct2_b (channels).
+ *   channels 1..16, hidden <= 128 even, res_hidden <= 256, 0..4 residual layers, emb 64, latent_w 1..64, B > 0,
+ *   8 <= L <= 2^20 -- a multiple of 4 OR NOT: the encoder's stride-2 convolutions give L/2 and L/4 positions (floor), the
+ *   decoder builds 4 * (L/4) samples and resamples them to L (F.interpolate linear, align_corners; skipped when L % 4 == 0).
+ * One launch per direction, one workgroup per (series, time tile), exact fp32, no atomics, bit-reproducible; neither entry
+ * allocates device memory, so both can run inside a captured graph.  A handle is EITHER kind: a single-channel entry
+ * (t2s_vae_encode, _decode, _decode_w, _encode_backward, _decode_backward) handed a multichannel handle returns
+ * T2S_E_INVALID naming the _mc entry, and the _mc entries refuse a t2s_vae_create handle likewise; a handle made here with
+ * channels = 1 is a multichannel handle.  t2s_vae_update_weights and t2s_vae_destroy serve both kinds.  There is no HIP
+ * backward for C channels yet (the host mirror trains through torch ops). */
+int t2s_vae_create_mc(const t2s_vae_weights* w, int channels, t2s_vae** out);
+int t2s_vae_channels(const t2s_vae* h);            /* 0 for a handle made by t2s_vae_create */
+/* x (B,channels,L) -> z (B,emb,latent_w), before (B,emb,L/4) (may be NULL while L/4 <= 32; longer series run in time
+ * tiles that write `before`, and a second launch interpolates it to the latent, so the buffer is required) */
+int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream);
+/* z (B,emb,latent_w) -> recon (B,channels,L) (never squeezed), after (B,emb,L/4) (may be NULL) */
+int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream);
+
 /* Backward of Encoder.forward (vqvae.py:57-71) for the one reference configuration that TRAINS the LA-VAE encoder (train.py:31-33,
  * `usepretrainedvae` false: the encoder is grafted into the denoiser and its parameters join the optimizer).
  *   x (B,L) the forward's input; dz (B,64,30) = dLoss/dz; dbefore (B,64,L/4) = dLoss/dbefore or NULL (train.py uses z only);
@@ -506,6 +526,9 @@ void t2s_sampler_destroy(t2s_sampler* s);
  *   noise  (steps,B,64,30) injected per-step draws (parity mode) or NULL (Philox, perf mode)
  *   series (B,L) decoded output, or NULL
  *   trace0 (steps,L) or NULL: decode of row 0 after every step (infer.py:90-93)
+ *          With a multichannel decoder handle (t2s_vae_create_mc, C channels) given at create, the decodes run
+ *          t2s_vae_decode_mc at latent width 30: series is (B,C,L), trace0 (steps,C,L), and cfg->length may be any value
+ *          >= 8.  A single-channel handle takes the path above unchanged (length a multiple of 4).
  *   stream NULL = the default stream.  With use_graph = 1 the graphs are then captured and replayed on a stream
  *          the sampler owns (the default stream cannot be captured), ordered after everything queued on the default
  *          stream before the call and joined back to it before the call returns -- same semantics, never an eager

@@ -204,6 +204,10 @@ SYMBOLS = {
     "t2s_vae_decode_backward": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeDecGrads), _VP, _I, _I, _I, _VP]),
     "t2s_vae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_vae_encode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
+    "t2s_vae_create_mc": (_I, [C.POINTER(VaeWeights), _I, C.POINTER(_VP)]),
+    "t2s_vae_channels": (_I, [_VP]),
+    "t2s_vae_encode_mc": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "t2s_vae_decode_mc": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_sampler_create": (_I, [_VP, _VP, C.POINTER(SampleConfig), C.POINTER(_VP)]),
     "t2s_sampler_create_lms": (_I, [_VP, _VP, C.POINTER(SampleConfig), _VP, C.POINTER(_VP)]),
     "t2s_sampler_destroy": (None, [_VP]),

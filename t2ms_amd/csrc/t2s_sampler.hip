@@ -762,6 +762,7 @@ std::recursive_mutex* lib_pool_lock(int dev) { return dev >= 0 && dev < 16 ? &g_
 }  // namespace t2s
 
 extern "C" int t2s_dit_max_seqs(const t2s_dit* h);
+extern "C" int t2s_vae_channels(const t2s_vae* h);
 
 // t2s_sampler_create (lms_coef NULL; modes DDPM / RF) and t2s_sampler_create_lms (mode LMS, HOST (steps,6) table)
 static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, const float* lms_coef, t2s_sampler** out) {
@@ -770,7 +771,8 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
                 "t2s_sampler_create: batch=%d needs 2*batch <= dit max_seqs=%d", cfg->batch, t2s_dit_max_seqs(dit));
     T2S_REQUIRE(cfg->t_values, "t2s_sampler_create: t_values is NULL");
     T2S_REQUIRE(cfg->mode != T2S_MODE_DDPM || cfg->ddpm_coef, "t2s_sampler_create: DDPM needs ddpm_coef");
-    T2S_REQUIRE(!vae || (cfg->length >= 4 && cfg->length % 4 == 0 && cfg->length <= (1 << 20)),
+    // a multichannel decoder (t2s_vae_create_mc) resamples to any length >= 8; the single-channel one builds multiples of 4
+    T2S_REQUIRE(!vae || (t2s_vae_channels(vae) ? cfg->length >= 8 : cfg->length >= 4 && cfg->length % 4 == 0) && cfg->length <= (1 << 20),
                 "t2s_sampler_create: length=%d unsupported", cfg->length);
     // allocations, synchronous copies and a stream synchronisation follow: not while another thread's run has a capture open
     // on the pool streams (same lock as t2s_sampler_run; see include/t2s.h "Threads")
@@ -928,6 +930,13 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
 }
 
 extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, void* stream);
+extern "C" int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream);
+
+// the sampler's decode of n latents: a multichannel decoder handle writes (n,C,L) at latent width 30, a single-channel one (n,L)
+static int sampler_decode(t2s_vae* vae, const float* x, float* out, int n, int L, hipStream_t st) {
+    if (t2s_vae_channels(vae) != 0) return t2s_vae_decode_mc(vae, x, out, nullptr, n, L, LATW, st);
+    return t2s_vae_decode(vae, x, out, nullptr, n, L, st);
+}
 
 extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, const float* noise, float* series,
                                float* trace0, void* stream) {
@@ -1053,8 +1062,8 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         }
         if (trace0) {
             // infer.py:90-93: decode row 0 of the first batch after every step
-            if ((rc = t2s_vae_decode(s->vae, x, trace0 + (size_t)j * c.length, nullptr, 1, c.length, st)) != T2S_OK)
-                return rc;
+            const int ch = t2s_vae_channels(s->vae);
+            if ((rc = sampler_decode(s->vae, x, trace0 + (size_t)j * (ch ? ch : 1) * c.length, 1, c.length, st)) != T2S_OK) return rc;
         }
     }
     for (int l = 1; l < lanes; ++l) {   // join before the decode (and before anything the caller queues next)
@@ -1062,7 +1071,7 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         T2S_HIP_CHECK(hipStreamWaitEvent(st, s->ev_join[l], 0));
     }
     if (series) {
-        if ((rc = t2s_vae_decode(s->vae, x, series, nullptr, c.batch, c.length, st)) != T2S_OK) return rc;
+        if ((rc = sampler_decode(s->vae, x, series, c.batch, c.length, st)) != T2S_OK) return rc;
     }
     if (via_own) {      // whatever the caller queues on its stream next sees the results
         T2S_HIP_CHECK(hipEventRecord(s->ev_out, st));

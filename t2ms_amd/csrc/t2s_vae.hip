@@ -330,6 +330,158 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_interp_z_kernel(const float* 
     }
 }
 
+// ------------------------------------------------------------------------------------------------ multichannel codec
+// The T2MS motion codec (reference model/pretrained/myvqvae.py:32-86): the same stack on C-channel series -- _conv_1 reads C
+// channels, _conv_trans_2 writes C -- with a latent `W` wide (flow_dim, <= 64) and ANY length L >= 8: the stride-2
+// convolutions give L/2 and L/4 positions (floor; the last taps of an odd length are real samples), the decoder builds
+// 4 T samples (T = L/4) and resamples them to L (myvqvae.py:85; the identity, skipped, when L % 4 == 0).  Same design as the
+// kernels above: one workgroup per (series, time tile), the stack resident in LDS, exact fp32, no atomics.
+constexpr int VAE_MC_CMAX = 16;          // series channels
+constexpr int VAE_MC_WMAX = 64;          // latent width
+constexpr int LDZ = VAE_MC_WMAX + 1;     // LDS row stride of a staged latent wider than VAE_TMAX: 64 x 65 floats fit in bufB
+constexpr int LDY = 4 * VAE_TMAX + 1;    // LDS row stride of a tile's samples in front of the final resampling
+static_assert(T2S_LAT_C * LDZ <= VAE_CMAX * LD && VAE_MC_CMAX * LDY <= VAE_CMAX * LD, "staging rows exceed an LDS buffer");
+
+// Decoder.forward (myvqvae.py:76-86).  The final resampling 4 T -> L: output position t reads samples i0(t) and i0(t) + 1; a tile
+// owns the outputs whose i0 falls in its core [4 c0, 4 c1), and the one sample beyond, 4 c1, lies inside its halo window (it
+// reads the same first-transposed-convolution outputs as the core sample 4 c1 - 1).  i0 is monotone in t, so every output
+// has exactly one owner.
+__global__ __launch_bounds__(VAE_THREADS) void vae_decode_mc_kernel(const VaeDev w, const float* __restrict__ z,
+                                                                    float* __restrict__ recon, float* __restrict__ after,
+                                                                    int L, int W, int C) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* bufA = smem;
+    float* bufB = smem + VAE_CMAX * LD;
+    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][2 Tw]
+    const int b = blockIdx.x;
+    const int T = L / 4, L4 = 4 * T;
+    const VaeTile tl = vae_tile(T, w.n_res + 2, blockIdx.y);
+    const int Tw = tl.w1 - tl.w0;
+    const int ldz = W <= VAE_TMAX ? LD : LDZ;
+    for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
+        const int c = o / W, t = o - c * W;
+        bufB[c * ldz + t] = z[(size_t)b * w.emb * W + o];
+    }
+    __syncthreads();
+    interp_linear_ac(bufB, w.emb, W, ldz, bufA, T, LD, tl.w0, Tw);
+    __syncthreads();
+    if (after) {
+        const int nc = tl.c1 - tl.c0;
+        for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
+            const int c = o / nc, t = tl.c0 + (o - c * nc);
+            after[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
+        }
+    }
+    conv1d_lds<3, 1, false, false>(bufA, w.emb, Tw, bufB, w.hidden, Tw, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
+    __syncthreads();
+    residual_stack(bufB, bufA, w.hidden, w.res_hidden, w.n_res, Tw, w.dec_c3, w.dec_c1, LD);
+    const int ldw = 2 * Tw;
+    convT1d_k4s2_lds<true>(bufB, w.hidden, Tw, wide, w.hidden / 2, w.dec_ct1_w, w.dec_ct1_b, LD, ldw);
+    __syncthreads();
+    // last transposed conv (hidden/2 -> C): the samples [y0, y1) go straight to global when L = 4 T, else to bufA [C][LDY]
+    const bool resample = L != L4;
+    const int y0 = 4 * tl.c0, yc = 4 * tl.c1;
+    const int y1 = resample && yc < L4 ? yc + 1 : yc, Ty = y1 - y0;
+    {
+        const int Tin = 2 * Tw, Cin = w.hidden / 2, i_g0 = 2 * tl.w0;
+        for (int o = threadIdx.x; o < C * Ty; o += VAE_THREADS) {
+            const int co = o / Ty, t = y0 + (o - co * Ty);
+            float acc = w.dec_ct2_b[co];
+            const int k0 = (t + 1) & 1;
+            for (int ci = 0; ci < Cin; ++ci) {
+#pragma unroll
+                for (int kk2 = 0; kk2 < 2; ++kk2) {
+                    const int kk = k0 + 2 * kk2;
+                    const int i = ((t + 1 - kk) >> 1) - i_g0;
+                    if (t + 1 - kk >= 0 && i >= 0 && i < Tin) acc += wide[ci * ldw + i] * w.dec_ct2_w[((size_t)ci * C + co) * 4 + kk];
+                }
+            }
+            if (resample) bufA[co * LDY + (t - y0)] = acc;
+            else recon[((size_t)b * C + co) * L + t] = acc;
+        }
+    }
+    if (!resample) return;
+    __syncthreads();
+    // candidates: every t whose i0 = floor(scale * t) can fall in [y0, yc), two positions of slack for the fp32 division;
+    // the ownership test itself is the tap's own arithmetic
+    const float scale = interp_scale_ac(L4, L);
+    int ta = (int)((float)y0 / scale) - 2, tb = (int)((float)yc / scale) + 3;
+    ta = ta > 0 ? ta : 0;
+    tb = tb < L ? tb : L;
+    const int nt = tb - ta;
+    for (int o = threadIdx.x; o < C * nt; o += VAE_THREADS) {
+        const int co = o / nt, t = ta + (o - co * nt);
+        const InterpTap p = interp_tap_ac(scale, t, L4);
+        if (p.i0 < y0 || p.i0 >= yc) continue;
+        recon[((size_t)b * C + co) * L + t] = p.l0 * bufA[co * LDY + (p.i0 - y0)] + p.l1 * bufA[co * LDY + (p.i1 - y0)];
+    }
+}
+
+// Encoder.forward (myvqvae.py:49-61): vae_encode_kernel with C input channels, floor lengths and a latent W wide.
+__global__ __launch_bounds__(VAE_THREADS) void vae_encode_mc_kernel(const VaeDev w, const float* __restrict__ x,
+                                                                    float* __restrict__ z, float* __restrict__ before,
+                                                                    int L, int W, int C) {
+    extern __shared__ __attribute__((aligned(16))) float smem[];
+    float* bufA = smem;
+    float* bufB = smem + VAE_CMAX * LD;
+    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][Tu]
+    const int b = blockIdx.x;
+    const int T2 = L / 2, T = L / 4;
+    const int half_c = w.hidden / 2;
+    const VaeTile tl = vae_tile(T, w.n_res + 1, blockIdx.y);
+    const int Tw = tl.w1 - tl.w0;
+    const int u0 = 2 * tl.w0 - 1 > 0 ? 2 * tl.w0 - 1 : 0;
+    const int u1 = 2 * (tl.w1 - 1) + 3 < T2 ? 2 * (tl.w1 - 1) + 3 : T2;
+    const int Tu = u1 - u0;
+    // conv_1: C -> hidden/2, k4 s2 p1, ReLU; output t reads x[2t-1 .. 2t+2] clipped to [0, L), straight from global
+    for (int o = threadIdx.x; o < half_c * Tu; o += VAE_THREADS) {
+        const int co = o / Tu, t = u0 + (o - co * Tu);
+        float acc = w.enc_conv1_b[co];
+        for (int ci = 0; ci < C; ++ci) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int ti = 2 * t + kk - 1;
+                if (ti >= 0 && ti < L) acc += w.enc_conv1_w[(co * C + ci) * 4 + kk] * x[((size_t)b * C + ci) * L + ti];
+            }
+        }
+        wide[co * Tu + (t - u0)] = fmaxf(acc, 0.f);
+    }
+    __syncthreads();
+    conv1d_lds<4, 2, true, false>(wide, half_c, Tu, bufA, w.hidden, Tw, w.enc_conv2_w, w.enc_conv2_b, 1, Tu, LD, u0, tl.w0);
+    __syncthreads();
+    conv1d_lds<3, 1, false, false>(bufA, w.hidden, Tw, bufB, w.hidden, Tw, w.enc_conv3_w, w.enc_conv3_b, 1, LD, LD);
+    __syncthreads();
+    residual_stack(bufB, bufA, w.hidden, w.res_hidden, w.n_res, Tw, w.enc_c3, w.enc_c1, LD);
+    conv1d_lds<1, 1, false, false>(bufB, w.hidden, Tw, bufA, w.emb, Tw, w.enc_prevq_w, w.enc_prevq_b, 0, LD, LD);
+    __syncthreads();
+    if (before) {
+        const int nc = tl.c1 - tl.c0;
+        for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
+            const int c = o / nc, t = tl.c0 + (o - c * nc);
+            before[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
+        }
+    }
+    if (gridDim.y > 1) return;            // tiled: vae_interp_rows_kernel finishes from `before`
+    const float scale = interp_scale_ac(T, W);
+    for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
+        const int c = o / W, t = o - c * W;
+        const InterpTap p = interp_tap_ac(scale, t, T);
+        z[(size_t)b * w.emb * W + o] = p.l0 * bufA[c * LD + p.i0] + p.l1 * bufA[c * LD + p.i1];
+    }
+}
+
+// out (B,C,Tout) = F.interpolate(in (B,C,Tin), Tout, mode='linear', align_corners=True): the latent of a tiled encode
+__global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                      int C, int Tin, int Tout) {
+    const float scale = interp_scale_ac(Tin, Tout);
+    const float* src = in + (size_t)blockIdx.x * C * Tin;
+    for (int o = threadIdx.x; o < C * Tout; o += VAE_THREADS) {
+        const int c = o / Tout, t = o - c * Tout;
+        const InterpTap p = interp_tap_ac(scale, t, Tin);
+        out[(size_t)blockIdx.x * C * Tout + o] = p.l0 * src[(size_t)c * Tin + p.i0] + p.l1 * src[(size_t)c * Tin + p.i1];
+    }
+}
+
 // ------------------------------------------------------------------------------------------------ encoder backward
 // Backward of Encoder.forward for the one configuration that trains the encoder (train.py:31-33 with `usepretrainedvae`
 // false).  Two stages:
@@ -697,6 +849,7 @@ struct t2s_vae {
     float* arena = nullptr;
     bool has_encoder = false;
     bool has_decoder = false;
+    int channels = 0;             // 0: the single-channel codec (t2s_vae_create); C: the multichannel one (t2s_vae_create_mc)
     // the two backwards (t2s_vae_encode_backward, t2s_vae_decode_backward): each its own row blocks, the weight-gradient
     // partial tiles `wg` shared; all grown on demand
     struct RowBuf {
@@ -715,19 +868,20 @@ size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
 struct VaeItem { const float* src; size_t n; const float** dst; };
 
 // every tensor of *w the handle keeps a device copy of, with the VaeDev slot that points at the copy
-int vae_items(const t2s_vae_weights* w, VaeDev& d, bool dec, bool enc, std::vector<VaeItem>& items) {
+// (C = series channels: 1 for the single-channel codec)
+int vae_items(const t2s_vae_weights* w, VaeDev& d, bool dec, bool enc, std::vector<VaeItem>& items, int C) {
     const int H = w->hidden, R = w->res_hidden, E = w->emb, NR = w->n_res_layers;
     if (dec)
         items = {{w->dec_conv1_w, (size_t)H * E * 3, &d.dec_conv1_w}, {w->dec_conv1_b, (size_t)H, &d.dec_conv1_b},
                  {w->dec_ct1_w, (size_t)H * (H / 2) * 4, &d.dec_ct1_w}, {w->dec_ct1_b, (size_t)H / 2, &d.dec_ct1_b},
-                 {w->dec_ct2_w, (size_t)(H / 2) * 4, &d.dec_ct2_w}, {w->dec_ct2_b, 1, &d.dec_ct2_b}};
+                 {w->dec_ct2_w, (size_t)(H / 2) * C * 4, &d.dec_ct2_w}, {w->dec_ct2_b, (size_t)C, &d.dec_ct2_b}};
     for (int l = 0; dec && l < NR; ++l) {
         T2S_REQUIRE(w->dec_stack.conv3_w[l] && w->dec_stack.conv1_w[l], "t2s_vae: NULL decoder residual weight %d", l);
         items.push_back({w->dec_stack.conv3_w[l], (size_t)R * H * 3, &d.dec_c3[l]});
         items.push_back({w->dec_stack.conv1_w[l], (size_t)H * R, &d.dec_c1[l]});
     }
     if (enc) {
-        items.push_back({w->enc_conv1_w, (size_t)(H / 2) * 4, &d.enc_conv1_w});
+        items.push_back({w->enc_conv1_w, (size_t)(H / 2) * C * 4, &d.enc_conv1_w});
         items.push_back({w->enc_conv1_b, (size_t)H / 2, &d.enc_conv1_b});
         items.push_back({w->enc_conv2_w, (size_t)H * (H / 2) * 4, &d.enc_conv2_w});
         items.push_back({w->enc_conv2_b, (size_t)H, &d.enc_conv2_b});
@@ -745,36 +899,38 @@ int vae_items(const t2s_vae_weights* w, VaeDev& d, bool dec, bool enc, std::vect
 }
 }
 
-extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
-    T2S_REQUIRE(w && out, "t2s_vae_create: NULL argument");
-    T2S_REQUIRE(w->hidden > 0 && w->hidden <= 128 && w->hidden % 2 == 0, "t2s_vae_create: hidden=%d unsupported (<=128, even)", w->hidden);
-    T2S_REQUIRE(w->res_hidden > 0 && w->res_hidden <= VAE_CMAX, "t2s_vae_create: res_hidden=%d unsupported (<=256)", w->res_hidden);
-    T2S_REQUIRE(w->n_res_layers >= 0 && w->n_res_layers <= 4, "t2s_vae_create: n_res_layers=%d unsupported (<=4)", w->n_res_layers);
-    T2S_REQUIRE(w->emb == T2S_LAT_C, "t2s_vae_create: embedding_dim=%d must be 64", w->emb);
+// t2s_vae_create (channels 0) and t2s_vae_create_mc (channels 1..16), `who` = the entry's name
+static int vae_create(const t2s_vae_weights* w, int channels, t2s_vae** out, const char* who) {
+    T2S_REQUIRE(w && out, "%s: NULL argument", who);
+    T2S_REQUIRE(w->hidden > 0 && w->hidden <= 128 && w->hidden % 2 == 0, "%s: hidden=%d unsupported (<=128, even)", who, w->hidden);
+    T2S_REQUIRE(w->res_hidden > 0 && w->res_hidden <= VAE_CMAX, "%s: res_hidden=%d unsupported (<=256)", who, w->res_hidden);
+    T2S_REQUIRE(w->n_res_layers >= 0 && w->n_res_layers <= 4, "%s: n_res_layers=%d unsupported (<=4)", who, w->n_res_layers);
+    T2S_REQUIRE(w->emb == T2S_LAT_C, "%s: embedding_dim=%d must be 64", who, w->emb);
     const bool dec = w->dec_conv1_w != nullptr;
     const bool enc = w->enc_conv1_w != nullptr;
-    T2S_REQUIRE(dec || enc, "t2s_vae_create: neither decoder nor encoder weights given");
+    T2S_REQUIRE(dec || enc, "%s: neither decoder nor encoder weights given", who);
     if (dec)
         T2S_REQUIRE(w->dec_conv1_b && w->dec_ct1_w && w->dec_ct1_b && w->dec_ct2_w && w->dec_ct2_b,
-                    "t2s_vae_create: partial decoder weights");
+                    "%s: partial decoder weights", who);
     const int H = w->hidden, R = w->res_hidden, E = w->emb, NR = w->n_res_layers;
     if (enc)
         T2S_REQUIRE(w->enc_conv1_b && w->enc_conv2_w && w->enc_conv2_b && w->enc_conv3_w && w->enc_conv3_b &&
                         w->enc_prevq_w && w->enc_prevq_b,
-                    "t2s_vae_create: partial encoder weights");
+                    "%s: partial encoder weights", who);
     t2s_vae* h = new t2s_vae();
     VaeDev& d = h->dev;
     d.hidden = H; d.res_hidden = R; d.n_res = NR; d.emb = E;
     std::vector<VaeItem> items;
     {
-        const int rc_items = vae_items(w, d, dec, enc, items);
+        const int rc_items = vae_items(w, d, dec, enc, items, channels ? channels : 1);
         if (rc_items != T2S_OK) {
             delete h;
             return rc_items;
         }
     }
-    for (auto& it : items) {      // sizes follow from hidden / res_hidden / emb: a tensor of another shape is an error code
-        const int rc_e = it.src ? check_device_extent(it.src, it.n * sizeof(float), "t2s_vae_create: a weight tensor (hyper-parameters vs tensor sizes)") : T2S_OK;
+    const std::string what = std::string(who) + ": a weight tensor (hyper-parameters vs tensor sizes)";
+    for (auto& it : items) {      // sizes follow from hidden / res_hidden / emb (/ channels): a tensor of another shape is an error code
+        const int rc_e = it.src ? check_device_extent(it.src, it.n * sizeof(float), what.c_str()) : T2S_OK;
         if (rc_e != T2S_OK) {
             delete h;
             return rc_e;
@@ -784,7 +940,7 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
     for (auto& it : items) total += r64(it.n);
     hipError_t e = hipMalloc(&h->arena, total * sizeof(float));
     if (e != hipSuccess) {
-        set_error("t2s_vae_create: hipMalloc failed: %s", hipGetErrorString(e));
+        set_error("%s: hipMalloc failed: %s", who, hipGetErrorString(e));
         delete h;
         return T2S_E_HIP;
     }
@@ -795,7 +951,7 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
         // stream capture open)
         e = hipMemcpyAsync(h->arena + off, it.src, it.n * sizeof(float), hipMemcpyDeviceToDevice, nullptr);
         if (e != hipSuccess) {
-            set_error("t2s_vae_create: weight copy failed: %s", hipGetErrorString(e));
+            set_error("%s: weight copy failed: %s", who, hipGetErrorString(e));
             t2s_vae_destroy(h);
             return T2S_E_HIP;
         }
@@ -804,12 +960,13 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
     }
     e = hipStreamSynchronize(nullptr);
     if (e != hipSuccess) {
-        set_error("t2s_vae_create: weight copy failed: %s", hipGetErrorString(e));
+        set_error("%s: weight copy failed: %s", who, hipGetErrorString(e));
         t2s_vae_destroy(h);
         return T2S_E_HIP;
     }
     h->has_encoder = enc;
     h->has_decoder = dec;
+    h->channels = channels;
     static bool attr = false;
     if (!attr) {
         const int bytes = VAE_LDS_FLOATS * 4;
@@ -821,11 +978,24 @@ extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) {
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_BWD_MASK_BYTES));
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_bwd_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_DBWD_MASK_BYTES));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_mc_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_mc_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         attr = true;
     }
     *out = h;
     return T2S_OK;
 }
+
+extern "C" int t2s_vae_create(const t2s_vae_weights* w, t2s_vae** out) { return vae_create(w, 0, out, "t2s_vae_create"); }
+
+extern "C" int t2s_vae_create_mc(const t2s_vae_weights* w, int channels, t2s_vae** out) {
+    T2S_REQUIRE(channels >= 1 && channels <= VAE_MC_CMAX, "t2s_vae_create_mc: channels=%d unsupported (1..%d)", channels, VAE_MC_CMAX);
+    return vae_create(w, channels, out, "t2s_vae_create_mc");
+}
+
+extern "C" int t2s_vae_channels(const t2s_vae* h) { return h ? h->channels : 0; }
 
 extern "C" void t2s_vae_destroy(t2s_vae* h) {
     if (!h) return;
@@ -845,7 +1015,7 @@ extern "C" int t2s_vae_update_weights(t2s_vae* h, const t2s_vae_weights* w, void
                 "t2s_vae_update_weights: the handle was created with %s%s weights", h->has_encoder ? "encoder " : "", h->has_decoder ? "decoder" : "");
     VaeDev d = h->dev;                       // the slots keep pointing at the handle's copies: only the contents change
     std::vector<VaeItem> items;
-    const int rc = vae_items(w, d, h->has_decoder, h->has_encoder, items);
+    const int rc = vae_items(w, d, h->has_decoder, h->has_encoder, items, h->channels ? h->channels : 1);
     if (rc != T2S_OK) return rc;
     for (auto& it : items) {
         T2S_REQUIRE(it.src, "t2s_vae_update_weights: NULL weight pointer");
@@ -859,6 +1029,7 @@ extern "C" int t2s_vae_update_weights(t2s_vae* h, const t2s_vae_weights* w, void
 extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* after, int B, int L,
                               void* stream) {
     T2S_REQUIRE(h && z && recon, "t2s_vae_decode: NULL argument");
+    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc");
     T2S_REQUIRE(h->has_decoder, "t2s_vae_decode: handle was created without decoder weights");
     T2S_REQUIRE(B > 0, "t2s_vae_decode: B=%d", B);
     T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_decode: L=%d unsupported (a multiple of 4)", L);
@@ -871,6 +1042,7 @@ extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* a
 extern "C" int t2s_vae_decode_w(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w,
                                 void* stream) {
     T2S_REQUIRE(h && z && recon, "t2s_vae_decode_w: NULL argument");
+    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode_w: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc");
     T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_w: handle was created without decoder weights");
     T2S_REQUIRE(B > 0, "t2s_vae_decode_w: B=%d", B);
     T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_decode_w: L=%d unsupported (a multiple of 4)", L);
@@ -884,6 +1056,7 @@ extern "C" int t2s_vae_decode_w(t2s_vae* h, const float* z, float* recon, float*
 extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* before, int B, int L,
                               void* stream) {
     T2S_REQUIRE(h && x && z, "t2s_vae_encode: NULL argument");
+    T2S_REQUIRE(h->channels == 0, "t2s_vae_encode: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_encode_mc");
     T2S_REQUIRE(h->has_encoder, "t2s_vae_encode: handle was created without encoder weights");
     T2S_REQUIRE(B > 0, "t2s_vae_encode: B=%d", B);
     T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_encode: L=%d unsupported (a multiple of 4)", L);
@@ -894,6 +1067,44 @@ extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* befor
     T2S_LAUNCH_CHECK();
     if (tiles > 1) vae_interp_z_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, h->dev.emb, L / 4);
     T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+// the checks the two multichannel entries share, `who` = the entry's name
+static int vae_mc_check(const char* who, const t2s_vae* h, int B, int L, int latent_w) {
+    T2S_REQUIRE(h->channels != 0, "%s: the handle is a single-channel one (t2s_vae_create); its entries are t2s_vae_encode / t2s_vae_decode[_w]", who);
+    T2S_REQUIRE(B > 0, "%s: B=%d", who, B);
+    T2S_REQUIRE(L >= 8 && L <= (1 << 20), "%s: L=%d unsupported (8 .. 2^20)", who, L);
+    T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_MC_WMAX, "%s: latent width %d unsupported (1..%d)", who, latent_w, VAE_MC_WMAX);
+    return T2S_OK;
+}
+
+extern "C" int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream) {
+    T2S_REQUIRE(h && z && recon, "t2s_vae_decode_mc: NULL argument");
+    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_mc: handle was created without decoder weights");
+    int rc;
+    if ((rc = vae_mc_check("t2s_vae_decode_mc", h, B, L, latent_w))) return rc;
+    vae_decode_mc_kernel<<<dim3(B, vae_tiles(L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
+        h->dev, z, recon, after, L, latent_w, h->channels);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+extern "C" int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream) {
+    T2S_REQUIRE(h && x && z, "t2s_vae_encode_mc: NULL argument");
+    T2S_REQUIRE(h->has_encoder, "t2s_vae_encode_mc: handle was created without encoder weights");
+    int rc;
+    if ((rc = vae_mc_check("t2s_vae_encode_mc", h, B, L, latent_w))) return rc;
+    const int tiles = vae_tiles(L / 4, h->dev.n_res + 1);
+    T2S_REQUIRE(tiles == 1 || before, "t2s_vae_encode_mc: L=%d (L/4 > 32) runs in time tiles and needs the `before` output buffer "
+                                      "(the interpolation to the latent reads the whole row)", L);
+    vae_encode_mc_kernel<<<dim3(B, tiles), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(h->dev, x, z, before, L, latent_w,
+                                                                                                 h->channels);
+    T2S_LAUNCH_CHECK();
+    if (tiles > 1) {
+        vae_interp_rows_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, h->dev.emb, L / 4, latent_w);
+        T2S_LAUNCH_CHECK();
+    }
     return T2S_OK;
 }
 
@@ -976,6 +1187,7 @@ int vae_stack_wgrad(t2s_vae* h, const VaeStackBufs& s, float* const* g_c3, float
 extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g,
                                        int B, int L, void* stream) {
     T2S_REQUIRE(h && x && dz && g, "t2s_vae_encode_backward: NULL argument");
+    T2S_REQUIRE(h->channels == 0, "t2s_vae_encode_backward: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_encode_mc (which has no backward yet)");
     T2S_REQUIRE(h->has_encoder, "t2s_vae_encode_backward: handle was created without encoder weights");
     const VaeDev& d = h->dev;
     int rc;
@@ -1015,6 +1227,7 @@ extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* 
 extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter,
                                        const t2s_vae_dec_grads* g, float* dz, int B, int L, int latent_w, void* stream) {
     T2S_REQUIRE(h && z && drecon && g, "t2s_vae_decode_backward: NULL argument");
+    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode_backward: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc (which has no backward yet)");
     T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_backward: handle was created without decoder weights");
     const VaeDev& d = h->dev;
     int rc;

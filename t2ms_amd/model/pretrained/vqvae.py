@@ -53,11 +53,15 @@ class ResidualStack(nn.Module):
 
 
 class _VaeHandle:
-    def __init__(self, w: L.VaeWeights, device):
+    def __init__(self, w: L.VaeWeights, device, channels=None):
+        """channels: None = the single-channel codec (t2s_vae_create); C = the multichannel one of myvqvae.py (t2s_vae_create_mc)."""
         self.ptr = C.c_void_p()
         torch.cuda.synchronize(device)
         with torch.cuda.device(device):
-            L.check(L.lib().t2s_vae_create(C.byref(w), C.byref(self.ptr)), "t2s_vae_create")
+            if channels is None:
+                L.check(L.lib().t2s_vae_create(C.byref(w), C.byref(self.ptr)), "t2s_vae_create")
+            else:
+                L.check(L.lib().t2s_vae_create_mc(C.byref(w), int(channels), C.byref(self.ptr)), "t2s_vae_create_mc")
         # what the C handle's backward row blocks hold (a mirror handle serves one direction, an encoder's or a decoder's):
         # vae_grow_rows (t2s_vae.hip) grows them when rows > held rows or B > held series; _vae_backward repeats that condition
         self.bwd_rows = self.bwd_series = 0
@@ -122,6 +126,10 @@ class _Codec(nn.Module):
     def _tensors(self):
         return [p for p in self.parameters()]
 
+    def _mc_channels(self):
+        """None: the single-channel codec of this module; the myvqvae.py mirrors return their channel count."""
+        return None
+
     def _handle(self, device):
         device = torch.device(device)
         ts = self._tensors()
@@ -137,7 +145,7 @@ class _Codec(nn.Module):
                 if h is not None:
                     h.close()
                 w, keep = self._weights_struct()
-                h = _VaeHandle(w, device)
+                h = _VaeHandle(w, device, self._mc_channels())
                 del keep  # the library made its own copies
             self.__dict__["_t2s_h"], self.__dict__["_t2s_stamp"], self.__dict__["_t2s_shape"] = h, stamp, shape
         elif stamp is None or self.__dict__.get("_t2s_stamp") != stamp:

@@ -309,6 +309,8 @@ class Sampler:
         if self.device.type != "cuda":
             raise L.T2SError("Sampler needs a GPU device; the HIP path has no CPU fallback")
         self.model, self.decoder = model, decoder
+        # a multichannel decoder (model/pretrained/myvqvae.py Decoder: C-channel motion series) decodes to (B,C,L), any L >= 8
+        self.channels = decoder._mc_channels() if getattr(decoder, "_t2s_multichannel", False) else None
         self.math = math or model.__dict__.get("_t2s_math") or default_math()
         if hasattr(model, "set_math"):
             model.set_math(self.math)
@@ -410,7 +412,8 @@ class Sampler:
 
     def run(self, text: torch.Tensor, x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
             decode: bool = True, trace: bool = False):
-        """Returns (latent (B,64,30), series (B,L) or None, trace (steps,L) or None).
+        """Returns (latent (B,64,30), series (B,L) or None, trace (steps,L) or None); with a multichannel decoder the series
+        is (B,C,L) and the trace (steps,C,L).
         ``noise`` (steps,B,64,30) injects the per-step draws (parity mode)."""
         with L.device_lock(self.device):
             dev = self.device
@@ -421,7 +424,7 @@ class Sampler:
             if self.__dict__.get("_x") is None:
                 self._x = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
                 self._text = torch.empty(self.batch, L.D_MODEL, device=dev, dtype=torch.float32)
-                self._series = torch.empty(self.batch, self.length, device=dev, dtype=torch.float32)
+                self._series = torch.empty(self.batch, *self._row_shape(), device=dev, dtype=torch.float32)
             self._text.copy_(text)
             if x_T is None:
                 self.draw_xT(self._x)
@@ -435,7 +438,7 @@ class Sampler:
                     raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,30)")
             if (decode or trace) and self.decoder is None:
                 raise L.T2SError("Sampler.run: decode requested but no decoder was given")
-            tr = torch.empty(self.steps, self.length, device=dev, dtype=torch.float32) if trace else None
+            tr = torch.empty(self.steps, *self._row_shape(), device=dev, dtype=torch.float32) if trace else None
             with torch.cuda.device(dev):
                 # weights may have changed since the last run: refresh the packed copy on the caller's stream
                 self.model.t2s_handle(dev, 2 * self.batch)
@@ -449,6 +452,10 @@ class Sampler:
                 cur.wait_stream(self.stream)
             self._last = (noise, tr)  # keep caller-provided buffers alive until the stream has consumed them
             return self._x.clone(), (self._series.clone() if decode else None), tr
+
+    def _row_shape(self):
+        """One decoded series: (L,), or (C,L) with a multichannel decoder."""
+        return (self.length,) if self.channels is None else (self.channels, self.length)
 
     @property
     def graph_lanes(self) -> int:

@@ -99,6 +99,37 @@ def make_vae_state_dict(seed: int = 2025, hidden: int = 128, n_res: int = 2, res
     return {k: torch.from_numpy(v) for k, v in sd.items()}
 
 
+def make_mvae_state_dict(seed: int = 2025, channels: int = 7, hidden: int = 128, n_res: int = 3, res_hidden: int = 256,
+                         emb: int = 64) -> Dict[str, torch.Tensor]:
+    """encoder.* and decoder.* of the reference's model/pretrained/myvqvae.py (the multichannel codec of the motion models):
+    the keys of make_vae_state_dict with `channels` in encoder._conv_1 (hidden/2,channels,4), decoder._conv_trans_2
+    (hidden/2,channels,4) and its bias (channels); drawn the same way, U(+-1/sqrt(fan_in)).  Defaults: the deadlift model."""
+    rs = np.random.RandomState(seed + 3)
+    sd: Dict[str, np.ndarray] = {}
+
+    def conv(name, out_c, in_c, k, bias=True, transposed=False):
+        a = 1.0 / math.sqrt(in_c * k)
+        shape = (in_c, out_c, k) if transposed else (out_c, in_c, k)
+        sd[name + ".weight"] = rs.uniform(-a, a, size=shape).astype(np.float32)
+        if bias:
+            sd[name + ".bias"] = rs.uniform(-a, a, size=(out_c,)).astype(np.float32)
+
+    conv("encoder._conv_1", hidden // 2, channels, 4)
+    conv("encoder._conv_2", hidden, hidden // 2, 4)
+    conv("encoder._conv_3", hidden, hidden, 3)
+    for i in range(n_res):
+        conv(f"encoder._residual_stack._layers.{i}._block.1", res_hidden, hidden, 3, bias=False)
+        conv(f"encoder._residual_stack._layers.{i}._block.3", hidden, res_hidden, 1, bias=False)
+    conv("encoder._pre_vq_conv", emb, hidden, 1)
+    conv("decoder._conv_1", hidden, emb, 3)
+    for i in range(n_res):
+        conv(f"decoder._residual_stack._layers.{i}._block.1", res_hidden, hidden, 3, bias=False)
+        conv(f"decoder._residual_stack._layers.{i}._block.3", hidden, res_hidden, 1, bias=False)
+    conv("decoder._conv_trans_1", hidden // 2, hidden, 4, transposed=True)
+    conv("decoder._conv_trans_2", channels, hidden // 2, 4, transposed=True)
+    return {k: torch.from_numpy(v) for k, v in sd.items()}
+
+
 def make_mlp_state_dict(seed: int = 2025) -> Dict[str, torch.Tensor]:
     """model/denoiser/mlp.py:49-94 (8 layers; includes the constructed-but-unused
     norm1/norm3/pos_emb/self_attn/self_attn2 so load_state_dict(strict) passes)."""
@@ -153,6 +184,18 @@ def make_series(seed: int, batch: int, length: int) -> torch.Tensor:
     """MinMax-scaled series stand-in: U[0,1], (batch, length) (dataset.py:81-82)."""
     rs = np.random.RandomState((seed + 11) % (2 ** 32))
     return torch.from_numpy(rs.uniform(0, 1, size=(batch, length)).astype(np.float32))
+
+
+def make_mseries(seed: int, batch: int, channels: int, length: int) -> torch.Tensor:
+    """MinMax-scaled multichannel (motion) series stand-in: U[0,1], (batch, channels, length)."""
+    rs = np.random.RandomState((seed + 13) % (2 ** 32))
+    return torch.from_numpy(rs.uniform(0, 1, size=(batch, channels, length)).astype(np.float32))
+
+
+def make_wide_latents(seed: int, batch: int, width: int, emb: int = 64) -> torch.Tensor:
+    """N(0,1) latents of another width, (batch, emb, width): what a decoder of flow_dim = width reads."""
+    rs = np.random.RandomState((seed + 17) % (2 ** 32))
+    return torch.from_numpy(rs.randn(batch, emb, width).astype(np.float32))
 
 
 def make_ts2vec_state_dict(seed: int = 2025, input_dims: int = 1, output_dims: int = 100, hidden: int = 64,
