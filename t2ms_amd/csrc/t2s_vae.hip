@@ -8,6 +8,9 @@
 // the reference's SUSHI set is 2048 long) are cut into tiles of 32 - 2 H core positions with a halo of H = the
 // convolutions' receptive radius on either side, recomputed per tile: every kept value sums the same terms in the
 // same order as the untiled computation, so the tiling is invisible in the results.
+// One kernel per direction (vae_encode_kernel, vae_decode_kernel) serves the single-channel codec (vqvae.py) and the C-channel
+// motion codec (myvqvae.py); vae_interp_rows_kernel finishes a tiled encode; the two backward kernels recompute the forward
+// through the forward's own __device__ pieces (encode_stem, stage_latent, interp_linear_ac, the convolutions).
 #include "t2s_wgrad.h"
 
 namespace t2s {
@@ -112,10 +115,16 @@ __device__ void convT1d_k4s2_lds(const float* in, int Cin, int Tin, float* out, 
 }
 
 // F.interpolate(mode='linear', align_corners=True) along the last axis maps Tin positions to Tout: output position t reads
-// l0 * in[i0] + l1 * in[i1].  The ONE copy of that index arithmetic, shared by the forward and its transpose.
+// l0 * in[i0] + l1 * in[i1].  The ONE copy of that index arithmetic and of its rounding, shared by every forward site and the
+// transpose.  The rounding sequence is the one of torch's CPU kernel, every named value rounded once:
+//   real = scale * t;  l1 = real - (float)i0;  l0 = 1 - l1;  out = fma(l0, in[i0], round(l1 * in[i1]))
+// so an interpolated value is torch's bit for bit, whichever loop iteration, tile or kernel computes it.  What pins it is
+// `#pragma clang fp contract(off)` in the two bodies plus the one explicit fma: left to the compiler, `real - i0` fuses with the
+// product in front of it in some iterations of a loop and not in others, and __fmul_rn / __fsub_rn do not stop that here.
 struct InterpTap { int i0, i1; float l0, l1; };
 __device__ inline float interp_scale_ac(int Tin, int Tout) { return Tout > 1 ? (float)(Tin - 1) / (float)(Tout - 1) : 0.f; }
 __device__ inline InterpTap interp_tap_ac(float scale, int t, int Tin) {
+#pragma clang fp contract(off)
     InterpTap p;
     const float real = scale * (float)t;
     p.i0 = (int)real;
@@ -123,6 +132,12 @@ __device__ inline InterpTap interp_tap_ac(float scale, int t, int Tin) {
     p.l1 = real - (float)p.i0;
     p.l0 = 1.0f - p.l1;
     return p;
+}
+// the interpolated value from the two samples a0 = in[p.i0], a1 = in[p.i1]
+__device__ inline float interp_apply(const InterpTap& p, float a0, float a1) {
+#pragma clang fp contract(off)
+    const float hi = p.l1 * a1;
+    return __builtin_fmaf(p.l0, a0, hi);
 }
 
 // [C][Tin] -> [C][Tout] (`out` holds the global output positions [out_g0, out_g0 + Tw) of Tout)
@@ -133,7 +148,7 @@ __device__ void interp_linear_ac(const float* in, int C, int Tin, int ld_in, flo
     for (int o = threadIdx.x; o < C * Tw; o += VAE_THREADS) {
         const int c = o / Tw, t = o - c * Tw;
         const InterpTap p = interp_tap_ac(scale, out_g0 + t, Tin);
-        out[c * ld_out + t] = p.l0 * in[c * ld_in + p.i0] + p.l1 * in[c * ld_in + p.i1];
+        out[c * ld_out + t] = interp_apply(p, in[c * ld_in + p.i0], in[c * ld_in + p.i1]);
     }
 }
 
@@ -205,163 +220,79 @@ __device__ inline VaeTile vae_tile(int T, int halo, int ti) {
     return v;
 }
 
-// Decoder.forward (vqvae.py:97-105).  Receptive radius at the L/4 resolution: conv_1 1 + residual stack n_res + the two
-// transposed convolutions 1 (the second one reads half a position beyond the first's window) = n_res + 2.
-__global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w,
-                                                                 const float* __restrict__ z,
-                                                                 float* __restrict__ recon,
-                                                                 float* __restrict__ after, int L, int W) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* bufA = smem;                   // [<=256][LD]
-    float* bufB = smem + VAE_CMAX * LD;   // [<=256][LD]
-    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][2 Tw] for the first transposed conv
-    const int b = blockIdx.x;
-    const int T = L / 4;
-    const VaeTile tl = vae_tile(T, w.n_res + 2, blockIdx.y);
-    const int Tw = tl.w1 - tl.w0;
-    // latent (64,W) -> bufB (row stride LD covers W <= 32; W = 30 on the DiT path, L/4 on the MLP-denoiser path)
-    for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
-        const int c = o / W, t = o - c * W;
-        bufB[c * LD + t] = z[(size_t)b * w.emb * W + o];
-    }
-    __syncthreads();
-    interp_linear_ac(bufB, w.emb, W, LD, bufA, T, LD, tl.w0, Tw);
-    __syncthreads();
-    if (after) {
-        const int nc = tl.c1 - tl.c0;
-        for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
-            const int c = o / nc, t = tl.c0 + (o - c * nc);
-            after[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
-        }
-    }
-    conv1d_lds<3, 1, false, false>(bufA, w.emb, Tw, bufB, w.hidden, Tw, w.dec_conv1_w, w.dec_conv1_b, 1,
-                                   LD, LD);
-    __syncthreads();
-    residual_stack(bufB, bufA, w.hidden, w.res_hidden, w.n_res, Tw, w.dec_c3, w.dec_c1, LD);
-    const int ldw = 2 * Tw;      // `wide` holds L/2-resolution positions [2 w0, 2 w1)
-    convT1d_k4s2_lds<true>(bufB, w.hidden, Tw, wide, w.hidden / 2, w.dec_ct1_w, w.dec_ct1_b, LD, ldw);
-    __syncthreads();
-    // last transposed conv (hidden/2 -> 1) writes the core samples [4 c0, 4 c1) straight to global
-    {
-        const int Tin = 2 * Tw, Cin = w.hidden / 2, i_g0 = 2 * tl.w0;
-        for (int t = 4 * tl.c0 + threadIdx.x; t < 4 * tl.c1; t += VAE_THREADS) {
-            float acc = w.dec_ct2_b[0];
-            const int k0 = (t + 1) & 1;
-            for (int ci = 0; ci < Cin; ++ci) {
-#pragma unroll
-                for (int kk2 = 0; kk2 < 2; ++kk2) {
-                    const int kk = k0 + 2 * kk2;
-                    const int i = ((t + 1 - kk) >> 1) - i_g0;
-                    if (t + 1 - kk >= 0 && i >= 0 && i < Tin) acc += wide[ci * ldw + i] * w.dec_ct2_w[ci * 4 + kk];
-                }
-            }
-            recon[(size_t)b * L + t] = acc;
-        }
-    }
-}
-
-// Encoder.forward (vqvae.py:57-71).  Receptive radius at the L/4 resolution behind conv_2: conv_3 1 + residual stack n_res.
-// The final interpolation to 30 positions needs the WHOLE `before` row: fused here when the series is one tile, otherwise
-// vae_interp_z_kernel reads the rows the tiles wrote.
-__global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w,
-                                                                 const float* __restrict__ x,
-                                                                 float* __restrict__ z,
-                                                                 float* __restrict__ before, int L) {
-    extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* bufA = smem;
-    float* bufB = smem + VAE_CMAX * LD;
-    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][Tu]: conv_1 outputs at L/2-resolution positions [u0, u1)
-    const int b = blockIdx.x;
-    const int T2 = L / 2, T = L / 4;
-    const int half_c = w.hidden / 2;
-    const VaeTile tl = vae_tile(T, w.n_res + 1, blockIdx.y);
-    const int Tw = tl.w1 - tl.w0;
-    // conv_2 (k4 s2 p1) output t reads conv_1 outputs 2t-1 .. 2t+2
-    const int u0 = 2 * tl.w0 - 1 > 0 ? 2 * tl.w0 - 1 : 0;
-    const int u1 = 2 * (tl.w1 - 1) + 3 < T2 ? 2 * (tl.w1 - 1) + 3 : T2;
-    const int Tu = u1 - u0;
-    // conv_1: 1 -> hidden/2, k4 s2 p1, ReLU ; input straight from global
-    for (int o = threadIdx.x; o < half_c * Tu; o += VAE_THREADS) {
-        const int co = o / Tu, t = u0 + (o - co * Tu);
-        float acc = w.enc_conv1_b[co];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int ti = 2 * t + kk - 1;
-            if (ti >= 0 && ti < L) acc += w.enc_conv1_w[co * 4 + kk] * x[(size_t)b * L + ti];
-        }
-        wide[co * Tu + (t - u0)] = fmaxf(acc, 0.f);
-    }
-    __syncthreads();
-    conv1d_lds<4, 2, true, false>(wide, half_c, Tu, bufA, w.hidden, Tw, w.enc_conv2_w, w.enc_conv2_b, 1,
-                                  Tu, LD, u0, tl.w0);
-    __syncthreads();
-    conv1d_lds<3, 1, false, false>(bufA, w.hidden, Tw, bufB, w.hidden, Tw, w.enc_conv3_w, w.enc_conv3_b,
-                                   1, LD, LD);
-    __syncthreads();
-    residual_stack(bufB, bufA, w.hidden, w.res_hidden, w.n_res, Tw, w.enc_c3, w.enc_c1, LD);
-    conv1d_lds<1, 1, false, false>(bufB, w.hidden, Tw, bufA, w.emb, Tw, w.enc_prevq_w, w.enc_prevq_b, 0,
-                                   LD, LD);
-    __syncthreads();
-    if (before) {
-        const int nc = tl.c1 - tl.c0;
-        for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
-            const int c = o / nc, t = tl.c0 + (o - c * nc);
-            before[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
-        }
-    }
-    if (gridDim.y > 1) return;            // tiled: vae_interp_z_kernel finishes from `before`
-    interp_linear_ac(bufA, w.emb, T, LD, bufB, LATW, LD);
-    __syncthreads();
-    for (int o = threadIdx.x; o < w.emb * LATW; o += VAE_THREADS) {
-        const int c = o / LATW, t = o - c * LATW;
-        z[(size_t)b * w.emb * LATW + o] = bufB[c * LD + t];
-    }
-}
-
-// z = F.interpolate(before, 30, mode='linear', align_corners=True) (vqvae.py:70) from the (B,64,T) rows in global memory
-__global__ __launch_bounds__(VAE_THREADS) void vae_interp_z_kernel(const float* __restrict__ before, float* __restrict__ z,
-                                                                   int C, int T) {
-    const float scale = interp_scale_ac(T, LATW);
-    const float* in = before + (size_t)blockIdx.x * C * T;
-    for (int o = threadIdx.x; o < C * LATW; o += VAE_THREADS) {
-        const int c = o / LATW, t = o - c * LATW;
-        const InterpTap p = interp_tap_ac(scale, t, T);
-        z[(size_t)blockIdx.x * C * LATW + o] = p.l0 * in[(size_t)c * T + p.i0] + p.l1 * in[(size_t)c * T + p.i1];
-    }
-}
-
-// ------------------------------------------------------------------------------------------------ multichannel codec
-// The T2MS motion codec (reference model/pretrained/myvqvae.py:32-86): the same stack on C-channel series -- _conv_1 reads C
-// channels, _conv_trans_2 writes C -- with a latent `W` wide (flow_dim, <= 64) and ANY length L >= 8: the stride-2
-// convolutions give L/2 and L/4 positions (floor; the last taps of an odd length are real samples), the decoder builds
-// 4 T samples (T = L/4) and resamples them to L (myvqvae.py:85; the identity, skipped, when L % 4 == 0).  Same design as the
-// kernels above: one workgroup per (series, time tile), the stack resident in LDS, exact fp32, no atomics.
+// ------------------------------------------------------------------------------------------------ forward
+// One codec, C channels.  The single-channel LA-VAE (vqvae.py:36-105) is C = 1 with L % 4 == 0 and a latent W <= 32 wide
+// (30 on the DiT path, L/4 on the MLP-denoiser path); the T2MS motion codec (reference model/pretrained/myvqvae.py:32-86) is
+// the same kernels at C channels -- _conv_1 reads C channels, _conv_trans_2 writes C -- with a latent up to 64 wide
+// (flow_dim) and ANY length L >= 8: the stride-2 convolutions give L/2 and L/4 positions (floor; the last taps of an odd length
+// are real samples), the decoder builds 4 T samples (T = L/4) and resamples them to L (myvqvae.py:85; the identity, skipped,
+// when L % 4 == 0).  The channel count is a run-time argument: one instantiation, no atomics, exact fp32.
 constexpr int VAE_MC_CMAX = 16;          // series channels
 constexpr int VAE_MC_WMAX = 64;          // latent width
 constexpr int LDZ = VAE_MC_WMAX + 1;     // LDS row stride of a staged latent wider than VAE_TMAX: 64 x 65 floats fit in bufB
 constexpr int LDY = 4 * VAE_TMAX + 1;    // LDS row stride of a tile's samples in front of the final resampling
 static_assert(T2S_LAT_C * LDZ <= VAE_CMAX * LD && VAE_MC_CMAX * LDY <= VAE_CMAX * LD, "staging rows exceed an LDS buffer");
 
-// Decoder.forward (myvqvae.py:76-86).  The final resampling 4 T -> L: output position t reads samples i0(t) and i0(t) + 1; a tile
-// owns the outputs whose i0 falls in its core [4 c0, 4 c1), and the one sample beyond, 4 c1, lies inside its halo window (it
-// reads the same first-transposed-convolution outputs as the core sample 4 c1 - 1).  i0 is monotone in t, so every output
-// has exactly one owner.
-__global__ __launch_bounds__(VAE_THREADS) void vae_decode_mc_kernel(const VaeDev w, const float* __restrict__ z,
-                                                                    float* __restrict__ recon, float* __restrict__ after,
-                                                                    int L, int W, int C) {
+// Encoder conv_1 (C -> hidden/2, k4 s2 p1, ReLU) of one series x (C, L), straight from global: the outputs at the
+// L/2-resolution positions [u0, u1) -> wide [hidden/2][u1 - u0].  Output t reads x[2t-1 .. 2t+2] clipped to [0, L).
+__device__ void encode_stem(const VaeDev& w, const float* __restrict__ x, int C, int L, int u0, int u1, float* wide) {
+    const int Tu = u1 - u0;
+    for (int o = threadIdx.x; o < (w.hidden / 2) * Tu; o += VAE_THREADS) {
+        const int co = o / Tu, t = u0 + (o - co * Tu);
+        float acc = w.enc_conv1_b[co];
+        for (int ci = 0; ci < C; ++ci) {
+#pragma unroll
+            for (int kk = 0; kk < 4; ++kk) {
+                const int ti = 2 * t + kk - 1;
+                if (ti >= 0 && ti < L) acc += w.enc_conv1_w[(co * C + ci) * 4 + kk] * x[(size_t)ci * L + ti];
+            }
+        }
+        wide[co * Tu + (t - u0)] = fmaxf(acc, 0.f);
+    }
+}
+
+// the latent z (emb, W) of one series -> buf[emb][ld]
+__device__ void stage_latent(const float* __restrict__ z, int E, int W, float* buf, int ld) {
+    for (int o = threadIdx.x; o < E * W; o += VAE_THREADS) {
+        const int c = o / W, t = o - c * W;
+        buf[c * ld + t] = z[o];
+    }
+}
+
+// One sample of the decoder's last transposed convolution (hidden/2 -> C, k4 s2 p1): channel co at position t, from `wide`
+// = the first transposed convolution's outputs at the L/2-resolution positions [i_g0, i_g0 + Tin), row stride ldw.
+__device__ inline float decode_last_sample(const VaeDev& w, const float* wide, int ldw, int Tin, int i_g0, int C, int co, int t) {
+    float acc = w.dec_ct2_b[co];
+    const int k0 = (t + 1) & 1;      // t+1-kk even  ->  kk has the parity of t+1
+    for (int ci = 0; ci < w.hidden / 2; ++ci) {
+#pragma unroll
+        for (int kk2 = 0; kk2 < 2; ++kk2) {
+            const int kk = k0 + 2 * kk2;
+            const int i = ((t + 1 - kk) >> 1) - i_g0;
+            if (t + 1 - kk >= 0 && i >= 0 && i < Tin) acc += wide[ci * ldw + i] * w.dec_ct2_w[((size_t)ci * C + co) * 4 + kk];
+        }
+    }
+    return acc;
+}
+
+// Decoder.forward (vqvae.py:97-105, myvqvae.py:76-86).  Receptive radius at the L/4 resolution: conv_1 1 + residual stack n_res
+// + the two transposed convolutions 1 (the second one reads half a position beyond the first's window) = n_res + 2.
+// The final resampling 4 T -> L: output position t reads samples i0(t) and i0(t) + 1; a tile owns the outputs whose i0 falls in
+// its core [4 c0, 4 c1), and the one sample beyond, 4 c1, lies inside its halo window (it reads the same
+// first-transposed-convolution outputs as the core sample 4 c1 - 1).  i0 is monotone in t, so every output has exactly one owner.
+__global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w, const float* __restrict__ z,
+                                                                 float* __restrict__ recon, float* __restrict__ after,
+                                                                 int L, int W, int C) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
-    float* bufA = smem;
-    float* bufB = smem + VAE_CMAX * LD;
-    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][2 Tw]
+    float* bufA = smem;                   // [<=256][LD]
+    float* bufB = smem + VAE_CMAX * LD;   // [<=256][LD]
+    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][2 Tw] for the first transposed conv
     const int b = blockIdx.x;
     const int T = L / 4, L4 = 4 * T;
     const VaeTile tl = vae_tile(T, w.n_res + 2, blockIdx.y);
     const int Tw = tl.w1 - tl.w0;
     const int ldz = W <= VAE_TMAX ? LD : LDZ;
-    for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
-        const int c = o / W, t = o - c * W;
-        bufB[c * ldz + t] = z[(size_t)b * w.emb * W + o];
-    }
+    stage_latent(z + (size_t)b * w.emb * W, w.emb, W, bufB, ldz);
     __syncthreads();
     interp_linear_ac(bufB, w.emb, W, ldz, bufA, T, LD, tl.w0, Tw);
     __syncthreads();
@@ -375,30 +306,18 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_mc_kernel(const VaeDev
     conv1d_lds<3, 1, false, false>(bufA, w.emb, Tw, bufB, w.hidden, Tw, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
     __syncthreads();
     residual_stack(bufB, bufA, w.hidden, w.res_hidden, w.n_res, Tw, w.dec_c3, w.dec_c1, LD);
-    const int ldw = 2 * Tw;
+    const int ldw = 2 * Tw;      // `wide` holds L/2-resolution positions [2 w0, 2 w1)
     convT1d_k4s2_lds<true>(bufB, w.hidden, Tw, wide, w.hidden / 2, w.dec_ct1_w, w.dec_ct1_b, LD, ldw);
     __syncthreads();
     // last transposed conv (hidden/2 -> C): the samples [y0, y1) go straight to global when L = 4 T, else to bufA [C][LDY]
     const bool resample = L != L4;
     const int y0 = 4 * tl.c0, yc = 4 * tl.c1;
     const int y1 = resample && yc < L4 ? yc + 1 : yc, Ty = y1 - y0;
-    {
-        const int Tin = 2 * Tw, Cin = w.hidden / 2, i_g0 = 2 * tl.w0;
-        for (int o = threadIdx.x; o < C * Ty; o += VAE_THREADS) {
-            const int co = o / Ty, t = y0 + (o - co * Ty);
-            float acc = w.dec_ct2_b[co];
-            const int k0 = (t + 1) & 1;
-            for (int ci = 0; ci < Cin; ++ci) {
-#pragma unroll
-                for (int kk2 = 0; kk2 < 2; ++kk2) {
-                    const int kk = k0 + 2 * kk2;
-                    const int i = ((t + 1 - kk) >> 1) - i_g0;
-                    if (t + 1 - kk >= 0 && i >= 0 && i < Tin) acc += wide[ci * ldw + i] * w.dec_ct2_w[((size_t)ci * C + co) * 4 + kk];
-                }
-            }
-            if (resample) bufA[co * LDY + (t - y0)] = acc;
-            else recon[((size_t)b * C + co) * L + t] = acc;
-        }
+    for (int o = threadIdx.x; o < C * Ty; o += VAE_THREADS) {
+        const int co = o / Ty, t = y0 + (o - co * Ty);
+        const float acc = decode_last_sample(w, wide, ldw, 2 * Tw, 2 * tl.w0, C, co, t);
+        if (resample) bufA[co * LDY + (t - y0)] = acc;
+        else recon[((size_t)b * C + co) * L + t] = acc;
     }
     if (!resample) return;
     __syncthreads();
@@ -413,39 +332,30 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_mc_kernel(const VaeDev
         const int co = o / nt, t = ta + (o - co * nt);
         const InterpTap p = interp_tap_ac(scale, t, L4);
         if (p.i0 < y0 || p.i0 >= yc) continue;
-        recon[((size_t)b * C + co) * L + t] = p.l0 * bufA[co * LDY + (p.i0 - y0)] + p.l1 * bufA[co * LDY + (p.i1 - y0)];
+        recon[((size_t)b * C + co) * L + t] = interp_apply(p, bufA[co * LDY + (p.i0 - y0)], bufA[co * LDY + (p.i1 - y0)]);
     }
 }
 
-// Encoder.forward (myvqvae.py:49-61): vae_encode_kernel with C input channels, floor lengths and a latent W wide.
-__global__ __launch_bounds__(VAE_THREADS) void vae_encode_mc_kernel(const VaeDev w, const float* __restrict__ x,
-                                                                    float* __restrict__ z, float* __restrict__ before,
-                                                                    int L, int W, int C) {
+// Encoder.forward (vqvae.py:57-71, myvqvae.py:49-61).  Receptive radius at the L/4 resolution behind conv_2: conv_3 1 + residual
+// stack n_res.  The final interpolation to W positions needs the WHOLE `before` row: fused here when the series is one tile,
+// otherwise vae_interp_rows_kernel reads the rows the tiles wrote.
+__global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w, const float* __restrict__ x,
+                                                                 float* __restrict__ z, float* __restrict__ before,
+                                                                 int L, int W, int C) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bufA = smem;
     float* bufB = smem + VAE_CMAX * LD;
-    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][Tu]
+    float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][Tu]: conv_1 outputs at L/2-resolution positions [u0, u1)
     const int b = blockIdx.x;
     const int T2 = L / 2, T = L / 4;
     const int half_c = w.hidden / 2;
     const VaeTile tl = vae_tile(T, w.n_res + 1, blockIdx.y);
     const int Tw = tl.w1 - tl.w0;
+    // conv_2 (k4 s2 p1) output t reads conv_1 outputs 2t-1 .. 2t+2
     const int u0 = 2 * tl.w0 - 1 > 0 ? 2 * tl.w0 - 1 : 0;
     const int u1 = 2 * (tl.w1 - 1) + 3 < T2 ? 2 * (tl.w1 - 1) + 3 : T2;
     const int Tu = u1 - u0;
-    // conv_1: C -> hidden/2, k4 s2 p1, ReLU; output t reads x[2t-1 .. 2t+2] clipped to [0, L), straight from global
-    for (int o = threadIdx.x; o < half_c * Tu; o += VAE_THREADS) {
-        const int co = o / Tu, t = u0 + (o - co * Tu);
-        float acc = w.enc_conv1_b[co];
-        for (int ci = 0; ci < C; ++ci) {
-#pragma unroll
-            for (int kk = 0; kk < 4; ++kk) {
-                const int ti = 2 * t + kk - 1;
-                if (ti >= 0 && ti < L) acc += w.enc_conv1_w[(co * C + ci) * 4 + kk] * x[((size_t)b * C + ci) * L + ti];
-            }
-        }
-        wide[co * Tu + (t - u0)] = fmaxf(acc, 0.f);
-    }
+    encode_stem(w, x + (size_t)b * C * L, C, L, u0, u1, wide);
     __syncthreads();
     conv1d_lds<4, 2, true, false>(wide, half_c, Tu, bufA, w.hidden, Tw, w.enc_conv2_w, w.enc_conv2_b, 1, Tu, LD, u0, tl.w0);
     __syncthreads();
@@ -466,7 +376,7 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_encode_mc_kernel(const VaeDev
     for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
         const int c = o / W, t = o - c * W;
         const InterpTap p = interp_tap_ac(scale, t, T);
-        z[(size_t)b * w.emb * W + o] = p.l0 * bufA[c * LD + p.i0] + p.l1 * bufA[c * LD + p.i1];
+        z[(size_t)b * w.emb * W + o] = interp_apply(p, bufA[c * LD + p.i0], bufA[c * LD + p.i1]);
     }
 }
 
@@ -478,15 +388,15 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_kernel(const floa
     for (int o = threadIdx.x; o < C * Tout; o += VAE_THREADS) {
         const int c = o / Tout, t = o - c * Tout;
         const InterpTap p = interp_tap_ac(scale, t, Tin);
-        out[(size_t)blockIdx.x * C * Tout + o] = p.l0 * src[(size_t)c * Tin + p.i0] + p.l1 * src[(size_t)c * Tin + p.i1];
+        out[(size_t)blockIdx.x * C * Tout + o] = interp_apply(p, src[(size_t)c * Tin + p.i0], src[(size_t)c * Tin + p.i1]);
     }
 }
 
 // ------------------------------------------------------------------------------------------------ encoder backward
 // Backward of Encoder.forward for the one configuration that trains the encoder (train.py:31-33 with `usepretrainedvae`
 // false).  Two stages:
-//   vae_encode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS exactly as
-//                           vae_encode_kernel computes it, every layer's INPUT leaves as an im2col'd row block X (rows = b * T
+//   vae_encode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS by the
+//                           functions vae_encode_kernel calls, every layer's INPUT leaves as an im2col'd row block X (rows = b * T
 //                           + t) and its ReLU pattern stays as one bit word per channel; then the data gradients walk back
 //                           through the layers in LDS (transposed convolutions, fixed summation order) and every layer's
 //                           OUTPUT gradient leaves as a row block dY.  conv_1 (1 -> hidden/2, 4 taps: 320 values) is reduced
@@ -620,17 +530,8 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_encode_bwd_kernel(const VaeDe
     const int b = blockIdx.x;
     const int T2 = L / 2, T = L / 4, H = w.hidden, R = w.res_hidden, half_c = H / 2;
     const size_t row0 = (size_t)b * T;
-    // ---------------- forward, recomputed as vae_encode_kernel computes it (one tile)
-    for (int o = threadIdx.x; o < half_c * T2; o += VAE_THREADS) {
-        const int co = o / T2, t = o - co * T2;
-        float acc = w.enc_conv1_b[co];
-#pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int ti = 2 * t + kk - 1;
-            if (ti >= 0 && ti < L) acc += w.enc_conv1_w[co * 4 + kk] * x[(size_t)b * L + ti];
-        }
-        wide[co * T2 + t] = fmaxf(acc, 0.f);
-    }
+    // ---------------- forward, recomputed with vae_encode_kernel's pieces (one tile: the window is the series; C = 1)
+    encode_stem(w, x + (size_t)b * L, 1, L, 0, T2, wide);
     __syncthreads();
     relu_mask(wide, half_c, T2, T2, m_w1, 2);
     im2col_rows<4, 2>(wide, half_c, T2, T2, s.Xc2, row0, T, 1);
@@ -701,8 +602,8 @@ __global__ __launch_bounds__(256) void vae_part_reduce_kernel(const float* __res
 // ------------------------------------------------------------------------------------------------ decoder backward
 // Backward of Decoder.forward (vqvae.py:97-105), what LA-VAE pre-training (pretrained_lavae_unified.py) adds to the encoder
 // backward above; the same two stages:
-//   vae_decode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS exactly as
-//                           vae_decode_kernel computes it up to the ReLU behind _conv_trans_1 (the samples themselves are not
+//   vae_decode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS by the
+//                           functions vae_decode_kernel calls up to the ReLU behind _conv_trans_1 (the samples themselves are not
 //                           needed), layer inputs leave as row blocks and ReLU patterns stay as bit words; then the data
 //                           gradients walk back from drecon to the latent.  _conv_trans_2 (hidden/2 x 4 = 256 values) and the
 //                           two small biases are reduced per series into partial rows.
@@ -761,11 +662,8 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDe
     const int b = blockIdx.x;
     const int T2 = L / 2, T = L / 4, H = w.hidden, R = w.res_hidden, half_c = H / 2, E = w.emb;
     const size_t row0 = (size_t)b * T;
-    // ---------------- forward, recomputed as vae_decode_kernel computes it (one tile)
-    for (int o = threadIdx.x; o < E * W; o += VAE_THREADS) {
-        const int c = o / W, t = o - c * W;
-        bufB[c * LD + t] = z[(size_t)b * E * W + o];
-    }
+    // ---------------- forward, recomputed with vae_decode_kernel's pieces (one tile)
+    stage_latent(z + (size_t)b * E * W, E, W, bufB, LD);
     for (int t = threadIdx.x; t < L; t += VAE_THREADS) dr[t] = drecon[(size_t)b * L + t];
     __syncthreads();
     interp_linear_ac(bufB, E, W, LD, bufA, T, LD);
@@ -978,10 +876,6 @@ static int vae_create(const t2s_vae_weights* w, int channels, t2s_vae** out, con
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_BWD_MASK_BYTES));
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_bwd_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_DBWD_MASK_BYTES));
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_mc_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_mc_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         attr = true;
     }
     *out = h;
@@ -1026,86 +920,74 @@ extern "C" int t2s_vae_update_weights(t2s_vae* h, const t2s_vae_weights* w, void
     return T2S_OK;
 }
 
-extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* after, int B, int L,
-                              void* stream) {
-    T2S_REQUIRE(h && z && recon, "t2s_vae_decode: NULL argument");
-    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc");
-    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode: handle was created without decoder weights");
-    T2S_REQUIRE(B > 0, "t2s_vae_decode: B=%d", B);
-    T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_decode: L=%d unsupported (a multiple of 4)", L);
-    vae_decode_kernel<<<dim3(B, vae_tiles(L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
-        h->dev, z, recon, after, L, LATW);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-extern "C" int t2s_vae_decode_w(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w,
-                                void* stream) {
-    T2S_REQUIRE(h && z && recon, "t2s_vae_decode_w: NULL argument");
-    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode_w: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc");
-    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_w: handle was created without decoder weights");
-    T2S_REQUIRE(B > 0, "t2s_vae_decode_w: B=%d", B);
-    T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_decode_w: L=%d unsupported (a multiple of 4)", L);
-    T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_TMAX, "t2s_vae_decode_w: latent width %d unsupported (1..%d)", latent_w, VAE_TMAX);
-    vae_decode_kernel<<<dim3(B, vae_tiles(L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
-        h->dev, z, recon, after, L, latent_w);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* before, int B, int L,
-                              void* stream) {
-    T2S_REQUIRE(h && x && z, "t2s_vae_encode: NULL argument");
-    T2S_REQUIRE(h->channels == 0, "t2s_vae_encode: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_encode_mc");
-    T2S_REQUIRE(h->has_encoder, "t2s_vae_encode: handle was created without encoder weights");
-    T2S_REQUIRE(B > 0, "t2s_vae_encode: B=%d", B);
-    T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "t2s_vae_encode: L=%d unsupported (a multiple of 4)", L);
-    const int tiles = vae_tiles(L / 4, h->dev.n_res + 1);
-    T2S_REQUIRE(tiles == 1 || before, "t2s_vae_encode: L=%d > 128 runs in time tiles and needs the `before` output buffer "
-                                      "(the interpolation to the latent reads the whole row)", L);
-    vae_encode_kernel<<<dim3(B, tiles), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(h->dev, x, z, before, L);
-    T2S_LAUNCH_CHECK();
-    if (tiles > 1) vae_interp_z_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, h->dev.emb, L / 4);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
-}
-
-// the checks the two multichannel entries share, `who` = the entry's name
-static int vae_mc_check(const char* who, const t2s_vae* h, int B, int L, int latent_w) {
-    T2S_REQUIRE(h->channels != 0, "%s: the handle is a single-channel one (t2s_vae_create); its entries are t2s_vae_encode / t2s_vae_decode[_w]", who);
+// ------------------------------------------------------------------------ what the forward entries share on the host
+namespace {
+// The handle's kind and the shape, `who` = the entry's name, `mc` = its family: the multichannel entries take a t2s_vae_create_mc
+// handle, any L >= 8 and a latent up to 64 wide; the single-channel ones a t2s_vae_create handle, L a multiple of 4 and a latent
+// up to 32 wide.
+int vae_fwd_check(const char* who, const t2s_vae* h, bool mc, int B, int L, int W) {
+    if (mc)
+        T2S_REQUIRE(h->channels != 0, "%s: the handle is a single-channel one (t2s_vae_create); its entries are t2s_vae_encode / t2s_vae_decode[_w]", who);
+    else
+        T2S_REQUIRE(h->channels == 0, "%s: the handle is a multichannel one (t2s_vae_create_mc); its entries are t2s_vae_encode_mc / t2s_vae_decode_mc", who);
     T2S_REQUIRE(B > 0, "%s: B=%d", who, B);
-    T2S_REQUIRE(L >= 8 && L <= (1 << 20), "%s: L=%d unsupported (8 .. 2^20)", who, L);
-    T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_MC_WMAX, "%s: latent width %d unsupported (1..%d)", who, latent_w, VAE_MC_WMAX);
+    if (mc)
+        T2S_REQUIRE(L >= 8 && L <= (1 << 20), "%s: L=%d unsupported (8 .. 2^20)", who, L);
+    else
+        T2S_REQUIRE(L >= 4 && L % 4 == 0 && L <= (1 << 20), "%s: L=%d unsupported (a multiple of 4)", who, L);
+    const int wmax = mc ? VAE_MC_WMAX : VAE_TMAX;
+    T2S_REQUIRE(W >= 1 && W <= wmax, "%s: latent width %d unsupported (1..%d)", who, W, wmax);
     return T2S_OK;
 }
 
-extern "C" int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream) {
-    T2S_REQUIRE(h && z && recon, "t2s_vae_decode_mc: NULL argument");
-    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_mc: handle was created without decoder weights");
+int vae_decode(const char* who, bool mc, t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int W, void* stream) {
+    T2S_REQUIRE(h && z && recon, "%s: NULL argument", who);
+    T2S_REQUIRE(h->has_decoder, "%s: handle was created without decoder weights", who);
     int rc;
-    if ((rc = vae_mc_check("t2s_vae_decode_mc", h, B, L, latent_w))) return rc;
-    vae_decode_mc_kernel<<<dim3(B, vae_tiles(L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
-        h->dev, z, recon, after, L, latent_w, h->channels);
+    if ((rc = vae_fwd_check(who, h, mc, B, L, W))) return rc;
+    vae_decode_kernel<<<dim3(B, vae_tiles(L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
+        h->dev, z, recon, after, L, W, h->channels ? h->channels : 1);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
-extern "C" int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream) {
-    T2S_REQUIRE(h && x && z, "t2s_vae_encode_mc: NULL argument");
-    T2S_REQUIRE(h->has_encoder, "t2s_vae_encode_mc: handle was created without encoder weights");
+int vae_encode(const char* who, bool mc, t2s_vae* h, const float* x, float* z, float* before, int B, int L, int W, void* stream) {
+    T2S_REQUIRE(h && x && z, "%s: NULL argument", who);
+    T2S_REQUIRE(h->has_encoder, "%s: handle was created without encoder weights", who);
     int rc;
-    if ((rc = vae_mc_check("t2s_vae_encode_mc", h, B, L, latent_w))) return rc;
+    if ((rc = vae_fwd_check(who, h, mc, B, L, W))) return rc;
     const int tiles = vae_tiles(L / 4, h->dev.n_res + 1);
-    T2S_REQUIRE(tiles == 1 || before, "t2s_vae_encode_mc: L=%d (L/4 > 32) runs in time tiles and needs the `before` output buffer "
-                                      "(the interpolation to the latent reads the whole row)", L);
-    vae_encode_mc_kernel<<<dim3(B, tiles), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(h->dev, x, z, before, L, latent_w,
-                                                                                                 h->channels);
+    T2S_REQUIRE(tiles == 1 || before, "%s: L=%d (L/4 > 32) runs in time tiles and needs the `before` output buffer "
+                                      "(the interpolation to the latent reads the whole row)", who, L);
+    vae_encode_kernel<<<dim3(B, tiles), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(h->dev, x, z, before, L, W,
+                                                                                              h->channels ? h->channels : 1);
     T2S_LAUNCH_CHECK();
     if (tiles > 1) {
-        vae_interp_rows_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, h->dev.emb, L / 4, latent_w);
+        vae_interp_rows_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, h->dev.emb, L / 4, W);
         T2S_LAUNCH_CHECK();
     }
     return T2S_OK;
+}
+}
+
+extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, void* stream) {
+    return vae_decode("t2s_vae_decode", false, h, z, recon, after, B, L, LATW, stream);
+}
+
+extern "C" int t2s_vae_decode_w(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream) {
+    return vae_decode("t2s_vae_decode_w", false, h, z, recon, after, B, L, latent_w, stream);
+}
+
+extern "C" int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream) {
+    return vae_decode("t2s_vae_decode_mc", true, h, z, recon, after, B, L, latent_w, stream);
+}
+
+extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* before, int B, int L, void* stream) {
+    return vae_encode("t2s_vae_encode", false, h, x, z, before, B, L, LATW, stream);
+}
+
+extern "C" int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream) {
+    return vae_encode("t2s_vae_encode_mc", true, h, x, z, before, B, L, latent_w, stream);
 }
 
 // ------------------------------------------------------------------------ what the two backward entries share on the host

@@ -303,9 +303,8 @@ def test_width_and_channel_edges(gold, dev, cfg, W, Ln):
 @pytest.mark.gpu
 @pytest.mark.parametrize("Ln", [24, 96])
 def test_one_channel_agrees_with_the_single_channel_entries(gold, dev, Ln):
-    """C = 1, W = 30: the _mc entries against t2s_vae_encode / t2s_vae_decode on the same weights, within the bar.  Measured
-    on an MI355X: `before` is bit-equal; z, after (1.5e-8) and recon (1.0e-8) differ in the last bit -- the two kernels' interpolation
-    and last-layer loops are compiled separately and contract their multiply-adds differently."""
+    """C = 1, W = 30: the _mc entries against t2s_vae_encode / t2s_vae_decode on the same weights, bit for bit -- both families
+    of entries launch the same kernels (the single-channel codec is C = 1), and the interpolation tap's rounding is pinned."""
     from model.pretrained.vqvae import vqvae as vqvae1
     m = _gpu_model(gold, dev, "c1", 30)
     k = gold["plan"]["cfgs"]["c1"]
@@ -323,7 +322,57 @@ def test_one_channel_agrees_with_the_single_channel_entries(gold, dev, Ln):
     for n, a, b in (("z", z, z1), ("before", before, before1), ("after", after, after1), ("rec", rec[:, 0, :], rec1)):
         d = _maxdiff(a, b)
         print(f"C=1 L={Ln} {n}: mc vs single-channel max|d| = {d:.3e}")
-        assert d < TOL, (n, d)
+        assert torch.equal(a, b), (n, d)
+
+
+def _single_channel_model(dev):
+    if "single" not in _GPU_MODELS:
+        from model.pretrained.vqvae import vqvae as vqvae1
+        s = vqvae1(types.SimpleNamespace(block_hidden_size=128, num_residual_layers=2, res_hidden_size=256, embedding_dim=64))
+        s.load_state_dict(synth.make_vae_state_dict(2025), strict=True)
+        _GPU_MODELS["single"] = s.to(dev).eval()
+    return _GPU_MODELS["single"]
+
+
+def _interp_cpu(t, size):
+    return F.interpolate(t.cpu(), size=size, mode="linear", align_corners=True)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ch,W,Ln", [(1, 30, 24), (1, 30, 96), (1, 30, 136), (7, 64, 36), (7, 1, 24), (7, 50, 263)])
+def test_decode_after_is_torch_interpolation_bit_for_bit(gold, dev, ch, W, Ln):
+    """`after` of a decode is pure interpolation of the latent: torch.equal with F.interpolate(align_corners=True) on the CPU,
+    whose rounding sequence the tap restates (t2s_vae.hip, InterpTap).  Single-channel entries at W 30 -- L 136 is two decoder
+    tiles, the windowed form -- and the multichannel ones at C 7 with W in {64, 1, 50}; B = 2."""
+    if ch == 1:
+        m, z = _single_channel_model(dev), synth.make_latents(Ln, 2)
+    else:
+        m, z = _gpu_model(gold, dev, "c7", W), synth.make_wide_latents(Ln, 2, W)
+    assert tuple(z.shape) == (2, 64, W)
+    with torch.no_grad():
+        _, after = m.decoder(z.to(dev), Ln)
+    want = _interp_cpu(z, Ln // 4)
+    print(f"C={ch} W={W} L={Ln} after vs torch CPU: max|d| = {_maxdiff(after, want):.3e}")
+    assert torch.equal(after.cpu(), want)
+
+
+@pytest.mark.gpu
+@pytest.mark.parametrize("ch,W,Ln", [(1, 30, 24), (1, 30, 128), (1, 30, 136), (7, 64, 36), (7, 2, 37), (7, 50, 263)])
+def test_encode_z_is_torch_interpolation_of_before_bit_for_bit(gold, dev, ch, W, Ln):
+    """z of an encode is the interpolation of the `before` the same call wrote: torch.equal with F.interpolate on the CPU.
+    Single-channel: L 128 is the largest series the encode kernel finishes itself, 136 runs in tiles and vae_interp_rows_kernel
+    finishes it from the whole row -- so a tiled and a fused latent are the same function of `before`.  Multichannel C 7: one
+    tile with W 64 and W 2 (L 37: floor lengths) and three ragged tiles at L 263; B = 2."""
+    if ch == 1:
+        m, x = _single_channel_model(dev), synth.make_series(Ln, 2, Ln)
+    else:
+        m, x = _gpu_model(gold, dev, "c7", W), synth.make_mseries(Ln, 2, 7, Ln)
+    with torch.no_grad():
+        z, before = m.encoder(x.to(dev))
+    assert tuple(z.shape) == (2, 64, W) and tuple(before.shape) == (2, 64, Ln // 4)
+    want = _interp_cpu(before, W)
+    print(f"C={ch} W={W} L={Ln} z vs torch CPU interpolation of before: max|d| = {_maxdiff(z, want):.3e}")
+    assert torch.equal(z.cpu(), want)
 
 
 @pytest.mark.gpu
