@@ -7,6 +7,7 @@
 // (time-embedding row, DDPM coefficients, noise stream / injected-noise slice) is looked up on
 // the device through a step counter that the last node of the graph advances.
 #include <cmath>
+#include <cstddef>
 #include <cstring>
 #include <mutex>
 #include <stdlib.h>
@@ -89,193 +90,192 @@ __global__ void philox_uniform_kernel(float* __restrict__ out, uint64_t seed, ui
 }
 
 // ---------------------------------------------------------------- sampler update kernels
-struct StepArgs {
+// A lane's loop state on the device.  set_step_kernel writes it at the start of a run, every kernel of a step reads its loop
+// index from it (the DiT kernels through a const int* to `index`, which therefore stays the first member) and the last
+// workgroup of the update kernel advances it.  All of it is read on the device, so one captured graph serves every step,
+// every shard position and runs with or without per-row tables.
+struct LoopState {
+    int index;      // loop index j
+    int row0;       // global row of the lane's first series (Philox key)
+    int arrivals;   // arrival counter of the update kernel (advance_step_when_last)
+    int rows;       // ROWS_* bits: the per-row tables this run uses (t2s_sampler_set_rows)
+};
+static_assert(offsetof(LoopState, index) == 0 && sizeof(LoopState) == 16, "the DiT kernels read LoopState::index through an int*");
+constexpr int LANE_STATES = 4;   // LoopStates from one lane's to the next: 64 bytes apart
+constexpr int ROWS_SEED = 1, ROWS_KEY = 2, ROWS_CFG = 4;
+
+// What every update kernel takes: the sampling loop's (loop != NULL) and the stand-alone C entries' (loop == NULL) alike.
+struct UpdateArgs {
     float* x;             // (B,1920) in place
-    const float* eps_u;   // (B,1920)
-    const float* eps_c;   // (B,1920) or NULL
-    const float* noise;   // injected draws: (steps,noise_rows,1920) indexed by step (this shard's first row), or
-                          // (B,1920) if step_ptr NULL
-    const float* coef;    // DEVICE (T,3)
-    const int* step_ptr;  // device {loop index j, global row of the first series}, or NULL (then t_index / stream_id /
-                          // row0 are immediate)
-    int steps;            // T (t = steps-1-j when step_ptr != NULL)
-    int t_index;
+    float* hist;          // (B,1920) in place; LMS only
+    const float* pred_u;  // (B,1920)
+    const float* pred_c;  // (B,1920) or NULL
+    const float* noise;   // injected draws: (steps,noise_rows,1920) indexed by step (this shard's first row), or (B,1920)
+                          // if loop NULL; NULL: Philox
+    const float* coef;    // DEVICE (T,3) DDPM by timestep, (S,6) LMS by loop index
+    const LoopState* loop;   // the lane's loop state, or NULL: then index / stream_id / row0 below are immediate
+    int index;            // loop NULL: the coefficient row (DDPM: t_index; LMS: loop index)
+    int steps;            // DDPM in the loop: T (t = steps-1-j)
     float cfg;
+    float dt;             // RF
     uint64_t seed;
     uint32_t stream_id;
     uint32_t row0;
     int B;
     int noise_rows;       // rows per step of the injected-noise array (>= B: a lane steps a row range of the batch)
-    int* advance;         // sampling loop: device {loop index, row0, arrival counter}; the last workgroup increments the index
-    // per-row tables (t2s_sampler_set_rows), this lane's slice: used where bit ROWS_SEED / ROWS_KEY / ROWS_CFG of step_ptr[3]
-    // is set (read on the device, so a captured graph serves tables and uniform runs alike); NULL outside the sampler
+    LoopState* advance;   // sampling loop: the last workgroup increments the lane's loop index (advance_step_when_last)
+    // per-row tables (t2s_sampler_set_rows), this lane's slice: used where bit ROWS_SEED / ROWS_KEY / ROWS_CFG of loop->rows
+    // is set; NULL outside the sampler
     const uint64_t* row_seed;
     const uint32_t* row_key;
     const float* row_cfg;
 };
 
-constexpr int ROWS_SEED = 1, ROWS_KEY = 2, ROWS_CFG = 4;
-
-// Last workgroup to finish advances the device loop index (step[0]; step[2] is the arrival counter): every
-// workgroup has read step[0] before it arrives, so the increment cannot overtake a reader, and the stand-alone
-// one-thread set_step launch per step (4 us of a 690 us step at 32 series) is gone.
-__device__ __forceinline__ void advance_step_when_last(int* step) {
+// Last workgroup to finish advances the device loop index: every workgroup has read it before it arrives, so the
+// increment cannot overtake a reader, and the stand-alone one-thread set_step launch per step (4 us of a 690 us step at
+// 32 series) is gone.
+__device__ __forceinline__ void advance_step_when_last(LoopState* loop) {
     __syncthreads();
     if (threadIdx.x == 0) {
         __threadfence();
-        if (atomicAdd(&step[2], 1) == (int)gridDim.x - 1) {
-            step[2] = 0;
-            step[0] += 1;
+        if (atomicAdd(&loop->arrivals, 1) == (int)gridDim.x - 1) {
+            loop->arrivals = 0;
+            loop->index += 1;
         }
     }
 }
 
-// Grid-stride over the quads with at most STEP_MAX_WGS workgroups: the arrival counter is ONE address, and same-address
-// atomics serialise at ~25 ns each -- 480 of them (one per 256 quads at B = 256) made this 6 us kernel 18 us.
-constexpr int STEP_MAX_WGS = 96;
-__global__ __launch_bounds__(256) void ddpm_step_kernel(const StepArgs a) {
-    constexpr int QPR = LAT / 4;
-    int t = a.t_index;
-    uint32_t sid = a.stream_id, row0 = a.row0;
-    const float* noise = a.noise;
-    int rows = 0;
-    if (a.step_ptr) {
-        const int j = a.step_ptr[0];
-        row0 = (uint32_t)a.step_ptr[1];   // read on the device so a captured graph serves every shard position
-        rows = a.step_ptr[3];             // which per-row tables this run uses (t2s_sampler_set_rows)
-        t = a.steps - 1 - j;
-        sid = (uint32_t)j;
-        if (noise) noise += (size_t)j * a.noise_rows * LAT;
+// The prologue: where this launch stands.  In the loop everything comes from the lane's state: the draw of loop index j is
+// stream j, and the injected noise of step j is slice j.
+struct Step {
+    int index;            // loop index j (stand-alone: UpdateArgs::index)
+    uint32_t stream_id, row0;
+    int rows;             // ROWS_* bits
+    const float* noise;
+};
+__device__ __forceinline__ Step resolve_step(const UpdateArgs& a) {
+    Step s{a.index, a.stream_id, a.row0, 0, a.noise};
+    if (a.loop) {
+        s.index = a.loop->index;
+        s.row0 = (uint32_t)a.loop->row0;
+        s.rows = a.loop->rows;
+        s.stream_id = (uint32_t)s.index;
+        if (s.noise) s.noise += (size_t)s.index * a.noise_rows * LAT;
     }
-    const float c0 = a.coef[t * 3 + 0], c1 = a.coef[t * 3 + 1], c2 = a.coef[t * 3 + 2];
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {  // one float4 (quad) at a time
-        const int row = idx / QPR;
-        const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[idx];
-        const f32x4 u = reinterpret_cast<const f32x4*>(a.eps_u)[idx];
+    return s;
+}
+
+// An Update is built once per thread from the arguments and the loop index (it picks its coefficient row), says which
+// operands it needs -- reads_h / draws / writes_h, launch-uniform -- and maps one quad: x, u, c (guided: pred_c given, with
+// the row's guidance scale), h, z -> the new x (returned) and the new h.  Operands it did not ask for hold placeholders.
+// The arithmetic of each is fixed: results repeat bit for bit.
+
+// DDPM.p_sample: x' = c0 * (x - c1 * pred) + c2 * z with the coefficient row of timestep t
+struct DdpmUpdate {
+    float c0, c1, c2;
+    __device__ DdpmUpdate(const UpdateArgs& a, int j) {
+        const int t = a.loop ? a.steps - 1 - j : j;
+        c0 = a.coef[t * 3 + 0], c1 = a.coef[t * 3 + 1], c2 = a.coef[t * 3 + 2];
+    }
+    __device__ bool reads_h() const { return false; }
+    __device__ bool draws() const { return true; }
+    __device__ bool writes_h() const { return false; }
+    __device__ f32x4 operator()(f32x4 x, f32x4 u, f32x4 c, bool guided, float scale, f32x4, f32x4 z, f32x4&) const {
         f32x4 pred = u;
-        if (a.eps_c) {
-            const f32x4 c = reinterpret_cast<const f32x4*>(a.eps_c)[idx];
-            pred = u + ((rows & ROWS_CFG) ? a.row_cfg[row] : a.cfg) * (c - u);
-        }
-        f32x4 z;
-        if (noise) {
-            z = reinterpret_cast<const f32x4*>(noise)[idx];
-        } else {
-            const int quad = idx - row * QPR;
-            const uint64_t seed = (rows & ROWS_SEED) ? a.row_seed[row] : a.seed;
-            const uint32_t key = (rows & ROWS_KEY) ? a.row_key[row] : row0 + (uint32_t)row;
-            z = normal4(seed, sid, key, (uint32_t)quad);
-        }
+        if (guided) pred = u + scale * (c - u);
         const f32x4 mean = c0 * (x - c1 * pred);
-        reinterpret_cast<f32x4*>(a.x)[idx] = mean + c2 * z;
+        return mean + c2 * z;
     }
-    if (a.advance) advance_step_when_last(a.advance);
-}
+};
 
-// ---------------------------------------------------------------- linear multistep update (DDIM, DPM-Solver++(2M), AB2)
-// One table-driven update for every few-step solver: per element, with pred = u + cfg * (c - u) (pred = u without eps_c),
+// RectifiedFlow.euler: x' = x + pred * dt
+struct RfUpdate {
+    float dt;
+    __device__ RfUpdate(const UpdateArgs& a, int) : dt(a.dt) {}
+    __device__ bool reads_h() const { return false; }
+    __device__ bool draws() const { return false; }
+    __device__ bool writes_h() const { return false; }
+    __device__ f32x4 operator()(f32x4 x, f32x4 u, f32x4 c, bool guided, float scale, f32x4, f32x4, f32x4&) const {
+        f32x4 pred = u;
+        if (guided) pred = u + scale * (c - u);
+        return x + pred * dt;
+    }
+};
+
+// Linear multistep update (DDIM, DPM-Solver++(2M), AB2): one table-driven update for every few-step solver, per element
 //   x' = c0 * x + c1 * pred + c2 * h + c3 * z        h' = c4 * x + c5 * pred   (from the OLD x)
 // coef row j = {c0 .. c5} belongs to LOOP INDEX j (not steps-1-j: the solver's grid is in t_values, the table follows the
 // loop).  A coefficient that is exactly 0 means its operand is not touched -- c2 == 0: h is not loaded (NaN / uninitialised
 // history on the first step is fine); c3 == 0: no draw, no Philox work, noise may be NULL; c4 == c5 == 0: h is not
 // written.  The coefficients are launch-uniform, so are the branches.
-// Arithmetic (fixed: results repeat bit for bit): the fp32 operands are widened, the update is evaluated in fp64 in the order
+// Arithmetic: the fp32 operands are widened, the update is evaluated in fp64 in the order
 // pred = fma(cfg, c - u, u); acc = c0 * x; acc = fma(c1, pred, acc); acc = fma(c2, h, acc); acc = fma(c3, z, acc);
 // hn = fma(c5, pred, c4 * x), and acc / hn are rounded to fp32 ONCE.  Why fp64: the x0-prediction history of DPM-Solver++ is
 // (x - s * eps) / a with 1 / a = 157 at t = 999 of the 1000-step schedule -- two large terms that cancel -- and a four-term
 // fp32 sum carries four roundings of partial sums larger than its result; the kernel is bound by its four to seven
 // (B,1920) streams, the ~40 fp64 operations per quad do not show (tools/solver_probe.py).
-struct LmsArgs {
-    float* x;             // (B,1920) in place
-    float* hist;          // (B,1920) in place
-    const float* eps_u;   // (B,1920)
-    const float* eps_c;   // (B,1920) or NULL
-    const float* noise;   // injected draws: (steps,noise_rows,1920) indexed by step (this shard's first row), or (B,1920)
-                          // if step_ptr NULL; NULL: Philox
-    const float* coef;    // DEVICE (S,6)
-    const int* step_ptr;  // device {loop index j, global row of the first series, -, ROWS_* bits}, or NULL (then index /
-                          // stream_id / row0 are immediate)
-    int index;
-    float cfg;
-    uint64_t seed;
-    uint32_t stream_id;
-    uint32_t row0;
-    int B;
-    int noise_rows;
-    int* advance;         // sampling loop: the last workgroup increments the lane's loop index (advance_step_when_last)
-    const uint64_t* row_seed;   // per-row tables as in StepArgs
-    const uint32_t* row_key;
-    const float* row_cfg;
-};
-
-__global__ __launch_bounds__(256) void lms_step_kernel(const LmsArgs a) {
-    constexpr int QPR = LAT / 4;
-    int j = a.index;
-    uint32_t sid = a.stream_id, row0 = a.row0;
-    const float* noise = a.noise;
-    int rows = 0;
-    if (a.step_ptr) {
-        j = a.step_ptr[0];
-        row0 = (uint32_t)a.step_ptr[1];
-        rows = a.step_ptr[3];
-        sid = (uint32_t)j;               // the draw of loop index j is stream j, as ddpm_step_kernel keys it
-        if (noise) noise += (size_t)j * a.noise_rows * LAT;
+struct LmsUpdate {
+    float c0, c1, c2, c3, c4, c5;
+    __device__ LmsUpdate(const UpdateArgs& a, int j) {
+        const float* cj = a.coef + (size_t)j * 6;
+        c0 = cj[0], c1 = cj[1], c2 = cj[2], c3 = cj[3], c4 = cj[4], c5 = cj[5];
     }
-    const float* cj = a.coef + (size_t)j * 6;
-    const float c0 = cj[0], c1 = cj[1], c2 = cj[2], c3 = cj[3], c4 = cj[4], c5 = cj[5];
-    const bool use_h = c2 != 0.0f, use_z = c3 != 0.0f, put_h = c4 != 0.0f || c5 != 0.0f;
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {
-        const int row = idx / QPR;
-        const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[idx];
-        const f32x4 u = reinterpret_cast<const f32x4*>(a.eps_u)[idx];
-        f32x4 c = u, h = x, z = x;                   // (placeholders where the operand is not read)
-        double cfg = 0.0;
-        if (a.eps_c) {
-            c = reinterpret_cast<const f32x4*>(a.eps_c)[idx];
-            cfg = (double)((rows & ROWS_CFG) ? a.row_cfg[row] : a.cfg);
-        }
-        if (use_h) h = reinterpret_cast<const f32x4*>(a.hist)[idx];
-        if (use_z) {
-            if (noise) {
-                z = reinterpret_cast<const f32x4*>(noise)[idx];
-            } else {
-                const int quad = idx - row * QPR;
-                const uint64_t seed = (rows & ROWS_SEED) ? a.row_seed[row] : a.seed;
-                const uint32_t key = (rows & ROWS_KEY) ? a.row_key[row] : row0 + (uint32_t)row;
-                z = normal4(seed, sid, key, (uint32_t)quad);
-            }
-        }
-        f32x4 xn, hn;
+    __device__ bool reads_h() const { return c2 != 0.0f; }
+    __device__ bool draws() const { return c3 != 0.0f; }
+    __device__ bool writes_h() const { return c4 != 0.0f || c5 != 0.0f; }
+    __device__ f32x4 operator()(f32x4 x, f32x4 u, f32x4 c, bool guided, float scale, f32x4 h, f32x4 z, f32x4& hn) const {
+        const double cfg = (double)scale;
+        f32x4 xn;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             double pred = (double)u[e];
-            if (a.eps_c) pred = fma(cfg, (double)c[e] - (double)u[e], pred);
+            if (guided) pred = fma(cfg, (double)c[e] - (double)u[e], pred);
             double acc = (double)c0 * (double)x[e];
             acc = fma((double)c1, pred, acc);
-            if (use_h) acc = fma((double)c2, (double)h[e], acc);
-            if (use_z) acc = fma((double)c3, (double)z[e], acc);
+            if (reads_h()) acc = fma((double)c2, (double)h[e], acc);
+            if (draws()) acc = fma((double)c3, (double)z[e], acc);
             xn[e] = (float)acc;
             hn[e] = (float)fma((double)c5, pred, (double)c4 * (double)x[e]);
         }
-        if (put_h) reinterpret_cast<f32x4*>(a.hist)[idx] = hn;
+        return xn;
+    }
+};
+
+// The scaffold of every update: prologue, grid-stride loop over the quads (one float4 at a time), the operands of a quad,
+// the Update's arithmetic, and the loop's advance.
+constexpr int STEP_MAX_WGS = 96;   // see launch_update
+template <class Update>
+__global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
+    constexpr int QPR = LAT / 4;
+    const Step s = resolve_step(a);
+    const Update update(a, s.index);
+    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {
+        const int row = idx / QPR;
+        const f32x4 x = reinterpret_cast<const f32x4*>(a.x)[idx];
+        const f32x4 u = reinterpret_cast<const f32x4*>(a.pred_u)[idx];
+        f32x4 c = u, h = x, z = x;                   // (placeholders where the operand is not read)
+        float scale = 0.0f;
+        if (a.pred_c) {
+            c = reinterpret_cast<const f32x4*>(a.pred_c)[idx];
+            scale = (s.rows & ROWS_CFG) ? a.row_cfg[row] : a.cfg;
+        }
+        if (update.reads_h()) h = reinterpret_cast<const f32x4*>(a.hist)[idx];
+        if (update.draws()) {
+            if (s.noise) {
+                z = reinterpret_cast<const f32x4*>(s.noise)[idx];
+            } else {
+                const int quad = idx - row * QPR;
+                const uint64_t seed = (s.rows & ROWS_SEED) ? a.row_seed[row] : a.seed;
+                const uint32_t key = (s.rows & ROWS_KEY) ? a.row_key[row] : s.row0 + (uint32_t)row;
+                z = normal4(seed, s.stream_id, key, (uint32_t)quad);
+            }
+        }
+        f32x4 hn;
+        const f32x4 xn = update(x, u, c, a.pred_c != nullptr, scale, h, z, hn);
+        if (update.writes_h()) reinterpret_cast<f32x4*>(a.hist)[idx] = hn;
         reinterpret_cast<f32x4*>(a.x)[idx] = xn;
     }
     if (a.advance) advance_step_when_last(a.advance);
-}
-
-// row_cfg: this lane's slice of the per-row guidance table, used when bit ROWS_CFG of advance[3] is set (NULL: never)
-__global__ __launch_bounds__(256) void rf_step_kernel(float* __restrict__ x, const float* __restrict__ vu,
-                                                      const float* __restrict__ vc, float cfg, float dt,
-                                                      int n4, int* advance, const float* __restrict__ row_cfg) {
-    const bool per_row = row_cfg && advance && (advance[3] & ROWS_CFG);
-    for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < n4; idx += gridDim.x * blockDim.x) {
-        const f32x4 u = reinterpret_cast<const f32x4*>(vu)[idx];
-        f32x4 pred = u;
-        if (vc) pred = u + (per_row ? row_cfg[idx / (LAT / 4)] : cfg) * (reinterpret_cast<const f32x4*>(vc)[idx] - u);
-        f32x4 xv = reinterpret_cast<f32x4*>(x)[idx];
-        reinterpret_cast<f32x4*>(x)[idx] = xv + pred * dt;
-    }
-    if (advance) advance_step_when_last(advance);
 }
 
 __global__ __launch_bounds__(256) void q_sample_kernel(const float* __restrict__ x0, const float* __restrict__ eps,
@@ -366,22 +366,30 @@ __global__ __launch_bounds__(256) void mse_final_kernel(const float* __restrict_
     if (threadIdx.x == 0) *out = ((part[0] + part[1]) + (part[2] + part[3])) / (float)n;
 }
 
-// step[0] = loop index, step[1] = global row index of the lane's first series (Philox key), step[2] = arrival counter
-// of the update kernel (advance_step_when_last), step[3] = the per-row tables in use (ROWS_* bits)
-__global__ void set_step_kernel(int* step, int value, uint32_t row0, int rows) {
-    if (threadIdx.x == 0 && blockIdx.x == 0) {
-        step[0] = value;
-        step[1] = (int)row0;
-        step[2] = 0;
-        step[3] = rows;
-    }
+__global__ void set_step_kernel(LoopState* loop, int value, uint32_t row0, int rows) {
+    if (threadIdx.x == 0 && blockIdx.x == 0) *loop = LoopState{value, (int)row0, 0, rows};
 }
 
 }  // namespace t2s
 
 using namespace t2s;
 
-extern "C" int t2s_time_embedding(const t2s_dit* h, const float* t, float* out, int B, void* stream);
+// The one launch of an update kernel, mode = T2S_MODE_*.  Grid rule: a workgroup per 256 quads, capped at STEP_MAX_WGS
+// (the rest by grid stride) exactly when the kernel advances the loop: the arrival counter is ONE address, and same-address
+// atomics serialise at ~25 ns each -- 480 of them (one per 256 quads at B = 256) made this 6 us kernel 18 us.  The result
+// of a quad does not depend on the grid.
+static int launch_update(int mode, const UpdateArgs& a, hipStream_t st) {
+    const int wgs = (a.B * (LAT / 4) + 255) / 256;
+    const int grid = (a.advance && wgs > STEP_MAX_WGS) ? STEP_MAX_WGS : wgs;
+    switch (mode) {
+    case T2S_MODE_DDPM: update_kernel<DdpmUpdate><<<grid, 256, 0, st>>>(a); break;
+    case T2S_MODE_LMS: update_kernel<LmsUpdate><<<grid, 256, 0, st>>>(a); break;
+    case T2S_MODE_RF: update_kernel<RfUpdate><<<grid, 256, 0, st>>>(a); break;
+    default: T2S_REQUIRE(false, "launch_update: mode=%d", mode);
+    }
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
 
 // ---------------------------------------------------------------- C ABI: single-step entry points
 extern "C" int t2s_philox_normal(float* out, uint64_t seed, uint32_t stream_id, uint32_t row0, int n_rows,
@@ -419,14 +427,11 @@ extern "C" int t2s_ddpm_step(float* x, const float* eps_u, const float* eps_c, c
                              const float* coef, int t_index, float cfg, uint64_t seed, uint32_t stream_id,
                              uint32_t row0, int B, void* stream) {
     T2S_REQUIRE(x && eps_u && coef, "t2s_ddpm_step: NULL argument");
-    T2S_REQUIRE(B > 0 && t_index >= 0, "t2s_ddpm_step: B=%d t_index=%d", B, t_index);
-    StepArgs a{};
-    a.x = x; a.eps_u = eps_u; a.eps_c = eps_c; a.noise = noise; a.coef = coef; a.step_ptr = nullptr;
-    a.t_index = t_index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
-    const int total = B * (LAT / 4);
-    ddpm_step_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(a);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
+    T2S_REQUIRE(B > 0 && t_index >= 0 && (long long)B * LAT < (1ll << 31), "t2s_ddpm_step: B=%d t_index=%d", B, t_index);
+    UpdateArgs a{};
+    a.x = x; a.pred_u = eps_u; a.pred_c = eps_c; a.noise = noise; a.coef = coef;
+    a.index = t_index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
+    return launch_update(T2S_MODE_DDPM, a, (hipStream_t)stream);
 }
 
 extern "C" int t2s_lms_step(float* x, float* hist, const float* pred_u, const float* pred_c, const float* noise,
@@ -434,21 +439,18 @@ extern "C" int t2s_lms_step(float* x, float* hist, const float* pred_u, const fl
                             void* stream) {
     T2S_REQUIRE(x && hist && pred_u && coef, "t2s_lms_step: NULL argument");
     T2S_REQUIRE(B > 0 && index >= 0 && (long long)B * LAT < (1ll << 31), "t2s_lms_step: B=%d index=%d", B, index);
-    LmsArgs a{};
-    a.x = x; a.hist = hist; a.eps_u = pred_u; a.eps_c = pred_c; a.noise = noise; a.coef = coef; a.step_ptr = nullptr;
+    UpdateArgs a{};
+    a.x = x; a.hist = hist; a.pred_u = pred_u; a.pred_c = pred_c; a.noise = noise; a.coef = coef;
     a.index = index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
-    const int total = B * (LAT / 4), wgs = (total + 255) / 256;
-    lms_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, (hipStream_t)stream>>>(a);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
+    return launch_update(T2S_MODE_LMS, a, (hipStream_t)stream);
 }
 
 extern "C" int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float dt, int B, void* stream) {
-    T2S_REQUIRE(x && v_u && B > 0, "t2s_rf_step: bad argument");
-    const int n4 = B * (LAT / 4);
-    rf_step_kernel<<<(n4 + 255) / 256, 256, 0, (hipStream_t)stream>>>(x, v_u, v_c, cfg, dt, n4, nullptr, nullptr);
-    T2S_LAUNCH_CHECK();
-    return T2S_OK;
+    T2S_REQUIRE(x && v_u, "t2s_rf_step: NULL argument");
+    T2S_REQUIRE(B > 0 && (long long)B * LAT < (1ll << 31), "t2s_rf_step: B=%d", B);
+    UpdateArgs a{};
+    a.x = x; a.pred_u = v_u; a.pred_c = v_c; a.cfg = cfg; a.dt = dt; a.B = B;
+    return launch_update(T2S_MODE_RF, a, (hipStream_t)stream);
 }
 
 extern "C" int t2s_ddpm_q_sample_n(const float* x0, const float* eps, const int32_t* t, const float* sqrt_ab,
@@ -534,7 +536,7 @@ struct t2s_sampler {
     float* eps_c = nullptr;
     float* tvals = nullptr;       // (steps)
     float* mod_table = nullptr;   // (steps, batch + 1, 3072): the adaLN modulation of every step, refreshed at the start of a run
-    int* step = nullptr;          // device loop indices, one per lane (16 ints apart)
+    LoopState* step = nullptr;    // device loop states, one per lane (LANE_STATES apart)
     // Lanes: the rows of the batch are independent through the whole loop, so the batch can run as TWO half
     // batches, each a complete chain (own step counter, own hipGraph, own slice of the DiT workspace) on its own
     // stream, joined only before the decode.  One chain alone drains and refills the chip at each of its 9 kernel
@@ -680,41 +682,25 @@ hipStream_t* lane_streams() {
 int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise, hipStream_t st, int lane, int r0,
                  int n) {
     const t2s_sample_config& c = s->cfg;
-    int* step = s->step + 16 * lane;
+    LoopState* loop = s->step + LANE_STATES * lane;
     float* xl = x + (size_t)r0 * LAT;
     float* eu = s->eps_u + (size_t)r0 * LAT;
     float* ec = s->eps_c + (size_t)r0 * LAT;
-    int rc = dit_forward_cfg_step(s->dit, xl, s->temb_table, step, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
+    int rc = dit_forward_cfg_step(s->dit, xl, s->temb_table, &loop->index, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
                                   s->mod_table, c.batch + 1, r0);
     if (rc != T2S_OK) return rc;
-    if (c.mode == T2S_MODE_DDPM) {
-        StepArgs a{};
-        a.x = xl; a.eps_u = eu; a.eps_c = ec; a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
-        a.step_ptr = step; a.steps = c.steps; a.cfg = c.cfg_scale; a.seed = c.seed; a.row0 = c.row0 + (uint32_t)r0;
-        a.B = n; a.noise_rows = c.batch; a.advance = step;
-        a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
-        a.row_key = rows_key(s->d_rows, c.batch) + r0;
-        a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
-        const int total = n * (LAT / 4), wgs = (total + 255) / 256;
-        ddpm_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(a);
-    } else if (c.mode == T2S_MODE_LMS) {
-        LmsArgs a{};
-        a.x = xl; a.hist = s->hist + (size_t)r0 * LAT; a.eps_u = eu; a.eps_c = ec;
-        a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
-        a.step_ptr = step; a.cfg = c.cfg_scale; a.seed = c.seed; a.row0 = c.row0 + (uint32_t)r0;
-        a.B = n; a.noise_rows = c.batch; a.advance = step;
-        a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
-        a.row_key = rows_key(s->d_rows, c.batch) + r0;
-        a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
-        const int total = n * (LAT / 4), wgs = (total + 255) / 256;
-        lms_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(a);
-    } else {
-        const int n4 = n * (LAT / 4), wgs = (n4 + 255) / 256;
-        rf_step_kernel<<<wgs < STEP_MAX_WGS ? wgs : STEP_MAX_WGS, 256, 0, st>>>(xl, eu, ec, c.cfg_scale, 1.0f / (float)c.steps, n4, step,
-                                                                               rows_cfg(s->d_rows, c.batch) + r0);
+    UpdateArgs a{};
+    a.x = xl; a.pred_u = eu; a.pred_c = ec; a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
+    a.loop = loop; a.cfg = c.cfg_scale; a.seed = c.seed; a.B = n; a.noise_rows = c.batch; a.advance = loop;
+    a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
+    a.row_key = rows_key(s->d_rows, c.batch) + r0;
+    a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
+    switch (c.mode) {   // (the create entries admit these three modes only; launch_update refuses any other)
+    case T2S_MODE_DDPM: a.steps = c.steps; break;
+    case T2S_MODE_LMS: a.hist = s->hist + (size_t)r0 * LAT; break;
+    case T2S_MODE_RF: a.dt = 1.0f / (float)c.steps; break;
     }
-    T2S_LAUNCH_CHECK();   // (the update kernel's last workgroup advanced the lane's loop index)
-    return T2S_OK;
+    return launch_update(c.mode, a, st);   // (the update kernel's last workgroup advances the lane's loop index)
 }
 
 // Whole-loop graphs by default?  Same-box A/B (tools/ab_loop_graph.sh, profiles/r04_loop_graph_ab.txt), series/s one-step /
@@ -761,9 +747,6 @@ hipStream_t lib_setup_stream(int dev) { return setup_stream(dev); }
 std::recursive_mutex* lib_pool_lock(int dev) { return dev >= 0 && dev < 16 ? &g_pool_use[dev] : nullptr; }
 }  // namespace t2s
 
-extern "C" int t2s_dit_max_seqs(const t2s_dit* h);
-extern "C" int t2s_vae_channels(const t2s_vae* h);
-
 // t2s_sampler_create (lms_coef NULL; modes DDPM / RF) and t2s_sampler_create_lms (mode LMS, HOST (steps,6) table)
 static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* cfg, const float* lms_coef, t2s_sampler** out) {
     T2S_REQUIRE(cfg->steps > 0 && cfg->steps <= 100000, "t2s_sampler_create: steps=%d", cfg->steps);
@@ -792,7 +775,7 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
     alloc((void**)&s->eps_u, B * LAT * sizeof(float));
     alloc((void**)&s->eps_c, B * LAT * sizeof(float));
     alloc((void**)&s->tvals, T * sizeof(float));
-    alloc((void**)&s->step, t2s_sampler::MAX_LANES * 16 * sizeof(int));   // one counter per lane, 64 B apart
+    alloc((void**)&s->step, t2s_sampler::MAX_LANES * LANE_STATES * sizeof(LoopState));   // one per lane, 64 B apart
     alloc(&s->d_rows, rows_bytes(cfg->batch));                            // per-row tables (t2s_sampler_set_rows)
     if (e == hipSuccess) e = hipHostMalloc(&s->h_stage, rows_bytes(cfg->batch), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_rows, hipEventDisableTiming);
@@ -929,9 +912,6 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     delete s;
 }
 
-extern "C" int t2s_vae_decode(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, void* stream);
-extern "C" int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream);
-
 // the sampler's decode of n latents: a multichannel decoder handle writes (n,C,L) at latent width 30, a single-channel one (n,L)
 static int sampler_decode(t2s_vae* vae, const float* x, float* out, int n, int L, hipStream_t st) {
     if (t2s_vae_channels(vae) != 0) return t2s_vae_decode_mc(vae, x, out, nullptr, n, L, LATW, st);
@@ -1047,7 +1027,7 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         for (int l = 1; l < lanes; ++l) T2S_HIP_CHECK(hipStreamWaitEvent(s->side[l], s->ev_fork, 0));
     }
     for (int l = 0; l < lanes; ++l) {
-        set_step_kernel<<<1, 64, 0, lst[l]>>>(s->step + 16 * l, 0, c.row0 + (uint32_t)r0[l], s->rows);
+        set_step_kernel<<<1, 64, 0, lst[l]>>>(s->step + LANE_STATES * l, 0, c.row0 + (uint32_t)r0[l], s->rows);
         T2S_LAUNCH_CHECK();
     }
     if (graph_ok && whole)

@@ -276,10 +276,11 @@ def test_rectified_flow_golden(golden_dir, dev):
     assert _maxdiff(xt, g["x_t"]) < 1e-6
 
 
-def test_fused_ddpm_step_vs_oracle(dev):
+@pytest.mark.parametrize("B", [6, 53])      # 53: 25,440 quads, past one sweep of a 96-workgroup grid
+def test_fused_ddpm_step_vs_oracle(dev, B):
     from t2ms_amd.model.backbone.DDPM import ddpm_host_tables
     rs = np.random.RandomState(3)
-    B, T = 6, 1000
+    T = 1000
     x, u, c, z = (torch.from_numpy(rs.randn(B, 64, 30).astype(np.float32)) for _ in range(4))
     tab = O.ddpm_tables(T)
     coef = ddpm_host_tables(T)["coef"].to(dev)
@@ -297,6 +298,19 @@ def test_fused_ddpm_step_vs_oracle(dev):
     L.check(L.lib().t2s_rf_step(xd.data_ptr(), ud.data_ptr(), cd.data_ptr(), 5.0, 0.01, B,
                                 L.stream_ptr(dev)))
     assert _maxdiff(xd, ref) < 2e-6
+
+
+@pytest.mark.parametrize("B,row0", [(3, 1000), (53, 7)])
+def test_philox_through_ddpm_step_is_the_library_stream(dev, B, row0):
+    """x = 0 and the coefficient row {1, 0, 1}: x' = 1 * (0 - 0 * pred) + 1 * z = z exactly, the draw of the given key."""
+    from t2ms_amd.sampler import philox_normal
+    seed, sid = 2025, 17
+    x = torch.zeros(B, 1920, device=dev)
+    u = torch.from_numpy(np.random.RandomState(1).randn(B, 1920).astype(np.float32)).to(dev)
+    coef = torch.tensor([[1, 0, 1]], dtype=torch.float32, device=dev)
+    L.check(L.lib().t2s_ddpm_step(x.data_ptr(), u.data_ptr(), None, None, coef.data_ptr(), 0, 0.0, seed, sid, row0, B,
+                                  L.stream_ptr(dev)))
+    assert torch.equal(x, philox_normal(B, 1920, seed, sid, row0, dev))
 
 
 def test_mse(dev):

@@ -304,6 +304,35 @@ def test_sampler_bitwise_properties(dev, vae, model, monkeypatch, solver, eta):
         assert _same(make(**kw).run(text)[:2], ref), kw
 
 
+@pytest.mark.parametrize("backbone,solver,total,kw", [("ddpm", "ancestral", 3, {}), ("flowmatching", "euler", 3, {}),
+                                                      ("ddpm", "ddim", 60, dict(eta=0.5, sample_steps=3))])
+def test_loop_update_past_one_grid_sweep(dev, vae, model, backbone, solver, total, kw):
+    """Inside the loop the update kernel's grid is capped at 96 workgroups of 256 quads = 51.2 rows: at B = 53 the last rows
+    are updated in a second grid-stride sweep.  Their idx -> (row, quad, Philox key) mapping must be that of the first: the
+    53-row latent equals, bit for bit, a 50-row sampler's (24,000 quads, one sweep) followed by a 3-row sampler's at row0 =
+    50, and a graph replay repeats it.  Every sampler carries its rows of one per-row guidance table (set_rows)."""
+    from t2ms_amd.sampler import Sampler
+    B, steps, Ls = 53, 3, 24                  # three loop steps (ddim: 3 of a 60-step schedule)
+    text = synth.make_text_embeddings(1, B).to(dev)
+    scales = [5.0 if r % 3 else 9.0 for r in range(B)]      # a guidance scale per row: the flow update, which makes no
+                                                            # draw, reaches the row of a quad through this table alone
+
+    def make(batch, row0):
+        s = Sampler(model, vae.decoder, backbone, total, 5.0, batch, Ls, dev, use_graph=True, seed=7, row0=row0, lanes=1,
+                    math="f32", solver=solver, **kw)
+        s.set_rows(cfg=scales[row0:row0 + batch])
+        return s
+
+    s = make(B, 0)
+    assert s.steps == steps
+    whole = s.run(text)[0].clone()
+    assert s.graph_lanes == 1 and bool(torch.isfinite(whole).all())
+    assert torch.equal(s.run_inplace()[0], whole)                    # the replay of the captured graph
+    head = make(50, 0).run(text[:50])[0].clone()
+    tail = make(3, 50).run(text[50:])[0]
+    assert torch.equal(torch.cat([head, tail]), whole)
+
+
 def test_injected_noise_shape_and_todays_modes_are_untouched(dev, vae, model):
     """self.steps = S is the first dimension of `noise`; solver None / "ancestral" / "euler" build today's sampler (same bits)."""
     from t2ms_amd.sampler import Sampler
