@@ -94,6 +94,16 @@ typedef struct t2s_dit_weights {
  * sampling step over a batch of B series uses 2*B sequences).  Packs the
  * weights into the kernels' MFMA-fragment layout (synchronous). */
 int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out);
+/* The same denoiser over a WIDE latent (the T2MS motion models, model/denoiser/mytransformer.py Transformer(dim)): the latent
+ * is (64, latent_w), patchified 2x2 into 16*latent_w tokens -- latent_w 30 (480 tokens; this IS t2s_dit_create), 50 (800,
+ * the deadlift model) or 64 (1024, the bench-press model); anything else is T2S_E_INVALID with a message.  The weights are
+ * those of t2s_dit_weights except pos_embed, which holds 16*latent_w*128 floats (an undersized one is T2S_E_INVALID naming
+ * "pos_embed").  On such a handle every entry below takes and gives (S,64,latent_w) latents and (S,16*latent_w,128) token
+ * streams.  A handle with latent_w != 30 runs T2S_MATH_F32 and inference only: t2s_dit_set_math(T2S_MATH_BF16X3 / _BF16),
+ * t2s_dit_set_train_dtype and every t2s_dit_train_* entry return T2S_E_INVALID with a message, before any launch. */
+int t2s_dit_create_w(const t2s_dit_weights* w, int latent_w, int max_seqs, t2s_dit** out);
+/* latent width of a handle (30 for t2s_dit_create); 0 for NULL */
+int t2s_dit_latent_w(const t2s_dit* h);
 /* t2s_dit_weights is T2S_DIT_N_TENSORS device pointers: 10 top-level fields in declaration order, then the 10 fields of each
  * of the 4 blocks.  The ABI carries no sizes, so: n_floats[i] (HOST array, n_entries == T2S_DIT_N_TENSORS, or NULL) = the
  * number of floats the caller holds behind pointer i; the call returns T2S_E_INVALID -- naming the tensor by its state-dict
@@ -103,6 +113,8 @@ int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out);
  * code, never a memory fault.  The host mirror calls this with the numel() of every parameter before it hands a new struct over. */
 #define T2S_DIT_N_TENSORS (10 + 10 * T2S_N_BLOCKS)
 int t2s_dit_weights_check(const t2s_dit_weights* w, const uint64_t* n_floats, int n_entries);
+/* The same check for a handle of t2s_dit_create_w: pos_embed must hold 16*latent_w*128 floats (latent_w 30, 50 or 64). */
+int t2s_dit_weights_check_w(const t2s_dit_weights* w, int latent_w, const uint64_t* n_floats, int n_entries);
 /* Re-pack after the caller changed the weights (load_state_dict, optimizer step). */
 int t2s_dit_update_weights(t2s_dit* h, const t2s_dit_weights* w, void* stream);
 void t2s_dit_destroy(t2s_dit* h);
@@ -208,6 +220,10 @@ int t2s_attn_fwd(const float* q, const float* k, const float* v, float* o, int B
  *     o[(((row/32)*16 + G)*64 + 32*h + row%32)*4 + e] = O[row][8*G + 4*h + e]  (G = col/8). */
 int t2s_attn_fwd_packed(const float* q, const float* k, const float* vT, float* o, int n_seq,
                         void* stream);
+/* The same fragment-major contract for a sequence of n_tok tokens, n_tok = 480, 800 or 1024 (n_tok/32 tiles per head; q, k,
+ * vT: (n_seq*4, n_tok, 32) per head, o: (n_seq*n_tok, 128)).  At 480 it launches what t2s_attn_fwd_packed launches; at 800 /
+ * 1024 the packed kernel's body over 25 / 32 key blocks, four workgroups per head (the wide DiT's attention). */
+int t2s_attn_fwd_packed_n(const float* q, const float* k, const float* vT, float* o, int n_seq, int n_tok, void* stream);
 
 /* The "bf16x3" attention kernel (T2S_MATH_BF16X3, see t2s_dit_set_math) on plain tensors: same
  * contract as t2s_attn_fwd (q, k, v, o: (BH, 480, 32) fp32, BH a multiple of 4), fp32-accurate
@@ -340,6 +356,11 @@ int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float d
 int t2s_lms_step(float* x, float* hist, const float* pred_u, const float* pred_c /* may be NULL */,
                  const float* noise /* (B,1920) or NULL */, const float* coef /* DEVICE (S,6) */, int index,
                  float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B, void* stream);
+/* The same update on rows of row_elems values (a multiple of 4; 64*W for a wide latent): x, hist, pred_*, noise are
+ * (B,row_elems), and the Philox draw of a row covers row_elems values.  t2s_lms_step is row_elems = 1920. */
+int t2s_lms_step_n(float* x, float* hist, const float* pred_u, const float* pred_c /* may be NULL */,
+                   const float* noise /* (B,row_elems) or NULL */, const float* coef /* DEVICE (S,6) */, int index,
+                   float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B, int row_elems, void* stream);
 /* DDPM.q_sample (DDPM.py:19-27): out = sqrt_ab[t[b]]*x0 + sqrt_1mab[t[b]]*eps.
  * sqrt_ab, sqrt_1mab: (T) host-built tables, T = n_steps; t: (B) int32 (out of range -> NaN row, see p_sample). */
 int t2s_ddpm_q_sample(const float* x0, const float* eps, const int32_t* t, const float* sqrt_ab,
@@ -506,6 +527,10 @@ typedef struct t2s_sample_config {
                                DDPM steps-1-j (infer.py:84), RF round(j/steps*steps)/steps (:78) */
 } t2s_sample_config;
 
+/* On a DiT handle of t2s_dit_create_w the sampler's rows are 64*W values: x is (B,64,W), noise (steps,B,64,W), the Philox draw
+ * of a row covers 64*W values, the history / eps buffers follow.  With W > 32 `vae` must be a multichannel decoder handle
+ * (t2s_vae_create_mc; it decodes at latent width W) or NULL: a single-channel t2s_vae_create handle is T2S_E_INVALID here and
+ * in t2s_sampler_create_lms, before any allocation. */
 int t2s_sampler_create(t2s_dit* dit, t2s_vae* vae /* may be NULL: no decode */,
                        const t2s_sample_config* cfg, t2s_sampler** out);
 /* The same sampler with the few-step update of t2s_lms_step in place of the ancestral DDPM / Euler update: cfg->mode =

@@ -143,12 +143,15 @@ SYMBOLS = {
     "t2s_last_error": (C.c_char_p, []),
     "t2s_version": (C.c_char_p, []),
     "t2s_dit_create": (_I, [C.POINTER(DitWeights), _I, C.POINTER(_VP)]),
+    "t2s_dit_create_w": (_I, [C.POINTER(DitWeights), _I, _I, C.POINTER(_VP)]),
+    "t2s_dit_latent_w": (_I, [_VP]),
     "t2s_dit_update_weights": (_I, [_VP, C.POINTER(DitWeights), _VP]),
     "t2s_dit_destroy": (None, [_VP]),
     "t2s_dit_max_seqs": (_I, [_VP]),
     "t2s_time_embedding": (_I, [_VP, _VP, _VP, _I, _VP]),
     "t2s_time_embedding_freqs": (_I, [_VP, _VP, _VP, _I, _VP]),
     "t2s_dit_weights_check": (_I, [C.POINTER(DitWeights), C.POINTER(C.c_uint64), _I]),
+    "t2s_dit_weights_check_w": (_I, [C.POINTER(DitWeights), _I, C.POINTER(C.c_uint64), _I]),
     "t2s_dit_forward": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _I, _VP]),
     "t2s_dit_forward_cfg": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_dit_forward_cfg_rows": (_I, [_VP, _VP, _VP, _I, _VP, _VP, _VP, _I, _VP]),
@@ -184,8 +187,10 @@ SYMBOLS = {
     "t2s_mse_backward": (_I, [_VP, _VP, _VP, _VP, _VP, _U64, _VP]),
     "t2s_attn_fwd": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_attn_fwd_packed": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
+    "t2s_attn_fwd_packed_n": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_ddpm_step": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _F, _U64, _U32, _U32, _I, _VP]),
     "t2s_lms_step": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _F, _U64, _U32, _U32, _I, _VP]),
+    "t2s_lms_step_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _F, _U64, _U32, _U32, _I, _I, _VP]),
     "t2s_ddpm_p_sample": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_ddpm_p_sample_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_ddpm_q_sample_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),

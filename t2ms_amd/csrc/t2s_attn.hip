@@ -1,4 +1,4 @@
-// Fused attention for the DiT: softmax(q k^T / sqrt(32)) v, N = 480 keys, head_dim 32,
+// Fused attention for the DiT: softmax(q k^T / sqrt(32)) v, N = 480 keys (800 / 1024 for the wide latents), head_dim 32,
 // exact fp32 on v_mfma_f32_32x32x2_f32.  (timm 1.0.11 Attention.forward core; reference
 // call site model/denoiser/transformer.py:104,116.)
 //
@@ -18,7 +18,8 @@
 // s_barrier, so the DMA stays in flight across barriers); every LDS read is a lane-linear,
 // conflict-free ds_read_b128 and feeds 2 MFMAs (both query tiles).  Two workgroups cover the
 // 15 query tiles of a (sequence, head); LDS is 32 KiB, so several workgroups share a CU and
-// one's softmax (VALU) overlaps another's MFMAs.
+// one's softmax (VALU) overlaps another's MFMAs.  attn_fwd_packed_wide_kernel<25 | 32>: the same body over 25 / 32 key blocks,
+// four workgroups per head (800 / 1024 tokens).
 //
 // attn_fwd_plain_kernel: same math on plain (BH,480,32) tensors for the standalone C-ABI entry.
 #include <stdlib.h>
@@ -131,7 +132,8 @@ __device__ __forceinline__ float rereference(const f32x4 (&kf)[4], const f32x4 (
 //   ds_read V(jb) | QK_A, QK_B | exp+sum (A, B), overflow check | PV_A |
 //   wait+barrier(jb+1), DMA(jb+3), ds_read K(jb+1) | PV_B
 // so the LDS latencies and the barrier hide behind matrix work.
-template <int NT>
+// NKBT = key blocks (= query tiles) of a sequence: 15, 25 or 32 (480, 800, 1024 tokens).
+template <int NT, int NKBT>
 __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, const f32x4* kg,
                                                  const f32x4* vg, f32x4* og, int bh, int t0, int lane,
                                                  int wave) {
@@ -155,7 +157,7 @@ __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, c
     // wave) ahead for the WHOLE loop -- past the end it re-fetches the last block into a slot nobody
     // reads -- so every wait is the same counted `vmcnt(4)`.
     auto issue_clamped = [&](int jb) {
-        const int src = jb < NKB ? jb : NKB - 1;
+        const int src = jb < NKBT ? jb : NKBT - 1;
         f32x4* slot = ring + (jb & (ATT_SLOTS - 1)) * ATT_SLOT_F4;
         glds16_asm(kg + (src * 4 + wave) * 64 + lane, slot + wave * 64);
         glds16_asm(vg + (src * 4 + wave) * 64 + lane, slot + 256 + wave * 64);
@@ -168,7 +170,7 @@ __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, c
     for (int g = 0; g < 4; ++g) kf[g] = ring[g * 64 + lane];
 
 #pragma unroll 1
-    for (int jb = 0; jb < NKB; ++jb) {
+    for (int jb = 0; jb < NKBT; ++jb) {
         const f32x4* slot = ring + (jb & (ATT_SLOTS - 1)) * ATT_SLOT_F4 + lane;
         f32x4 vf[4];
 #pragma unroll
@@ -229,7 +231,7 @@ __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, c
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const f32x4 w = {oa[4 * g] * inv, oa[4 * g + 1] * inv, oa[4 * g + 2] * inv, oa[4 * g + 3] * inv};
-            og[(((size_t)seq * NKB + t0) * 16 + head * 4 + g) * 64 + lane] = w;
+            og[(((size_t)seq * NKBT + t0) * 16 + head * 4 + g) * 64 + lane] = w;
         }
     }
     if (NT == 2) {
@@ -237,7 +239,7 @@ __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, c
 #pragma unroll
         for (int g = 0; g < 4; ++g) {
             const f32x4 w = {ob[4 * g] * inv, ob[4 * g + 1] * inv, ob[4 * g + 2] * inv, ob[4 * g + 3] * inv};
-            og[(((size_t)seq * NKB + t0 + 1) * 16 + head * 4 + g) * 64 + lane] = w;
+            og[(((size_t)seq * NKBT + t0 + 1) * 16 + head * 4 + g) * 64 + lane] = w;
         }
     }
 }
@@ -246,23 +248,22 @@ __device__ __forceinline__ void attn_packed_body(f32x4* ring, const f32x4* qg, c
 // otherwise): four workgroups per head, ONE query tile per wave -- twice the waves per SIMD for the same matrix work, K / V
 // streamed four times per head from L2.  Tile 15 does not exist: the wave that would own it repeats tile 14 (same bits,
 // stored twice).
-template <int PARTS>
-__global__ __launch_bounds__(256, 2) void attn_fwd_packed_kernel(const float* __restrict__ q,
-                                                                 const float* __restrict__ k,
-                                                                 const float* __restrict__ vT,
-                                                                 float* __restrict__ o, int BH) {
+// TPW = query tiles per wave (2 or 1), NKBT = tiles of a sequence.  Slots past the last tile repeat it (same bits, stored again).
+template <int PARTS, int TPW, int NKBT>
+__device__ __forceinline__ void attn_packed_head(const float* __restrict__ q, const float* __restrict__ k,
+                                                 const float* __restrict__ vT, float* __restrict__ o, int BH) {
     extern __shared__ __attribute__((aligned(16))) f32x4 ring[];
     // The workgroups of a (sequence, head) stream the same K/V: give them ids r, r+8, ... of a
     // (8 PARTS)-id group so that (round-robin XCD placement) they share an L2.  Speed only.
     const int grp = blockIdx.x / (8 * PARTS), rr = blockIdx.x % (8 * PARTS);
     const int bh = grp * 8 + (rr & 7);
-    const int part = rr >> 3;                 // query tiles [8*part, 8*part+8) (PARTS = 2) / [4*part, 4*part+4) (PARTS = 4)
+    const int part = rr >> 3;                 // query tiles [8*part, 8*part+8) (TPW = 2) / [4*part, 4*part+4) (TPW = 1)
     if (bh >= BH) return;                     // whole workgroup (grid is padded to whole groups)
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
-    const f32x4* qg = reinterpret_cast<const f32x4*>(q) + (size_t)bh * NKB * 256;
-    const f32x4* kg = reinterpret_cast<const f32x4*>(k) + (size_t)bh * NKB * 256;
-    const f32x4* vg = reinterpret_cast<const f32x4*>(vT) + (size_t)bh * NKB * 256;
+    const f32x4* qg = reinterpret_cast<const f32x4*>(q) + (size_t)bh * NKBT * 256;
+    const f32x4* kg = reinterpret_cast<const f32x4*>(k) + (size_t)bh * NKBT * 256;
+    const f32x4* vg = reinterpret_cast<const f32x4*>(vT) + (size_t)bh * NKBT * 256;
     f32x4* og = reinterpret_cast<f32x4*>(o);
 
     // this wave DMAs K fragment {wave} and V^T fragment {wave} of every block (8 pieces / 4 waves)
@@ -277,16 +278,39 @@ __global__ __launch_bounds__(256, 2) void attn_fwd_packed_kernel(const float* __
         glds16_asm(kg + (2 * 4 + wave) * 64 + lane, slot2 + wave * 64);
         glds16_asm(vg + (2 * 4 + wave) * 64 + lane, slot2 + 256 + wave * 64);
     }
-    if constexpr (PARTS == 2) {
-        const int t0 = part * 8 + wave * 2;       // query tiles t0, t0+1 (tile 15 does not exist)
-        if (t0 + 1 < NKB)
-            attn_packed_body<2>(ring, qg, kg, vg, og, bh, t0, lane, wave);
-        else
-            attn_packed_body<1>(ring, qg, kg, vg, og, bh, t0, lane, wave);
+    if constexpr (TPW == 2) {
+        const int t0 = part * 8 + wave * 2;       // query tiles t0, t0+1
+        if (t0 + 1 < NKBT) {
+            attn_packed_body<2, NKBT>(ring, qg, kg, vg, og, bh, t0, lane, wave);
+        } else if constexpr (PARTS * 8 > NKBT + 1) {   // 800 tokens: 25 tiles in 32 slots, the waves past tile 24 repeat it
+            attn_packed_body<1, NKBT>(ring, qg, kg, vg, og, bh, t0 < NKBT ? t0 : NKBT - 1, lane, wave);
+        } else {                                       // (480: tile 15 does not exist, its wave holds tile 14 alone)
+            attn_packed_body<1, NKBT>(ring, qg, kg, vg, og, bh, t0, lane, wave);
+        }
     } else {
         const int t = part * 4 + wave;
-        attn_packed_body<1>(ring, qg, kg, vg, og, bh, t < NKB ? t : NKB - 1, lane, wave);
+        attn_packed_body<1, NKBT>(ring, qg, kg, vg, og, bh, t < NKBT ? t : NKBT - 1, lane, wave);
     }
+}
+
+template <int PARTS>
+__global__ __launch_bounds__(256, 2) void attn_fwd_packed_kernel(const float* __restrict__ q,
+                                                                 const float* __restrict__ k,
+                                                                 const float* __restrict__ vT,
+                                                                 float* __restrict__ o, int BH) {
+    attn_packed_head<PARTS, PARTS == 2 ? 2 : 1, NKB>(q, k, vT, o, BH);
+}
+
+// The wide token counts of the motion models (800 = 25 tiles, 1024 = 32): four workgroups per (sequence, head), two query
+// tiles per wave, the same body over 25 / 32 key blocks.  At 1024 every slot holds a tile; at 800 the last workgroup of a
+// head holds tile 24 alone in wave 0 and its other three waves repeat it (they must stream K / V with the workgroup anyway).
+template <int NKBT>
+__global__ __launch_bounds__(256, 2) void attn_fwd_packed_wide_kernel(const float* __restrict__ q,
+                                                                      const float* __restrict__ k,
+                                                                      const float* __restrict__ vT,
+                                                                      float* __restrict__ o, int BH) {
+    static_assert(NKBT > 24 && NKBT <= 32, "four workgroups of 8 tile slots");
+    attn_packed_head<4, 2, NKBT>(q, k, vT, o, BH);
 }
 
 // ------------------------------------------------------------------ persistent variant
@@ -567,6 +591,22 @@ __global__ __launch_bounds__(512) void attn_fwd_plain_kernel(const float* __rest
     }
 }
 
+// n_tok = 480: the launch above; 800 / 1024: the wide packed kernel (no persistent / small-launch form)
+int launch_attn_packed_n(const float* q, const float* k, const float* vT, float* o, int BH, int n_tok, hipStream_t st) {
+    if (n_tok == NTOK) return launch_attn_packed(q, k, vT, o, BH, st);
+    const int grid = ((BH + 7) / 8) * 32;
+    if (n_tok == 800) {
+        attn_fwd_packed_wide_kernel<25><<<grid, 256, ATT_LDS_BYTES, st>>>(q, k, vT, o, BH);
+    } else if (n_tok == 1024) {
+        attn_fwd_packed_wide_kernel<32><<<grid, 256, ATT_LDS_BYTES, st>>>(q, k, vT, o, BH);
+    } else {
+        set_error("attention: n_tok=%d (480, 800 or 1024)", n_tok);
+        return T2S_E_INVALID;
+    }
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
 int attn_init() {  // once, outside any stream capture
     static bool attr_set = false;
     if (!attr_set) {
@@ -595,4 +635,12 @@ extern "C" int t2s_attn_fwd_packed(const float* q, const float* k, const float* 
     T2S_REQUIRE(q && k && vT && o, "t2s_attn_fwd_packed: NULL pointer");
     T2S_REQUIRE(n_seq > 0, "t2s_attn_fwd_packed: n_seq=%d must be > 0", n_seq);
     return t2s::launch_attn_packed(q, k, vT, o, n_seq * t2s::NH, (hipStream_t)stream);
+}
+
+extern "C" int t2s_attn_fwd_packed_n(const float* q, const float* k, const float* vT, float* o, int n_seq, int n_tok,
+                                     void* stream) {
+    T2S_REQUIRE(q && k && vT && o, "t2s_attn_fwd_packed_n: NULL pointer");
+    T2S_REQUIRE(n_seq > 0 && n_seq <= (1 << 20), "t2s_attn_fwd_packed_n: n_seq=%d out of range", n_seq);
+    T2S_REQUIRE(n_tok == 480 || n_tok == 800 || n_tok == 1024, "t2s_attn_fwd_packed_n: n_tok=%d must be 480, 800 or 1024", n_tok);
+    return t2s::launch_attn_packed_n(q, k, vT, o, n_seq * t2s::NH, n_tok, (hipStream_t)stream);
 }

@@ -150,25 +150,25 @@ __global__ __launch_bounds__(256) void adaln_kernel(float* __restrict__ mod, con
     }
 }
 
-// patchify (transformer.py:166-172): token n = hh*32 + ww reads the 2x2 patch
+// patchify (transformer.py:166-172): token n = hh*32 + ww (ntok = 16 W tokens of a (64, W) latent) reads the 2x2 patch
 // in[b][2ww+j][2hh+i]; conv 1->4 (2x2, stride 2), Linear 4->128, + pos_embed.
 // Sequence s reads latent row s % B (both CFG branches share x).  Output fragment-major.
 __global__ __launch_bounds__(256) void patchify_kernel(
     const float* __restrict__ x, int B, float* __restrict__ h, int S, const float* __restrict__ cw,
     const float* __restrict__ cb, const float* __restrict__ pw, const float* __restrict__ pb,
-    const float* __restrict__ pos) {
+    const float* __restrict__ pos, int ntok) {
     // one thread per output float4; consecutive threads walk the fragment-major order
-    const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= S * NTOK * 32) return;
-    const int l = gid & 63, G = (gid >> 6) & 15, tile = gid >> 10;
+    const size_t gid = (size_t)blockIdx.x * blockDim.x + threadIdx.x;   // (65,536 sequences of 1024 tokens are 2^31 float4)
+    if (gid >= (size_t)S * ntok * 32) return;
+    const int l = (int)(gid & 63), G = (int)(gid >> 6) & 15, tile = (int)(gid >> 10);
     const int tokg = tile * 32 + (l & 31);
     const int c4 = 2 * G + (l >> 5);  // float4 column index: cols 4*c4 .. 4*c4+3
-    const int s = tokg / NTOK, n = tokg - s * NTOK;
+    const int s = tokg / ntok, n = tokg - s * ntok;
     // the SAME helpers as the row kernels' patchify prologue (t2s_rows.h): explicit fmaf chains, so the two forms agree bit for
     // bit whatever the compiler would contract on its own (tests/test_hip_contracts.py runs both)
     struct { const float* p_lat; int p_B; const float *p_cw, *p_cb; } pa{x, B, cw, cb};
     float cv[4];
-    patch_conv(pa, s, n, cv);
+    patch_conv(pa, s, n, cv, ntok / 16);
     f32x4 o;
 #pragma unroll
     for (int e = 0; e < 4; ++e) {
@@ -180,9 +180,9 @@ __global__ __launch_bounds__(256) void patchify_kernel(
 
 // fragment-major (rows,128) -> row-major, for the test tap
 __global__ void unfrag128_kernel(const float* __restrict__ src, float* __restrict__ dst, int rows) {
-    const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= rows * D) return;
-    const int row = idx >> 7, col = idx & 127;
+    const size_t idx = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (idx >= (size_t)rows * D) return;
+    const int row = (int)(idx >> 7), col = (int)(idx & 127);
     dst[idx] = src[frag_index(row, col, D)];
 }
 
@@ -235,10 +235,14 @@ static_assert(sizeof(t2s_dit_weights) == sizeof(void*) * T2S_DIT_N_TENSORS, "t2s
 // (hipMemGetAddressRange; a pointer HIP cannot place is passed through: nothing known, nothing refused).  An undersized
 // tensor is T2S_E_INVALID here, not a memory fault in a pack kernel (round 4: a 480 x 128 dummy behind the (768,128) adaLN
 // matrix read 148 KB past its buffer and faulted only when that happened to end an allocator segment).
-int check_weights(const t2s_dit_weights* w, const uint64_t* n_floats, bool ranges) {
+constexpr int POS_EMBED_ENTRY = 4;   // TOP_NEED's one entry that follows the latent width: 16 W rows
+bool latent_w_ok(int latent_w) { return latent_w == 30 || latent_w == 50 || latent_w == 64; }
+
+int check_weights(const t2s_dit_weights* w, const uint64_t* n_floats, bool ranges, int latw = LATW) {
     const float* const* ptrs = reinterpret_cast<const float* const*>(w);
     for (int i = 0; i < T2S_DIT_N_TENSORS; ++i) {
-        const WeightNeed& need = i < 10 ? TOP_NEED[i] : BLK_NEED[(i - 10) % 10];
+        WeightNeed need = i < 10 ? TOP_NEED[i] : BLK_NEED[(i - 10) % 10];
+        if (i == POS_EMBED_ENTRY) need.floats = (size_t)16 * latw * D;
         const int blk = i < 10 ? -1 : (i - 10) / 10;
         char name[96];
         if (blk < 0) snprintf(name, sizeof(name), "%s", need.name);
@@ -270,7 +274,7 @@ int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
     cp(h->conv_b, w->conv_b, 4);
     cp(h->patch_w, w->patch_w, 128 * 4);
     cp(h->patch_b, w->patch_b, 128);
-    cp(h->pos, w->pos_embed, NTOK * D);
+    cp(h->pos, w->pos_embed, h->ntok() * D);
     cp(h->ln_w, w->ln_w, D);
     cp(h->ln_b, w->ln_b, D);
     cp(h->out_w, w->out_w, 4 * D);
@@ -316,7 +320,8 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
                 int temb_rows, const int* step_ptr, const float* text, float* out0, float* out1,
                 int split, hipStream_t st, bool keep_stream = true, int ws_seq0 = 0, ModTable mt = ModTable()) {
     int rc;
-    const size_t tok0 = (size_t)ws_seq0 * NTOK * D;
+    const int ntok = h->ntok();
+    const size_t tok0 = (size_t)ws_seq0 * ntok * D;
     float* const w_h = h->h + tok0;
     float* const w_q = h->q + tok0;
     float* const w_k = h->k + tok0;
@@ -348,13 +353,13 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
     static const bool patch_launch = getenv("T2S_PATCHIFY_KERNEL") && atoi(getenv("T2S_PATCHIFY_KERNEL")) != 0;
     const bool patch_fused = !patch_launch;
     if (!patch_fused) {
-        const int threads = in_seqs * NTOK * 32;
+        const size_t threads = (size_t)in_seqs * ntok * 32;
         TimeScope ts(h, TC_OTHER, st);
-        patchify_kernel<<<(threads + 255) / 256, 256, 0, st>>>(x, B, tokens, in_seqs, h->conv_w, h->conv_b,
-                                                               h->patch_w, h->patch_b, h->pos);
+        patchify_kernel<<<(unsigned)((threads + 255) / 256), 256, 0, st>>>(x, B, tokens, in_seqs, h->conv_w, h->conv_b,
+                                                               h->patch_w, h->patch_b, h->pos, ntok);
         T2S_LAUNCH_CHECK();
     }
-    const int M = S * NTOK;
+    const int M = S * ntok;
     // Row-local chain as one register-resident kernel per block (t2s_rows.h):
     //   rows<qkv only>(block 0) ; { attention(i) ; rows<proj+MLP of i, qkv of i+1> } x 4
     // Small launches run the row chain on 16-token tiles (t2s_rows16.h; bit-identical results): up to 100 sequences, i.e.
@@ -397,13 +402,14 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
         if (blk >= 0) { a.Wp = h->proj_p[blk]; a.W1 = h->fc1_p[blk]; a.W2c = h->fc2_c[blk]; }
         if (qkv_blk >= 0) a.Wq = h->qkv_p[qkv_blk];
         a.k = w_k; a.v = w_v;
+        a.tps = ntok == NTOK ? 0 : ntok / 32;   // wide handle: the kernels that take the tiles per sequence at run time
         if (!use16) return launch_dit_rows<DO_MLP, DO_QKV>(a, st);
         if (blk >= 0) { a.Wp = h->proj_p16[blk]; a.W1 = h->fc1_p16[blk]; a.W2c = h->fc2_c16[blk]; }
         if (qkv_blk >= 0) a.Wq = h->qkv_p16[qkv_blk];
         return launch_dit_rows16<DO_MLP, DO_QKV>(a, st);
     };
     auto launch_attention = [&] {
-        return pl ? launch_attn_xn(pl->np, w_q, w_kp, w_vp, w_ao, S * NH, st) : launch_attn_packed(w_q, w_k, w_v, w_ao, S * NH, st);
+        return pl ? launch_attn_xn(pl->np, w_q, w_kp, w_vp, w_ao, S * NH, st) : launch_attn_packed_n(w_q, w_k, w_v, w_ao, S * NH, ntok, st);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -461,20 +467,26 @@ const char* t2s_last_error(void) { return t2s::g_err; }
 // 0.3: + t2s_philox_uniform, t2s_dit_forward_cfg_rows, t2s_sampler_set_loop_graph (additions only)
 // 0.4: + t2s_time_embedding_freqs, t2s_dit_weights_check, t2s_mse_ws, t2s_vae_update_weights, t2s_vae_encode_backward (additions only)
 // 0.5: + t2s_mlp_pack, t2s_mlp_forward, t2s_mlp_backward (additions only)
-const char* t2s_version(void) { return "t2s 0.5 gfx950 fp32-mfma"; }
+// 0.6: + t2s_dit_create_w, t2s_dit_latent_w, t2s_dit_weights_check_w, t2s_attn_fwd_packed_n, t2s_lms_step_n (additions only)
+const char* t2s_version(void) { return "t2s 0.6 gfx950 fp32-mfma"; }
 
-int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out) {
+int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out) { return t2s_dit_create_w(w, LATW, max_seqs, out); }
+
+int t2s_dit_create_w(const t2s_dit_weights* w, int latent_w, int max_seqs, t2s_dit** out) {
     T2S_REQUIRE(w && out, "t2s_dit_create: NULL argument");
+    T2S_REQUIRE(latent_w_ok(latent_w), "t2s_dit_create_w: latent_w=%d must be 30, 50 or 64 (480, 800 or 1024 tokens)", latent_w);
     T2S_REQUIRE(max_seqs > 0 && max_seqs <= 65536, "t2s_dit_create: max_seqs=%d out of range", max_seqs);
     {
-        const int rc_w = check_weights(w, nullptr, /*ranges=*/true);
+        const int rc_w = check_weights(w, nullptr, /*ranges=*/true, latent_w);
         if (rc_w != T2S_OK) return rc_w;
     }
     t2s_dit* h = new t2s_dit();
     h->max_seqs = max_seqs;
+    h->latw = latent_w;
+    const int ntok = h->ntok();   // every size below follows the handle's token count
     ArenaPlan p;
     const size_t o_conv_w = p.take(16), o_conv_b = p.take(4), o_patch_w = p.take(512),
-                 o_patch_b = p.take(128), o_pos = p.take(NTOK * D), o_ln_w = p.take(D),
+                 o_patch_b = p.take(128), o_pos = p.take((size_t)ntok * D), o_ln_w = p.take(D),
                  o_ln_b = p.take(D), o_out_w = p.take(4 * D), o_out_b = p.take(4),
                  o_freqs = p.take(64), o_ada_b = p.take(MODROW), o_ada_p = p.take((size_t)MODROW * D);
     size_t o_qkv_b[NBLK], o_proj_b[NBLK], o_fc1_b[NBLK], o_fc2_b[NBLK];
@@ -511,9 +523,9 @@ int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out) {
         h->fc1_p16[i] = reinterpret_cast<f32x4*>(A + o_fc1_p16[i]);
         h->fc2_c16[i] = reinterpret_cast<f32x4*>(A + o_fc2_c16[i]);
     }
-    const size_t S = (size_t)max_seqs, tokD = S * NTOK * D;
+    const size_t S = (size_t)max_seqs, tokD = S * ntok * D;
     float** bufs[] = {&h->h, &h->q, &h->k, &h->v, &h->ao, &h->mod, &h->h0};
-    const size_t sizes[] = {tokD, tokD, tokD, tokD, tokD, S * MODROW, (S / 2 + 1) * NTOK * D};
+    const size_t sizes[] = {tokD, tokD, tokD, tokD, tokD, S * MODROW, (S / 2 + 1) * ntok * D};
     for (int i = 0; i < 7; ++i) {
         e = hipMalloc(bufs[i], sizes[i] * sizeof(float));
         if (e != hipSuccess) {
@@ -541,7 +553,7 @@ int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out) {
 
 int t2s_dit_update_weights(t2s_dit* h, const t2s_dit_weights* w, void* stream) {
     T2S_REQUIRE(h && w, "t2s_dit_update_weights: NULL argument");
-    const int rc_w = check_weights(w, nullptr, /*ranges=*/true);
+    const int rc_w = check_weights(w, nullptr, /*ranges=*/true, h->latw);
     if (rc_w != T2S_OK) return rc_w;
     const int rc = upload_weights(h, w, (hipStream_t)stream);
     // a later first t2s_dit_set_math(T2S_MATH_BF16X3 / _BF16) packs from these copies on the set-up stream: leave it something to wait for
@@ -597,6 +609,8 @@ int alloc_bf_planes(t2s_dit* h, BfPlanes& out) {
 int t2s_dit_set_math(t2s_dit* h, int math) {
     T2S_REQUIRE(h, "t2s_dit_set_math: NULL handle");
     T2S_REQUIRE(math == T2S_MATH_F32 || math == T2S_MATH_BF16X3 || math == T2S_MATH_BF16, "t2s_dit_set_math: unknown mode %d", math);
+    T2S_REQUIRE(math == T2S_MATH_F32 || h->latw == LATW, "t2s_dit_set_math: a handle of latent width %d runs T2S_MATH_F32 only (bf16x3 / bf16 exist at width 30)",
+                h->latw);
     if (math != T2S_MATH_F32 && h->bf[math - T2S_MATH_BF16X3].w == nullptr)
         if (int rc = alloc_bf_planes(h, h->bf[math - T2S_MATH_BF16X3])) return rc;
     h->math = math;
@@ -617,6 +631,7 @@ void t2s_dit_destroy(t2s_dit* h) {
 }
 
 int t2s_dit_max_seqs(const t2s_dit* h) { return h ? h->max_seqs : 0; }
+int t2s_dit_latent_w(const t2s_dit* h) { return h ? h->latw : 0; }
 
 int t2s_time_embedding(const t2s_dit* h, const float* t, float* out, int B, void* stream) {
     T2S_REQUIRE(h && t && out && B > 0, "t2s_time_embedding: bad argument");
@@ -637,6 +652,14 @@ int t2s_dit_weights_check(const t2s_dit_weights* w, const uint64_t* n_floats, in
     T2S_REQUIRE(!n_floats || n_entries == T2S_DIT_N_TENSORS, "t2s_dit_weights_check: n_entries=%d, t2s_dit_weights has %d tensors", n_entries,
                 T2S_DIT_N_TENSORS);
     return check_weights(w, n_floats, /*ranges=*/true);
+}
+
+int t2s_dit_weights_check_w(const t2s_dit_weights* w, int latent_w, const uint64_t* n_floats, int n_entries) {
+    T2S_REQUIRE(w, "t2s_dit_weights_check_w: NULL weights");
+    T2S_REQUIRE(latent_w_ok(latent_w), "t2s_dit_weights_check_w: latent_w=%d must be 30, 50 or 64", latent_w);
+    T2S_REQUIRE(!n_floats || n_entries == T2S_DIT_N_TENSORS, "t2s_dit_weights_check_w: n_entries=%d, t2s_dit_weights has %d tensors", n_entries,
+                T2S_DIT_N_TENSORS);
+    return check_weights(w, n_floats, /*ranges=*/true, latent_w);
 }
 
 int t2s_dit_forward(t2s_dit* h, const float* x, const float* temb, int temb_rows, const float* text,
@@ -703,8 +726,8 @@ int t2s_dit_timing_end_ex(t2s_dit* h, double* out, int n_classes) {
 
 int t2s_dit_read_stream(const t2s_dit* h, float* out, int S, void* stream) {
     T2S_REQUIRE(h && out && S > 0 && S <= h->max_seqs, "t2s_dit_read_stream: bad argument");
-    const int total = S * NTOK * D;
-    unfrag128_kernel<<<(total + 255) / 256, 256, 0, (hipStream_t)stream>>>(h->h, out, S * NTOK);
+    const size_t total = (size_t)S * h->ntok() * D;
+    unfrag128_kernel<<<(unsigned)((total + 255) / 256), 256, 0, (hipStream_t)stream>>>(h->h, out, S * h->ntok());
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

@@ -10,6 +10,9 @@ struct t2s_train_ws;   // training workspace (t2s_train.hip), created on first u
 
 struct t2s_dit {
     int max_seqs = 0;
+    int latw = t2s::LATW;        // latent width W: the latent is (64, W), a sequence 16 W tokens (30 / 50 / 64: 480 / 800 / 1024)
+    int ntok() const { return 16 * latw; }
+    int lat() const { return t2s::LATC * latw; }
     // parameters (device)
     float* arena = nullptr;  // all parameters, offsets below
     float *conv_w, *conv_b, *patch_w, *patch_b, *pos, *ln_w, *ln_b, *out_w, *out_b, *freqs;
@@ -63,6 +66,7 @@ struct TimeScope {   // records an event pair around the launches issued in its 
 // t2s_attn.hip
 int attn_init();
 int launch_attn_packed(const float* q, const float* k, const float* vT, float* o, int BH, hipStream_t st);
+int launch_attn_packed_n(const float* q, const float* k, const float* vT, float* o, int BH, int n_tok, hipStream_t st);
 // t2s_attn_x3.hip; np = 3: bf16x3, np = 1: bf16 (k / vT: np planes)
 int attn_xn_init(int np);
 int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st);

@@ -67,7 +67,7 @@ struct RowArgs {
     // from the latent (patchify, transformer.py:166-172: conv 2x2 stride 2 -> Linear 4 -> 128, + pos_embed) and, for the
     // in_seqs distinct sequences, written to x_in's buffer for block 0's <proj + MLP> kernel -- the stand-alone patchify
     // launch (and one read of its output) leaves the sampling loop's critical path
-    const float* p_lat;   // (p_B, 64, 30); sequence s reads latent row s % p_B
+    const float* p_lat;   // (p_B, 64, W), W = 30 (wide kernels: 2 tps); sequence s reads latent row s % p_B
     int p_B;
     const float *p_cw, *p_cb, *p_pw, *p_pb, *p_pos;   // conv.weight (4,1,2,2) / bias (4), patch_emb.weight (128,4) / bias, pos_embed (480,128)
     const float* ao;   // (M,128) attention output (pre-proj), fragment-major
@@ -76,7 +76,8 @@ struct RowArgs {
     // row b): sequence s of this pass reads step *mod_step, row 0 if s < mod_uncond, else 1 + mod_row0 + (s - mod_uncond)
     const int* mod_step;
     int mod_rows, mod_uncond, mod_row0;
-    int M;             // S*480 (multiple of 32)
+    int M;             // S*480 (multiple of 32); the wide kernels: S * 32 * tps
+    int tps;           // wide kernels only: 32-token tiles per sequence, 25 or 32 (latent width 2 tps: 800 / 1024 tokens)
     int blk;           // block whose proj+MLP run (ignored if !DO_MLP)
     int qkv_blk;       // block whose LN1/modulate/qkv run (ignored if !DO_QKV)
     const f32x4 *Wp, *W1, *W2c, *Wq;    // packed weights; W2c is fc2 in chunk order [c][nt][g]
@@ -85,15 +86,16 @@ struct RowArgs {
 };
 
 // patchify of one token (shared by the 32- and the 16-token kernel: the same expression, hence the same bits)
+// latw = latent width W: the latent row is (64, W), token n = hh * 32 + ww with hh < W / 2
 template <class Args>   // RowArgs or RowArgsX3 (t2s_rows_x3.h): the same p_* fields
-__device__ __forceinline__ void patch_conv(const Args& a, int seq, int n, float (&cv)[4]) {
+__device__ __forceinline__ void patch_conv(const Args& a, int seq, int n, float (&cv)[4], int latw = LATW) {
     const int hh = n >> 5, ww = n & 31;
-    const float* xin = a.p_lat + (size_t)(seq % a.p_B) * LAT;
+    const float* xin = a.p_lat + (size_t)(seq % a.p_B) * (LATC * latw);
     float px[4];
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
-        for (int j = 0; j < 2; ++j) px[i * 2 + j] = xin[(2 * ww + j) * LATW + 2 * hh + i];
+        for (int j = 0; j < 2; ++j) px[i * 2 + j] = xin[(2 * ww + j) * latw + 2 * hh + i];
 #pragma unroll
     for (int c = 0; c < 4; ++c) {
         float acc = a.p_cw[c * 4 + 0] * px[0];
@@ -247,8 +249,10 @@ __device__ __forceinline__ void ktile_mfma(const f32x4* __restrict__ wb, BOP&& b
         __builtin_amdgcn_s_barrier();                                    \
     } while (0)
 
-template <bool DO_MLP, bool DO_QKV>
-__global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(const RowArgs a) {
+// TPS = 32-token tiles per sequence: 15 (480 tokens, compile-time index arithmetic) or 0 = RowArgs::tps at run time (the wide
+// kernels).  The latent width is 2 TPS.  It enters the prologue's and the stores' addresses only, never the chunk loops.
+template <bool DO_MLP, bool DO_QKV, int TPS>
+__device__ __forceinline__ void dit_rows_body(const RowArgs& a) {
     extern __shared__ __attribute__((aligned(16))) f32x4 wring[];  // [ROWS_SLOTS][1024]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);   // provably wave-uniform: scalar addressing
@@ -257,7 +261,8 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
     int tile = blockIdx.x * ROWS_NW + wave;       // 32-token tile of this wave
     const bool active = tile < n_tiles;           // tail waves compute on a clamped tile, store nothing
     if (!active) tile = n_tiles - 1;
-    const int seq = (tile * 32) / NTOK;           // 480 = 15*32: a tile never straddles sequences
+    const int tps = TPS ? TPS : a.tps, latw = 2 * tps;
+    const int seq = tile / tps;                   // 16 W tokens = W / 2 tiles: a tile never straddles sequences
     const float* __restrict__ modrow = mod_row_of(a, seq);
 
     constexpr int N_CHUNKS = (DO_MLP ? 20 : 0) + (DO_QKV ? 12 : 0);
@@ -361,7 +366,7 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
 
     // residual stream of this lane's token, accumulator layout: x[nt][4g+e] = X[row][32nt+8g+4half+e]
     f32x16 x[4];
-    const int tile_src = tile - (seq - seq % a.in_seqs) * (NTOK / 32);   // same tile of sequence seq % in_seqs
+    const int tile_src = tile - (seq - seq % a.in_seqs) * tps;   // same tile of sequence seq % in_seqs
     bool generated = false;
     if constexpr (!DO_MLP) {
         if (a.p_lat != nullptr) {
@@ -370,9 +375,9 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
             for (int i = threadIdx.x; i < 512; i += 64 * ROWS_NW) cb[i] = a.p_pw[i];
             *reinterpret_cast<f32x4*>(cm + 256 + (lane & 31) * 4) = *reinterpret_cast<const f32x4*>(a.p_pb + (lane & 31) * 4);
             __syncthreads();
-            const int n = (tile - seq * (NTOK / 32)) * 32 + (lane & 31);
+            const int n = (tile - seq * tps) * 32 + (lane & 31);
             float cv[4];
-            patch_conv(a, seq, n, cv);
+            patch_conv(a, seq, n, cv, latw);
             const float* posrow = a.p_pos + (size_t)n * D;
 #pragma unroll
             for (int G = 0; G < 16; ++G) {
@@ -562,20 +567,21 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
             const float f0 = fl[0] + xhalf(fl[0]), f1 = fl[1] + xhalf(fl[1]);
             const float f2 = fl[2] + xhalf(fl[2]), f3 = fl[3] + xhalf(fl[3]);
             if (active) {   // lane half 0 writes patch outputs p = 0,1; half 1 writes p = 2,3
-                const int n = (tile - seq * (NTOK / 32)) * 32 + (lane & 31);
+                const int n = (tile - seq * tps) * 32 + (lane & 31);
                 const int hh = n >> 5, ww = n & 31;
-                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * LAT : a.out1 + (size_t)(seq - a.split) * LAT;
+                const int lat = LATC * latw;
+                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * lat : a.out1 + (size_t)(seq - a.split) * lat;
                 // p = 2 half + q2 -> element (2 ww + q2, 2 hh + half); selects, not an indexed array (that went to scratch)
                 const float ob0 = half ? a.f_ob[2] : a.f_ob[0], ob1 = half ? a.f_ob[3] : a.f_ob[1];
-                dst[(2 * ww + 0) * LATW + 2 * hh + half] = (half ? f2 : f0) + ob0;
-                dst[(2 * ww + 1) * LATW + 2 * hh + half] = (half ? f3 : f1) + ob1;
+                dst[(2 * ww + 0) * latw + 2 * hh + half] = (half ? f2 : f0) + ob0;
+                dst[(2 * ww + 1) * latw + 2 * hh + half] = (half ? f3 : f1) + ob1;
             }
         }
     }
     if constexpr (DO_QKV) {
         f32x16 xm[4];
         ln_modulate(x, xm, cm, cm + D, half, 1e-6f);
-        const int tile_in_seq = tile - seq * (NTOK / 32);
+        const int tile_in_seq = tile - seq * tps;
 #pragma unroll 1
         for (int t = 0; t < 12; ++t) {  // output tile t = which*4 + head
             prefetch(ci);
@@ -583,7 +589,7 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
             const int which = t >> 2, head = t & 3;
             float* base = which == 0 ? a.q : (which == 1 ? a.k : a.v);
             f32x4* dst = reinterpret_cast<f32x4*>(base) +
-                         (((size_t)seq * NH + head) * (NTOK / 32) + tile_in_seq) * 4 * 64 + lane;
+                         (((size_t)seq * NH + head) * tps + tile_in_seq) * 4 * 64 + lane;
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -632,13 +638,26 @@ __global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(con
 }
 
 template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_kernel(const RowArgs a) {
+    dit_rows_body<DO_MLP, DO_QKV, NTOK / 32>(a);
+}
+// the same body for the wide latents (800 / 1024 tokens): tiles per sequence from RowArgs::tps
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(64 * ROWS_NW, 8 / ROWS_NW) void dit_rows_wide_kernel(const RowArgs a) {
+    dit_rows_body<DO_MLP, DO_QKV, 0>(a);
+}
+
+template <bool DO_MLP, bool DO_QKV>
 inline int launch_dit_rows(const RowArgs& a, hipStream_t st) {
     if (a.M <= 0 || a.M % 32 != 0) {
         set_error("dit_rows: M=%d must be a positive multiple of 32", a.M);
         return T2S_E_INVALID;
     }
     const int tiles = a.M / 32;
-    dit_rows_kernel<DO_MLP, DO_QKV><<<(tiles + ROWS_NW - 1) / ROWS_NW, 64 * ROWS_NW, ROWS_LDS_BYTES, st>>>(a);
+    if (a.tps != 0)
+        dit_rows_wide_kernel<DO_MLP, DO_QKV><<<(tiles + ROWS_NW - 1) / ROWS_NW, 64 * ROWS_NW, ROWS_LDS_BYTES, st>>>(a);
+    else
+        dit_rows_kernel<DO_MLP, DO_QKV><<<(tiles + ROWS_NW - 1) / ROWS_NW, 64 * ROWS_NW, ROWS_LDS_BYTES, st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -648,6 +667,9 @@ inline int dit_rows_init() {
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_wide_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_wide_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows_wide_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     return T2S_OK;
 }
 

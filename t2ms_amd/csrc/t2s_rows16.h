@@ -177,8 +177,8 @@ __device__ __forceinline__ void kchunk16(const f32x4* __restrict__ wb, const f32
     }
 }
 
-template <bool DO_MLP, bool DO_QKV>
-__global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
+template <bool DO_MLP, bool DO_QKV, int TPS>   // TPS as in t2s_rows.h: 15, or 0 = RowArgs::tps
+__device__ __forceinline__ void dit_rows16_body(const RowArgs& a) {
     extern __shared__ __attribute__((aligned(16))) f32x4 wring[];  // [ROWS_SLOTS][1024]
     const int lane = threadIdx.x & 63;
     const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
@@ -188,8 +188,9 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
     const bool active = t16 < n16;                // tail waves compute on a clamped tile, store nothing
     if (!active) t16 = n16 - 1;
     const int tile = t16 >> 1, row = 16 * (t16 & 1) + tok;
-    const int seq = (tile * 32) / NTOK;
-    const int tile_in_seq = tile - seq * (NTOK / 32);
+    const int tps = TPS ? TPS : a.tps, latw = 2 * tps;
+    const int seq = tile / tps;
+    const int tile_in_seq = tile - seq * tps;
     const float* __restrict__ modrow = mod_row_of(a, seq);
 
     constexpr int N_CHUNKS = (DO_MLP ? 20 : 0) + (DO_QKV ? 12 : 0);
@@ -282,7 +283,7 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
 
     // residual stream of this lane's token
     f32x4 x[8];
-    const int tile_src = tile - (seq - seq % a.in_seqs) * (NTOK / 32);   // same tile of sequence seq % in_seqs
+    const int tile_src = tile - (seq - seq % a.in_seqs) * tps;   // same tile of sequence seq % in_seqs
     bool generated = false;
     if constexpr (!DO_MLP) {
         if (a.p_lat != nullptr) {
@@ -293,7 +294,7 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
             __syncthreads();
             const int n = tile_in_seq * 32 + row;
             float cv[4];
-            patch_conv(a, seq, n, cv);
+            patch_conv(a, seq, n, cv, latw);
             const float* posrow = a.p_pos + (size_t)n * D;
 #pragma unroll
             for (int mt = 0; mt < 8; ++mt) {
@@ -436,9 +437,10 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
             if (active) {
                 const int n = tile_in_seq * 32 + row;
                 const int hh = n >> 5, ww = n & 31;
-                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * LAT : a.out1 + (size_t)(seq - a.split) * LAT;
+                const int lat = LATC * latw;
+                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * lat : a.out1 + (size_t)(seq - a.split) * lat;
                 const float v = g == 0 ? ft[0] : (g == 1 ? ft[1] : (g == 2 ? ft[2] : ft[3]));
-                dst[(2 * ww + (g & 1)) * LATW + 2 * hh + (g >> 1)] = v + a.f_ob[g];
+                dst[(2 * ww + (g & 1)) * latw + 2 * hh + (g >> 1)] = v + a.f_ob[g];
             }
         }
     }
@@ -453,7 +455,7 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
             const f32x4* wb = wring + (ci % ROWS_SLOTS) * ROWS_CHUNK_F4 + lane;
             const int which = t >> 2, head = t & 3;
             float* base = which == 0 ? a.q : (which == 1 ? a.k : a.v);
-            f32x4* dst = reinterpret_cast<f32x4*>(base) + (((size_t)seq * NH + head) * (NTOK / 32) + tile_in_seq) * 4 * 64;
+            f32x4* dst = reinterpret_cast<f32x4*>(base) + (((size_t)seq * NH + head) * tps + tile_in_seq) * 4 * 64;
             f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
             if (which < 2) {
                 // q / k tile, transposed product: lane = token, registers = features (16-layout of the head's 32)
@@ -490,13 +492,25 @@ __global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
 }
 
 template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) void dit_rows16_kernel(const RowArgs a) {
+    dit_rows16_body<DO_MLP, DO_QKV, NTOK / 32>(a);
+}
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) void dit_rows16_wide_kernel(const RowArgs a) {
+    dit_rows16_body<DO_MLP, DO_QKV, 0>(a);
+}
+
+template <bool DO_MLP, bool DO_QKV>
 inline int launch_dit_rows16(const RowArgs& a, hipStream_t st) {
     if (a.M <= 0 || a.M % 32 != 0) {
         set_error("dit_rows16: M=%d must be a positive multiple of 32", a.M);
         return T2S_E_INVALID;
     }
     const int n16 = a.M / 16;
-    dit_rows16_kernel<DO_MLP, DO_QKV><<<(n16 + 3) / 4, 256, ROWS_LDS_BYTES, st>>>(a);
+    if (a.tps != 0)
+        dit_rows16_wide_kernel<DO_MLP, DO_QKV><<<(n16 + 3) / 4, 256, ROWS_LDS_BYTES, st>>>(a);
+    else
+        dit_rows16_kernel<DO_MLP, DO_QKV><<<(n16 + 3) / 4, 256, ROWS_LDS_BYTES, st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -505,6 +519,9 @@ inline int dit_rows16_init() {
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_wide_kernel<false, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_wide_kernel<true, true>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
+    T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(dit_rows16_wide_kernel<true, false>), hipFuncAttributeMaxDynamicSharedMemorySize, ROWS_LDS_BYTES));
     return T2S_OK;
 }
 

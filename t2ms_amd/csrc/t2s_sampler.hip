@@ -122,6 +122,7 @@ struct UpdateArgs {
     uint32_t stream_id;
     uint32_t row0;
     int B;
+    int qpr;              // quads (float4) per row: 64 W / 4 of the (64, W) latent -- 480 at W = 30
     int noise_rows;       // rows per step of the injected-noise array (>= B: a lane steps a row range of the batch)
     LoopState* advance;   // sampling loop: the last workgroup increments the lane's loop index (advance_step_when_last)
     // per-row tables (t2s_sampler_set_rows), this lane's slice: used where bit ROWS_SEED / ROWS_KEY / ROWS_CFG of loop->rows
@@ -160,7 +161,7 @@ __device__ __forceinline__ Step resolve_step(const UpdateArgs& a) {
         s.row0 = (uint32_t)a.loop->row0;
         s.rows = a.loop->rows;
         s.stream_id = (uint32_t)s.index;
-        if (s.noise) s.noise += (size_t)s.index * a.noise_rows * LAT;
+        if (s.noise) s.noise += (size_t)s.index * a.noise_rows * a.qpr * 4;
     }
     return s;
 }
@@ -246,7 +247,7 @@ struct LmsUpdate {
 constexpr int STEP_MAX_WGS = 96;   // see launch_update
 template <class Update>
 __global__ __launch_bounds__(256) void update_kernel(const UpdateArgs a) {
-    constexpr int QPR = LAT / 4;
+    const int QPR = a.qpr;
     const Step s = resolve_step(a);
     const Update update(a, s.index);
     for (int idx = blockIdx.x * blockDim.x + threadIdx.x; idx < a.B * QPR; idx += gridDim.x * blockDim.x) {
@@ -379,7 +380,7 @@ using namespace t2s;
 // atomics serialise at ~25 ns each -- 480 of them (one per 256 quads at B = 256) made this 6 us kernel 18 us.  The result
 // of a quad does not depend on the grid.
 static int launch_update(int mode, const UpdateArgs& a, hipStream_t st) {
-    const int wgs = (a.B * (LAT / 4) + 255) / 256;
+    const int wgs = (a.B * a.qpr + 255) / 256;
     const int grid = (a.advance && wgs > STEP_MAX_WGS) ? STEP_MAX_WGS : wgs;
     switch (mode) {
     case T2S_MODE_DDPM: update_kernel<DdpmUpdate><<<grid, 256, 0, st>>>(a); break;
@@ -430,26 +431,33 @@ extern "C" int t2s_ddpm_step(float* x, const float* eps_u, const float* eps_c, c
     T2S_REQUIRE(B > 0 && t_index >= 0 && (long long)B * LAT < (1ll << 31), "t2s_ddpm_step: B=%d t_index=%d", B, t_index);
     UpdateArgs a{};
     a.x = x; a.pred_u = eps_u; a.pred_c = eps_c; a.noise = noise; a.coef = coef;
-    a.index = t_index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
+    a.index = t_index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B; a.qpr = LAT / 4;
     return launch_update(T2S_MODE_DDPM, a, (hipStream_t)stream);
+}
+
+extern "C" int t2s_lms_step_n(float* x, float* hist, const float* pred_u, const float* pred_c, const float* noise,
+                              const float* coef, int index, float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B,
+                              int row_elems, void* stream) {
+    T2S_REQUIRE(x && hist && pred_u && coef, "t2s_lms_step: NULL argument");
+    T2S_REQUIRE(row_elems > 0 && row_elems % 4 == 0, "t2s_lms_step: row_elems=%d must be a positive multiple of 4", row_elems);
+    T2S_REQUIRE(B > 0 && index >= 0 && (long long)B * row_elems < (1ll << 31), "t2s_lms_step: B=%d index=%d", B, index);
+    UpdateArgs a{};
+    a.x = x; a.hist = hist; a.pred_u = pred_u; a.pred_c = pred_c; a.noise = noise; a.coef = coef;
+    a.index = index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B; a.qpr = row_elems / 4;
+    return launch_update(T2S_MODE_LMS, a, (hipStream_t)stream);
 }
 
 extern "C" int t2s_lms_step(float* x, float* hist, const float* pred_u, const float* pred_c, const float* noise,
                             const float* coef, int index, float cfg, uint64_t seed, uint32_t stream_id, uint32_t row0, int B,
                             void* stream) {
-    T2S_REQUIRE(x && hist && pred_u && coef, "t2s_lms_step: NULL argument");
-    T2S_REQUIRE(B > 0 && index >= 0 && (long long)B * LAT < (1ll << 31), "t2s_lms_step: B=%d index=%d", B, index);
-    UpdateArgs a{};
-    a.x = x; a.hist = hist; a.pred_u = pred_u; a.pred_c = pred_c; a.noise = noise; a.coef = coef;
-    a.index = index; a.cfg = cfg; a.seed = seed; a.stream_id = stream_id; a.row0 = row0; a.B = B;
-    return launch_update(T2S_MODE_LMS, a, (hipStream_t)stream);
+    return t2s_lms_step_n(x, hist, pred_u, pred_c, noise, coef, index, cfg, seed, stream_id, row0, B, LAT, stream);
 }
 
 extern "C" int t2s_rf_step(float* x, const float* v_u, const float* v_c, float cfg, float dt, int B, void* stream) {
     T2S_REQUIRE(x && v_u, "t2s_rf_step: NULL argument");
     T2S_REQUIRE(B > 0 && (long long)B * LAT < (1ll << 31), "t2s_rf_step: B=%d", B);
     UpdateArgs a{};
-    a.x = x; a.pred_u = v_u; a.pred_c = v_c; a.cfg = cfg; a.dt = dt; a.B = B;
+    a.x = x; a.pred_u = v_u; a.pred_c = v_c; a.cfg = cfg; a.dt = dt; a.B = B; a.qpr = LAT / 4;
     return launch_update(T2S_MODE_RF, a, (hipStream_t)stream);
 }
 
@@ -526,6 +534,7 @@ extern "C" int t2s_rf_create_flow(const float* x1, const float* x0, const float*
 
 // ---------------------------------------------------------------- fused sampling loop
 struct t2s_sampler {
+    int lat = LAT;                // elements of a latent row: 64 W, W = t2s_dit_latent_w(dit)
     t2s_dit* dit = nullptr;
     t2s_vae* vae = nullptr;
     t2s_sample_config cfg{};
@@ -683,21 +692,22 @@ int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise
                  int n) {
     const t2s_sample_config& c = s->cfg;
     LoopState* loop = s->step + LANE_STATES * lane;
-    float* xl = x + (size_t)r0 * LAT;
-    float* eu = s->eps_u + (size_t)r0 * LAT;
-    float* ec = s->eps_c + (size_t)r0 * LAT;
+    const size_t lat = (size_t)s->lat;   // the sampler's row length
+    float* xl = x + (size_t)r0 * lat;
+    float* eu = s->eps_u + (size_t)r0 * lat;
+    float* ec = s->eps_c + (size_t)r0 * lat;
     int rc = dit_forward_cfg_step(s->dit, xl, s->temb_table, &loop->index, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
                                   s->mod_table, c.batch + 1, r0);
     if (rc != T2S_OK) return rc;
     UpdateArgs a{};
-    a.x = xl; a.pred_u = eu; a.pred_c = ec; a.noise = noise ? noise + (size_t)r0 * LAT : nullptr; a.coef = s->coef;
-    a.loop = loop; a.cfg = c.cfg_scale; a.seed = c.seed; a.B = n; a.noise_rows = c.batch; a.advance = loop;
+    a.x = xl; a.pred_u = eu; a.pred_c = ec; a.noise = noise ? noise + (size_t)r0 * lat : nullptr; a.coef = s->coef;
+    a.loop = loop; a.cfg = c.cfg_scale; a.seed = c.seed; a.B = n; a.qpr = s->lat / 4; a.noise_rows = c.batch; a.advance = loop;
     a.row_seed = rows_seed(s->d_rows, c.batch) + r0;
     a.row_key = rows_key(s->d_rows, c.batch) + r0;
     a.row_cfg = rows_cfg(s->d_rows, c.batch) + r0;
     switch (c.mode) {   // (the create entries admit these three modes only; launch_update refuses any other)
     case T2S_MODE_DDPM: a.steps = c.steps; break;
-    case T2S_MODE_LMS: a.hist = s->hist + (size_t)r0 * LAT; break;
+    case T2S_MODE_LMS: a.hist = s->hist + (size_t)r0 * lat; break;
     case T2S_MODE_RF: a.dt = 1.0f / (float)c.steps; break;
     }
     return launch_update(c.mode, a, st);   // (the update kernel's last workgroup advances the lane's loop index)
@@ -753,6 +763,10 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
     T2S_REQUIRE(cfg->batch > 0 && 2 * cfg->batch <= t2s_dit_max_seqs(dit),
                 "t2s_sampler_create: batch=%d needs 2*batch <= dit max_seqs=%d", cfg->batch, t2s_dit_max_seqs(dit));
     T2S_REQUIRE(cfg->t_values, "t2s_sampler_create: t_values is NULL");
+    const int latw = t2s_dit_latent_w(dit);
+    T2S_REQUIRE(!vae || latw <= 32 || t2s_vae_channels(vae) != 0,
+                "t2s_sampler_create: a DiT of latent width %d needs a multichannel decoder (t2s_vae_create_mc) or NULL", latw);
+    T2S_REQUIRE((long long)cfg->batch * LATC * latw < (1ll << 31), "t2s_sampler_create: batch=%d at latent width %d", cfg->batch, latw);
     T2S_REQUIRE(cfg->mode != T2S_MODE_DDPM || cfg->ddpm_coef, "t2s_sampler_create: DDPM needs ddpm_coef");
     // a multichannel decoder (t2s_vae_create_mc) resamples to any length >= 8; the single-channel one builds multiples of 4
     T2S_REQUIRE(!vae || (t2s_vae_channels(vae) ? cfg->length >= 8 : cfg->length >= 4 && cfg->length % 4 == 0) && cfg->length <= (1 << 20),
@@ -764,16 +778,17 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
     T2S_REQUIRE(cur_dev >= 0 && cur_dev < 16, "t2s_sampler_create: device %d", cur_dev);
     std::lock_guard<std::recursive_mutex> pool_lock(g_pool_use[cur_dev]);
     t2s_sampler* s = new t2s_sampler();
-    s->dit = dit; s->vae = vae; s->cfg = *cfg;
+    s->dit = dit; s->vae = vae; s->cfg = *cfg; s->lat = LATC * latw;
+    const size_t lat = (size_t)s->lat;
     s->cfg.ddpm_coef = nullptr; s->cfg.t_values = nullptr;  // host pointers are not retained
     const size_t B = (size_t)cfg->batch, T = (size_t)cfg->steps;
     hipError_t e = hipSuccess;
     auto alloc = [&](void** p, size_t bytes) { if (e == hipSuccess) e = hipMalloc(p, bytes); };
     alloc((void**)&s->temb_table, T * D * sizeof(float));
     alloc((void**)&s->coef, T * (lms_coef ? 6 : 3) * sizeof(float));
-    if (lms_coef) alloc((void**)&s->hist, B * LAT * sizeof(float));
-    alloc((void**)&s->eps_u, B * LAT * sizeof(float));
-    alloc((void**)&s->eps_c, B * LAT * sizeof(float));
+    if (lms_coef) alloc((void**)&s->hist, B * lat * sizeof(float));
+    alloc((void**)&s->eps_u, B * lat * sizeof(float));
+    alloc((void**)&s->eps_c, B * lat * sizeof(float));
     alloc((void**)&s->tvals, T * sizeof(float));
     alloc((void**)&s->step, t2s_sampler::MAX_LANES * LANE_STATES * sizeof(LoopState));   // one per lane, 64 B apart
     alloc(&s->d_rows, rows_bytes(cfg->batch));                            // per-row tables (t2s_sampler_set_rows)
@@ -805,7 +820,7 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
         e = hipMemcpyAsync(s->coef, cfg->ddpm_coef, T * 3 * sizeof(float), hipMemcpyHostToDevice, setup);
     if (e == hipSuccess && lms_coef) e = hipMemcpyAsync(s->coef, lms_coef, T * 6 * sizeof(float), hipMemcpyHostToDevice, setup);
     // a caller's table may read the history at its first step (the solvers of t2ms_amd.sampler.solver_tables never do)
-    if (e == hipSuccess && lms_coef) e = hipMemsetAsync(s->hist, 0, B * LAT * sizeof(float), setup);
+    if (e == hipSuccess && lms_coef) e = hipMemsetAsync(s->hist, 0, B * lat * sizeof(float), setup);
     if (e == hipSuccess) e = hipStreamSynchronize(setup);      // the host tables may go away when the call returns
     if (e != hipSuccess) {
         set_error("t2s_sampler_create: allocation/upload failed: %s", hipGetErrorString(e));
@@ -912,9 +927,10 @@ extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     delete s;
 }
 
-// the sampler's decode of n latents: a multichannel decoder handle writes (n,C,L) at latent width 30, a single-channel one (n,L)
-static int sampler_decode(t2s_vae* vae, const float* x, float* out, int n, int L, hipStream_t st) {
-    if (t2s_vae_channels(vae) != 0) return t2s_vae_decode_mc(vae, x, out, nullptr, n, L, LATW, st);
+// the sampler's decode of n latents: a multichannel decoder handle writes (n,C,L) at the DiT's latent width, a single-channel
+// one (n,L) (width 30 only: sampler_create refuses it on a wider DiT)
+static int sampler_decode(t2s_vae* vae, const float* x, float* out, int n, int L, int latw, hipStream_t st) {
+    if (t2s_vae_channels(vae) != 0) return t2s_vae_decode_mc(vae, x, out, nullptr, n, L, latw, st);
     return t2s_vae_decode(vae, x, out, nullptr, n, L, st);
 }
 
@@ -1043,7 +1059,7 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         if (trace0) {
             // infer.py:90-93: decode row 0 of the first batch after every step
             const int ch = t2s_vae_channels(s->vae);
-            if ((rc = sampler_decode(s->vae, x, trace0 + (size_t)j * (ch ? ch : 1) * c.length, 1, c.length, st)) != T2S_OK) return rc;
+            if ((rc = sampler_decode(s->vae, x, trace0 + (size_t)j * (ch ? ch : 1) * c.length, 1, c.length, s->lat / LATC, st)) != T2S_OK) return rc;
         }
     }
     for (int l = 1; l < lanes; ++l) {   // join before the decode (and before anything the caller queues next)
@@ -1051,7 +1067,7 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         T2S_HIP_CHECK(hipStreamWaitEvent(st, s->ev_join[l], 0));
     }
     if (series) {
-        if ((rc = sampler_decode(s->vae, x, series, c.batch, c.length, st)) != T2S_OK) return rc;
+        if ((rc = sampler_decode(s->vae, x, series, c.batch, c.length, s->lat / LATC, st)) != T2S_OK) return rc;
     }
     if (via_own) {      // whatever the caller queues on its stream next sees the results
         T2S_HIP_CHECK(hipEventRecord(s->ev_out, st));

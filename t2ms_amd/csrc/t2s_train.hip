@@ -892,6 +892,7 @@ extern "C" {
 
 int t2s_dit_set_train_dtype(t2s_dit* h, int dtype) {
     T2S_REQUIRE(h, "t2s_dit_set_train_dtype: NULL handle");
+    T2S_REQUIRE(h->latw == LATW, "t2s_dit_set_train_dtype: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_dit_set_train_dtype: unknown dtype %d", dtype);
     h->train_dtype = dtype;
     return T2S_OK;
@@ -901,6 +902,7 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
                           const float* text, float* out, int B, void* stream) {
     t2s::reset_tile_dir();
     T2S_REQUIRE(h && w && x && temb && out, "t2s_dit_train_forward: NULL argument");
+    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_forward: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(B > 0 && B <= h->max_seqs, "t2s_dit_train_forward: B=%d exceeds max_seqs=%d", B, h->max_seqs);
     T2S_REQUIRE(temb_rows == 1 || temb_rows == B, "t2s_dit_train_forward: temb_rows=%d", temb_rows);
     hipStream_t st = (hipStream_t)stream;
@@ -1040,6 +1042,7 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
 int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g, int B, void* stream) {
     t2s::reset_tile_dir();
     T2S_REQUIRE(h && dout && g, "t2s_dit_train_backward: NULL argument");
+    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_backward: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(h->train && h->train->S == B, "t2s_dit_train_backward: no matching t2s_dit_train_forward (B=%d)", B);
     T2S_REQUIRE(h->train->dtype == h->train_dtype, "t2s_dit_train_backward: training dtype changed since the forward");
     hipStream_t st = (hipStream_t)stream;
@@ -1223,6 +1226,7 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
 
 int t2s_dit_train_input_grad(t2s_dit* h, float* dinput, int B, void* stream) {
     T2S_REQUIRE(h && dinput, "t2s_dit_train_input_grad: NULL argument");
+    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_input_grad: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(h->train && h->train->S == B, "t2s_dit_train_input_grad: no matching t2s_dit_train_backward (B=%d)", B);
     t2s_train_ws* ws = h->train;
     TimeScope ts(h, TC_TR_TAIL, (hipStream_t)stream);

@@ -26,6 +26,7 @@ __all__ = ["Transformer", "Transformerlayer", "TimeEmbedding", "modulate",
 EMB, HEADS, DEPTH, PATCH = 128, 4, 4, 2
 LAT_H, LAT_W = 30, 64           # the reference's self.H / self.W (transformer.py:132-133)
 N_PATCH = (LAT_H // PATCH) * (LAT_W // PATCH)
+DIMS = (30, 50, 64)             # latent widths the kernels are built for: 480 / 800 / 1024 tokens (mytransformer.Transformer(dim))
 
 
 def modulate(x, shift, scale):
@@ -147,12 +148,12 @@ class _DitHandle:
     for the life of the process: a re-created handle often gets the freed one's address back, so users that cache
     state bound to a handle (Sampler's captured hipGraph, a pending backward) compare uids, never pointers."""
 
-    def __init__(self, weights: L.DitWeights, keep, max_seqs: int):
+    def __init__(self, weights: L.DitWeights, keep, max_seqs: int, latent_w: int = LAT_H):
         self.uid = next(_HANDLE_IDS)
         self.ptr = C.c_void_p()
         self.keep = keep
         self.max_seqs = max_seqs
-        L.check(L.lib().t2s_dit_create(C.byref(weights), max_seqs, C.byref(self.ptr)), "t2s_dit_create")
+        L.check(L.lib().t2s_dit_create_w(C.byref(weights), latent_w, max_seqs, C.byref(self.ptr)), "t2s_dit_create_w")
         dev = f"cuda:{torch.cuda.current_device()}"          # created under torch.cuda.device(device)
         self._fin = weakref.finalize(self, L.destroy_locked, "t2s_dit_destroy", dev, self.ptr)
 
@@ -161,11 +162,16 @@ class _DitHandle:
 
 
 class Transformer(nn.Module):
-    """Drop-in for ``model.denoiser.transformer.Transformer`` (transformer.py:128-204)."""
+    """Drop-in for ``model.denoiser.transformer.Transformer`` (transformer.py:128-204).  `dim` is the reference's
+    ``self.H``, the latent width: this class is also the body of ``model.denoiser.mytransformer.Transformer(dim)`` (the
+    motion models' denoiser, mytransformer.py:128-204 -- the same network over a (B,64,dim) latent, 16 * dim tokens)."""
 
-    def __init__(self):
+    def __init__(self, dim: int = LAT_H):
         super().__init__()
-        self.channel, self.H, self.W, self.patch_size = 1, LAT_H, LAT_W, PATCH
+        if dim not in DIMS:
+            raise L.T2SError(f"Transformer: the HIP kernels are built for dim 30, 50 or 64 (480, 800 or 1024 tokens), got {dim!r}")
+        self.channel, self.H, self.W, self.patch_size = 1, dim, LAT_W, PATCH
+        N_PATCH = (dim // PATCH) * (LAT_W // PATCH)
         self.patch_count = N_PATCH
         self.conv = nn.Conv2d(1, PATCH * PATCH, kernel_size=PATCH, padding=0, stride=PATCH)
         self.patch_emb = nn.Linear(PATCH * PATCH, EMB)
@@ -239,8 +245,8 @@ class Transformer(nn.Module):
         # state-dict key in the message -- not an out-of-bounds read in a pack kernel
         counts = [t.numel() for t in keep[:9]] + [_freqs_on(device).numel()] + [t.numel() for t in keep[9:]]
         with torch.cuda.device(device):
-            L.check(L.lib().t2s_dit_weights_check(C.byref(w), (C.c_uint64 * L.DIT_N_TENSORS)(*counts), L.DIT_N_TENSORS),
-                    "t2s_dit_weights_check")
+            L.check(L.lib().t2s_dit_weights_check_w(C.byref(w), self.H, (C.c_uint64 * L.DIT_N_TENSORS)(*counts), L.DIT_N_TENSORS),
+                    "t2s_dit_weights_check_w")
         if all(k.data_ptr() == t.data_ptr() for k, t in zip(keep, ts)):      # fp32 contiguous parameters: no copies made
             self.__dict__["_t2s_ws"] = (device, w, keep, stamp)
         return w, keep, stamp
@@ -264,7 +270,7 @@ class Transformer(nn.Module):
                     cap = max(cap, (n_seqs + n_seqs // 8 + 63) // 64 * 64)
                 torch.cuda.synchronize(device)
                 with torch.cuda.device(device):
-                    h = _DitHandle(w, keep, cap)
+                    h = _DitHandle(w, keep, cap, self.H)
             self.__dict__["_t2s_h"], self.__dict__["_t2s_dev"], self.__dict__["_t2s_stamp"] = h, device, stamp
             self.__dict__.pop("_t2s_math_applied", None)
         elif stamp is None or self.__dict__.get("_t2s_stamp") != stamp:
@@ -273,6 +279,8 @@ class Transformer(nn.Module):
             h.keep = keep
             self.__dict__["_t2s_stamp"] = stamp
         math = self.__dict__.get("_t2s_math", "f32")
+        if self.H != LAT_H and math != "f32":          # (set_math refuses it; a pickled or hand-set attribute ends here)
+            raise L.T2SError(f"Transformer(dim={self.H}) runs math 'f32' only, got {math!r}")
         if self.__dict__.get("_t2s_math_applied") != math:
             with L.device_lock(device), torch.cuda.device(device):       # (first bf16x3 / bf16 use allocates and synchronises)
                 L.check(L.lib().t2s_dit_set_math(h.ptr, L.MATH_CODES[math]), "t2s_dit_set_math")
@@ -292,6 +300,9 @@ class Transformer(nn.Module):
         Set it before building a Sampler: a captured hipGraph keeps its kernels."""
         if math not in L.MATH_CODES:
             raise ValueError(f"math must be 'f32', 'bf16x3' or 'bf16', got {math!r}")
+        if self.H != LAT_H and math != "f32":
+            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents run math 'f32' only (bf16x3 / bf16 exist at dim 30), "
+                             f"got {math!r}")
         self.__dict__["_t2s_math"] = math
         return self
 
@@ -325,11 +336,13 @@ class Transformer(nn.Module):
 
     # ---------------------------------------------------------------- forward (transformer.py:158-193)
     def forward(self, input: torch.Tensor, t: torch.Tensor, text_input):
-        """input (B,64,30) latent, t (B,) int64 (DDPM) or float (flow), text_input (B,128) or None."""
+        """input (B,64,dim) latent, t (B,) int64 (DDPM) or float (flow), text_input (B,128) or None."""
         if not input.is_cuda:
             raise L.T2SError("Transformer.forward: input must live on a GPU; the HIP path has no CPU fallback")
-        if input.dim() != 3 or input.shape[1] != LAT_W or input.shape[2] != LAT_H:
-            raise L.T2SError(f"Transformer.forward: input must be (B,64,30), got {tuple(input.shape)}")
+        if input.dim() != 3 or input.shape[1] != LAT_W or input.shape[2] != self.H:
+            raise L.T2SError(f"Transformer.forward: input must be (B,64,{self.H}), got {tuple(input.shape)}")
+        if self.H != LAT_H and torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self._dit_tensors())):
+            raise L.T2SError(f"Transformer(dim={self.H}): training runs at dim 30 only; call the wide model under torch.no_grad()")
         if torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self._dit_tensors())):
             from ...train import dit_forward_autograd
             return dit_forward_autograd(self, input, t, text_input)
@@ -386,7 +399,7 @@ class Transformer(nn.Module):
             h = self.t2s_handle(dev, 2 * B if speculate else B)
             st = L.stream_ptr(dev)
             temb = torch.empty(B, EMB, device=dev, dtype=torch.float32)
-            out = torch.empty(B, LAT_W, LAT_H, device=dev, dtype=torch.float32)
+            out = torch.empty(B, LAT_W, self.H, device=dev, dtype=torch.float32)
             lib = L.lib()
             L.check(lib.t2s_time_embedding(h, L.dev_ptr(tf, "t"), L.dev_ptr(temb), B, st), "t2s_time_embedding")
             if speculate:

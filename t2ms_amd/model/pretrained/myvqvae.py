@@ -165,6 +165,8 @@ class vqvae(BaseModel):
         self.decoder = Decoder(in_channels=args.embedding_dim, num_hiddens=args.block_hidden_size,
                                num_residual_layers=args.num_residual_layers, num_residual_hiddens=args.res_hidden_size,
                                out_channels=args.input_dim)
+        # the reference's Decoder takes any latent width; the codec was trained at one: the Sampler checks it against the DiT's
+        self.decoder.flow_dim = int(args.flow_dim)
 
     def shared_eval(self, batch, optimizer, mode):  # pyright: ignore[reportIncompatibleMethodOverride]
         """myvqvae.py:116-136.  'train' is one optimisation step through the torch-op forwards under autograd (no HIP backward

@@ -275,21 +275,25 @@ def philox_uniform(n_rows: int, row_elems: int, seed: int, stream_id: int, row0:
 def lms_step(x: torch.Tensor, hist: torch.Tensor, pred_u: torch.Tensor, pred_c: Optional[torch.Tensor], coef: torch.Tensor,
              index: int, cfg: float = 0.0, noise: Optional[torch.Tensor] = None, seed: int = 0, stream_id: int = 0,
              row0: int = 0) -> None:
-    """One update of t2s_lms_step, IN PLACE on x and hist ((B,64,30) or (B,1920) fp32 on the GPU):
+    """One update of t2s_lms_step, IN PLACE on x and hist ((B,64,W) or (B,64 W) fp32 on the GPU; W = 30, or the width of a
+    wide model -- t2s_lms_step_n):
     x' = c0*x + c1*pred + c2*h + c3*z, h' = c4*x + c5*pred with {c0..c5} = coef[index] (DEVICE (S,6)), pred = u + cfg*(c-u)
     (pred = u when pred_c is None), z = `noise` or, when None, the Philox draw (seed, stream_id, row0 + row).  For stepwise
     loops; the Sampler runs the same kernel from its loop."""
     B = x.shape[0]
+    row = x.numel() // max(B, 1)
+    if row % L.LAT_C or row // L.LAT_C not in (30, 50, 64):
+        raise L.T2SError(f"lms_step: x must hold ({B},64,W) values with W 30, 50 or 64, got {tuple(x.shape)}")
     for name, v in (("x", x), ("hist", hist), ("pred_u", pred_u), ("pred_c", pred_c), ("noise", noise)):
-        if v is not None and (v.shape[0] != B or v.numel() != B * L.LAT):
-            raise L.T2SError(f"lms_step: {name} must hold ({B},1920) values, got {tuple(v.shape)}")
+        if v is not None and (v.shape[0] != B or v.numel() != B * row):
+            raise L.T2SError(f"lms_step: {name} must hold ({B},{row}) values, got {tuple(v.shape)}")
     if coef.dim() != 2 or coef.shape[1] != 6 or not 0 <= int(index) < coef.shape[0]:
         raise L.T2SError(f"lms_step: coef must be (S,6) with 0 <= index < S, got {tuple(coef.shape)}, index {index}")
     with torch.cuda.device(x.device):
-        L.check(L.lib().t2s_lms_step(L.dev_ptr(x, "x"), L.dev_ptr(hist, "hist"), L.dev_ptr(pred_u, "pred_u"),
-                                     L.dev_ptr(pred_c, "pred_c"), L.dev_ptr(noise, "noise"), L.dev_ptr(coef, "coef"), int(index),
-                                     float(cfg), int(seed), int(stream_id) & 0xFFFFFFFF, int(row0), B, L.stream_ptr(x.device)),
-                "t2s_lms_step")
+        L.check(L.lib().t2s_lms_step_n(L.dev_ptr(x, "x"), L.dev_ptr(hist, "hist"), L.dev_ptr(pred_u, "pred_u"),
+                                       L.dev_ptr(pred_c, "pred_c"), L.dev_ptr(noise, "noise"), L.dev_ptr(coef, "coef"), int(index),
+                                       float(cfg), int(seed), int(stream_id) & 0xFFFFFFFF, int(row0), B, row,
+                                       L.stream_ptr(x.device)), "t2s_lms_step_n")
 
 
 class Sampler:
@@ -311,7 +315,14 @@ class Sampler:
         self.model, self.decoder = model, decoder
         # a multichannel decoder (model/pretrained/myvqvae.py Decoder: C-channel motion series) decodes to (B,C,L), any L >= 8
         self.channels = decoder._mc_channels() if getattr(decoder, "_t2s_multichannel", False) else None
-        self.math = math or model.__dict__.get("_t2s_math") or default_math()
+        # the model's latent width (mytransformer.Transformer(dim): 50 / 64 for the motion models); the wide widths run f32
+        self.width = int(getattr(model, "H", L.LAT_W))
+        flow_dim = getattr(decoder, "flow_dim", None)      # (stamped by myvqvae.vqvae; a bare Decoder does not know it)
+        if flow_dim is not None and int(flow_dim) != self.width:
+            raise L.T2SError(f"Sampler: the decoder's flow_dim {int(flow_dim)} differs from the model's latent width {self.width}")
+        if decoder is not None and self.width != L.LAT_W and not getattr(decoder, "_t2s_multichannel", False):
+            raise L.T2SError(f"Sampler: a model of latent width {self.width} needs the multichannel decoder (myvqvae)")
+        self.math = math or model.__dict__.get("_t2s_math") or ("f32" if self.width != L.LAT_W else default_math())
         if hasattr(model, "set_math"):
             model.set_math(self.math)
         self.backbone, self.steps, self.cfg_scale = backbone, int(steps), float(cfg_scale)
@@ -395,26 +406,27 @@ class Sampler:
         self._rows = (s, k, c)
 
     def draw_xT(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
-        """x_T ~ N(0,1) from the Philox stream (perf mode), (batch,64,30); per row as set_rows keyed it."""
+        """x_T ~ N(0,1) from the Philox stream (perf mode), (batch,64,W); per row as set_rows keyed it."""
+        row = L.LAT_C * self.width
         if out is None:
-            out = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=self.device, dtype=torch.float32)
+            out = torch.empty(self.batch, L.LAT_C, self.width, device=self.device, dtype=torch.float32)
         s, k, _ = self.__dict__.get("_rows") or (None, None, None)
         if s is not None or k is not None:
             if s is None:
                 s = np.full(self.batch, self.seed, dtype=np.uint64)
             if k is None:
                 k = (self.row0 + np.arange(self.batch, dtype=np.int64)).astype(np.uint32)
-            return philox_normal_rows(s, k, L.LAT, XT_STREAM, self.device, out=out)
+            return philox_normal_rows(s, k, row, XT_STREAM, self.device, out=out)
         with torch.cuda.device(self.device):
-            L.check(L.lib().t2s_philox_normal(L.dev_ptr(out), self.seed, XT_STREAM, self.row0, self.batch, L.LAT,
+            L.check(L.lib().t2s_philox_normal(L.dev_ptr(out), self.seed, XT_STREAM, self.row0, self.batch, row,
                                               L.stream_ptr(self.device)), "t2s_philox_normal")
         return out
 
     def run(self, text: torch.Tensor, x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
             decode: bool = True, trace: bool = False):
-        """Returns (latent (B,64,30), series (B,L) or None, trace (steps,L) or None); with a multichannel decoder the series
-        is (B,C,L) and the trace (steps,C,L).
-        ``noise`` (steps,B,64,30) injects the per-step draws (parity mode)."""
+        """Returns (latent (B,64,W), series (B,L) or None, trace (steps,L) or None); with a multichannel decoder the series
+        is (B,C,L) and the trace (steps,C,L).  W is the model's latent width (30; 50 / 64 for mytransformer.Transformer).
+        ``noise`` (steps,B,64,W) injects the per-step draws (parity mode)."""
         with L.device_lock(self.device):
             dev = self.device
             text = L.as_f32(text.to(dev))
@@ -422,20 +434,20 @@ class Sampler:
                 raise L.T2SError(f"Sampler.run: text must be ({self.batch},128), got {tuple(text.shape)}")
             # persistent device buffers: the captured hipGraph is bound to their addresses
             if self.__dict__.get("_x") is None:
-                self._x = torch.empty(self.batch, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
+                self._x = torch.empty(self.batch, L.LAT_C, self.width, device=dev, dtype=torch.float32)
                 self._text = torch.empty(self.batch, L.D_MODEL, device=dev, dtype=torch.float32)
                 self._series = torch.empty(self.batch, *self._row_shape(), device=dev, dtype=torch.float32)
             self._text.copy_(text)
             if x_T is None:
                 self.draw_xT(self._x)
             else:
-                if tuple(x_T.shape) != (self.batch, L.LAT_C, L.LAT_W):
-                    raise L.T2SError(f"Sampler.run: x_T must be ({self.batch},64,30), got {tuple(x_T.shape)}")
+                if tuple(x_T.shape) != (self.batch, L.LAT_C, self.width):
+                    raise L.T2SError(f"Sampler.run: x_T must be ({self.batch},64,{self.width}), got {tuple(x_T.shape)}")
                 self._x.copy_(x_T)
             if noise is not None:
                 noise = L.as_f32(noise.to(dev))
-                if tuple(noise.shape) != (self.steps, self.batch, L.LAT_C, L.LAT_W):
-                    raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,30)")
+                if tuple(noise.shape) != (self.steps, self.batch, L.LAT_C, self.width):
+                    raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,{self.width})")
             if (decode or trace) and self.decoder is None:
                 raise L.T2SError("Sampler.run: decode requested but no decoder was given")
             tr = torch.empty(self.steps, *self._row_shape(), device=dev, dtype=torch.float32) if trace else None

@@ -36,7 +36,9 @@ def _pos_embed(num_positions=480, d_model=128) -> torch.Tensor:
 
 
 def make_dit_state_dict(seed: int = 2025, gain: float = 1.0, bias_std: float = 0.02,
-                        adaln_std: float = 0.02) -> Dict[str, torch.Tensor]:
+                        adaln_std: float = 0.02, width: int = 30) -> Dict[str, torch.Tensor]:
+    """`width`: the latent width (mytransformer.Transformer(dim)); only pos_embed, (1, 16 * width, 128), follows it --
+    every drawn tensor is the same at every width."""
     rs = np.random.RandomState(seed)
     sd: Dict[str, np.ndarray] = {}
 
@@ -64,7 +66,7 @@ def make_dit_state_dict(seed: int = 2025, gain: float = 1.0, bias_std: float = 0
     lin("unpatch.fc1", 128, 60)
     lin("unpatch.fc2", 64, 128)
     out = {k: torch.from_numpy(v) for k, v in sd.items()}
-    out["pos_embed"] = _pos_embed()
+    out["pos_embed"] = _pos_embed(16 * width)
     return out
 
 
