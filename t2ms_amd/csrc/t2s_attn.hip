@@ -490,6 +490,344 @@ __global__ __launch_bounds__(PERSIST_THREADS, 2) void attn_fwd_persistent_kernel
         attn_persistent_body<1>(ring, qg, kg, vg, og, BH, lane, wave);   // tiles 14 only (15 is void)
 }
 
+// ------------------------------------------------------------------ persistent variant, heads walked in fours
+// The persistent kernel leaves one of its 16 tile slots empty: wave 7's SIMD carries 3 tiles per key block where the others
+// carry 4, and all meet at the block barrier.  Here the heads of a workgroup go in quads (A, B, C, D) of four passes; the
+// fourth head is spread over the spare slot of the first three, so that its own pass carries 12 tiles (3 per SIMD):
+//
+//   pass   waves 0-3          waves 4-6          wave 7, slot a | slot b         second ring streams
+//   1 (A)  A 2w, 2w+1         A 2w, 2w+1         A 14           | D 14            D
+//   2 (B)  B 2w, 2w+1         B 2w, 2w+1         D 12           | D 13            D
+//   3 (C)  C 2w, 2w+1         C 2w, 2w+1         C 14           | B 14            B
+//   4 (D)  D 2w, 2w+1         D w+4              D 11           |                 -
+//
+// Why not simply D 12, 13, 14 in the spare slot of passes 1-3: the tiles (2i, 2i+1) of a head are COUPLED.  The wave that
+// holds both re-references both when either is stale (one wave-uniform branch), so a tile's bits depend on its partner's
+// scores, block by block.  Every output bit stays what attn_fwd_persistent_kernel writes only if a coupled pair is decided
+// together: D 12 / 13 share wave 7 in pass 2 (B 14, which they displace, takes the spare slot of pass 3 from a second
+// stream of B), the uncoupled tiles 14 sit in slots that decide alone (wave 7 in passes 1 and 3: two tiles of different heads,
+// K / V^T fragments read one tile after the other, one re-reference branch per tile), and in pass 4 the pairs (8, 9) and (10, 11), split over the
+// waves (4, 5) and (6, 7), exchange their stale bits through LDS around the block barrier, which for these four waves sits
+// between the exponentials and PV (two flag sets, by block parity: a flag is rewritten two barriers after it was read).
+//
+// The main ring streams the heads in the order of the persistent kernel, continuously; the second 4-slot ring (LDS 64 KiB +
+// the flags) runs in step with it during passes 1-3.  Every wave issues piece `wave` of a block (K fragments 0-3, V^T
+// fragments 0-3) for the main ring and, when the block belongs to a pass 1-3, the same piece for the second ring: block gb + 3
+// while it works on block gb, right behind the exponentials (the slot was freed by the barrier of block gb - 1).  Issued there
+// a piece costs least: attention alone, 1024 heads, 238.0 us per launch against 240.6 behind the barrier, 240.5 in front of
+// the scores, 238.5 between the PV MFMAs (246.0 for the head walk; profiles/r06_attn_quad_ab.txt).  Every wave waits with
+// one count, vmcnt(2) (derived at wait_ring below).
+// The next pass's Q is requested between blocks 10 and 11 and taken (scaled) just before block 11's ring wait, where the
+// compiler's own wait for it finds nothing younger than half a block in flight.  The heads left after the last quad (and a
+// workgroup with fewer than four) are walked as plain passes: 15 tiles, wave 7 with tile 14 alone.
+constexpr int QUAD_RING_F4 = ATT_SLOTS * ATT_SLOT_F4;               // one ring, in float4
+constexpr int QUAD_LDS_BYTES = 2 * ATT_LDS_BYTES + 2 * 8 * 4;       // two rings + 2 x 8 stale flags
+enum { QV_PAIR, QV_ONE, QV_ONEX, QV_TWO };                          // pass forms of a wave, below
+enum { QP_PLAIN = 4 };                                              // pass types: 0-3 within a quad, 4 plain
+
+struct QuadSlots {   // the two tile slots of a wave in one pass: head, tile, ring offset (float4) of its K / V^T
+    int ha, ta, ra;
+    int hb, tb, rb;
+};
+
+template <int N>
+struct QuadForm {
+    static constexpr int value = N;
+};
+
+// ROLE 0: waves 0-3, 1: waves 4-6, 2: wave 7
+template <int ROLE>
+__device__ __forceinline__ void attn_quad_walk(f32x4* lds, const f32x4* qall, const f32x4* kall, const f32x4* vall,
+                                               f32x4* og, int BH, int lane, int wave) {
+    const int stride = gridDim.x, first = blockIdx.x;
+    const int n = (BH - first + stride - 1) / stride;     // heads (= passes) of this workgroup, >= 1: the grid has <= BH workgroups
+    const int nq4 = n & ~3;                               // the passes of whole quads
+    const unsigned flag_base = (unsigned)(size_t)((__attribute__((address_space(3))) char*)(lds + 2 * QUAD_RING_F4));
+    auto ptype = [&](int p) { return p < nq4 ? (p & 3) : (int)QP_PLAIN; };
+    auto slots = [&](int p) {
+        const int t = ptype(p), hm = first + p * stride;
+        QuadSlots s;
+        s.ha = s.hb = hm;
+        s.ta = 2 * wave;
+        s.tb = 2 * wave + 1;
+        s.ra = s.rb = 0;
+        if (ROLE == 1 && t == 3) s.ta = s.tb = wave + 4;
+        if (ROLE == 2) {
+            s.ta = s.tb = NKB - 1;
+            if (t == 0) { s.hb = hm + 3 * stride; s.rb = QUAD_RING_F4; }
+            if (t == 1) { s.ha = s.hb = hm + 2 * stride; s.ta = 12; s.tb = 13; s.ra = s.rb = QUAD_RING_F4; }
+            if (t == 2) { s.hb = hm - stride; s.rb = QUAD_RING_F4; }
+            if (t == 3) s.ta = s.tb = 11;
+        }
+        return s;
+    };
+
+    // ---- the DMA stream: blocks (ip, ij) in pass order, this wave's piece(s) of each ----
+    const f32x4* const piece_src = (wave < 4 ? kall : vall) + (wave & 3) * 64 + lane;
+    int ip = 0, ij = 0, islot = 0;
+    auto issue_next = [&]() {
+        const int ph = ip < n ? ip : n - 1, pj = ip < n ? ij : NKB - 1;   // past the end: harmless re-fetch
+        f32x4* dst = lds + islot * ATT_SLOT_F4 + wave * 64;
+        glds16_asm(piece_src + ((size_t)(first + ph * stride) * NKB + pj) * 256, dst);
+        const int t = ptype(ip);   // plain past the end (nq4 <= n)
+        if (t < 3) {
+            const int hs = first + (ip + (t == 0 ? 3 : (t == 1 ? 2 : -1))) * stride;   // D, D, B: heads of this quad
+            glds16_asm(piece_src + ((size_t)hs * NKB + ij) * 256, dst + QUAD_RING_F4);
+        }
+        islot = (islot + 1) & (ATT_SLOTS - 1);
+        if (++ij == NKB) { ij = 0; ++ip; }
+    };
+    // Counted wait of every wave: its TWO youngest vector-memory operations may stay in flight.  A block is one or two pieces
+    // per wave, and at the wait of block gb the blocks up to gb + 3 are issued: the two youngest are pieces of blocks gb + 2
+    // and gb + 3 (gb + 3 alone in passes 1-3), never of gb + 1, the block the barrier behind this wait hands over.  Younger stores and Q loads only make the wait
+    // stricter.  (lgkmcnt(0): this block's fragment reads have returned before the barrier frees their slot, whichever MFMA
+    // uses them.)
+    auto wait_ring = [&]() { asm volatile("s_waitcnt vmcnt(2) lgkmcnt(0)" ::: "memory"); };
+    issue_next();
+    issue_next();
+    issue_next();
+
+    QuadSlots cur = slots(0);
+    f32x4 qa[4], qb[4], qna[4], qnb[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) {
+        qa[g] = qall[((size_t)cur.ha * NKB + cur.ta) * 256 + g * 64 + lane] * QSCALE;
+        qb[g] = qall[((size_t)cur.hb * NKB + cur.tb) * 256 + g * 64 + lane] * QSCALE;
+        qna[g] = qa[g];
+        qnb[g] = qb[g];
+    }
+    wait_ring();
+    __builtin_amdgcn_s_barrier();
+    f32x4 kf[4];
+#pragma unroll
+    for (int g = 0; g < 4; ++g) kf[g] = lds[cur.ra + g * 64 + lane];
+    int gb = 0;                                      // global block counter -> ring slot
+
+    auto store_tile = [&](const f32x16& o, const TileState& t, int bh, int tile) {
+        const int seq = bh / NH, head = bh % NH;
+        const float inv = 1.0f / pair_sum(t.l_lane);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            const f32x4 w = {o[4 * g] * inv, o[4 * g + 1] * inv, o[4 * g + 2] * inv, o[4 * g + 3] * inv};
+            og[(((size_t)seq * NKB + tile) * 16 + head * 4 + g) * 64 + lane] = w;
+        }
+    };
+
+    // One pass = the 15 key blocks of the head(s) in `cur`.  Forms:
+    //   QV_PAIR  two coupled tiles on one K / V^T stream (the persistent kernel's two-tile wave)
+    //   QV_ONE   one tile (the persistent kernel's wave 7)
+    //   QV_ONEX  one tile whose partner sits in wave ^ 1: the stale bits cross at the block barrier
+    //   QV_TWO   two uncoupled tiles of different heads: fragments and re-reference branch per tile
+    auto run_pass = [&](auto form, const QuadSlots nxt, const bool has_next) {
+        constexpr int V = decltype(form)::value;
+        constexpr bool TWO_TILES = V == QV_PAIR || V == QV_TWO;
+        f32x16 oa, ob;
+        TileState ta, tb;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            oa[r] = ob[r] = 0.f;
+            ta.negm[r] = tb.negm[r] = INFINITY;
+        }
+        ta.m_ref = tb.m_ref = -INFINITY;
+        ta.l_lane = tb.l_lane = 0.f;
+
+        // two runs of blocks, 0-10 and 11-14, with the request for the next pass's Q between them: the block loop itself
+        // holds no vector load
+        int jb = 0;
+#pragma unroll 1
+        for (int run = 0; run < 2; ++run) {
+        const int jend = run == 0 ? NKB - 4 : NKB;
+#pragma unroll 1
+        for (; jb < jend; ++jb, ++gb) {
+            const int soff = (gb & (ATT_SLOTS - 1)) * ATT_SLOT_F4 + lane;
+            f32x4 vf[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) vf[g] = lds[cur.ra + soff + 256 + g * 64];
+            const bool take_q = jb == NKB - 4 && has_next;
+            // block 11 takes the next pass's Q (scaled), pinned in front of its ring wait (see the head comment)
+            auto land_q = [&]() {
+                if (take_q) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g) {
+                        qna[g] = qna[g] * QSCALE;
+                        qnb[g] = qnb[g] * QSCALE;
+                        asm volatile("" : "+v"(qna[g]), "+v"(qnb[g]));
+                    }
+                }
+            };
+            // K fragments of block gb + 1: the last block of a pass fetches for the next pass's slots
+            auto next_k = [&]() {
+                const int noff = ((gb + 1) & (ATT_SLOTS - 1)) * ATT_SLOT_F4 + lane;
+                const int kra = jb < NKB - 1 ? cur.ra : nxt.ra;
+#pragma unroll
+                for (int g = 0; g < 4; ++g) kf[g] = lds[kra + noff + g * 64];
+            };
+            f32x16 sta = ta.negm, stb = tb.negm;
+            float psa = 0.f, psb = 0.f;
+
+            if constexpr (V == QV_ONEX) {
+                unsigned mine = 1;                                    // block 0 sets the reference in both partners
+                if (jb != 0) {
+                    sta = mfma32_from(kf[0][0], qa[0][0], ta.negm);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int e = (g == 0 ? 1 : 0); e < 4; ++e) sta = mfma32(kf[g][e], qa[g][e], sta);
+                    psa = exp_sum(sta);
+                    mine = __builtin_amdgcn_ballot_w64(!(psa < SM_BIG)) != 0;
+                }
+                issue_next();   // block gb + 3, behind the exponentials
+                // publish the stale bit; lgkmcnt(0) also retires this block's V^T reads before the barrier frees their slot
+                const unsigned fset = flag_base + (jb & 1) * 32;
+                asm volatile("ds_write_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" ::"v"(fset + wave * 4), "v"(mine) : "memory");
+                land_q();
+                wait_ring();
+                __builtin_amdgcn_s_barrier();
+                unsigned theirs;
+                asm volatile("ds_read_b32 %0, %1\n\ts_waitcnt lgkmcnt(0)" : "=&v"(theirs) : "v"(fset + (wave ^ 1) * 4) : "memory");
+                if (mine | __builtin_amdgcn_readfirstlane(theirs)) psa = rereference(kf, qa, sta, oa, ta);
+                ta.l_lane += psa;
+                next_k();
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oa = mfma32(vf[g][e], sta[4 * g + e], oa);
+            } else if constexpr (V == QV_TWO) {
+                // one tile after the other through the same fragment registers: K_b(gb) is read behind tile a's scores,
+                // V_b(gb) behind PV_A (the empty asm keeps the compiler from hoisting the reads into registers of their own)
+                auto scores = [&](const f32x4(&qx)[4], f32x16& st, f32x16& ot, TileState& tx) {
+                    float ps = 0.f;
+                    bool redo = jb == 0;                              // scalar
+                    if (jb != 0) {
+                        st = mfma32_from(kf[0][0], qx[0][0], tx.negm);
+#pragma unroll
+                        for (int g = 0; g < 4; ++g)
+#pragma unroll
+                            for (int e = (g == 0 ? 1 : 0); e < 4; ++e) st = mfma32(kf[g][e], qx[g][e], st);
+                        ps = exp_sum(st);
+                        redo = __builtin_amdgcn_ballot_w64(!(ps < SM_BIG)) != 0;
+                    }
+                    if (redo) ps = rereference(kf, qx, st, ot, tx);
+                    tx.l_lane += ps;
+                };
+                scores(qa, sta, oa, ta);
+                issue_next();   // block gb + 3, behind the exponentials
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int g = 0; g < 4; ++g) kf[g] = lds[cur.rb + soff + g * 64];
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oa = mfma32(vf[g][e], sta[4 * g + e], oa);      // PV_A
+                asm volatile("" ::: "memory");
+#pragma unroll
+                for (int g = 0; g < 4; ++g) vf[g] = lds[cur.rb + soff + 256 + g * 64];
+                scores(qb, stb, ob, tb);
+                land_q();
+                wait_ring();
+                __builtin_amdgcn_s_barrier();
+                next_k();
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) ob = mfma32(vf[g][e], stb[4 * g + e], ob);      // PV_B
+            } else {
+                bool redo = jb == 0;                                  // scalar
+                if (!redo) {
+                    sta = mfma32_from(kf[0][0], qa[0][0], ta.negm);
+                    if (TWO_TILES) stb = mfma32_from(kf[0][0], qb[0][0], tb.negm);
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int e = (g == 0 ? 1 : 0); e < 4; ++e) {
+                            sta = mfma32(kf[g][e], qa[g][e], sta);
+                            if (TWO_TILES) stb = mfma32(kf[g][e], qb[g][e], stb);
+                        }
+                    psa = exp_sum(sta);
+                    if (TWO_TILES) psb = exp_sum(stb);
+                    const bool stale = !(psa < SM_BIG) || !(psb < SM_BIG);
+                    redo = __builtin_amdgcn_ballot_w64(stale) != 0;   // wave-uniform, rare
+                }
+                issue_next();   // block gb + 3, behind the exponentials
+                if (redo) {
+                    psa = rereference(kf, qa, sta, oa, ta);
+                    if (TWO_TILES) psb = rereference(kf, qb, stb, ob, tb);
+                }
+                ta.l_lane += psa;
+                tb.l_lane += psb;
+#pragma unroll
+                for (int g = 0; g < 4; ++g)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) oa = mfma32(vf[g][e], sta[4 * g + e], oa);      // PV_A
+                // ---- make block gb+1 visible, fetch its K fragments
+                land_q();
+                wait_ring();
+                __builtin_amdgcn_s_barrier();
+                next_k();
+                if (TWO_TILES) {
+#pragma unroll
+                    for (int g = 0; g < 4; ++g)
+#pragma unroll
+                        for (int e = 0; e < 4; ++e) ob = mfma32(vf[g][e], stb[4 * g + e], ob);  // PV_B
+                }
+            }
+        }
+        if (run == 0 && has_next) {
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                qna[g] = qall[((size_t)nxt.ha * NKB + nxt.ta) * 256 + g * 64 + lane];
+                qnb[g] = qall[((size_t)nxt.hb * NKB + nxt.tb) * 256 + g * 64 + lane];
+            }
+        }
+        }
+        store_tile(oa, ta, cur.ha, cur.ta);
+        if (TWO_TILES) store_tile(ob, tb, cur.hb, cur.tb);
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            qa[g] = qna[g];
+            qb[g] = qnb[g];
+        }
+    };
+
+#pragma unroll 1
+    for (int p = 0; p < n; ++p) {
+        const bool has_next = p + 1 < n;
+        const QuadSlots nxt = has_next ? slots(p + 1) : cur;
+        const int t = ptype(p);
+        if constexpr (ROLE == 0) {
+            run_pass(QuadForm<QV_PAIR>{}, nxt, has_next);
+        } else if constexpr (ROLE == 1) {
+            if (t == 3) run_pass(QuadForm<QV_ONEX>{}, nxt, has_next);
+            else run_pass(QuadForm<QV_PAIR>{}, nxt, has_next);
+        } else {
+            if (t == QP_PLAIN) run_pass(QuadForm<QV_ONE>{}, nxt, has_next);
+            else if (t == 3) run_pass(QuadForm<QV_ONEX>{}, nxt, has_next);
+            else if (t == 1) run_pass(QuadForm<QV_PAIR>{}, nxt, has_next);
+            else run_pass(QuadForm<QV_TWO>{}, nxt, has_next);
+        }
+        cur = nxt;
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the trailing (unused) DMAs
+}
+
+__global__ __launch_bounds__(PERSIST_THREADS, 2) void attn_fwd_persistent_quad_kernel(
+    const float* __restrict__ q, const float* __restrict__ k, const float* __restrict__ vT,
+    float* __restrict__ o, int BH) {
+    extern __shared__ __attribute__((aligned(16))) f32x4 ring[];
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const f32x4* qg = reinterpret_cast<const f32x4*>(q);
+    const f32x4* kg = reinterpret_cast<const f32x4*>(k);
+    const f32x4* vg = reinterpret_cast<const f32x4*>(vT);
+    f32x4* og = reinterpret_cast<f32x4*>(o);
+    if (wave < 4)
+        attn_quad_walk<0>(ring, qg, kg, vg, og, BH, lane, wave);
+    else if (wave < 7)
+        attn_quad_walk<1>(ring, qg, kg, vg, og, BH, lane, wave);
+    else
+        attn_quad_walk<2>(ring, qg, kg, vg, og, BH, lane, wave);
+}
+
 int launch_attn_packed(const float* q, const float* k, const float* vT, float* o, int BH, hipStream_t st) {
     static int n_cu = 0;
     if (n_cu == 0) {
@@ -507,11 +845,22 @@ int launch_attn_packed(const float* q, const float* k, const float* vT, float* o
     // 63.1-63.4 / 63.9-64.1.  (Alone on the chip the persistent kernel wins from one head per CU: 69 vs 75 us at 256 heads --
     // the switch sat there while the 32-series shard ran as one chain.)  T2S_ATTN_PERSIST_MIN=<heads> moves the switch.
     static const int persist_min = getenv("T2S_ATTN_PERSIST_MIN") ? atoi(getenv("T2S_ATTN_PERSIST_MIN")) : 0;
+    // T2S_ATTN_GRID=<n> caps the persistent grid (tests, experiments); T2S_ATTN_QUAD=0 keeps the head-by-head walk (A/B)
+    static const int grid_cap = getenv("T2S_ATTN_GRID") ? atoi(getenv("T2S_ATTN_GRID")) : 0;
+    static const bool quad_on = !(getenv("T2S_ATTN_QUAD") && atoi(getenv("T2S_ATTN_QUAD")) == 0);
     if (BH >= (persist_min > 0 ? persist_min : 3 * n_cu)) {
         // persistent: one 8-wave workgroup per CU walks the heads.  Never more workgroups than heads: a workgroup without a head
         // of its own would start its K / V ring at a negative head index (the default switch keeps BH >= 3 n_cu; the A/B
         // switch T2S_ATTN_PERSIST_MIN can put fewer heads than CUs here -- found by tests/test_hip_contracts.py in round 5)
-        attn_fwd_persistent_kernel<<<BH < n_cu ? BH : n_cu, PERSIST_THREADS, ATT_LDS_BYTES, st>>>(q, k, vT, o, BH);
+        int grid = BH < n_cu ? BH : n_cu;
+        if (grid_cap > 0 && grid_cap < grid) grid = grid_cap;
+        // heads in fours once every workgroup has a whole quad (BH / grid heads at least); below that there is nothing to spread
+        if (quad_on && BH / grid >= 4) {
+            if (int rc = attn_init()) return rc;   // LDS above 64 KiB (already set by every handle's create: a no-op then)
+            attn_fwd_persistent_quad_kernel<<<grid, PERSIST_THREADS, QUAD_LDS_BYTES, st>>>(q, k, vT, o, BH);
+        } else {
+            attn_fwd_persistent_kernel<<<grid, PERSIST_THREADS, ATT_LDS_BYTES, st>>>(q, k, vT, o, BH);
+        }
     } else {
         // four workgroups per head while two per head would leave CUs without a workgroup of this launch (fewer than 128 heads:
         // 16 sequences, i.e. 8 series with CFG): series/s at 8 series 27.5 against 22.8 (+20 %); from 128 heads on two per head
@@ -612,6 +961,8 @@ int attn_init() {  // once, outside any stream capture
     if (!attr_set) {
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_plain_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, PLAIN_LDS_BYTES));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_fwd_persistent_quad_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, QUAD_LDS_BYTES));
         attr_set = true;
     }
     return T2S_OK;
