@@ -269,6 +269,25 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
  * scores.  For tests / benchmarking of that kernel (incl. its stale-reference branch). */
 int t2s_attn_fwd_bf16(const float* q, const float* k, const float* v, float* o_rows, float* lse,
                       int n_seq, void* stream);
+/* The attention of the training path alone, forward then backward, on fp32 buffers: exactly the kernels
+ * t2s_dit_train_forward / t2s_dit_train_backward launch for one block, through the same host launchers.
+ * q, k, v (n_seq*4, 480, 32) heads, UNSCALED; do_rows, o_rows (n_seq*480, 128) token rows, head h at columns
+ * 32h..32h+31; lse (n_seq*4, 480) log2-domain log-sum-exp of the scaled scores; dqkv_rows (n_seq*480, 384) =
+ * [dq | dk | dv], the gradient with respect to the unscaled q, k, v.  dtype T2S_TRAIN_F32 or T2S_TRAIN_BF16; bf16
+ * converts on the way in (q times 32^-0.5 log2(e) before the rounding, as the qkv GEMM's epilogue stores it; k, v, dO
+ * rounded) and back on the way out.  Allocates its temporaries and synchronises the stream.  For tests /
+ * benchmarking of those kernels. */
+int t2s_attn_train(const float* q, const float* k, const float* v, const float* do_rows, float* o_rows,
+                   float* lse, float* dqkv_rows, int n_seq, int dtype, void* stream);
+/* The weight-gradient kernels of the training path (and of the LA-VAE backwards) alone, on fp32 buffers:
+ * dW (N,K) = dY^T X over the M rows of dY (M,N) and X (M,K), db (N) = column sums of dY (db may be NULL).
+ * N % 128 == 0, K % 128 == 0, M > 0.  dtype T2S_TRAIN_F32 (the exact-fp32 kernel) or T2S_TRAIN_BF16 (operands
+ * rounded to bf16 on the way in, fp32 accumulation).  flags bit 0: the X operand is gelu(X), applied after the rounding
+ * and rounded again (the fc2 weight gradient; bf16 only).  flags bit 1: walk the row slabs in reverse (bf16; the fp32
+ * kernel has no direction).  Allocates its temporaries and synchronises the stream.  For tests / benchmarking of
+ * those kernels. */
+int t2s_wgrad(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, int dtype,
+              int flags, void* stream);
 /* Backward of the last t2s_dit_train_forward: dout (B,64,30) = dLoss/dout; writes (overwrites)
  * every gradient tensor of `g`.  Every gradient is reduced in a fixed order (bit-reproducible from run to run): the block
  * weights / biases per row slab in slab order, the small final-layer and patchify gradients (ln, linear_emb_to_patch,

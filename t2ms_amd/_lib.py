@@ -179,6 +179,8 @@ SYMBOLS = {
     "t2s_attn_fwd_x3": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_attn_fwd_bf16p": (_I, [_VP, _VP, _VP, _VP, _I, _VP]),
     "t2s_attn_fwd_bf16": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _VP]),
+    "t2s_attn_train": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
+    "t2s_wgrad": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _I, _I, _VP]),
     "t2s_dit_train_forward": (_I, [_VP, C.POINTER(DitWeights), _VP, _VP, _I, _VP, _VP, _I, _VP]),
     "t2s_dit_train_backward": (_I, [_VP, _VP, C.POINTER(DitGrads), _I, _VP]),
     "t2s_dit_train_input_grad": (_I, [_VP, _VP, _I, _VP]),

@@ -353,9 +353,14 @@ int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* 
     return T2S_OK;
 }
 
+int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* o_rows, float* lse, int BH,
+                         hipStream_t st);                                                       // t2s_attn_bwd.hip
+int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows, const float* do_rows,
+             const float* lse, float* dsum, float* dqkv_rows, int BH, hipStream_t st);
+
 }  // namespace t2s
 
-// ------------------------------------------------------------------ C ABI: stand-alone bf16 attention forward
+// ------------------------------------------------------------------ C ABI: stand-alone training attention (tests, benchmarking)
 namespace {
 __global__ void f32_to_bf16_kernel(const float* __restrict__ src, __bf16* __restrict__ dst, size_t n4, float scale) {
     const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -366,6 +371,20 @@ __global__ void bf16_to_f32_kernel(const __bf16* __restrict__ src, float* __rest
     if (i < n4) reinterpret_cast<t2s::f32x4*>(dst)[i] = t2s::unpack4(reinterpret_cast<const t2s::bf16x4*>(src)[i]);
 }
 }  // namespace
+
+namespace t2s {
+// fp32 <-> bf16 copies of the stand-alone doors (n % 4 == 0); also used by t2s_wgrad (t2s_train.hip)
+int f32_to_bf16(const float* src, __bf16* dst, size_t n, float scale, hipStream_t st) {
+    f32_to_bf16_kernel<<<(unsigned)((n / 4 + 255) / 256), 256, 0, st>>>(src, dst, n / 4, scale);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+int bf16_to_f32(const __bf16* src, float* dst, size_t n, hipStream_t st) {
+    bf16_to_f32_kernel<<<(unsigned)((n / 4 + 255) / 256), 256, 0, st>>>(src, dst, n / 4);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+}  // namespace t2s
 
 extern "C" int t2s_attn_fwd_bf16(const float* q, const float* k, const float* v, float* o_rows, float* lse, int n_seq,
                                  void* stream) {
@@ -389,3 +408,38 @@ extern "C" int t2s_attn_fwd_bf16(const float* q, const float* k, const float* v,
     return rc;
 }
 
+extern "C" int t2s_attn_train(const float* q, const float* k, const float* v, const float* do_rows, float* o_rows, float* lse,
+                              float* dqkv_rows, int n_seq, int dtype, void* stream) {
+    using namespace t2s;
+    T2S_REQUIRE(q && k && v && do_rows && o_rows && lse && dqkv_rows && n_seq > 0, "t2s_attn_train: bad argument");
+    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_attn_train: unknown dtype %d", dtype);
+    hipStream_t st = (hipStream_t)stream;
+    const int BH = n_seq * NH;
+    const size_t n = (size_t)BH * NTOK * DH;               // elements of each of q, k, v, o, do; dqkv has 3 n
+    float* dsum = nullptr;                                 // D_i (BH, 480)
+    __bf16* buf = nullptr;                                 // bf16: q | k | v | o | do | dqkv
+    T2S_HIP_CHECK(hipMalloc(&dsum, (size_t)BH * NTOK * sizeof(float)));
+    reset_tile_dir();                                      // as at the top of a training forward
+    int rc = T2S_OK;
+    if (dtype == T2S_TRAIN_F32) {
+        rc = attn_plain_train_fwd(q, k, v, o_rows, lse, BH, st);
+        if (rc == T2S_OK) rc = attn_bwd(q, k, v, o_rows, do_rows, lse, dsum, dqkv_rows, BH, st);
+    } else if (hipMalloc(&buf, 8 * n * sizeof(__bf16)) != hipSuccess) {
+        set_error("t2s_attn_train: out of memory for %zu bf16 values", 8 * n);
+        rc = T2S_E_HIP;
+    } else {
+        __bf16 *qh = buf, *kh = buf + n, *vh = buf + 2 * n, *oh = buf + 3 * n, *doh = buf + 4 * n, *dh = buf + 5 * n;
+        rc = f32_to_bf16(q, qh, n, ATT_QS, st);            // the kernels take q pre-scaled (as the qkv GEMM stores it)
+        if (rc == T2S_OK) rc = f32_to_bf16(k, kh, n, 1.0f, st);
+        if (rc == T2S_OK) rc = f32_to_bf16(v, vh, n, 1.0f, st);
+        if (rc == T2S_OK) rc = f32_to_bf16(do_rows, doh, n, 1.0f, st);
+        if (rc == T2S_OK) rc = attn16_train_fwd(qh, kh, vh, oh, lse, BH, st);
+        if (rc == T2S_OK) rc = attn16_bwd(qh, kh, vh, oh, doh, lse, dsum, dh, BH, st);
+        if (rc == T2S_OK) rc = bf16_to_f32(oh, o_rows, n, st);
+        if (rc == T2S_OK) rc = bf16_to_f32(dh, dqkv_rows, 3 * n, st);
+    }
+    (void)hipStreamSynchronize(st);
+    if (buf) (void)hipFree(buf);
+    (void)hipFree(dsum);
+    return rc;
+}

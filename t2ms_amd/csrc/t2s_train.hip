@@ -29,6 +29,7 @@ int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows
 int attn16_train_fwd(const __bf16* q, const __bf16* k, const __bf16* v, __bf16* o_rows, float* lse, int BH, hipStream_t st);
 int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* o_rows, const __bf16* do_rows,
                const float* lse, float* dsum, __bf16* dqkv_rows, int BH, hipStream_t st);
+int f32_to_bf16(const float* src, __bf16* dst, size_t n, float scale, hipStream_t st);   // t2s_attn_bf16.hip
 }
 
 // ------------------------------------------------------------------ workspace
@@ -1265,6 +1266,43 @@ int t2s_mse_backward(const float* a, const float* b, const float* grad_out, floa
     if (db) mse_bwd_kernel<<<blocks, 256, 0, (hipStream_t)stream>>>(a, b, grad_out, db, (size_t)n, -1.0f);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
+}
+
+int t2s_wgrad(const float* dY, const float* X, float* dW, float* db, int M, int N, int K, int dtype, int flags, void* stream) {
+    T2S_REQUIRE(dY && X && dW, "t2s_wgrad: NULL argument");
+    T2S_REQUIRE(M > 0 && N > 0 && K > 0 && N % 128 == 0 && K % 128 == 0, "t2s_wgrad: unsupported shape M=%d N=%d K=%d", M, N, K);
+    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_wgrad: unknown dtype %d", dtype);
+    T2S_REQUIRE((flags & ~3) == 0, "t2s_wgrad: unknown flags %d", flags);
+    T2S_REQUIRE(!(flags & 1) || dtype == T2S_TRAIN_BF16, "t2s_wgrad: gelu on the X operand (flags bit 0) is a bf16 kernel only");
+    hipStream_t st = (hipStream_t)stream;
+    int dev = 0;
+    hipDeviceProp_t prop;
+    T2S_HIP_CHECK(hipGetDevice(&dev));
+    T2S_HIP_CHECK(hipGetDeviceProperties(&prop, dev));
+    const int n_cu = prop.multiProcessorCount;
+    const size_t scratch_floats = wgrad16_shape_scratch_floats(N, K, n_cu);
+    float* scratch = nullptr;
+    __bf16* buf = nullptr;                                  // bf16: dY (M,N) | X (M,K)
+    T2S_HIP_CHECK(hipMalloc(&scratch, scratch_floats * sizeof(float)));
+    t2s::g_tile_flip = (flags & 2) ? 1u : 0u;               // the direction next_tile_dir() hands the launch
+    int rc = T2S_OK;
+    if (dtype == T2S_TRAIN_F32) {
+        rc = launch_wgrad32(dY, X, dW, db, M, N, K, scratch, scratch_floats, n_cu, st);
+    } else if (hipMalloc(&buf, (size_t)M * (N + K) * sizeof(__bf16)) != hipSuccess) {
+        set_error("t2s_wgrad: out of memory for %zu bf16 values", (size_t)M * (N + K));
+        rc = T2S_E_HIP;
+    } else {
+        __bf16 *yh = buf, *xh = buf + (size_t)M * N;
+        rc = f32_to_bf16(dY, yh, (size_t)M * N, 1.0f, st);
+        if (rc == T2S_OK) rc = f32_to_bf16(X, xh, (size_t)M * K, 1.0f, st);
+        if (rc == T2S_OK)
+            rc = (flags & 1) ? launch_wgrad16<true>(yh, xh, dW, db, M, N, K, scratch, scratch_floats, n_cu, st)
+                             : launch_wgrad16<false>(yh, xh, dW, db, M, N, K, scratch, scratch_floats, n_cu, st);
+    }
+    (void)hipStreamSynchronize(st);
+    if (buf) (void)hipFree(buf);
+    (void)hipFree(scratch);
+    return rc;
 }
 
 }  // extern "C"
