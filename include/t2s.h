@@ -471,8 +471,8 @@ int t2s_vae_update_weights(t2s_vae* h, const t2s_vae_weights* w, void* stream);
  * allocates device memory, so both can run inside a captured graph.  A handle is EITHER kind: a single-channel entry
  * (t2s_vae_encode, _decode, _decode_w, _encode_backward, _decode_backward) handed a multichannel handle returns
  * T2S_E_INVALID naming the _mc entry, and the _mc entries refuse a t2s_vae_create handle likewise; a handle made here with
- * channels = 1 is a multichannel handle.  t2s_vae_update_weights and t2s_vae_destroy serve both kinds.  There is no HIP
- * backward for C channels yet (the host mirror trains through torch ops). */
+ * channels = 1 is a multichannel handle.  t2s_vae_update_weights and t2s_vae_destroy serve both kinds.  The backward of the
+ * two _mc entries is t2s_vae_encode_backward_mc / t2s_vae_decode_backward_mc below. */
 int t2s_vae_create_mc(const t2s_vae_weights* w, int channels, t2s_vae** out);
 int t2s_vae_channels(const t2s_vae* h);            /* 0 for a handle made by t2s_vae_create */
 /* x (B,channels,L) -> z (B,emb,latent_w), before (B,emb,L/4) (may be NULL while L/4 <= 32; longer series run in time
@@ -520,6 +520,22 @@ typedef struct t2s_vae_dec_grads {
 } t2s_vae_dec_grads;
 int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter, const t2s_vae_dec_grads* g,
                             float* dz, int B, int L, int latent_w, void* stream);
+
+/* The two backwards for the multichannel codec (a t2s_vae_create_mc handle): one optimisation step of the motion codec's
+ * pre-training (myvqvae.py:116-136) with t2s_vae_encode_mc / t2s_vae_decode_mc, and the encoder's part of a DiT step
+ * (mytrain.py:37-40).  The same kernels and host path as the single-channel entries above, which are their C = 1 case (a
+ * channels = 1 handle gives the single-channel entries' bits); the same gradient structs, with
+ *   conv1_w (hidden/2,channels,4), ct2_w (hidden/2,channels,4), ct2_b (channels);
+ *   x (B,channels,L), dz (B,64,latent_w), drecon (B,channels,L); dbefore, dafter and the decoder's dz may be NULL as above.
+ * When L % 4 != 0 the decoder's way back starts with the transpose of the final resampling 4 (L/4) -> L.
+ *   channels 1..16, hidden 128, res_hidden 128 / 256, 1..4 residual layers, emb 64, latent_w 1..64, B > 0, 8 <= L <= 192 (the
+ *   whole series is one LDS tile: L/4 <= 32 in today's geometry, L/4 <= 48 in about 150 KiB of LDS);
+ * anything else, a t2s_vae_create handle or a NULL gradient pointer is T2S_E_INVALID before any launch or allocation.
+ * T2S_E_HIP if the runtime refuses the kernels' dynamic-LDS cap.  Row blocks grow like the single-channel entries'. */
+int t2s_vae_encode_backward_mc(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g, int B,
+                               int L, int latent_w, void* stream);
+int t2s_vae_decode_backward_mc(t2s_vae* h, const float* z, const float* drecon, const float* dafter, const t2s_vae_dec_grads* g,
+                               float* dz, int B, int L, int latent_w, void* stream);
 
 /* ------------------------------------------------------------------------ *
  * Fused sampling loop: infer.py:75-95 (x_T -> steps x [2 DiT forwards + CFG +

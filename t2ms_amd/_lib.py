@@ -209,6 +209,8 @@ SYMBOLS = {
     "t2s_vae_update_weights": (_I, [_VP, C.POINTER(VaeWeights), _VP]),
     "t2s_vae_encode_backward": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeEncGrads), _I, _I, _VP]),
     "t2s_vae_decode_backward": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeDecGrads), _VP, _I, _I, _I, _VP]),
+    "t2s_vae_encode_backward_mc": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeEncGrads), _I, _I, _I, _VP]),
+    "t2s_vae_decode_backward_mc": (_I, [_VP, _VP, _VP, _VP, C.POINTER(VaeDecGrads), _VP, _I, _I, _I, _VP]),
     "t2s_vae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_vae_encode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_vae_create_mc": (_I, [C.POINTER(VaeWeights), _I, C.POINTER(_VP)]),

@@ -393,14 +393,18 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_kernel(const floa
 }
 
 // ------------------------------------------------------------------------------------------------ encoder backward
-// Backward of Encoder.forward for the one configuration that trains the encoder (train.py:31-33 with `usepretrainedvae`
-// false).  Two stages:
-//   vae_encode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS by the
+// Backward of Encoder.forward: what trains the encoder (train.py:31-33 with `usepretrainedvae` false, LA-VAE pre-training) and,
+// at C channels, the motion codec (myvqvae.py).  One scaffold, as the forward is one codec: the single-channel backward is its
+// C = 1 case with L % 4 == 0, L <= 128 and the 30-wide latent.  Both backward kernels are templated on a tile bound TB (the whole
+// series is ONE tile of T = L/4 <= TB positions): TB = 32 serves L <= 128 with the geometry the single-channel backward always
+// had, TB = 48 serves 128 < L <= 192 (the motion models train at up to 4 x 48) in 139 / 150 KiB of the CU's 160 KiB of LDS.
+// Two stages:
+//   vae_encode_bwd_kernel   one workgroup per series: the forward is recomputed in LDS by the
 //                           functions vae_encode_kernel calls, every layer's INPUT leaves as an im2col'd row block X (rows = b * T
 //                           + t) and its ReLU pattern stays as one bit word per channel; then the data gradients walk back
 //                           through the layers in LDS (transposed convolutions, fixed summation order) and every layer's
-//                           OUTPUT gradient leaves as a row block dY.  conv_1 (1 -> hidden/2, 4 taps: 320 values) is reduced
-//                           per series into one partial row.
+//                           OUTPUT gradient leaves as a row block dY.  conv_1 (C -> hidden/2, 4 taps: 64 (4 C + 1) values) is
+//                           reduced per series into one partial row.
 //   launch_wgrad32          dW = dY^T X per layer on the exact-fp32 MFMA (t2s_wgrad.h), deterministic two-stage reduction;
 //                           vae_part_reduce_kernel adds the conv_1 partial rows in series order.
 struct VaeStackBufs {   // per residual layer: the rows of r and m (inputs of c3 / c1), the output gradients of c1 / c3
@@ -410,8 +414,22 @@ struct VaeBwdBufs {
     float *Xc2, *Xc3, *Xp, *dYp, *dY3, *dY2, *part1;
     VaeStackBufs st;
 };
-constexpr int VAE_BWD_MASK_BYTES = (128 + 128 + 5 * 128 + 4 * 256) * 4;   // ReLU bit words of vae_encode_bwd_kernel
-constexpr int VAE_P1 = 320;   // conv_1 partial row: dW (hidden/2 x 4 = 256) | db (64) at hidden = 128
+// The LDS of a backward kernel at tile bound TB: the forward's two activation buffers, slack and `wide` at row stride TB + 1,
+// then the ReLU bit words -- WT words per channel for a pattern over T positions, WT2 for one over the L/2 resolution -- and,
+// in the decoder, the C x 4 T output-gradient samples (sized per launch).
+template <int TB>
+struct VaeBwdGeom {
+    static constexpr int LD = TB + 1;
+    static constexpr int WT = (TB + 31) / 32, WT2 = (2 * TB + 31) / 32;
+    static constexpr int FLOATS = 2 * VAE_CMAX * LD + 128 * 4 + 64 * (2 * TB + 2);
+    static constexpr int STACK_WORDS = 5 * 128 * WT + 4 * 256 * WT;
+    static constexpr int ENC_BYTES = (FLOATS + 64 * WT2 + 128 * WT + STACK_WORDS) * 4;
+    static constexpr int DEC_BYTES = (FLOATS + STACK_WORDS + 64 * WT2) * 4;        // + C * 4 T floats
+    static constexpr int DEC_BYTES_MAX = DEC_BYTES + VAE_MC_CMAX * 4 * TB * 4;
+};
+static_assert(VaeBwdGeom<VAE_TMAX>::FLOATS == VAE_LDS_FLOATS, "TB = 32 is the forward's geometry");
+static_assert(VaeBwdGeom<48>::ENC_BYTES <= 160 * 1024 && VaeBwdGeom<48>::DEC_BYTES_MAX <= 160 * 1024, "a backward tile exceeds the LDS of a CU");
+__host__ __device__ inline int vae_p1(int C) { return 64 * (4 * C + 1); }   // conv_1 partial row: dW (hidden/2, C, 4) | db (64) at hidden = 128
 
 // din[ci][t'] (+)= sum_{co, kk : t * STRIDE + kk - pad = t'} W[co][ci][kk] * dout[co][t]   -- data gradient of conv1d_lds --
 // then zeroed where the layer input's ReLU was off (mask: one word per channel, bit = position; NULL: no ReLU in front).
@@ -481,102 +499,115 @@ __device__ void rows_out(const float* buf, int C, int T, int ld, float* __restri
 // residual_stack for the backward kernels: the same arithmetic on x = bufB (tmp = bufA), and what the backward needs stays
 // behind -- the ReLU patterns m_r [n_res + 1][128] (r_l = relu(h_l), then r_final) and m_m [n_res][256] (m_l), the rows of r_l
 // (im2col'd) and m_l.  Ends behind the final relu_mask: the caller writes r_final's rows where its next layer wants them.
+template <int TB>
 __device__ void residual_stack_recompute(float* bufB, float* bufA, int H, int R, int n_res, int T, const float* const* c3,
                                          const float* const* c1, const VaeStackBufs& s, size_t row0, unsigned* m_r, unsigned* m_m) {
+    constexpr int LD = VaeBwdGeom<TB>::LD, WT = VaeBwdGeom<TB>::WT;
     for (int l = 0; l < n_res; ++l) {
         relu_inplace(bufB, H, T, LD);
         __syncthreads();
-        relu_mask(bufB, H, T, LD, m_r + l * 128, 1);               // r_l > 0  <=>  h_l > 0
+        relu_mask(bufB, H, T, LD, m_r + l * 128 * WT, WT);     // r_l > 0  <=>  h_l > 0
         im2col_rows<3, 1>(bufB, H, T, LD, s.Xr3[l], row0, T, 1);
         conv1d_lds<3, 1, true, false>(bufB, H, T, bufA, R, T, c3[l], nullptr, 1, LD, LD);
         __syncthreads();
-        relu_mask(bufA, R, T, LD, m_m + l * 256, 1);
+        relu_mask(bufA, R, T, LD, m_m + l * 256 * WT, WT);
         rows_out(bufA, R, T, LD, s.Xm[l], row0, R);
         conv1d_lds<1, 1, false, true>(bufA, R, T, bufB, H, T, c1[l], nullptr, 0, LD, LD);
         __syncthreads();
     }
     relu_inplace(bufB, H, T, LD);
     __syncthreads();
-    relu_mask(bufB, H, T, LD, m_r + n_res * 128, 1);
+    relu_mask(bufB, H, T, LD, m_r + n_res * 128 * WT, WT);
 }
 
 // The way back through the stack: bufB holds dL/dh_out of the last layer on entry (already masked by r_final > 0) and
 // dL/dh_in of the first on return; every layer's output gradients leave as the row blocks dYc1 / dYc3.
+template <int TB>
 __device__ void residual_stack_backward(float* bufB, float* bufA, int H, int R, int n_res, int T, const float* const* c3,
                                         const float* const* c1, const VaeStackBufs& s, size_t row0, const unsigned* m_r,
                                         const unsigned* m_m) {
+    constexpr int LD = VaeBwdGeom<TB>::LD, WT = VaeBwdGeom<TB>::WT;
     for (int l = n_res - 1; l >= 0; --l) {
         // bufB = dL/dh_out, h_out = r + c1(m), m = relu(c3(r)), r = relu(h_in)
         rows_out(bufB, H, T, LD, s.dYc1[l], row0, H);
-        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, c1[l], 0, LD, LD, m_m + l * 256, 1);       // d(pre-ReLU of m)
+        conv1d_dgrad_lds<1, 1, false>(bufB, H, T, bufA, R, T, c1[l], 0, LD, LD, m_m + l * 256 * WT, WT);   // d(pre-ReLU of m)
         __syncthreads();
         rows_out(bufA, R, T, LD, s.dYc3[l], row0, R);
-        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, c3[l], 1, LD, LD, m_r + l * 128, 1);        // + skip, masked: dL/dh_in
+        conv1d_dgrad_lds<3, 1, true>(bufA, R, T, bufB, H, T, c3[l], 1, LD, LD, m_r + l * 128 * WT, WT);    // + skip, masked: dL/dh_in
         __syncthreads();
     }
 }
 
+template <int TB>
 __global__ __launch_bounds__(VAE_THREADS) void vae_encode_bwd_kernel(const VaeDev w, const float* __restrict__ x,
                                                                      const float* __restrict__ dz,
-                                                                     const float* __restrict__ dbefore, const VaeBwdBufs s, int L) {
+                                                                     const float* __restrict__ dbefore, const VaeBwdBufs s, int L,
+                                                                     int W, int C) {
+    using G = VaeBwdGeom<TB>;
+    constexpr int LD = G::LD, WT = G::WT, WT2 = G::WT2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bufA = smem;
     float* bufB = smem + VAE_CMAX * LD;
     float* wide = bufB + VAE_CMAX * LD;                            // [hidden/2][T2]
-    unsigned* m_w1 = reinterpret_cast<unsigned*>(smem + VAE_LDS_FLOATS);   // [64][2]
-    unsigned* m_a = m_w1 + 128;                                    // [128]
-    unsigned* m_r = m_a + 128;                                     // [5][128]: r_l = relu(h_l) for l < n_res, then r_final
-    unsigned* m_m = m_r + 5 * 128;                                 // [4][256]
+    unsigned* m_w1 = reinterpret_cast<unsigned*>(smem + G::FLOATS);        // [64][WT2]
+    unsigned* m_a = m_w1 + 64 * WT2;                               // [128][WT]
+    unsigned* m_r = m_a + 128 * WT;                                // [5][128][WT]: r_l = relu(h_l) for l < n_res, then r_final
+    unsigned* m_m = m_r + 5 * 128 * WT;                            // [4][256][WT]
     const int b = blockIdx.x;
     const int T2 = L / 2, T = L / 4, H = w.hidden, R = w.res_hidden, half_c = H / 2;
     const size_t row0 = (size_t)b * T;
-    // ---------------- forward, recomputed with vae_encode_kernel's pieces (one tile: the window is the series; C = 1)
-    encode_stem(w, x + (size_t)b * L, 1, L, 0, T2, wide);
+    const float* xb = x + (size_t)b * C * L;
+    // ---------------- forward, recomputed with vae_encode_kernel's pieces (one tile: the window is the series, conv_1's
+    // outputs [0, T2) -- an odd T2 = 2 T + 1 keeps the last one, which conv_2's last window reads)
+    encode_stem(w, xb, C, L, 0, T2, wide);
     __syncthreads();
-    relu_mask(wide, half_c, T2, T2, m_w1, 2);
+    relu_mask(wide, half_c, T2, T2, m_w1, WT2);
     im2col_rows<4, 2>(wide, half_c, T2, T2, s.Xc2, row0, T, 1);
     conv1d_lds<4, 2, true, false>(wide, half_c, T2, bufA, H, T, w.enc_conv2_w, w.enc_conv2_b, 1, T2, LD, 0, 0);
     __syncthreads();
-    relu_mask(bufA, H, T, LD, m_a, 1);
+    relu_mask(bufA, H, T, LD, m_a, WT);
     im2col_rows<3, 1>(bufA, H, T, LD, s.Xc3, row0, T, 1);
     conv1d_lds<3, 1, false, false>(bufA, H, T, bufB, H, T, w.enc_conv3_w, w.enc_conv3_b, 1, LD, LD);
     __syncthreads();
-    residual_stack_recompute(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
+    residual_stack_recompute<TB>(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.Xp, row0, H);
     __syncthreads();
     // ---------------- backward.  dbefore_total = dbefore (if given) + interp^T(dz)  -> bufA [emb][T]
     {
-        const float* g = dz + (size_t)b * w.emb * LATW;
+        const float* g = dz + (size_t)b * w.emb * W;
         if (dbefore != nullptr)
-            interp_linear_ac_transposed<true, false>(g, LATW, nullptr, 0, dbefore + (size_t)b * w.emb * T, T, bufA, LD, w.emb, T, LATW);
+            interp_linear_ac_transposed<true, false>(g, W, nullptr, 0, dbefore + (size_t)b * w.emb * T, T, bufA, LD, w.emb, T, W);
         else
-            interp_linear_ac_transposed<false, false>(g, LATW, nullptr, 0, nullptr, 0, bufA, LD, w.emb, T, LATW);
+            interp_linear_ac_transposed<false, false>(g, W, nullptr, 0, nullptr, 0, bufA, LD, w.emb, T, W);
     }
     __syncthreads();
     rows_out(bufA, w.emb, T, LD, s.dYp, row0, 128);                // padded to 128 columns for the weight-gradient GEMM
     // d r_final = Wp^T dbefore, masked by r_final > 0: the gradient at the stack's output h
-    conv1d_dgrad_lds<1, 1, false>(bufA, w.emb, T, bufB, H, T, w.enc_prevq_w, 0, LD, LD, m_r + w.n_res * 128, 1);
+    conv1d_dgrad_lds<1, 1, false>(bufA, w.emb, T, bufB, H, T, w.enc_prevq_w, 0, LD, LD, m_r + w.n_res * 128 * WT, WT);
     __syncthreads();
-    residual_stack_backward(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
+    residual_stack_backward<TB>(bufB, bufA, H, R, w.n_res, T, w.enc_c3, w.enc_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.dY3, row0, H);                       // dL/d(conv_3 output)
-    conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, H, T, w.enc_conv3_w, 1, LD, LD, m_a, 1);                     // dL/d(conv_2 pre-ReLU)
+    conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, H, T, w.enc_conv3_w, 1, LD, LD, m_a, WT);                    // dL/d(conv_2 pre-ReLU)
     __syncthreads();
     rows_out(bufA, H, T, LD, s.dY2, row0, H);
-    conv1d_dgrad_lds<4, 2, false>(bufA, H, T, wide, half_c, T2, w.enc_conv2_w, 1, LD, T2, m_w1, 2);              // dL/d(conv_1 pre-ReLU)
+    conv1d_dgrad_lds<4, 2, false>(bufA, H, T, wide, half_c, T2, w.enc_conv2_w, 1, LD, T2, m_w1, WT2);            // dL/d(conv_1 pre-ReLU)
     __syncthreads();
-    // conv_1: dW[co][kk] = sum_u d[co][u] x[2u + kk - 1], db[co] = sum_u d[co][u]: one partial row per series
-    for (int o = threadIdx.x; o < half_c * 5; o += VAE_THREADS) {
-        const int co = o / 5, kk = o - co * 5;
+    // conv_1: dW[co][c][kk] = sum_u d[co][u] x[c][2u + kk - 1], db[co] = sum_u d[co][u]: one partial row per series, torch's
+    // (hidden/2, C, 4) layout and the bias behind it
+    const int per_co = 4 * C + 1;
+    for (int o = threadIdx.x; o < half_c * per_co; o += VAE_THREADS) {
+        const int co = o / per_co, j = o - co * per_co;
+        const int c = j >> 2, kk = j & 3;
         float acc = 0.f;
         for (int u = 0; u < T2; ++u) {
             const float d = wide[co * T2 + u];
-            if (kk == 4) acc += d;
+            if (j == 4 * C) acc += d;
             else {
                 const int ti = 2 * u + kk - 1;
-                if (ti >= 0 && ti < L) acc += d * x[(size_t)b * L + ti];
+                if (ti >= 0 && ti < L) acc += d * xb[(size_t)c * L + ti];
             }
         }
-        s.part1[(size_t)b * VAE_P1 + (kk == 4 ? half_c * 4 + co : co * 4 + kk)] = acc;
+        s.part1[(size_t)b * vae_p1(C) + (j == 4 * C ? half_c * 4 * C + co : co * 4 * C + j)] = acc;
     }
 }
 
@@ -600,13 +631,15 @@ __global__ __launch_bounds__(256) void vae_part_reduce_kernel(const float* __res
 }
 
 // ------------------------------------------------------------------------------------------------ decoder backward
-// Backward of Decoder.forward (vqvae.py:97-105), what LA-VAE pre-training (pretrained_lavae_unified.py) adds to the encoder
-// backward above; the same two stages:
-//   vae_decode_bwd_kernel   one workgroup per series (L <= 128: one tile): the forward is recomputed in LDS by the
+// Backward of Decoder.forward (vqvae.py:97-105, myvqvae.py:76-86), what LA-VAE pre-training (pretrained_lavae_unified.py) adds to
+// the encoder backward above; the same scaffold (C channels, tile bound TB) and the same two stages:
+//   vae_decode_bwd_kernel   one workgroup per series: the forward is recomputed in LDS by the
 //                           functions vae_decode_kernel calls up to the ReLU behind _conv_trans_1 (the samples themselves are not
 //                           needed), layer inputs leave as row blocks and ReLU patterns stay as bit words; then the data
-//                           gradients walk back from drecon to the latent.  _conv_trans_2 (hidden/2 x 4 = 256 values) and the
-//                           two small biases are reduced per series into partial rows.
+//                           gradients walk back from drecon to the latent.  When L != 4 T the way back starts with the transpose
+//                           of the final resampling 4 T -> L (the forward's interp_tap_ac taps): either way C x 4 T sample
+//                           gradients are staged in LDS.  _conv_trans_2 (hidden/2 x C x 4 values) and the two small biases are
+//                           reduced per series into partial rows.
 //   launch_wgrad32          dW = dY^T X per layer.  _conv_1: K = emb * 3 = 192, im2col rows padded to 256 columns.
 //                           _conv_trans_1 (Cin, Cout * 4): the layer INPUT rows are the N operand, the gathered rows of the
 //                           output gradient (column co * 4 + kk = d[co][2 i - 1 + kk]) the K operand.
@@ -614,14 +647,13 @@ struct VaeDecBwdBufs {
     float *Xc1, *dY1, *Xct1, *Gct1, *part2, *partb1;
     VaeStackBufs st;
 };
-constexpr int VAE_DBWD_MASK_BYTES = (5 * 128 + 4 * 256 + 128) * 4;   // ReLU bit words of vae_decode_bwd_kernel
-constexpr int VAE_P2 = 257;   // _conv_trans_2 partial row: dW (hidden/2 x 4 = 256) | db (1) at hidden = 128
+__host__ __device__ inline int vae_p2(int C) { return 64 * 4 * C + C; }   // _conv_trans_2 partial row: dW (hidden/2, C, 4) | db (C) at hidden = 128
 constexpr int VAE_PB1 = 64;   // _conv_trans_1 bias partial row (hidden/2)
 
 // din[ci][i] = sum_{co, kk : 0 <= 2 i - 1 + kk < Tout} W[ci][co][kk] * dout[co][2 i - 1 + kk]   -- data gradient of
 // convT1d_k4s2_lds (a stride-2 convolution of the output gradient) -- zeroed where the layer input's ReLU was off.
 __device__ void convT1d_k4s2_dgrad_lds(const float* dout, int Cout, int Tout, float* din, int Cin, int Tin,
-                                       const float* __restrict__ W, int ld_out, int ld_in, const unsigned* mask) {
+                                       const float* __restrict__ W, int ld_out, int ld_in, const unsigned* mask, int mask_words) {
     constexpr int CP = VAE_CO_PER_THREAD;
     for (int o = threadIdx.x; o < (Cin / CP) * Tin; o += VAE_THREADS) {
         const int ci = (o / Tin) * CP, i = o - (o / Tin) * Tin;
@@ -641,32 +673,42 @@ __device__ void convT1d_k4s2_dgrad_lds(const float* dout, int Cout, int Tout, fl
         }
 #pragma unroll
         for (int u = 0; u < CP; ++u) {
-            const bool on = mask == nullptr || ((mask[ci + u] >> i) & 1u);
+            const bool on = mask == nullptr || ((mask[(ci + u) * mask_words + (i >> 5)] >> (i & 31)) & 1u);
             din[(ci + u) * ld_in + i] = on ? acc[u] : 0.f;
         }
     }
 }
 
+template <int TB>
 __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDev w, const float* __restrict__ z,
                                                                      const float* __restrict__ drecon,
                                                                      const float* __restrict__ dafter, float* __restrict__ dz,
-                                                                     const VaeDecBwdBufs s, int L, int W) {
+                                                                     const VaeDecBwdBufs s, int L, int W, int C) {
+    using G = VaeBwdGeom<TB>;
+    constexpr int LD = G::LD, WT = G::WT, WT2 = G::WT2;
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bufA = smem;
     float* bufB = smem + VAE_CMAX * LD;
-    float* wide = bufB + VAE_CMAX * LD;                            // [hidden/2][T2]
-    float* dr = wide + 64 * 2 * VAE_TMAX;                          // [L]: this series' drecon
-    unsigned* m_r = reinterpret_cast<unsigned*>(smem + VAE_LDS_FLOATS);    // [5][128]: r_l for l < n_res, then r_final
-    unsigned* m_m = m_r + 5 * 128;                                 // [4][256]
-    unsigned* m_w = m_m + 4 * 256;                                 // [64][2]: the ReLU behind _conv_trans_1
+    float* wide = bufB + VAE_CMAX * LD;                            // [hidden/2][2 T]
+    unsigned* m_r = reinterpret_cast<unsigned*>(smem + G::FLOATS);         // [5][128][WT]: r_l for l < n_res, then r_final
+    unsigned* m_m = m_r + 5 * 128 * WT;                            // [4][256][WT]
+    unsigned* m_w = m_m + 4 * 256 * WT;                            // [64][WT2]: the ReLU behind _conv_trans_1
+    float* dr = reinterpret_cast<float*>(m_w + 64 * WT2);          // [C][4 T]: this series' gradient at the samples of _conv_trans_2
     const int b = blockIdx.x;
-    const int T2 = L / 2, T = L / 4, H = w.hidden, R = w.res_hidden, half_c = H / 2, E = w.emb;
+    const int T = L / 4, T2 = 2 * T, L4 = 4 * T, H = w.hidden, R = w.res_hidden, half_c = H / 2, E = w.emb;
     const size_t row0 = (size_t)b * T;
+    const int ldz = W <= TB ? LD : LDZ;
     // ---------------- forward, recomputed with vae_decode_kernel's pieces (one tile)
-    stage_latent(z + (size_t)b * E * W, E, W, bufB, LD);
-    for (int t = threadIdx.x; t < L; t += VAE_THREADS) dr[t] = drecon[(size_t)b * L + t];
+    stage_latent(z + (size_t)b * E * W, E, W, bufB, ldz);
+    {
+        const float* g = drecon + (size_t)b * C * L;
+        if (L == L4)
+            for (int o = threadIdx.x; o < C * L; o += VAE_THREADS) dr[o] = g[o];
+        else      // recon = interp(samples, 4 T -> L): the sample gradients are its transpose
+            interp_linear_ac_transposed<false, false>(g, L, nullptr, 0, nullptr, 0, dr, L4, C, L4, L);
+    }
     __syncthreads();
-    interp_linear_ac(bufB, E, W, LD, bufA, T, LD);
+    interp_linear_ac(bufB, E, W, ldz, bufA, T, LD);
     __syncthreads();
     // _conv_1's im2col rows, K = emb * 3 = 192 padded to 256 columns
     for (int o = threadIdx.x; o < T * 256; o += VAE_THREADS) {
@@ -676,37 +718,40 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDe
     }
     conv1d_lds<3, 1, false, false>(bufA, E, T, bufB, H, T, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
     __syncthreads();
-    residual_stack_recompute(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
+    residual_stack_recompute<TB>(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.Xct1, row0, H);
     convT1d_k4s2_lds<true>(bufB, H, T, wide, half_c, w.dec_ct1_w, w.dec_ct1_b, LD, T2);
     __syncthreads();
-    relu_mask(wide, half_c, T2, T2, m_w, 2);
-    // ---------------- backward.  _conv_trans_2: recon[t] = b + sum_{ci,kk : t = 2 i - 1 + kk} wide[ci][i] W[ci][kk]
-    // dW[ci][kk] = sum_i wide[ci][i] drecon[2 i - 1 + kk], db = sum_t drecon[t]: one partial row per series
-    for (int o = threadIdx.x; o < half_c * 4 + 1; o += VAE_THREADS) {
+    relu_mask(wide, half_c, T2, T2, m_w, WT2);
+    // ---------------- backward.  _conv_trans_2: y[c][t] = b[c] + sum_{ci,kk : t = 2 i - 1 + kk} wide[ci][i] W[ci][c][kk]
+    // dW[ci][c][kk] = sum_i wide[ci][i] dy[c][2 i - 1 + kk], db[c] = sum_t dy[c][t]: one partial row per series
+    for (int o = threadIdx.x; o < vae_p2(C); o += VAE_THREADS) {
         float acc = 0.f;
-        if (o == half_c * 4) {
-            for (int t = 0; t < L; ++t) acc += dr[t];
+        if (o >= half_c * 4 * C) {
+            const float* d = dr + (o - half_c * 4 * C) * L4;
+            for (int t = 0; t < L4; ++t) acc += d[t];
         } else {
-            const int ci = o >> 2, kk = o & 3;
+            const int ci = o / (4 * C), c = (o >> 2) - ci * C, kk = o & 3;
             for (int i = 0; i < T2; ++i) {
                 const int t = 2 * i - 1 + kk;
-                if (t >= 0 && t < L) acc += wide[ci * T2 + i] * dr[t];
+                if (t >= 0 && t < L4) acc += wide[ci * T2 + i] * dr[c * L4 + t];
             }
         }
-        s.part2[(size_t)b * VAE_P2 + o] = acc;
+        s.part2[(size_t)b * vae_p2(C) + o] = acc;
     }
     __syncthreads();
-    // d(_conv_trans_1 pre-ReLU)[ci][i] = sum_kk W[ci][kk] drecon[2 i - 1 + kk], masked, in place of wide
+    // d(_conv_trans_1 pre-ReLU)[ci][i] = sum_c sum_kk W[ci][c][kk] dy[c][2 i - 1 + kk], masked, in place of wide
     for (int o = threadIdx.x; o < half_c * T2; o += VAE_THREADS) {
         const int ci = o / T2, i = o - ci * T2;
         float acc = 0.f;
+        for (int c = 0; c < C; ++c) {
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            const int t = 2 * i - 1 + kk;
-            if (t >= 0 && t < L) acc += w.dec_ct2_w[ci * 4 + kk] * dr[t];
+            for (int kk = 0; kk < 4; ++kk) {
+                const int t = 2 * i - 1 + kk;
+                if (t >= 0 && t < L4) acc += w.dec_ct2_w[(ci * C + c) * 4 + kk] * dr[c * L4 + t];
+            }
         }
-        wide[o] = ((m_w[ci * 2 + (i >> 5)] >> (i & 31)) & 1u) ? acc : 0.f;
+        wide[o] = ((m_w[ci * WT2 + (i >> 5)] >> (i & 31)) & 1u) ? acc : 0.f;
     }
     __syncthreads();
     for (int co = threadIdx.x; co < half_c; co += VAE_THREADS) {    // _conv_trans_1 bias: column sum of its output gradient
@@ -716,9 +761,9 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_bwd_kernel(const VaeDe
     }
     im2col_rows<4, 2>(wide, half_c, T2, T2, s.Gct1, row0, T, 1);    // column co * 4 + kk = d[co][2 i - 1 + kk]
     // d r_final, masked by r_final > 0: the gradient at the stack's output h (r_final itself left as Xct1)
-    convT1d_k4s2_dgrad_lds(wide, half_c, T2, bufB, H, T, w.dec_ct1_w, T2, LD, m_r + w.n_res * 128);
+    convT1d_k4s2_dgrad_lds(wide, half_c, T2, bufB, H, T, w.dec_ct1_w, T2, LD, m_r + w.n_res * 128 * WT, WT);
     __syncthreads();
-    residual_stack_backward(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
+    residual_stack_backward<TB>(bufB, bufA, H, R, w.n_res, T, w.dec_c3, w.dec_c1, s.st, row0, m_r, m_m);
     rows_out(bufB, H, T, LD, s.dY1, row0, H);                       // dL/d(_conv_1 output)
     if (dz == nullptr) return;
     conv1d_dgrad_lds<3, 1, false>(bufB, H, T, bufA, E, T, w.dec_conv1_w, 1, LD, LD, nullptr, 1);   // dL/d(after), decoder part
@@ -797,6 +842,8 @@ int vae_items(const t2s_vae_weights* w, VaeDev& d, bool dec, bool enc, std::vect
 }
 }
 
+namespace { int vae_bwd_init(); }
+
 // t2s_vae_create (channels 0) and t2s_vae_create_mc (channels 1..16), `who` = the entry's name
 static int vae_create(const t2s_vae_weights* w, int channels, t2s_vae** out, const char* who) {
     T2S_REQUIRE(w && out, "%s: NULL argument", who);
@@ -872,12 +919,9 @@ static int vae_create(const t2s_vae_weights* w, int channels, t2s_vae** out, con
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_bwd_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_BWD_MASK_BYTES));
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_bwd_kernel),
-                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes + VAE_DBWD_MASK_BYTES));
         attr = true;
     }
+    (void)vae_bwd_init();         // (here, outside any stream capture; a refusal is reported by the backward entries)
     *out = h;
     return T2S_OK;
 }
@@ -990,15 +1034,55 @@ extern "C" int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* be
     return vae_encode("t2s_vae_encode_mc", true, h, x, z, before, B, L, latent_w, stream);
 }
 
-// ------------------------------------------------------------------------ what the two backward entries share on the host
+// ------------------------------------------------------------------------ what the backward entries share on the host
 namespace {
-// the handle's shape and the batch, `who` = the entry's name
-int vae_bwd_check(const char* who, const VaeDev& d, int B, int L) {
+// The handle's kind and shape and the batch, `who` = the entry's name, `mc` = its family, as vae_fwd_check: the multichannel
+// entries take a t2s_vae_create_mc handle with at least one residual layer, any 8 <= L <= 192 and a latent up to 64 wide; the
+// single-channel ones a t2s_vae_create handle, L <= 128 a multiple of 4 and a latent up to 32 wide.
+int vae_bwd_check(const char* who, const t2s_vae* h, bool mc, bool enc, int B, int L, int W) {
+    const VaeDev& d = h->dev;
+    if (mc) {
+        T2S_REQUIRE(h->channels != 0, "%s: the handle is a single-channel one (t2s_vae_create); its entries are t2s_vae_encode_backward / t2s_vae_decode_backward", who);
+    } else {
+        T2S_REQUIRE(h->channels == 0, "%s: the handle is a multichannel one (t2s_vae_create_mc); its entries are t2s_vae_encode_mc / t2s_vae_decode_mc and their backwards t2s_vae_encode_backward_mc / t2s_vae_decode_backward_mc", who);
+    }
+    T2S_REQUIRE(enc ? h->has_encoder : h->has_decoder, "%s: handle was created without %s weights", who, enc ? "encoder" : "decoder");
+    if (mc) T2S_REQUIRE(d.n_res >= 1, "%s: n_res=0 unsupported (1..4 residual layers)", who);
     // the weight-gradient GEMMs work on 128-wide tiles: the reference's default LA-VAE (pretrained_lavae_unified.py:119-122)
     T2S_REQUIRE(d.hidden == 128 && d.res_hidden % 128 == 0 && d.emb == 64,
                 "%s: hidden=%d res_hidden=%d emb=%d unsupported (hidden 128, res_hidden 128 / 256, emb 64)", who, d.hidden, d.res_hidden, d.emb);
-    T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "%s: B=%d L=%d unsupported (8 <= L <= 128, a multiple of 4)", who, B, L);
+    if (mc)
+        T2S_REQUIRE(B > 0 && L >= 8 && L <= 4 * 48, "%s: B=%d L=%d unsupported (8 <= L <= 192)", who, B, L);
+    else
+        T2S_REQUIRE(B > 0 && L >= 8 && L % 4 == 0 && L <= 4 * VAE_TMAX, "%s: B=%d L=%d unsupported (8 <= L <= 128, a multiple of 4)", who, B, L);
+    const int wmax = mc ? VAE_MC_WMAX : VAE_TMAX;
+    T2S_REQUIRE(W >= 1 && W <= wmax, "%s: latent width %d unsupported (1..%d)", who, W, wmax);
     return T2S_OK;
+}
+
+// The dynamic-LDS caps of the four backward instantiations, requested once (the first backward call: training is never under a
+// stream capture).  A refusal is remembered and returned by every later call too: nothing launches without its cap.
+int vae_bwd_init() {
+    static int state = -1;
+    static std::string why;
+    if (state < 0) {
+        const struct { const void* k; int bytes; const char* name; } caps[4] = {
+            {reinterpret_cast<const void*>(vae_encode_bwd_kernel<32>), VaeBwdGeom<32>::ENC_BYTES, "vae_encode_bwd_kernel<32>"},
+            {reinterpret_cast<const void*>(vae_encode_bwd_kernel<48>), VaeBwdGeom<48>::ENC_BYTES, "vae_encode_bwd_kernel<48>"},
+            {reinterpret_cast<const void*>(vae_decode_bwd_kernel<32>), VaeBwdGeom<32>::DEC_BYTES_MAX, "vae_decode_bwd_kernel<32>"},
+            {reinterpret_cast<const void*>(vae_decode_bwd_kernel<48>), VaeBwdGeom<48>::DEC_BYTES_MAX, "vae_decode_bwd_kernel<48>"}};
+        state = T2S_OK;
+        for (auto& c : caps) {
+            const hipError_t e = hipFuncSetAttribute(c.k, hipFuncAttributeMaxDynamicSharedMemorySize, c.bytes);
+            if (e != hipSuccess) {
+                why = std::string(c.name) + ": the runtime refused " + std::to_string(c.bytes) + " bytes of dynamic LDS: " + hipGetErrorString(e);
+                state = T2S_E_HIP;
+                break;
+            }
+        }
+    }
+    if (state != T2S_OK) set_error("t2s_vae backward: %s", why.c_str());
+    return state;
 }
 
 int vae_cu_count(t2s_vae* h) {
@@ -1064,25 +1148,24 @@ int vae_stack_wgrad(t2s_vae* h, const VaeStackBufs& s, float* const* g_c3, float
     }
     return T2S_OK;
 }
-}
 
-extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g,
-                                       int B, int L, void* stream) {
-    T2S_REQUIRE(h && x && dz && g, "t2s_vae_encode_backward: NULL argument");
-    T2S_REQUIRE(h->channels == 0, "t2s_vae_encode_backward: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_encode_mc (which has no backward yet)");
-    T2S_REQUIRE(h->has_encoder, "t2s_vae_encode_backward: handle was created without encoder weights");
+// t2s_vae_encode_backward (C = 1, the 30-wide latent) and t2s_vae_encode_backward_mc
+int vae_encode_backward(const char* who, bool mc, t2s_vae* h, const float* x, const float* dz, const float* dbefore,
+                        const t2s_vae_enc_grads* g, int B, int L, int W, void* stream) {
+    T2S_REQUIRE(h && x && dz && g, "%s: NULL argument", who);
     const VaeDev& d = h->dev;
     int rc;
-    if ((rc = vae_bwd_check("t2s_vae_encode_backward", d, B, L))) return rc;
+    if ((rc = vae_bwd_check(who, h, mc, true, B, L, W))) return rc;
     T2S_REQUIRE(g->conv1_w && g->conv1_b && g->conv2_w && g->conv2_b && g->conv3_w && g->conv3_b && g->prevq_w && g->prevq_b,
-                "t2s_vae_encode_backward: NULL gradient pointer");
+                "%s: NULL gradient pointer", who);
     for (int l = 0; l < d.n_res; ++l)
-        T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "t2s_vae_encode_backward: NULL gradient pointer of residual layer %d", l);
+        T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "%s: NULL gradient pointer of residual layer %d", who, l);
+    if ((rc = vae_bwd_init())) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4);
+    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4), C = h->channels ? h->channels : 1, P1 = vae_p1(C);
     if ((rc = vae_cu_count(h))) return rc;
     // row blocks: floats per row, in the order the pointers are handed out below; conv_1's partial rows; prevq padded to 128 outputs
-    if ((rc = vae_grow_rows(h->bwd, (size_t)M, B, 256 + 384 + 128 + 128 + 128 + 128 + vae_stack_row_floats(NR, R), VAE_P1, 128 * 128 + 128)))
+    if ((rc = vae_grow_rows(h->bwd, (size_t)M, B, 256 + 384 + 128 + 128 + 128 + 128 + vae_stack_row_floats(NR, R), P1, 128 * 128 + 128)))
         return rc;
     const int shapes[5][2] = {{128, 256}, {128, 384}, {R, 384}, {128, R}, {128, 128}};
     if ((rc = vae_ensure_wg(h, shapes))) return rc;
@@ -1091,9 +1174,12 @@ extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* 
     s.Xc2 = take(256); s.Xc3 = take(384); s.Xp = take(128); s.dYp = take(128); s.dY3 = take(128); s.dY2 = take(128);
     vae_stack_take(take, s.st, NR, R);
     s.part1 = take.p;
-    float* tmp_w = s.part1 + (size_t)h->bwd.series * VAE_P1;       // (128,128) + (128): prevq padded to 128 outputs
+    float* tmp_w = s.part1 + (size_t)h->bwd.series * P1;           // (128,128) + (128): prevq padded to 128 outputs
     float* tmp_b = tmp_w + 128 * 128;
-    vae_encode_bwd_kernel<<<B, VAE_THREADS, VAE_LDS_FLOATS * 4 + VAE_BWD_MASK_BYTES, st>>>(d, x, dz, dbefore, s, L);
+    if (L <= 4 * 32)
+        vae_encode_bwd_kernel<32><<<B, VAE_THREADS, VaeBwdGeom<32>::ENC_BYTES, st>>>(d, x, dz, dbefore, s, L, W, C);
+    else
+        vae_encode_bwd_kernel<48><<<B, VAE_THREADS, VaeBwdGeom<48>::ENC_BYTES, st>>>(d, x, dz, dbefore, s, L, W, C);
     T2S_LAUNCH_CHECK();
     if ((rc = launch_wgrad32(s.dY2, s.Xc2, g->conv2_w, g->conv2_b, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     if ((rc = launch_wgrad32(s.dY3, s.Xc3, g->conv3_w, g->conv3_b, M, 128, 384, h->wg, h->wg_floats, h->n_cu, st))) return rc;
@@ -1101,28 +1187,27 @@ extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* 
     if ((rc = launch_wgrad32(s.dYp, s.Xp, tmp_w, tmp_b, M, 128, 128, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     T2S_HIP_CHECK(hipMemcpyAsync(g->prevq_w, tmp_w, (size_t)64 * 128 * sizeof(float), hipMemcpyDeviceToDevice, st));
     T2S_HIP_CHECK(hipMemcpyAsync(g->prevq_b, tmp_b, (size_t)64 * sizeof(float), hipMemcpyDeviceToDevice, st));
-    vae_part_reduce_kernel<<<VAE_P1 / 32, 256, 0, st>>>(s.part1, B, VAE_P1, g->conv1_w, 256, g->conv1_b);
+    vae_part_reduce_kernel<<<(P1 + 31) / 32, 256, 0, st>>>(s.part1, B, P1, g->conv1_w, 256 * C, g->conv1_b);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
-extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter,
-                                       const t2s_vae_dec_grads* g, float* dz, int B, int L, int latent_w, void* stream) {
-    T2S_REQUIRE(h && z && drecon && g, "t2s_vae_decode_backward: NULL argument");
-    T2S_REQUIRE(h->channels == 0, "t2s_vae_decode_backward: the handle is a multichannel one (t2s_vae_create_mc); its entry is t2s_vae_decode_mc (which has no backward yet)");
-    T2S_REQUIRE(h->has_decoder, "t2s_vae_decode_backward: handle was created without decoder weights");
+// t2s_vae_decode_backward (C = 1) and t2s_vae_decode_backward_mc
+int vae_decode_backward(const char* who, bool mc, t2s_vae* h, const float* z, const float* drecon, const float* dafter,
+                        const t2s_vae_dec_grads* g, float* dz, int B, int L, int W, void* stream) {
+    T2S_REQUIRE(h && z && drecon && g, "%s: NULL argument", who);
     const VaeDev& d = h->dev;
     int rc;
-    if ((rc = vae_bwd_check("t2s_vae_decode_backward", d, B, L))) return rc;
-    T2S_REQUIRE(latent_w >= 1 && latent_w <= VAE_TMAX, "t2s_vae_decode_backward: latent width %d unsupported (1..%d)", latent_w, VAE_TMAX);
-    T2S_REQUIRE(g->conv1_w && g->conv1_b && g->ct1_w && g->ct1_b && g->ct2_w && g->ct2_b, "t2s_vae_decode_backward: NULL gradient pointer");
+    if ((rc = vae_bwd_check(who, h, mc, false, B, L, W))) return rc;
+    T2S_REQUIRE(g->conv1_w && g->conv1_b && g->ct1_w && g->ct1_b && g->ct2_w && g->ct2_b, "%s: NULL gradient pointer", who);
     for (int l = 0; l < d.n_res; ++l)
-        T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "t2s_vae_decode_backward: NULL gradient pointer of residual layer %d", l);
+        T2S_REQUIRE(g->stack_conv3_w[l] && g->stack_conv1_w[l], "%s: NULL gradient pointer of residual layer %d", who, l);
+    if ((rc = vae_bwd_init())) return rc;
     hipStream_t st = (hipStream_t)stream;
-    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4);
+    const int R = d.res_hidden, NR = d.n_res, M = B * (L / 4), C = h->channels ? h->channels : 1, P2 = vae_p2(C);
     if ((rc = vae_cu_count(h))) return rc;
     // row blocks: floats per row, in the order the pointers are handed out below; the two partial rows; _conv_1 with K padded to 256
-    if ((rc = vae_grow_rows(h->dbwd, (size_t)M, B, 256 + 128 + 128 + 256 + vae_stack_row_floats(NR, R), VAE_P2 + VAE_PB1, 128 * 256))) return rc;
+    if ((rc = vae_grow_rows(h->dbwd, (size_t)M, B, 256 + 128 + 128 + 256 + vae_stack_row_floats(NR, R), P2 + VAE_PB1, 128 * 256))) return rc;
     const int shapes[3][2] = {{128, 256}, {R, 384}, {128, R}};
     if ((rc = vae_ensure_wg(h, shapes))) return rc;
     VaeDecBwdBufs s{};
@@ -1131,17 +1216,42 @@ extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* 
     vae_stack_take(take, s.st, NR, R);
     float* tmp_w = take.p;                                         // (128,256): _conv_1 with K padded from 192
     s.part2 = tmp_w + 128 * 256;
-    s.partb1 = s.part2 + (size_t)h->dbwd.series * VAE_P2;
-    vae_decode_bwd_kernel<<<B, VAE_THREADS, VAE_LDS_FLOATS * 4 + VAE_DBWD_MASK_BYTES, st>>>(d, z, drecon, dafter, dz, s, L, latent_w);
+    s.partb1 = s.part2 + (size_t)h->dbwd.series * P2;
+    const int dr_bytes = C * 4 * (L / 4) * (int)sizeof(float);     // the staged sample gradients
+    if (L <= 4 * 32)
+        vae_decode_bwd_kernel<32><<<B, VAE_THREADS, VaeBwdGeom<32>::DEC_BYTES + dr_bytes, st>>>(d, z, drecon, dafter, dz, s, L, W, C);
+    else
+        vae_decode_bwd_kernel<48><<<B, VAE_THREADS, VaeBwdGeom<48>::DEC_BYTES + dr_bytes, st>>>(d, z, drecon, dafter, dz, s, L, W, C);
     T2S_LAUNCH_CHECK();
     if ((rc = launch_wgrad32(s.dY1, s.Xc1, tmp_w, g->conv1_b, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
     vae_copy_cols_kernel<<<(128 * 192 + 255) / 256, 256, 0, st>>>(tmp_w, 256, g->conv1_w, 128, 192);
     T2S_LAUNCH_CHECK();
     if ((rc = vae_stack_wgrad(h, s.st, g->stack_conv3_w, g->stack_conv1_w, M, st))) return rc;
     if ((rc = launch_wgrad32(s.Xct1, s.Gct1, g->ct1_w, nullptr, M, 128, 256, h->wg, h->wg_floats, h->n_cu, st))) return rc;
-    vae_part_reduce_kernel<<<(VAE_P2 + 31) / 32, 256, 0, st>>>(s.part2, B, VAE_P2, g->ct2_w, 256, g->ct2_b);
+    vae_part_reduce_kernel<<<(P2 + 31) / 32, 256, 0, st>>>(s.part2, B, P2, g->ct2_w, 256 * C, g->ct2_b);
     T2S_LAUNCH_CHECK();
     vae_part_reduce_kernel<<<VAE_PB1 / 32, 256, 0, st>>>(s.partb1, B, VAE_PB1, g->ct1_b, VAE_PB1, nullptr);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
+}
+}
+
+extern "C" int t2s_vae_encode_backward(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g,
+                                       int B, int L, void* stream) {
+    return vae_encode_backward("t2s_vae_encode_backward", false, h, x, dz, dbefore, g, B, L, LATW, stream);
+}
+
+extern "C" int t2s_vae_encode_backward_mc(t2s_vae* h, const float* x, const float* dz, const float* dbefore, const t2s_vae_enc_grads* g,
+                                          int B, int L, int latent_w, void* stream) {
+    return vae_encode_backward("t2s_vae_encode_backward_mc", true, h, x, dz, dbefore, g, B, L, latent_w, stream);
+}
+
+extern "C" int t2s_vae_decode_backward(t2s_vae* h, const float* z, const float* drecon, const float* dafter,
+                                       const t2s_vae_dec_grads* g, float* dz, int B, int L, int latent_w, void* stream) {
+    return vae_decode_backward("t2s_vae_decode_backward", false, h, z, drecon, dafter, g, dz, B, L, latent_w, stream);
+}
+
+extern "C" int t2s_vae_decode_backward_mc(t2s_vae* h, const float* z, const float* drecon, const float* dafter,
+                                          const t2s_vae_dec_grads* g, float* dz, int B, int L, int latent_w, void* stream) {
+    return vae_decode_backward("t2s_vae_decode_backward_mc", true, h, z, drecon, dafter, g, dz, B, L, latent_w, stream);
 }

@@ -6,12 +6,18 @@ Class names, constructor signatures, attribute names and state-dict keys equal t
 ``Decoder.forward`` run the single-launch HIP kernels t2s_vae_encode_mc / t2s_vae_decode_mc (csrc/t2s_vae.hip): C <= 16,
 flow_dim <= 64, hidden <= 128, res_hidden <= 256, <= 4 residual layers, embedding_dim 64.  No CPU fallback.
 
-There is NO HIP backward for C channels yet: with grad enabled and a parameter or the input asking for a gradient, both
-forwards run as torch ops under autograd (``_forward_autograd``, host-level plumbing like the single-channel mirror's path
-for shapes its HIP backward does not cover), so ``vqvae.shared_eval(..., 'train')`` works with any optimizer.  The handle
-cache, version stamps, in-place weight refresh and the device lock are the single-channel mirror's (_Codec, _VaeHandle).
+With grad enabled and a parameter or the latent asking for a gradient, a covered shape (``_mc_backward_covers``: hidden 128,
+embedding_dim 64, res_hidden 128 / 256, 1..4 residual layers, 8 <= L <= 192, flow_dim <= 64, C <= 16) runs the same HIP forward
+behind the single-channel mirror's autograd nodes (_EncodeFn, _DecodeFn), whose backward is t2s_vae_encode_backward_mc /
+t2s_vae_decode_backward_mc: ``vqvae.shared_eval(..., 'train')`` and a trainable encoder grafted onto the DiT (mytrain.py:37-40)
+train on HIP.  Everything else -- and everything under ``T2S_MVAE_BACKWARD=torch`` -- runs as torch ops under autograd
+(``_forward_autograd``, host-level plumbing like the single-channel mirror's path for shapes its HIP backward does not cover).
+The handle cache, version stamps, in-place weight refresh and the device lock are the single-channel mirror's (_Codec,
+_VaeHandle).
 """
 from __future__ import annotations
+
+import os
 
 import torch
 import torch.nn as nn
@@ -62,6 +68,20 @@ def _wants_grad(module, inputs):
     return torch.is_grad_enabled() and (inputs.requires_grad or any(p.requires_grad for p in module.parameters()))
 
 
+def _mc_backward_covers(hidden, emb, res_hidden, n_res, Ln, W, channels):
+    """The shapes t2s_vae_encode_backward_mc / t2s_vae_decode_backward_mc take (`res_hidden` None: a stack without layers)."""
+    return (hidden == 128 and emb == 64 and res_hidden is not None and res_hidden % 128 == 0 and 1 <= n_res <= 4
+            and 8 <= Ln <= 192 and 1 <= W <= 64 and 1 <= channels <= 16)
+
+
+def _backward_mode():
+    """T2S_MVAE_BACKWARD = hip | torch, read at every call; unset: hip (profiles/mvae_train.json)."""
+    mode = os.environ.get("T2S_MVAE_BACKWARD", "") or "hip"
+    if mode not in ("hip", "torch"):
+        raise L.T2SError(f"T2S_MVAE_BACKWARD={mode!r}: expected 'hip' or 'torch'")
+    return mode
+
+
 class Encoder(_Codec):
     """myvqvae.py:32-61."""
 
@@ -81,9 +101,16 @@ class Encoder(_Codec):
 
     _weights_struct = _vq.Encoder._weights_struct      # the same attribute names; only _conv_1's shape carries the channels
 
+    def _hip_backward_ok(self, Ln):
+        return _mc_backward_covers(self._conv_2.out_channels, self._pre_vq_conv.out_channels, self._res_hidden(),
+                                   len(self._residual_stack._layers), Ln, int(self.flow_dim), self._conv_1.in_channels)
+
+    _grad_params = _vq.Encoder._grad_params            # the 12 encoder tensors in t2s_vae_enc_grads order
+
     def _forward_autograd(self, inputs):
-        """The same forward as torch ops UNDER AUTOGRAD: the training path of the multichannel codec, whose HIP backward is
-        not built -- host-level plumbing, no throughput claim."""
+        """The same forward as torch ops UNDER AUTOGRAD: the training path for shapes t2s_vae_encode_backward_mc does not
+        cover, for a series that itself asks for a gradient, and under T2S_MVAE_BACKWARD=torch -- host-level plumbing, no
+        throughput claim."""
         h = F.relu(self._conv_1(inputs.float()))
         h = F.relu(self._conv_2(h))
         before = self._pre_vq_conv(_stack_autograd(self._residual_stack, self._conv_3(h)))
@@ -96,9 +123,22 @@ class Encoder(_Codec):
         if inputs.dim() != 3 or inputs.shape[1] != self._conv_1.in_channels:
             raise L.T2SError(f"Encoder.forward: input must be (B,{self._conv_1.in_channels},L), got {tuple(inputs.shape)}")
         if _wants_grad(self, inputs):
+            # (the backward entry produces parameter gradients only: a series that asks for one takes the torch ops)
+            if self._hip_backward_ok(inputs.shape[2]) and not inputs.requires_grad and _backward_mode() == "hip":
+                return _vq._EncodeFn.apply(self, inputs, *self._grad_params())
             return self._forward_autograd(inputs)
+        return self._forward_hip(inputs)
+
+    def _series(self, inputs):
+        """The series as the kernels read it: (B,C,L) fp32."""
+        return L.as_f32(inputs)
+
+    def _backward_hip(self, h, x, dz, dbefore, g, B, Ln, W, st):
+        L.check(L.lib().t2s_vae_encode_backward_mc(h, x, dz, dbefore, g, B, Ln, W, st), "t2s_vae_encode_backward_mc")
+
+    def _forward_hip(self, inputs):
         B, Ln, W = inputs.shape[0], inputs.shape[2], int(self.flow_dim)
-        x = L.as_f32(inputs)
+        x = self._series(inputs)
         dev = x.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
@@ -127,6 +167,12 @@ class Decoder(_Codec):
 
     _weights_struct = _vq.Decoder._weights_struct      # the same attribute names; only _conv_trans_2's shapes carry the channels
 
+    def _hip_backward_ok(self, Ln, W):
+        return _mc_backward_covers(self._conv_1.out_channels, self._conv_1.in_channels, self._res_hidden(),
+                                   len(self._residual_stack._layers), Ln, W, self._conv_trans_2.out_channels)
+
+    _grad_params = _vq.Decoder._grad_params            # the 10 decoder tensors in t2s_vae_dec_grads order
+
     def _forward_autograd(self, inputs, length):
         """The same forward as torch ops UNDER AUTOGRAD (see Encoder._forward_autograd)."""
         after = F.interpolate(inputs.float(), size=int(length / 4), mode="linear", align_corners=True)
@@ -142,9 +188,16 @@ class Decoder(_Codec):
         if inputs.dim() != 3 or inputs.shape[1] != self._conv_1.in_channels:
             raise L.T2SError(f"Decoder.forward: latent must be (B,{self._conv_1.in_channels},W), got {tuple(inputs.shape)}")
         if _wants_grad(self, inputs):
+            if self._hip_backward_ok(int(length), inputs.shape[2]) and _backward_mode() == "hip":
+                return _vq._DecodeFn.apply(self, L.as_f32(inputs), int(length), *self._grad_params())
             return self._forward_autograd(inputs, length)
-        z = L.as_f32(inputs)
-        B, W, Ln, dev = z.shape[0], z.shape[2], int(length), z.device
+        return self._forward_hip(L.as_f32(inputs), int(length))
+
+    def _backward_hip(self, h, z, drecon, dafter, g, dz, B, Ln, W, st):
+        L.check(L.lib().t2s_vae_decode_backward_mc(h, z, drecon, dafter, g, dz, B, Ln, W, st), "t2s_vae_decode_backward_mc")
+
+    def _forward_hip(self, z, Ln):
+        B, W, dev = z.shape[0], z.shape[2], z.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
             recon = torch.empty(B, self._conv_trans_2.out_channels, Ln, device=dev, dtype=torch.float32)
@@ -169,8 +222,9 @@ class vqvae(BaseModel):
         self.decoder.flow_dim = int(args.flow_dim)
 
     def shared_eval(self, batch, optimizer, mode):  # pyright: ignore[reportIncompatibleMethodOverride]
-        """myvqvae.py:116-136.  'train' is one optimisation step through the torch-op forwards under autograd (no HIP backward
-        for C channels yet) with the caller's optimizer; 'val' / 'test' run the HIP forwards under no_grad."""
+        """myvqvae.py:116-136.  'train' is one optimisation step with the caller's optimizer: on a covered shape the HIP
+        forwards and backwards (_EncodeFn / _DecodeFn on t2s_vae_*_backward_mc), otherwise the torch-op forwards under
+        autograd; 'val' / 'test' run the HIP forwards under no_grad."""
         Ln = batch.shape[-1]
         if mode == "train":
             optimizer.zero_grad()

@@ -233,9 +233,16 @@ class Encoder(_Codec):
             return self._forward_autograd(inputs)
         return self._forward_hip(inputs)
 
+    def _series(self, inputs):
+        """The series as the kernels read it: (B,L) fp32."""
+        return L.as_f32(inputs).reshape(inputs.shape[0], inputs.shape[-1])
+
+    def _backward_hip(self, h, x, dz, dbefore, g, B, Ln, W, st):
+        L.check(L.lib().t2s_vae_encode_backward(h, x, dz, dbefore, g, B, Ln, st), "t2s_vae_encode_backward")
+
     def _forward_hip(self, inputs):
         B, Ln = inputs.shape[0], inputs.shape[-1]
-        x = L.as_f32(inputs).reshape(B, Ln)
+        x = self._series(inputs)
         dev = x.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
@@ -248,27 +255,28 @@ class Encoder(_Codec):
 
 
 class _EncodeFn(torch.autograd.Function):
-    """Encoder.forward under autograd, both directions in the HIP kernels: t2s_vae_encode now, t2s_vae_encode_backward for the
-    12 parameter gradients (the forward is recomputed from x there; nothing but x is saved).  The input series gets no
-    gradient (it is data, train.py:104-106)."""
+    """Encoder.forward under autograd, both directions in the HIP kernels: the encoder's _forward_hip now (t2s_vae_encode, or
+    t2s_vae_encode_mc for the myvqvae.py mirror), its _backward_hip (t2s_vae_encode_backward[_mc]) for the 12 parameter
+    gradients (the forward is recomputed from x there; nothing but x is saved).  The input series gets no gradient (it is
+    data, train.py:104-106)."""
 
     @staticmethod
     def forward(ctx, enc, inputs, *params):
         with torch.no_grad():
             z, before = enc._forward_hip(inputs)
-        ctx.enc = enc
-        ctx.save_for_backward(L.as_f32(inputs).reshape(inputs.shape[0], inputs.shape[-1]))
+        ctx.enc, ctx.W = enc, z.shape[2]
+        ctx.save_for_backward(enc._series(inputs))
         ctx.set_materialize_grads(False)      # train.py uses z only: `before` then arrives as None, not as a zero tensor
         return z, before
 
     @staticmethod
     def backward(ctx, dz, dbefore):
         (x,) = ctx.saved_tensors
-        B, Ln = x.shape
-        dzc = L.as_f32(dz) if dz is not None else torch.zeros(B, 64, L.LAT_W, device=x.device)
+        B, Ln, W = x.shape[0], x.shape[-1], ctx.W
+        dzc = L.as_f32(dz) if dz is not None else torch.zeros(B, 64, W, device=x.device)
         dbc = L.as_f32(dbefore) if dbefore is not None else None
-        out = _vae_backward(ctx.enc, L.VaeEncGrads, B, Ln, lambda h, g, st: L.check(L.lib().t2s_vae_encode_backward(
-            h, L.dev_ptr(x), L.dev_ptr(dzc), L.dev_ptr(dbc), g, B, Ln, st), "t2s_vae_encode_backward"))
+        out = _vae_backward(ctx.enc, L.VaeEncGrads, B, Ln, lambda h, g, st: ctx.enc._backward_hip(
+            h, L.dev_ptr(x), L.dev_ptr(dzc), L.dev_ptr(dbc), g, B, Ln, W, st))
         return (None, None, *out)
 
 
@@ -340,6 +348,9 @@ class Decoder(_Codec):
         recon, after = self._forward_hip(L.as_f32(inputs), Ln)
         return torch.squeeze(recon.unsqueeze(1)), after
 
+    def _backward_hip(self, h, z, drecon, dafter, g, dz, B, Ln, W, st):
+        L.check(L.lib().t2s_vae_decode_backward(h, z, drecon, dafter, g, dz, B, Ln, W, st), "t2s_vae_decode_backward")
+
     def _forward_hip(self, z, Ln):
         B, dev = z.shape[0], z.device
         with torch.cuda.device(dev):
@@ -352,14 +363,15 @@ class Decoder(_Codec):
 
 
 class _DecodeFn(torch.autograd.Function):
-    """Decoder.forward under autograd, both directions in the HIP kernels: t2s_vae_decode_w now, t2s_vae_decode_backward for
-    the 10 parameter gradients and the latent's (the forward is recomputed from z there; nothing but z is saved)."""
+    """Decoder.forward under autograd, both directions in the HIP kernels: the decoder's _forward_hip now (t2s_vae_decode_w, or
+    t2s_vae_decode_mc for the myvqvae.py mirror), its _backward_hip (t2s_vae_decode_backward[_mc]) for the 10 parameter
+    gradients and the latent's (the forward is recomputed from z there; nothing but z is saved)."""
 
     @staticmethod
     def forward(ctx, dec, z, Ln, *params):
         with torch.no_grad():
             recon, after = dec._forward_hip(z, Ln)
-        ctx.dec, ctx.Ln = dec, Ln
+        ctx.dec, ctx.Ln, ctx.recon_shape = dec, Ln, recon.shape
         ctx.save_for_backward(z)
         ctx.set_materialize_grads(False)      # a loss on `recon` alone: `after` then arrives as None, not as a zero tensor
         return recon, after
@@ -368,11 +380,11 @@ class _DecodeFn(torch.autograd.Function):
     def backward(ctx, drecon, dafter):
         (z,) = ctx.saved_tensors
         B, W, Ln = z.shape[0], z.shape[2], ctx.Ln
-        drc = L.as_f32(drecon).reshape(B, Ln) if drecon is not None else torch.zeros(B, Ln, device=z.device)
+        drc = L.as_f32(drecon).reshape(ctx.recon_shape) if drecon is not None else torch.zeros(ctx.recon_shape, device=z.device)
         dac = L.as_f32(dafter) if dafter is not None else None
         dz = torch.empty_like(z) if ctx.needs_input_grad[1] else None
-        out = _vae_backward(ctx.dec, L.VaeDecGrads, B, Ln, lambda h, g, st: L.check(L.lib().t2s_vae_decode_backward(
-            h, L.dev_ptr(z), L.dev_ptr(drc), L.dev_ptr(dac), g, L.dev_ptr(dz), B, Ln, W, st), "t2s_vae_decode_backward"))
+        out = _vae_backward(ctx.dec, L.VaeDecGrads, B, Ln, lambda h, g, st: ctx.dec._backward_hip(
+            h, L.dev_ptr(z), L.dev_ptr(drc), L.dev_ptr(dac), g, L.dev_ptr(dz), B, Ln, W, st))
         return (None, dz, None, *out)
 
 
