@@ -314,13 +314,13 @@ class Sampler:
             raise L.T2SError("Sampler needs a GPU device; the HIP path has no CPU fallback")
         self.model, self.decoder = model, decoder
         # a multichannel decoder (model/pretrained/myvqvae.py Decoder: C-channel motion series) decodes to (B,C,L), any L >= 8
-        self.channels = decoder._mc_channels() if getattr(decoder, "_t2s_multichannel", False) else None
+        self.channels = getattr(decoder, "channels", None)      # (None too without a decoder: the single-channel (B,L) layout)
         # the model's latent width (mytransformer.Transformer(dim): 50 / 64 for the motion models); the wide widths run f32
         self.width = int(getattr(model, "H", L.LAT_W))
         flow_dim = getattr(decoder, "flow_dim", None)      # (stamped by myvqvae.vqvae; a bare Decoder does not know it)
         if flow_dim is not None and int(flow_dim) != self.width:
             raise L.T2SError(f"Sampler: the decoder's flow_dim {int(flow_dim)} differs from the model's latent width {self.width}")
-        if decoder is not None and self.width != L.LAT_W and not getattr(decoder, "_t2s_multichannel", False):
+        if decoder is not None and self.width != L.LAT_W and self.channels is None:
             raise L.T2SError(f"Sampler: a model of latent width {self.width} needs the multichannel decoder (myvqvae)")
         self.math = math or model.__dict__.get("_t2s_math") or ("f32" if self.width != L.LAT_W else default_math())
         if hasattr(model, "set_math"):

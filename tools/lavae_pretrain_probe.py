@@ -6,7 +6,8 @@
 
 Both paths run the SAME module, optimizer (T2SAdamW) and MSE kernels; the torch-op path is forced with
 T2S_ENCODER_TORCH_AUTOGRAD=1 and T2S_DECODER_TORCH_AUTOGRAD=1 (Encoder / Decoder._forward_autograd: torch convolutions under
-autograd), the HIP path is _EncodeFn / _DecodeFn.  B = 8 is the reference's default batch, B = 1024 gives each of the 256 CUs
+autograd), the HIP path is _EncodeFn / _DecodeFn (all of the shared mirror, t2ms_amd/model/pretrained/_lavae.py, which reads
+the two switches in _torch_forced).  B = 8 is the reference's default batch, B = 1024 gives each of the 256 CUs
 four one-workgroup series.  Timing: one process; per shape a warm-up round of both paths, then `--rounds` rounds in which the
 two paths alternate (which goes first alternates too); a round is `--steps` optimisation steps on a resident batch between two
 device synchronisations, host clock.  Reported: median and spread (max - min) of the time per step and the ratio of the

@@ -1,5 +1,6 @@
 """The multichannel LA-VAE codec (t2s_vae_encode_mc / t2s_vae_decode_mc) against the torch-op path of the same mirror
-(model/pretrained/myvqvae.py Encoder / Decoder._forward_autograd) under no_grad, on the same GPU.
+(model/pretrained/myvqvae.py Encoder / Decoder; their _forward_autograd is the shared mirror's, t2ms_amd/model/pretrained/
+_lavae.py) under no_grad, on the same GPU.
 
     python tools/mvae_probe.py [--batch 256] [--rounds 5] [--iters 50] [--out profiles/mvae.json]
 

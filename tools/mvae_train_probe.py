@@ -8,7 +8,8 @@ A shape is channels:length:flow_dim; the defaults are the bench-press model at 4
 2 x 48, at the fork's batch size 128.  Both paths run the SAME module, optimizer (T2SAdamW) and torch MSE terms; the path is
 chosen with T2S_MVAE_BACKWARD = hip | torch, which the mirror reads at every call: `torch` is Encoder / Decoder
 ._forward_autograd (torch convolutions under autograd: what the codec trained through before it had a HIP backward), `hip` is
-t2s_vae_encode_mc / t2s_vae_decode_mc behind _EncodeFn / _DecodeFn with t2s_vae_encode_backward_mc / t2s_vae_decode_backward_mc.
+t2s_vae_encode_mc / t2s_vae_decode_mc behind _EncodeFn / _DecodeFn with t2s_vae_encode_backward_mc / t2s_vae_decode_backward_mc
+(the forwards, the nodes and the switch's reader, _torch_forced, are the shared mirror's: t2ms_amd/model/pretrained/_lavae.py).
 Timing: one process; per shape a warm-up round of both paths, then `--rounds` rounds in which the two paths alternate (which
 goes first alternates too); a round is `--steps` optimisation steps on a resident batch between two device synchronisations,
 host clock.  Reported: median and spread (max - min) of the time per step, the ratio of the medians, and `hip_not_slower`:
