@@ -14,7 +14,9 @@ calls them), and so may `MDD`, `ACD`, `SD`, `KD`, the feature-based measures of 
 rows changes nothing, so they need no --align_runs); `--align_runs` re-orders every run's rows to run_0's ground-truth order first -- each `infer()` call shuffles
 its test loader independently (dataloader.py:111; the reference never seeds), so WITHOUT it row i of one file is not row i of
 another, here exactly as in the reference; `--cfid_engine {torch,hip}` names what trains C-FID's TS2Vec encoder
-(t2ms_amd.ts2vec; left unset it is T2S_TS2VEC_FIT from the environment, else torch autograd as before).
+(t2ms_amd.ts2vec; left unset it is T2S_TS2VEC_FIT from the environment, else torch autograd as before).  C-FID takes
+series of up to 4096 steps like the other measures: past the LDS kernel's 136 steps the encoder's forward runs on
+t2s_ts2vec_encode_long (the torch engine trains at any such length; the HIP fit engine stops at 128).
 """
 import argparse
 import datetime

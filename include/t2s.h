@@ -735,6 +735,24 @@ typedef struct t2s_ts2vec_weights {
  * their maximum over time.  Time steps of x holding a NaN are zeroed as the reference does.  3 * max(hidden,
  * output_dims) * T * 4 bytes must fit in 160 KB of LDS (T <= 128 at the evaluation's 64 / 100 channels). */
 int t2s_ts2vec_encode(const t2s_ts2vec_weights* w, const float* x, float* rep, float* full, int B, int T, void* stream);
+/* The same function at any length 1 <= T <= T2S_TS2VEC_ENCODE_MAX_T (csrc/t2s_ts2vec_encode.hip): the three activation
+ * planes live in the caller's workspace as (B, C rounded up to 32, T) fp32 and every dilated convolution is a GEMM with
+ * K = 3 ci on the exact-f32 matrix instruction, one launch per convolution.  Supported: B >= 1, equal hidden widths,
+ * depth < T2S_TS2VEC_MAX_BLOCKS, 1 <= input_dims <= 64, hidden <= 128, output_dims <= 320 (no multiple of the 32-row
+ * tile is needed: the kernels pad); anything else, a NULL x / full / workspace or a workspace smaller than
+ * t2s_ts2vec_encode_workspace_bytes is T2S_E_INVALID before any launch.  fp32 throughout; an output element's sum over
+ * (tap, input channel[, projector channel]) runs in that one order whatever tile computes it, wherever the series sits
+ * in the batch and whatever B is; no floating-point atomics: the same input gives the same bits on every call, and row
+ * i of a batch equals that row encoded alone.  The summation order differs from t2s_ts2vec_encode's, so the two agree
+ * to rounding, not bit for bit.  The entry never allocates, copies synchronously or synchronises and keeps no state:
+ * the weights are re-packed into the workspace (whose contents are scratch) at every call; 2 depth + 5 launches, all on
+ * `stream`.  A block whose dilation is >= T runs its centre tap only. */
+#define T2S_TS2VEC_ENCODE_MAX_T 4096
+/* Bytes of workspace t2s_ts2vec_encode_long needs: the packed weights + 3 planes of B * roundup32(max(hidden,
+ * output_dims)) * T floats, each part rounded up to 256 bytes (0 and an error message if unsupported). */
+uint64_t t2s_ts2vec_encode_workspace_bytes(const t2s_ts2vec_weights* w, int B, int T);
+int t2s_ts2vec_encode_long(const t2s_ts2vec_weights* w, const float* x, float* rep /* may be NULL */, float* full,
+                           int B, int T, void* workspace, uint64_t workspace_bytes, void* stream);
 
 /* One training step of TS2Vec.fit (evaluate/ts2vec.py:113-140): the TRAINING forward of both cropped views (binomial
  * time mask after input_fc, dropout on the representations), hierarchical_contrastive_loss (:451-497) of their overlap,

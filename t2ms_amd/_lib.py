@@ -74,6 +74,7 @@ class VaeDecGrads(C.Structure):          # t2s_vae_dec_grads
 
 
 TS2VEC_MAX_BLOCKS = 16
+TS2VEC_ENCODE_MAX_T = 4096      # t2s.h: T2S_TS2VEC_ENCODE_MAX_T
 
 
 class Ts2vecWeights(C.Structure):
@@ -170,6 +171,8 @@ SYMBOLS = {
     "t2s_eval_moments": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
     "t2s_eval_mdd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
     "t2s_ts2vec_encode": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP]),
+    "t2s_ts2vec_encode_workspace_bytes": (_U64, [C.POINTER(Ts2vecWeights), _I, _I]),
+    "t2s_ts2vec_encode_long": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
     "t2s_ts2vec_train_workspace_bytes": (_U64, [C.POINTER(Ts2vecWeights), _I, _I]),
     "t2s_ts2vec_train_step": (_I, [C.POINTER(Ts2vecWeights), C.POINTER(Ts2vecGrads), C.POINTER(Ts2vecStep), _VP, _VP, _U64, _VP]),
     "t2s_swa_update_multi": (_I, [_VP, _I, _U64, C.c_int64, _VP]),

@@ -209,9 +209,68 @@ def crps(ori, gens, device="cuda"):
     return float(out.cpu()[0]), per.cpu()
 
 
+ENCODE_LDS_BYTES = 160 * 1024            # t2s_ts2vec_encode: three (cmax, T) fp32 planes in the LDS of one CU
+ENCODE_WORKSPACE_CAP = 256 << 20         # bytes of workspace one t2s_ts2vec_encode_long call of the mirror may ask for
+
+
+def _encode_path(T, cmax, path=None):
+    """'lds' (t2s_ts2vec_encode, the planes in LDS) or 'gemm' (t2s_ts2vec_encode_long, the planes in a workspace) for a
+    series of T steps through an encoder whose widest layer has cmax channels.  path=None keeps the LDS kernel wherever
+    it fits (the same bits as before the long entry existed); 'lds' / 'gemm' force one -- 'lds' beyond its bound is
+    refused by the entry itself."""
+    if path not in (None, "lds", "gemm"):
+        raise L.T2SError(f"TS2VecEncoder.encode: path must be None, 'lds' or 'gemm', got {path!r}")
+    if path is not None:
+        return path
+    return "lds" if 3 * cmax * T * 4 <= ENCODE_LDS_BYTES else "gemm"
+
+
+def _encode_workspace_bytes(rows, T, hidden, output_dims, depth):
+    """What t2s_ts2vec_encode_workspace_bytes returns for a supported shape (csrc/t2s_ts2vec_encode.hip, enc_plan): the
+    packed weights (per convolution: M tiles of 32 rows, rounded up to the group of <= 4 a wave runs, x K / 2 steps of 64
+    floats) and three (rows, cmax rounded up to 32, T) fp32 planes, each part rounded up to 256 bytes."""
+    def up(v, m):
+        return (v + m - 1) // m * m
+
+    def conv(ci, co, kp=0):
+        tiles = (co + 31) // 32
+        return up(tiles, min(tiles, 4)) * ((3 * up(ci, 2) + kp) // 2) * 64
+
+    packed = 2 * depth * conv(hidden, hidden) + conv(hidden, output_dims) + conv(output_dims, output_dims, up(hidden, 2))
+    plane = rows * up(max(hidden, output_dims), 32) * T
+    return up(4 * packed, 256) + 3 * up(4 * plane, 256)
+
+
+def _encode_chunks(B, T, hidden, output_dims, depth, cap=None):
+    """[(row0, rows), ...] covering rows 0 .. B-1 once, in order: chunks of the most rows whose workspace stays <= cap
+    (ENCODE_WORKSPACE_CAP), and of one row each if even a single row exceeds it."""
+    cap = ENCODE_WORKSPACE_CAP if cap is None else cap
+
+    def bytes_of_rows(rows):
+        return _encode_workspace_bytes(rows, T, hidden, output_dims, depth)
+
+    if B < 1:
+        return []
+    rows = 1
+    if bytes_of_rows(B) <= cap:
+        rows = B
+    else:
+        lo, hi = 1, B                    # bytes_of_rows(lo) <= cap or lo == 1; bytes_of_rows(hi) > cap
+        while hi - lo > 1:
+            mid = (lo + hi) // 2
+            if bytes_of_rows(mid) <= cap:
+                lo = mid
+            else:
+                hi = mid
+        rows = lo
+    return [(r0, min(rows, B - r0)) for r0 in range(0, B, rows)]
+
+
 class TS2VecEncoder:
     """Forward of evaluate/ts2vec.py's TSEncoder (:352-399, eval mode, mask 'all_true') on the GPU from its state dict
-    (keys input_fc.*, feature_extractor.net.<i>.conv{1,2}.conv.*, feature_extractor.net.<depth>.projector.*)."""
+    (keys input_fc.*, feature_extractor.net.<i>.conv{1,2}.conv.*, feature_extractor.net.<depth>.projector.*).  Series
+    whose three activation planes fit the LDS of a CU run on t2s_ts2vec_encode, longer ones (up to 4096 steps) on
+    t2s_ts2vec_encode_long with a workspace this object owns."""
 
     def __init__(self, state_dict, device="cuda"):
         self.device = _gpu(device, "TS2VecEncoder")
@@ -235,21 +294,47 @@ class TS2VecEncoder:
         p = f"feature_extractor.net.{depth}.projector."
         w.proj_w, w.proj_b = sd[p + "weight"].data_ptr(), sd[p + "bias"].data_ptr()
         self._w, self._keep = w, sd
+        self._ws = None                  # workspace of the long path, grown on demand
 
-    def encode(self, x, encoding_window="full_series"):
+    def _workspace_bytes(self, rows, T):
+        need = L.lib().t2s_ts2vec_encode_workspace_bytes(C.byref(self._w), rows, T)
+        if need == 0:
+            L.check(1, "t2s_ts2vec_encode_workspace_bytes")
+        return need
+
+    def encode(self, x, encoding_window="full_series", path=None):
         """x (B, T, input_dims) -> (B, output_dims) for 'full_series' (TS2Vec.encode, ts2vec.py:236-245), or the
-        per-step representations (B, T, output_dims) for encoding_window=None."""
+        per-step representations (B, T, output_dims) for encoding_window=None.  `path`: see _encode_path; on the 'gemm'
+        path the batch is cut into chunks whose workspace stays under ENCODE_WORKSPACE_CAP (rows are independent, so the
+        cut changes no bit)."""
         if encoding_window not in ("full_series", None):
             raise L.T2SError("TS2VecEncoder.encode: encoding_window must be 'full_series' or None")
         xs = torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).float().contiguous().to(self.device)
         if xs.dim() != 3 or xs.shape[2] != self._w.input_dims:
             raise L.T2SError(f"TS2VecEncoder.encode: x must be (B, T, {self._w.input_dims}), got {tuple(xs.shape)}")
         B, T = xs.shape[0], xs.shape[1]
-        full = torch.empty(B, self._w.output_dims, device=self.device)
-        rep = torch.empty(B, T, self._w.output_dims, device=self.device) if encoding_window is None else None
+        cin, cout = self._w.input_dims, self._w.output_dims
+        which = _encode_path(T, max(self._w.hidden, cout), path)
+        full = torch.empty(B, cout, device=self.device)
+        rep = torch.empty(B, T, cout, device=self.device) if encoding_window is None else None
+        if which == "lds":
+            with torch.cuda.device(self.device):
+                L.check(L.lib().t2s_ts2vec_encode(C.byref(self._w), xs.data_ptr(), None if rep is None else rep.data_ptr(),
+                                                  full.data_ptr(), B, T, L.stream_ptr(self.device)), "t2s_ts2vec_encode")
+            return full if rep is None else rep
+        self._workspace_bytes(B, T)      # an unsupported shape raises here, with the entry's message
+        chunks = _encode_chunks(B, T, self._w.hidden, cout, self._w.depth)
+        need = max(self._workspace_bytes(rows, T) for _, rows in chunks)
         with torch.cuda.device(self.device):
-            L.check(L.lib().t2s_ts2vec_encode(C.byref(self._w), xs.data_ptr(), None if rep is None else rep.data_ptr(),
-                                              full.data_ptr(), B, T, L.stream_ptr(self.device)), "t2s_ts2vec_encode")
+            if self._ws is None or self._ws.numel() < need:
+                with L.device_lock(self.device):
+                    self._ws = None
+                    self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            for r0, rows in chunks:
+                L.check(L.lib().t2s_ts2vec_encode_long(
+                    C.byref(self._w), xs.data_ptr() + 4 * r0 * T * cin,
+                    None if rep is None else rep.data_ptr() + 4 * r0 * T * cout, full.data_ptr() + 4 * r0 * cout,
+                    rows, T, self._ws.data_ptr(), self._ws.numel(), L.stream_ptr(self.device)), "t2s_ts2vec_encode_long")
         return full if rep is None else rep
 
 
@@ -268,7 +353,7 @@ def fid(act1, act2):
 
 def cfid(ori, gen, encoder: "TS2VecEncoder"):
     """C-FID as evaluation.py:238-243 computes it once the encoder exists: FID of the full-series representations of the
-    original and the generated (N, L, n_series) arrays."""
+    original and the generated (N, L, n_series) arrays, L <= 4096 (TS2VecEncoder.encode picks the kernel by L)."""
     return fid(encoder.encode(ori), encoder.encode(gen))
 
 

@@ -417,6 +417,8 @@ class TS2Vec:
         return self._hip
 
     def encode(self, data, encoding_window=None, batch_size=None):
+        """data (N, T, input_dims) -> the encoder's output, `batch_size` rows at a time.  Any T up to 4096: series whose
+        activation planes fit LDS run on t2s_ts2vec_encode, longer ones on t2s_ts2vec_encode_long (TS2VecEncoder.encode)."""
         data = np.asarray(data)
         assert data.ndim == 3
         bs = batch_size or self.batch_size
