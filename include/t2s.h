@@ -659,7 +659,11 @@ int t2s_sampler_lane_pool(void);
  * ------------------------------------------------------------------------ */
 /* ori, gen: (n, len) device arrays, len = L * n_series of the (N, L, n_series) arrays infer.py writes;
  * per_sample: (n, 2) output = [mse_i, wape_i (NaN when sum |ori_i| == 0)]; out: [MSE, WAPE] =
- * [mean_i mse_i, nanmean_i wape_i].  Deterministic summation order. */
+ * [mean_i mse_i, nanmean_i wape_i].  Deterministic summation order.
+ * Non-finite input is not filtered, IEEE arithmetic decides, as in the reference's numpy: a NaN in ori_i or gen_i makes mse_i
+ * and wape_i NaN; an Inf makes mse_i +Inf (NaN where Inf meets Inf of the same sign) and wape_i +Inf when it is in gen_i, NaN
+ * (Inf / Inf) when it is in ori_i.  MSE takes every mse_i, so it is NaN / Inf with them; WAPE skips every NaN wape_i, whatever
+ * made it NaN, and is NaN when none is left. */
 int t2s_eval_mse_wape(const float* ori, const float* gen, float* per_sample, float* out, int n, int len,
                       void* stream);
 
@@ -670,21 +674,30 @@ int t2s_eval_mse_wape(const float* ori, const float* gen, float* per_sample, flo
  * passes them in the order it loads them); sims (n, runs) output: the cosine similarities (0 where not finite);
  * score (n) output: 1 / (g + 1) for the best run g when its similarity exceeds `threshold` (the reference uses
  * 0.5, evaluation.py:300), else 0 -- g is the run INDEX, as the reference computes it; ties go to the largest
- * index; out[0] = mean score. */
+ * index; out[0] = mean score.
+ * A similarity that is not finite -- a NaN or an Inf anywhere in ori_i or in that run -- is stored as 0 and takes part in the
+ * search for the best run as 0 (the reference's nan_to_num); score and out[0] are always finite. */
 int t2s_eval_mrr(const float* ori, const float* gen, float* sims, float* score, float* out, int n, int len,
                  int runs, float threshold, void* stream);
 
 /* ED: evaluation.py:137-150 (calculate_ed).  ori, gen: (n, L, n_series); per_sample (n): mean over series of the
- * Euclidean distance over time; out[0] = mean over samples. */
+ * Euclidean distance over time; out[0] = mean over samples.  A NaN in ori_i or gen_i makes per_sample[i] and out[0] NaN, an Inf
+ * makes them +Inf (NaN where Inf meets Inf of the same sign); other samples are not touched. */
 int t2s_eval_ed(const float* ori, const float* gen, float* per_sample, float* out, int n, int L, int n_series,
                 void* stream);
 /* CRPS: evaluation.py:51-83 (calculate_crps) over the repeated generations evaluation.py:298-314 stacks.
- * ori (n, L, n_series); gen (runs, n, L, n_series) run-major; per_sample (n); out[0] = mean. */
+ * ori (n, L, n_series); gen (runs, n, L, n_series) run-major; per_sample (n); out[0] = mean.  Per series and run the mean
+ * and the population std over time are taken in fp64 and rounded once to fp32 (a std of exactly 0 becomes 1e-8f), the step
+ * is `obs < mean ? 0 : 1` on fp32 values, Phi runs in fp64.  A NaN or an Inf in gen_i (its mean or std is NaN then) or a NaN
+ * in ori_i makes per_sample[i] and out[0] NaN; an Inf in ori_i contributes 0 at that step (Phi = the step), the rest stays
+ * finite. */
 int t2s_eval_crps(const float* ori, const float* gen, float* per_sample, float* out, int n, int L, int n_series,
                   int runs, void* stream);
 /* DTW: evaluation.py:152-163 (calculate_dtw = dtaidistance 2.3 dtw_ndim.distance, no window, no penalty): sqrt of the
  * minimal warping-path cost with squared-Euclidean point costs between the (L, n_series) sequences of each sample.
- * per_sample (n); out[0] = mean.  L <= 4096. */
+ * per_sample (n); out[0] = mean.  L <= 4096 (T2S_E_INVALID beyond, before any launch).  A NaN anywhere in ori_i or gen_i
+ * makes per_sample[i] and out[0] NaN (every warping path crosses its row or column); an Inf makes them +Inf, NaN where Inf
+ * meets Inf of the same sign. */
 int t2s_eval_dtw(const float* ori, const float* gen, float* per_sample, float* out, int n, int L, int n_series,
                  void* stream);
 

@@ -104,7 +104,8 @@ __global__ __launch_bounds__(64) void eval_mrr_kernel(const float* __restrict__ 
             bb += __shfl_xor(bb, o, 64);
         }
         const double den = sqrt(aa) * sqrt(bb);
-        const float sf = den > 0.0 ? (float)(ab / den) : 0.f;   // 0/0 -> NaN -> nan_to_num -> 0 (a zero vector)
+        float sf = den > 0.0 ? (float)(ab / den) : 0.f;         // 0/0 -> NaN -> nan_to_num -> 0 (a zero vector)
+        if (!isfinite(sf)) sf = 0.f;                            // an Inf in either vector: inf/inf -> NaN -> 0, and it competes as 0
         if (best_g < 0 || sf >= best) { best = sf; best_g = g; }
         if (threadIdx.x == 0) sims[(size_t)i * runs + g] = sf;
     }
@@ -220,6 +221,7 @@ __global__ __launch_bounds__(256) void eval_dtw_kernel(const float* __restrict__
                 const double left = j > 0 ? p1[i] : INF;                   // (i, j-1)   on diagonal d-1
                 const double dg = (i > 0 && j > 0) ? p2[i - 1] : INF;      // (i-1, j-1) on diagonal d-2
                 best = fmin(dg, fmin(up, left));
+                if (up != up || left != left || dg != dg) best = __builtin_nan("");   // fmin drops a NaN: keep it, every path crosses its row
             }
             cur[i] = c + best;
         }

@@ -178,6 +178,28 @@ def test_mse_is_stateless_two_streams_and_two_threads(dev):
             assert torch.equal(out, single[i]), (k, i)
 
 
+# ------------------------------------------------------------------------------------------------ paired evaluation entries
+def test_eval_entries_refuse_bad_arguments_with_their_name(dev):
+    """t2s_eval_mse_wape / _mrr / _ed / _crps / _dtw check their arguments before any launch: a NULL array or an empty
+    extent is T2S_E_INVALID with a message that names the entry, and the outputs are not written (the full table of
+    refusals is tests/test_eval_paired.py's)."""
+    lib, st = L.lib(), L.stream_ptr(dev)
+    x = torch.rand(2, 8, 2, device=dev)
+    out = torch.full((8,), -7.0, device=dev)
+    p, o = x.data_ptr(), out.data_ptr()
+    calls = {"t2s_eval_mse_wape": (lambda a, n: lib.t2s_eval_mse_wape(a, p, o, o + 16, n, 16, st)),
+             "t2s_eval_mrr": (lambda a, n: lib.t2s_eval_mrr(a, p, o, o + 8, o + 16, n, 16, 1, 0.5, st)),
+             "t2s_eval_ed": (lambda a, n: lib.t2s_eval_ed(a, p, o, o + 16, n, 8, 2, st)),
+             "t2s_eval_crps": (lambda a, n: lib.t2s_eval_crps(a, p, o, o + 16, n, 8, 2, 1, st)),
+             "t2s_eval_dtw": (lambda a, n: lib.t2s_eval_dtw(a, p, o, o + 16, n, 8, 2, st))}
+    for name, call in calls.items():
+        for a, n in ((None, 2), (p, 0), (p, -1)):
+            assert call(a, n) == -1 and lib.t2s_last_error().decode().startswith(name + ":"), (name, a, n)
+    assert lib.t2s_eval_dtw(p, p, o, o + 16, 1, 4097, 1, st) == -1 and "4096" in lib.t2s_last_error().decode()
+    torch.cuda.synchronize()
+    assert (out.cpu() == -7.0).all()
+
+
 # ------------------------------------------------------------------------------------------------ class-API pairing limits
 def _ref_loop(m, x0, emb, steps, cfg, pairing):
     m.set_pairing(pairing)

@@ -1127,6 +1127,7 @@ def test_eval_ed_crps_mse_wape_mrr_reference_fixture(golden_dir, dev):
     m, sims, _ = M.mrr(ori, runs)
     assert abs(m - float(g["mrr"])) < 1e-6
     np.testing.assert_allclose(sims.numpy(), g["sims"], rtol=1e-5, atol=1e-6)
+    assert (sims[4] == 0).all() and bool(torch.isfinite(sims).all())          # the all-zero row: exact zeros, never NaN
     np.testing.assert_allclose(M.fid(g["fid_act1"], g["fid_act2"]), float(g["fid"]), rtol=1e-9)
 
 
