@@ -2,7 +2,7 @@
 """Drop-in evaluation driver (reference evaluation.py:269-314): same flags, same input files, same JSON outputs -- with the
 metrics computed by the HIP kernels of t2ms_amd.metrics (csrc/t2s_eval.hip) instead of numpy / scipy / dtaidistance loops.
 
-    python evaluation.py --dataset_name ETTh1_96 --cfg_scale 9.0 --total_step 10 [--method_list MSE,WAPE,MRR,CRPS,C-FID,ED,DTW,MDD,ACD,SD,KD]
+    python evaluation.py --dataset_name ETTh1_96 --cfg_scale 9.0 --total_step 10 [--method_list MSE,WAPE,MRR,CRPS,C-FID,ED,DTW,MDD,ACD,SD,KD,CS,SC]
 
 Kept from the reference: the path derivations (`{save_path}/generation/{backbone}_{denoiser}_{dataset}_{cfg}_{steps}/`, its
 `run_0 .. run_9/`, results under `{save_path}/evaluation/{model_name}/{model_name}_{dataset}_{time}[_multi].json`), the
@@ -11,7 +11,10 @@ files each metric reads (evaluation.py:285-314: `x_1` of run_0 against the base 
 Additions: `ED` and `DTW` may be named in --method_list (the reference defines both, evaluation.py:137-163, and never
 calls them), and so may `MDD`, `ACD`, `SD`, `KD`, the feature-based measures of evaluate/feature_based_measures.py
 (computed from the same x_1 of run_0 / x_t pair as MSE; they compare the two SETS of series, a common permutation of the
-rows changes nothing, so they need no --align_runs); `--align_runs` re-orders every run's rows to run_0's ground-truth order first -- each `infer()` call shuffles
+rows changes nothing, so they need no --align_runs), and `CS` and `SC`, the two motion measures of evaluate/metrics.py that the
+kernels of csrc/t2s_eval_motion.hip compute, from that same pair: `CS` is the correlational score (:112-137; with one
+channel it is trivially 1 whenever it is defined, and NaN when a channel of either set is constant), `SC` the mean over the
+rows of the minimal mean point distance that sequence_correlation (:219-266) finds over all time shifts; `--align_runs` re-orders every run's rows to run_0's ground-truth order first -- each `infer()` call shuffles
 its test loader independently (dataloader.py:111; the reference never seeds), so WITHOUT it row i of one file is not row i of
 another, here exactly as in the reference; `--cfid_engine {torch,hip}` names what trains C-FID's TS2Vec encoder
 (t2ms_amd.ts2vec; left unset it is T2S_TS2VEC_FIT from the environment, else torch autograd as before).  C-FID takes
@@ -55,7 +58,7 @@ def _save(result, args, suffix):
 
 
 def evaluate_data(args, ori_data, gen_data):
-    """evaluation.py:210-266 on (N, 1, L) arrays: C-FID, MSE, WAPE (+ ED, DTW, MDD, ACD, SD, KD) -> result dict, written as JSON."""
+    """evaluation.py:210-266 on (N, 1, L) arrays: C-FID, MSE, WAPE (+ ED, DTW, MDD, ACD, SD, KD, CS, SC) -> result dict, written as JSON."""
     _divider()
     print(f"Evalution with settings:{args}")
     methods = _methods(args.method_list)
@@ -86,6 +89,10 @@ def evaluate_data(args, ori_data, gen_data):
     if any(m in methods for m in ("MDD", "ACD", "SD", "KD")):
         features, _ = M.feature_measures(ori, gen, device=args.device)
         result.update({m: features[m] for m in ("MDD", "ACD", "SD", "KD") if m in methods})
+    if "CS" in methods:
+        result["CS"] = M.correlational_score(ori, gen, device=args.device)[0]
+    if "SC" in methods:
+        result["SC"] = M.sequence_correlation(ori, gen, device=args.device)[0]
     _save(result, args, "")
     print(f"Evaluation done. Results:{result}.")
     _divider()

@@ -729,6 +729,57 @@ int t2s_eval_moments(const float* ori, const float* gen, float* stats, float* ou
 int t2s_eval_mdd(const float* ori, const float* gen, float* per_column, float* out, int n, int L, int n_series,
                  void* workspace, uint64_t workspace_bytes, void* stream);
 
+/* Motion measures of evaluate/metrics.py, the ones its __main__ (:290-370) compares recordings of unequal length with:
+ * the correlational score (:112-137), the sequence correlation (:219-266) and DTW of two sequences of unequal length
+ * (calculate_dtw(seq1, seq2), :139-170).  Like the feature entries they use the caller's stream, never allocate, copy
+ * or synchronise and keep no state; every refusal is T2S_E_INVALID with the entry's name and the offending value in
+ * t2s_last_error, before any launch; the same input gives the same bits on every call, whatever the grid (fixed fp64
+ * summation orders, no floating-point atomics). */
+#define T2S_EVAL_CORR_MAX_SERIES 64    /* t2s_eval_corr: channels */
+#define T2S_EVAL_MOTION_MAX_LEN 4096   /* t2s_eval_shift / t2s_eval_dtw_ragged: padded length of either side */
+/* Bytes of workspace t2s_eval_corr needs at this shape (0 and an error message if unsupported): about 16 P n_series^2 with
+ * P = min(max(rows_ori, rows_gen), 1024), i.e. 1.6 MB at 10 channels and 64 MiB at 64. */
+uint64_t t2s_eval_corr_workspace_bytes(int rows_ori, int rows_gen, int n_series);
+/* Correlational score: calculate_correlation_matrix / calculate_correlational_score (:112-137).  ori (rows_ori, n_series),
+ * gen (rows_gen, n_series) fp32 contiguous -- the reference's reshape(N * T, D), so the two sets may differ in N and T;
+ * rows >= 2 each, 1 <= n_series <= T2S_EVAL_CORR_MAX_SERIES.  As np.corrcoef(rowvar=False), all in fp64: the channel
+ * means, the centred co-moments c_ij = sum_r (x_ri - mean_i)(x_rj - mean_j), C_ij = (c_ij / sqrt(c_ii)) / sqrt(c_jj)
+ * (two divisions, as numpy does them) clipped to [-1, 1]; out[0] = 1 - sum |C_ori - C_gen| / sum |C_ori|, NaN when that
+ * denominator is exactly 0.  corr (may be NULL): (2, n_series, n_series), set 0 = ori, 1 = gen; every stored value is
+ * rounded once from fp64, and the score is taken from the fp64 matrices.  Sums run over P = min(rows, 1024) chunks of
+ * rows (a function of rows alone), partials are folded in index order.
+ * Non-finite values are not filtered, IEEE arithmetic decides as in numpy: a constant channel (c_ii == 0) gives NaN in
+ * its row and column of that set's matrix (0 / 0) and a NaN score; a NaN or an Inf in the data makes the mean and with
+ * it every co-moment of that channel NaN, hence its row and column and the score NaN. */
+int t2s_eval_corr(const float* ori, const float* gen, float* corr, float* out, int rows_ori, int rows_gen, int n_series,
+                  void* workspace, uint64_t workspace_bytes, void* stream);
+/* Sequence correlation: sequence_correlation (:219-266) for n pairs in padded storage a (n, La, n_series), b (n, Lb,
+ * n_series); len_a, len_b: device int32 (n), the lengths m_i, n_i of the pairs, either NULL = the full La / Lb.  A length
+ * is clamped into [1, La] resp. [1, Lb] by the kernels, so no value in those arrays takes a read outside a or b (the
+ * Python mirror refuses such a length on the host); the padding is never read.  1 <= La, Lb <= 4096, n_series >= 1.
+ * Per pair, M = min(m, n) - 1 and for every shift s in -M .. M:
+ *   s >= 0: ov = min(m, n - s), a[0:ov] against b[s:s+ov];    s < 0: ov = min(m + s, n), a[-s:-s+ov] against b[0:ov];
+ *   dist_s = mean over the overlap of the Euclidean norm over the channels (norm and sum in fp64, rounded once).
+ * table (n, W), W = 2 min(La, Lb) - 1: dist_s in column min(La, Lb) - 1 + s, NaN where a pair has no such shift.
+ * Search rule: the reference's left-to-right scan min(keys, key=...) on the values AS STORED in fp32, starting at s = -M:
+ * a later shift wins only if its value is strictly smaller, so among equal values the most negative shift wins, and a
+ * NaN is never chosen unless it is the first shift's value, which then stays, as in the reference.  best_shift (n, int32);
+ * min_dist (n): bit for bit table[i, best]; out[0] = mean of min_dist.
+ * A NaN in an overlap makes that shift's distance NaN, an Inf makes it +Inf (NaN where Inf meets Inf of the same sign);
+ * shifts whose overlap avoids the value are not touched.
+ * The reference's wrapper calculate_sequence_correlation (:197-217) returns only the LAST pair's result; this entry returns
+ * every pair's. */
+int t2s_eval_shift(const float* a, const float* b, const int* len_a, const int* len_b, float* table, int* best_shift,
+                   float* min_dist, float* out, int n, int La, int Lb, int n_series, void* stream);
+/* DTW of sequences of unequal length: calculate_dtw(seq1, seq2) (:139-170) with its default squared-Euclidean cost, no
+ * window, no penalty, then a sqrt -- the recurrence of t2s_eval_dtw on an m x n table.  Storage, length arrays and
+ * clamping as for t2s_eval_shift; per_sample (n); out[0] = mean; La, Lb <= 4096 (T2S_E_INVALID beyond, before any
+ * launch).  With La == Lb and no length arrays the result equals t2s_eval_dtw's bit for bit.  As there, a NaN anywhere in
+ * a_i or b_i (inside the lengths) makes per_sample[i] and out[0] NaN, an Inf makes them +Inf, NaN where Inf meets Inf of
+ * the same sign. */
+int t2s_eval_dtw_ragged(const float* a, const float* b, const int* len_a, const int* len_b, float* per_sample, float* out,
+                        int n, int La, int Lb, int n_series, void* stream);
+
 /* TS2Vec encoder of the C-FID metric: evaluate/ts2vec.py:352-399 (TSEncoder.forward, eval mode, mask 'all_true') followed
  * by the 'full_series' pooling of TS2Vec.encode (:236-245).  Device pointers to the state-dict tensors:
  * input_fc.{weight (hidden,input_dims),bias}; block i in [0,depth]: feature_extractor.net.i.conv{1,2}.conv.{weight

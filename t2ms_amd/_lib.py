@@ -23,6 +23,7 @@ MATH_CODES = {"f32": MATH_F32, "bf16x3": MATH_BF16X3, "bf16": MATH_BF16}
 DIT_N_TENSORS = 10 + 10 * N_BLOCKS   # t2s.h: T2S_DIT_N_TENSORS (pointers of t2s_dit_weights, declaration order)
 MSE_SCRATCH_FLOATS = 1024       # t2s.h: T2S_MSE_SCRATCH_FLOATS
 EVAL_MAX_LAG, EVAL_MDD_BINS = 64, 50   # t2s.h: T2S_EVAL_MAX_LAG / T2S_EVAL_MDD_BINS
+EVAL_CORR_MAX_SERIES, EVAL_MOTION_MAX_LEN = 64, 4096   # t2s.h: T2S_EVAL_CORR_MAX_SERIES / T2S_EVAL_MOTION_MAX_LEN
 
 c_float_p = C.c_void_p  # device pointers travel as opaque addresses
 
@@ -170,6 +171,10 @@ SYMBOLS = {
     "t2s_eval_features_workspace_bytes": (_U64, [_I, _I, _I]),
     "t2s_eval_moments": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
     "t2s_eval_mdd": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
+    "t2s_eval_corr_workspace_bytes": (_U64, [_I, _I, _I]),
+    "t2s_eval_corr": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP, _U64, _VP]),
+    "t2s_eval_shift": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+    "t2s_eval_dtw_ragged": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
     "t2s_ts2vec_encode": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP]),
     "t2s_ts2vec_encode_workspace_bytes": (_U64, [C.POINTER(Ts2vecWeights), _I, _I]),
     "t2s_ts2vec_encode_long": (_I, [C.POINTER(Ts2vecWeights), _VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),

@@ -2,7 +2,9 @@
 evaluation.py defines them: MSE / WAPE (:166-206), ED (:137-150), DTW (:152-163), MRR (:21-45) and CRPS (:51-83) over
 the run_0..run_k repetitions `--run_multi` writes, the TS2Vec encoder forward + FID of the C-FID metric
 (:127-135,238-243; evaluate/ts2vec.py:352-399), and the set-against-set measures MDD / ACD / SD / KD of
-evaluate/feature_based_measures.py (calculate_mdd :30-94, _acd :98-161, _sd :165-191, _kd :195-223).  `python -m t2ms_amd.metrics <generation dir>` prints them for a
+evaluate/feature_based_measures.py (calculate_mdd :30-94, _acd :98-161, _sd :165-191, _kd :195-223), and the motion measures
+of evaluate/metrics.py for recordings of unequal length: correlational_score (:112-137), sequence_correlation (:219-266)
+and dtw_ragged (calculate_dtw(seq1, seq2), :139-170) on the kernels of csrc/t2s_eval_motion.hip.  `python -m t2ms_amd.metrics <generation dir>` prints them for a
 directory holding x_1.npy and x_t.npy ({save_path}/generation/{backbone}_{denoiser}_{dataset}_{cfg}_{steps}/[run_k/])
 and the run_* sub-directories.
 
@@ -178,6 +180,118 @@ def feature_measures(ori, gen, device="cuda"):
     (a, s, k), stats = f.moments()
     m, per = f.mdd()
     return {"MDD": m, "ACD": a, "SD": s, "KD": k}, {"per_column": per, "stats": stats}
+
+
+def _f32(x):
+    return torch.as_tensor(np.asarray(x) if not torch.is_tensor(x) else x).float()
+
+
+def correlational_score(ori, gen, device="cuda"):
+    """(score, corr (2, S, S)): calculate_correlational_score, evaluate/metrics.py:112-137 -- 1 - sum |C_ori - C_gen| /
+    sum |C_ori| of the two sets' channel correlation matrices (np.corrcoef over all rows; corr[0] = ori, corr[1] = gen).
+    Takes (N, L, S) arrays, flattened to (N * L, S) as the reference does, or (rows, S) arrays; the two sets may differ
+    in their number of rows.  A constant channel makes the score NaN; with S = 1 it is 1 whenever it is defined."""
+    a, b = _f32(ori), _f32(gen)
+    if a.dim() not in (2, 3) or b.dim() not in (2, 3):
+        raise L.T2SError(f"correlational_score: expected (N, L, S) or (rows, S) arrays, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[-1] != b.shape[-1]:
+        raise L.T2SError(f"correlational_score: channel counts differ, {a.shape[-1]} and {b.shape[-1]}")
+    s = int(a.shape[-1])
+    if not 1 <= s <= L.EVAL_CORR_MAX_SERIES:
+        raise L.T2SError(f"correlational_score: S={s} is outside [1, {L.EVAL_CORR_MAX_SERIES}]")
+    a, b = a.reshape(-1, s), b.reshape(-1, s)
+    if a.shape[0] < 2 or b.shape[0] < 2:
+        raise L.T2SError(f"correlational_score: {a.shape[0]} and {b.shape[0]} rows, a correlation needs at least 2")
+    dev = _gpu(device, "correlational_score")
+    a, b = a.contiguous().to(dev), b.contiguous().to(dev)
+    need = L.lib().t2s_eval_corr_workspace_bytes(a.shape[0], b.shape[0], s)
+    if need == 0:
+        L.check(1, "t2s_eval_corr_workspace_bytes")
+    ws = torch.empty(need, dtype=torch.uint8, device=dev)
+    corr, out = torch.empty(2, s, s, device=dev), torch.empty(1, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().t2s_eval_corr(a.data_ptr(), b.data_ptr(), corr.data_ptr(), out.data_ptr(), a.shape[0], b.shape[0], s,
+                                      ws.data_ptr(), ws.numel(), L.stream_ptr(dev)), "t2s_eval_corr")
+    return float(out.cpu()[0]), corr.cpu()
+
+
+def pad_ragged(seqs):
+    """[(T_i, S) arrays] -> (array (n, Lmax, S) fp32 zero-padded, lengths (n,) int32)."""
+    seqs = [np.asarray(s.cpu() if torch.is_tensor(s) else s, dtype=np.float32) for s in seqs]
+    if not seqs:
+        raise L.T2SError("pad_ragged: no sequence")
+    seqs = [s[:, None] if s.ndim == 1 else s for s in seqs]
+    if any(s.ndim != 2 or s.shape[0] < 1 for s in seqs) or len({s.shape[1] for s in seqs}) != 1:
+        raise L.T2SError(f"pad_ragged: expected non-empty (T_i, S) arrays of one S, got {[tuple(s.shape) for s in seqs]}")
+    out = np.zeros((len(seqs), max(s.shape[0] for s in seqs), seqs[0].shape[1]), np.float32)
+    for i, s in enumerate(seqs):
+        out[i, :s.shape[0]] = s
+    return out, np.asarray([s.shape[0] for s in seqs], dtype=np.int32)
+
+
+def _ragged(a, b, lengths, what):
+    """Host side of the two ragged measures: a (n, La, S), b (n, Lb, S) (or two lists of (T_i, S) arrays) and `lengths`
+    = None or (len_a, len_b), each None or n integers -> fp32 tensors and int32 length tensors (None = full length).
+    Everything the kernels would clamp is refused here."""
+    if isinstance(a, (list, tuple)) or isinstance(b, (list, tuple)):
+        if not (isinstance(a, (list, tuple)) and isinstance(b, (list, tuple))) or lengths is not None:
+            raise L.T2SError(f"{what}: give two lists of (T_i, S) arrays (and no lengths), or two padded arrays")
+        (a, la), (b, lb) = pad_ragged(a), pad_ragged(b)
+        lengths = (la, lb)
+    a, b = _f32(a), _f32(b)
+    if a.dim() != 3 or b.dim() != 3 or a.shape[0] != b.shape[0] or a.shape[0] < 1:
+        raise L.T2SError(f"{what}: expected (n, La, S) and (n, Lb, S) arrays, got {tuple(a.shape)} and {tuple(b.shape)}")
+    if a.shape[2] != b.shape[2] or a.shape[2] < 1:
+        raise L.T2SError(f"{what}: channel counts differ, {a.shape[2]} and {b.shape[2]}")
+    lens = []
+    for x, ln, name in ((a, None if lengths is None else lengths[0], "a"), (b, None if lengths is None else lengths[1], "b")):
+        cap = int(x.shape[1])
+        if not 1 <= cap <= L.EVAL_MOTION_MAX_LEN:
+            raise L.T2SError(f"{what}: L={cap} of {name} is outside [1, {L.EVAL_MOTION_MAX_LEN}]")
+        if ln is not None:
+            ln = np.asarray(ln.cpu() if torch.is_tensor(ln) else ln)
+            if ln.shape != (a.shape[0],) or not np.issubdtype(ln.dtype, np.integer):
+                raise L.T2SError(f"{what}: lengths of {name} must be {a.shape[0]} integers")
+            if ln.min() < 1 or ln.max() > cap:
+                raise L.T2SError(f"{what}: a length of {name} is outside [1, {cap}]: min {ln.min()}, max {ln.max()}")
+            ln = torch.from_numpy(ln.astype(np.int32))
+        lens.append(ln)
+    return a, b, lens[0], lens[1]
+
+
+def sequence_correlation(a, b, lengths=None, device="cuda"):
+    """(mean_min_dist, best_shift (n,) int32, min_dist (n,), table (n, W)): sequence_correlation, evaluate/metrics.py:219-266,
+    for every pair (a_i, b_i) -- the mean point distance at every shift -M .. M, M = min(len_a, len_b) - 1 (table, W = 2
+    min(La, Lb) - 1, shift 0 in column min(La, Lb) - 1, NaN where the pair has no such shift), and the reference's
+    left-to-right search for the smallest.  a (n, La, S), b (n, Lb, S) with lengths = (len_a, len_b) (each None or n
+    integers), or two lists of (T_i, S) arrays."""
+    a, b, la, lb = _ragged(a, b, lengths, "sequence_correlation")
+    dev = _gpu(device, "sequence_correlation")
+    a, b = a.contiguous().to(dev), b.contiguous().to(dev)
+    la, lb = (None if v is None else v.to(dev) for v in (la, lb))
+    n, w = a.shape[0], 2 * min(a.shape[1], b.shape[1]) - 1
+    table, best = torch.empty(n, w, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+    dist, out = torch.empty(n, device=dev), torch.empty(1, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().t2s_eval_shift(a.data_ptr(), b.data_ptr(), None if la is None else la.data_ptr(),
+                                       None if lb is None else lb.data_ptr(), table.data_ptr(), best.data_ptr(), dist.data_ptr(),
+                                       out.data_ptr(), n, a.shape[1], b.shape[1], a.shape[2], L.stream_ptr(dev)), "t2s_eval_shift")
+    return float(out.cpu()[0]), best.cpu(), dist.cpu(), table.cpu()
+
+
+def dtw_ragged(a, b, lengths=None, device="cuda"):
+    """(mean, per_sample (n,)): calculate_dtw(seq1, seq2), evaluate/metrics.py:139-170 (squared-Euclidean point costs, then
+    a sqrt), for every pair of sequences of unequal length; arguments as for sequence_correlation."""
+    a, b, la, lb = _ragged(a, b, lengths, "dtw_ragged")
+    dev = _gpu(device, "dtw_ragged")
+    a, b = a.contiguous().to(dev), b.contiguous().to(dev)
+    la, lb = (None if v is None else v.to(dev) for v in (la, lb))
+    per, out = torch.empty(a.shape[0], device=dev), torch.empty(1, device=dev)
+    with torch.cuda.device(dev):
+        L.check(L.lib().t2s_eval_dtw_ragged(a.data_ptr(), b.data_ptr(), None if la is None else la.data_ptr(),
+                                            None if lb is None else lb.data_ptr(), per.data_ptr(), out.data_ptr(), a.shape[0],
+                                            a.shape[1], b.shape[1], a.shape[2], L.stream_ptr(dev)), "t2s_eval_dtw_ragged")
+    return float(out.cpu()[0]), per.cpu()
 
 
 def _runs_first(ori, gens, what):
