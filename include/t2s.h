@@ -919,6 +919,70 @@ int t2s_mlp_backward(const t2s_mlp_weights* w, const float* packed, const float*
                      const float* text, const float* dout, float* dx, const t2s_mlp_grads* grads, float* scratch,
                      uint64_t scratch_floats, int B, void* stream);
 
+/* ------------------------------------------------------------------------ *
+ * TSae: the attention seq2seq codec of the motion models, model/pretrained/TSae.py
+ * (AttentionSeq2SeqAutoencoder): pre-norm transformer encoder, teacher-forced
+ * decoder, and the autoregressive generation with a key/value cache.  fp32.
+ * ------------------------------------------------------------------------ */
+#define T2S_TSAE_D_MODEL 64
+#define T2S_TSAE_MAX_LAYERS 6
+#define T2S_TSAE_MAX_T 2000      /* the reference's positional table */
+#define T2S_TSAE_MAX_FEATURES 16
+#define T2S_TSAE_MAX_D_FF 512
+typedef struct t2s_tsae t2s_tsae;
+/* Device pointers to the state-dict tensors, torch layouts (nn.MultiheadAttention, nn.Linear, nn.LayerNorm). */
+typedef struct t2s_tsae_attn_weights {
+    const float *in_proj_w, *in_proj_b;   /* (192,64), (192): q, k, v rows */
+    const float *out_proj_w, *out_proj_b; /* (64,64), (64) */
+} t2s_tsae_attn_weights;
+typedef struct t2s_tsae_enc_layer { /* encoder.transformer_encoder.layers.<i> */
+    t2s_tsae_attn_weights self_attn;
+    const float *linear1_w, *linear1_b; /* (d_ff,64), (d_ff) */
+    const float *linear2_w, *linear2_b; /* (64,d_ff), (64) */
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b;
+} t2s_tsae_enc_layer;
+typedef struct t2s_tsae_dec_layer { /* decoder.transformer_decoder.layers.<i> */
+    t2s_tsae_attn_weights self_attn, multihead_attn;
+    const float *linear1_w, *linear1_b, *linear2_w, *linear2_b;
+    const float *norm1_w, *norm1_b, *norm2_w, *norm2_b, *norm3_w, *norm3_b;
+} t2s_tsae_dec_layer;
+typedef struct t2s_tsae_weights {
+    int n_features, d_model, d_ff, heads, n_enc, n_dec;
+    const float *value_embedding_w, *value_embedding_b; /* encoder.value_embedding (64,F), (64) */
+    const float *embedding_ln_w, *embedding_ln_b;       /* encoder.embedding_ln (64) */
+    t2s_tsae_enc_layer enc[T2S_TSAE_MAX_LAYERS];
+    t2s_tsae_dec_layer dec[T2S_TSAE_MAX_LAYERS];
+    const float *input_projection_w, *input_projection_b;   /* decoder.input_projection (64,F), (64) */
+    const float *output_projection_w, *output_projection_b; /* decoder.output_projection (F,64), (F) */
+} t2s_tsae_weights;
+/* Reads every tensor once (extents checked), packs the transposes and the sinusoidal table (a function of position and channel,
+ * computed here) into one device buffer the handle owns; later calls copy nothing.  Covered: d_model 64, heads 4 or 8, d_ff a
+ * multiple of 64 up to 512, 1..6 layers on each side, 1..16 features; anything else is T2S_E_INVALID naming the value.  n_enc 0 or
+ * n_dec 0 (not both) makes a one-sided handle: that side's tensors are not read, and its entries are T2S_E_INVALID.  Create again
+ * after the weights change.  Synchronous (not for use inside a stream capture). */
+int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out);
+void t2s_tsae_destroy(t2s_tsae* h);
+/* Rows [first, first + count) of the handle's positional table -> pe (count,64), device. */
+int t2s_tsae_positional(const t2s_tsae* h, float* pe, int first, int count, void* stream);
+/* Bytes of workspace the three entries below need for (B, T) -- one size serves all three; 0 (and a message) out of range.
+ * The entries allocate nothing and never synchronise; each refuses, before any launch and with its outputs untouched, T outside
+ * 1..T2S_TSAE_MAX_T, B outside 1..65535, a NULL pointer and a workspace smaller than this.  A series' result is a function of that
+ * series alone: bitwise the same at any B and any place in the batch, and from call to call. */
+uint64_t t2s_tsae_workspace_bytes(const t2s_tsae* h, int B, int T);
+/* x (B,T,F) -> memory (B,T,64): value embedding, LayerNorm, + position, n_enc pre-norm layers (unmasked attention, ReLU FFN),
+ * no final norm.  1 + 4 n_enc launches. */
+int t2s_tsae_encode(const t2s_tsae* h, const float* x, float* memory, int B, int T, void* workspace, uint64_t workspace_bytes,
+                    void* stream);
+/* Teacher-forced decoder: memory (B,T,64), target (B,T,F) -> prediction (B,T,F).  Input row 0 is the zero BOS row, row i > 0
+ * input_projection(target[i-1]); + position; n_dec pre-norm layers (causal self-attention, cross-attention over the T memory rows,
+ * ReLU FFN); output_projection.  3 + 7 n_dec launches. */
+int t2s_tsae_decode(const t2s_tsae* h, const float* memory, const float* target, float* prediction, int B, int T, void* workspace,
+                    uint64_t workspace_bytes, void* stream);
+/* decoder.generate: memory (B,S,64) -> series (B,S,F), autoregressively.  One launch projects the memory to every layer's
+ * cross-attention K / V, one launch (a workgroup per series) runs all S steps with the self-attention K / V cached in the workspace. */
+int t2s_tsae_generate(const t2s_tsae* h, const float* memory, float* series, int B, int S, void* workspace, uint64_t workspace_bytes,
+                      void* stream);
+
 #ifdef __cplusplus
 }
 #endif

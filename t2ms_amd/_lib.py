@@ -131,6 +131,34 @@ class MlpGrads(C.Structure):            # t2s_mlp_grads: the same fields, writab
     _fields_ = [("layer", MlpLayerWeights * MLP_LAYERS)]
 
 
+TSAE_D_MODEL, TSAE_MAX_LAYERS, TSAE_MAX_T = 64, 6, 2000   # t2s.h: T2S_TSAE_D_MODEL / _MAX_LAYERS / _MAX_T
+TSAE_MAX_FEATURES, TSAE_MAX_D_FF = 16, 512                 # t2s.h: T2S_TSAE_MAX_FEATURES / _MAX_D_FF
+
+
+class TsaeAttnWeights(C.Structure):
+    _fields_ = [(n, C.c_void_p) for n in ("in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b")]
+
+
+class TsaeEncLayer(C.Structure):
+    _fields_ = [("self_attn", TsaeAttnWeights)] + \
+               [(n, C.c_void_p) for n in ("linear1_w", "linear1_b", "linear2_w", "linear2_b",
+                                          "norm1_w", "norm1_b", "norm2_w", "norm2_b")]
+
+
+class TsaeDecLayer(C.Structure):
+    _fields_ = [("self_attn", TsaeAttnWeights), ("multihead_attn", TsaeAttnWeights)] + \
+               [(n, C.c_void_p) for n in ("linear1_w", "linear1_b", "linear2_w", "linear2_b",
+                                          "norm1_w", "norm1_b", "norm2_w", "norm2_b", "norm3_w", "norm3_b")]
+
+
+class TsaeWeights(C.Structure):
+    _fields_ = [(n, C.c_int) for n in ("n_features", "d_model", "d_ff", "heads", "n_enc", "n_dec")] + \
+               [(n, C.c_void_p) for n in ("value_embedding_w", "value_embedding_b", "embedding_ln_w", "embedding_ln_b")] + \
+               [("enc", TsaeEncLayer * TSAE_MAX_LAYERS), ("dec", TsaeDecLayer * TSAE_MAX_LAYERS)] + \
+               [(n, C.c_void_p) for n in ("input_projection_w", "input_projection_b",
+                                          "output_projection_w", "output_projection_b")]
+
+
 class SampleConfig(C.Structure):
     _fields_ = [("mode", C.c_int), ("steps", C.c_int), ("cfg_scale", C.c_float), ("batch", C.c_int),
                 ("length", C.c_int), ("use_graph", C.c_int), ("seed", C.c_uint64), ("row0", C.c_uint32),
@@ -236,6 +264,13 @@ SYMBOLS = {
     "t2s_philox_normal_rows": (_I, [_VP, _VP, _VP, _U32, _I, _I, _VP]),
     "t2s_sampler_graph_lanes": (_I, [_VP]),
     "t2s_sampler_lane_pool": (_I, []),
+    "t2s_tsae_create": (_I, [C.POINTER(TsaeWeights), C.POINTER(_VP)]),
+    "t2s_tsae_destroy": (None, [_VP]),
+    "t2s_tsae_positional": (_I, [_VP, _VP, _I, _I, _VP]),
+    "t2s_tsae_workspace_bytes": (_U64, [_VP, _I, _I]),
+    "t2s_tsae_encode": (_I, [_VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
+    "t2s_tsae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
+    "t2s_tsae_generate": (_I, [_VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -1,0 +1,404 @@
+"""Host-side mirror of the reference's attention seq2seq codec (model/pretrained/TSae.py, AttentionSeq2SeqAutoencoder): the
+codec the motion pipeline's ``vae:`` block configures (flow_dim 64, d_ff 128, 3 + 3 layers, 8 heads, input_dim 10) and
+``pretrained_mylavae.py`` trains and reconstructs with.
+
+Class names, constructor signatures, attribute names and state-dict keys equal the reference's (the two ``pe`` buffers and the
+``condition_fusion.*`` tensors included), so a state dict the reference saved loads with ``strict=True``.
+
+Routing (``_route``): eval mode, no gradient wanted, no masks and a covered shape (d_model 64, 4 or 8 heads, d_ff a multiple of
+64 up to 512, 1..6 layers, 1..16 features, 1 <= T <= 2000) run the HIP entries of csrc/t2s_tsae.hip -- ``encoder(x)`` is
+t2s_tsae_encode, ``decoder(memory, target)`` t2s_tsae_decode, ``decoder.generate(memory)`` t2s_tsae_generate (all steps in one
+launch, key/value cached); a CPU tensor on that route is a T2SError.  Everything else -- training mode (dropout), a gradient
+wanted (``shared_eval(..., 'train')``), masks, the text-fusion path of ``forward()``, uncovered shapes, and everything under
+``T2S_TSAE=torch`` (read at call time) -- runs the ``_forward_torch`` methods: torch ops on the same parameters, plumbing with
+no throughput claim.
+"""
+import ctypes as C
+import math
+import os
+import weakref
+
+import torch
+import torch.nn as nn
+import torch.nn.functional as F
+
+from ... import _lib as L
+from .core import BaseModel
+
+
+def _torch_forced():
+    v = os.environ.get("T2S_TSAE", "") or "hip"
+    if v not in ("hip", "torch"):
+        raise L.T2SError(f"T2S_TSAE must be 'hip' or 'torch' (got {v!r})")
+    return v == "torch"
+
+
+def _covered(n_features, d_model, d_ff, heads, layers, T, B=1):
+    return (d_model == L.TSAE_D_MODEL and heads in (4, 8) and d_ff % 64 == 0 and 64 <= d_ff <= L.TSAE_MAX_D_FF
+            and 1 <= layers <= L.TSAE_MAX_LAYERS and 1 <= n_features <= L.TSAE_MAX_FEATURES and 1 <= T <= L.TSAE_MAX_T
+            and 1 <= B <= 65535)
+
+
+def _route(training, grad, masks, covered, forced):
+    """'hip' or 'torch' for one call: each condition alone sends the call to the torch ops."""
+    return "torch" if (training or grad or masks or not covered or forced) else "hip"
+
+
+class PositionalEncoding(nn.Module):
+    """x + pe[:, :T], then dropout; pe (1, max_len, d_model) is a buffer of the state dict."""
+
+    def __init__(self, d_model, max_len=5000, dropout=0.1):
+        super().__init__()
+        self.dropout = nn.Dropout(p=dropout)
+        pe = torch.zeros(max_len, d_model)
+        position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+        div_term = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float) * -(math.log(10000.0) / d_model))
+        pe[:, 0::2] = torch.sin(position * div_term)
+        pe[:, 1::2] = torch.cos(position * div_term[: d_model // 2])
+        self.register_buffer("pe", pe.unsqueeze(0))
+
+    def forward(self, x):
+        return self.dropout(x + self.pe[:, : x.size(1), :])
+
+
+class AdaLN(nn.Module):
+    def __init__(self, d_model):
+        super().__init__()
+        self.ln = nn.LayerNorm(d_model)
+        self.mlp = nn.Sequential(nn.Linear(d_model, d_model * 4), nn.GELU(), nn.Linear(d_model * 4, d_model * 2))
+
+    def forward(self, x, condition):
+        gamma, beta = self.mlp(condition).chunk(2, dim=1)
+        return gamma.unsqueeze(1) * self.ln(x) + beta.unsqueeze(1)
+
+
+class AdaptiveLinear(nn.Module):
+    """A Linear that reads the first in_dim columns of a (out, max_in) weight.  The fusion block's is (64, 393216): drawn in one
+    uniform_ pass at the xavier bound."""
+
+    def __init__(self, out_features, max_in_features=2048):
+        super().__init__()
+        a = math.sqrt(6.0 / (out_features + max_in_features))
+        self.weight = nn.Parameter(torch.empty(out_features, max_in_features).uniform_(-a, a))
+        self.bias = nn.Parameter(torch.zeros(out_features))
+
+    def forward(self, x):
+        return F.linear(x, self.weight[:, : x.size(-1)], self.bias)
+
+
+def _xavier_(linear, zero_bias=True):
+    nn.init.xavier_uniform_(linear.weight)
+    if zero_bias:
+        nn.init.zeros_(linear.bias)
+
+
+class ConditionFusionModule(nn.Module):
+    """Text-condition fusion (torch ops only; the reference's live paths skip it)."""
+
+    def __init__(self, flow_dim=128, max_text_length=512, text_embedding_dim=768, dropout=0.1):
+        super().__init__()
+        self.flow_dim = flow_dim
+        self.text_projection = AdaptiveLinear(out_features=flow_dim, max_in_features=max_text_length * text_embedding_dim)
+        self.condition_projection = nn.Linear(flow_dim, flow_dim)
+        _xavier_(self.condition_projection)
+        self.fusion = nn.Sequential(nn.Linear(flow_dim * 2, flow_dim * 4), nn.ReLU(), nn.Dropout(dropout),
+                                    nn.Linear(flow_dim * 4, flow_dim))
+        for layer in self.fusion:
+            if isinstance(layer, nn.Linear):
+                _xavier_(layer)
+        self.fusion_ln = nn.LayerNorm(flow_dim)
+        self.ada_ln = AdaLN(flow_dim)
+
+    def forward(self, encoder_output, text_embedding):
+        B, T, _ = encoder_output.shape
+        text_cond = self.text_projection(text_embedding.reshape(B, -1))
+        combined = torch.cat([encoder_output, text_cond.unsqueeze(1).expand(-1, T, -1)], dim=-1)
+        fused = self.fusion_ln(self.fusion(combined) + encoder_output)
+        return self.ada_ln(fused, self.condition_projection(text_cond))
+
+
+class _TsaeHandle:
+    def __init__(self, w, device):
+        self.ptr = C.c_void_p()
+        torch.cuda.synchronize(device)
+        with torch.cuda.device(device):
+            L.check(L.lib().t2s_tsae_create(C.byref(w), C.byref(self.ptr)), "t2s_tsae_create")
+        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_tsae_destroy", str(torch.device(device)), self.ptr)
+
+    def close(self):
+        self._fin()
+
+
+def _attn_ptrs(dst, attn, keep):
+    for field, t in (("in_proj_w", attn.in_proj_weight), ("in_proj_b", attn.in_proj_bias),
+                     ("out_proj_w", attn.out_proj.weight), ("out_proj_b", attn.out_proj.bias)):
+        c = L.as_f32(t.detach())
+        keep.append(c)
+        setattr(dst, field, c.data_ptr())
+
+
+def _fill(dst, pairs, keep):
+    for field, t in pairs:
+        c = L.as_f32(t.detach())
+        keep.append(c)
+        setattr(dst, field, c.data_ptr())
+
+
+def _layer_ptrs(dst, layer, norms, keep):
+    _fill(dst, [("linear1_w", layer.linear1.weight), ("linear1_b", layer.linear1.bias), ("linear2_w", layer.linear2.weight),
+                ("linear2_b", layer.linear2.bias)], keep)
+    for n in norms:
+        _fill(dst, [(n + "_w", getattr(layer, n).weight), (n + "_b", getattr(layer, n).bias)], keep)
+
+
+class _Side(nn.Module):
+    """What TimeSeriesEncoder and TimeSeriesDecoder share: a one-sided library handle cached against the parameters' storage and
+    version, and the module-owned workspace."""
+
+    def _layers(self):
+        raise NotImplementedError
+
+    def _shape(self):
+        """(n_features, d_model, d_ff, heads, layers) as the modules hold them."""
+        layers = self._layers()
+        l0 = layers[0]
+        return (int(self.n_features), int(self.flow_dim), int(l0.linear1.out_features), int(l0.self_attn.num_heads), len(layers))
+
+    def _plain(self):
+        """The layer options the kernels implement: pre-norm, ReLU, eps 1e-5 (what the constructors below set)."""
+        return all(l.norm_first and l.norm1.eps == 1e-5 and getattr(l, "activation_relu_or_gelu", 1) == 1 for l in self._layers())
+
+    def _route_of(self, x, T, masks, B=1):
+        grad = torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters()))
+        F_, d, dff, heads, layers = self._shape()
+        covered = x.dim() == 3 and self._plain() and _covered(F_, d, dff, heads, layers, T, B)
+        return _route(self.training, grad, masks, covered, _torch_forced())
+
+    def _handle(self, device):
+        device = torch.device(device)
+        ts = list(self.parameters())
+        for t in ts:
+            if t.device != device:
+                raise L.T2SError(f"TSae parameters live on {t.device} but the input is on {device}")
+        inference = any(t.is_inference() for t in ts)
+        stamp = None if inference else (str(device),) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in ts)
+        h = self.__dict__.get("_t2s_h")
+        if h is None or stamp is None or self.__dict__.get("_t2s_stamp") != stamp:
+            with L.device_lock(device):       # frees, allocations, synchronous copies: not inside another thread's capture
+                if h is not None:
+                    h.close()
+                w, keep = self._weights_struct()
+                h = _TsaeHandle(w, device)
+                del keep                      # the library packed its own copy
+            self.__dict__["_t2s_h"], self.__dict__["_t2s_stamp"] = h, stamp
+        return h
+
+    def _workspace(self, h, B, T, device):
+        need = int(L.lib().t2s_tsae_workspace_bytes(h.ptr, B, T))
+        if need == 0:
+            raise L.T2SError("TSae: " + L.lib().t2s_last_error().decode("utf-8", "replace"))
+        ws = self.__dict__.get("_t2s_ws")
+        if ws is None or ws.numel() < need or ws.device != torch.device(device):
+            with L.device_lock(device):
+                ws = torch.empty(need, dtype=torch.uint8, device=device)
+            self.__dict__["_t2s_ws"] = ws
+        return ws
+
+    def _gpu(self, who, *tensors):
+        for t in tensors:
+            if not t.is_cuda:
+                raise L.T2SError(f"{who}: input must live on a GPU (got device {t.device}); the HIP path has no CPU fallback "
+                                 f"(T2S_TSAE=torch selects the torch ops)")
+
+    def __getstate__(self):
+        state = self.__dict__.copy()
+        for k in ("_t2s_h", "_t2s_stamp", "_t2s_ws"):
+            state.pop(k, None)
+        return state
+
+
+class TimeSeriesEncoder(_Side):
+    def __init__(self, n_features, flow_dim=128, num_layers=6, d_ff=2048, num_heads=8, dropout=0.1, max_seq_len=2000):
+        super().__init__()
+        self.num_layers, self.flow_dim, self.n_features = num_layers, flow_dim, n_features
+        self.value_embedding = nn.Linear(n_features, flow_dim)
+        _xavier_(self.value_embedding)
+        self.embedding_dropout = nn.Dropout(p=dropout)
+        self.embedding_ln = nn.LayerNorm(flow_dim)
+        self.positional_encoding = PositionalEncoding(d_model=flow_dim, max_len=max_seq_len, dropout=dropout)
+        layer = nn.TransformerEncoderLayer(d_model=flow_dim, nhead=num_heads, dim_feedforward=d_ff, dropout=dropout,
+                                           batch_first=True, norm_first=True)
+        self.transformer_encoder = nn.TransformerEncoder(layer, num_layers=num_layers, enable_nested_tensor=False)
+
+    def _layers(self):
+        return self.transformer_encoder.layers
+
+    def _weights_struct(self):
+        F_, d, dff, heads, n = self._shape()
+        w, keep = L.TsaeWeights(), []
+        w.n_features, w.d_model, w.d_ff, w.heads, w.n_enc, w.n_dec = F_, d, dff, heads, n, 0
+        _fill(w, [("value_embedding_w", self.value_embedding.weight), ("value_embedding_b", self.value_embedding.bias),
+                  ("embedding_ln_w", self.embedding_ln.weight), ("embedding_ln_b", self.embedding_ln.bias)], keep)
+        for i, layer in enumerate(self._layers()):
+            _attn_ptrs(w.enc[i].self_attn, layer.self_attn, keep)
+            _layer_ptrs(w.enc[i], layer, ("norm1", "norm2"), keep)
+        return w, keep
+
+    def forward(self, time_series, src_key_padding_mask=None):
+        """x (B,T,F) -> memory (B,T,flow_dim)."""
+        T = time_series.shape[1] if time_series.dim() == 3 else 0
+        B = time_series.shape[0] if time_series.dim() == 3 else 0
+        if self._route_of(time_series, T, src_key_padding_mask is not None, B) == "torch":
+            return self._forward_torch(time_series, src_key_padding_mask)
+        self._gpu("TimeSeriesEncoder.forward", time_series)
+        x = L.as_f32(time_series)
+        dev = x.device
+        with torch.cuda.device(dev):
+            h = self._handle(dev)
+            ws = self._workspace(h, B, T, dev)
+            memory = torch.empty(B, T, L.TSAE_D_MODEL, dtype=torch.float32, device=dev)
+            L.check(L.lib().t2s_tsae_encode(h.ptr, x.data_ptr(), memory.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
+                                            L.stream_ptr(dev)), "t2s_tsae_encode")
+        return memory
+
+    def _forward_torch(self, time_series, src_key_padding_mask=None):
+        """The same forward as torch ops on the same parameters (autograd, dropout in training mode, masks)."""
+        e = self.embedding_ln(self.embedding_dropout(self.value_embedding(time_series)))
+        return self.transformer_encoder(self.positional_encoding(e), src_key_padding_mask=src_key_padding_mask)
+
+
+class TimeSeriesDecoder(_Side):
+    def __init__(self, n_features, num_layers=6, d_ff=2048, num_heads=8, dropout=0.1, max_seq_len=2000, flow_dim=128):
+        super().__init__()
+        self.max_seq_len, self.flow_dim, self.n_features = max_seq_len, flow_dim, n_features
+        self.positional_encoding = PositionalEncoding(d_model=flow_dim, max_len=max_seq_len, dropout=dropout)
+        layer = nn.TransformerDecoderLayer(d_model=flow_dim, nhead=num_heads, dim_feedforward=d_ff, dropout=dropout,
+                                           batch_first=True, norm_first=True)
+        self.transformer_decoder = nn.TransformerDecoder(layer, num_layers=num_layers)
+        self.output_projection = nn.Linear(flow_dim, n_features)
+        self.input_projection = nn.Linear(n_features, flow_dim)
+        nn.init.xavier_uniform_(self.input_projection.weight)
+
+    def _layers(self):
+        return self.transformer_decoder.layers
+
+    def _weights_struct(self):
+        F_, d, dff, heads, n = self._shape()
+        w, keep = L.TsaeWeights(), []
+        w.n_features, w.d_model, w.d_ff, w.heads, w.n_enc, w.n_dec = F_, d, dff, heads, 0, n
+        _fill(w, [("input_projection_w", self.input_projection.weight), ("input_projection_b", self.input_projection.bias),
+                  ("output_projection_w", self.output_projection.weight), ("output_projection_b", self.output_projection.bias)],
+              keep)
+        for i, layer in enumerate(self._layers()):
+            _attn_ptrs(w.dec[i].self_attn, layer.self_attn, keep)
+            _attn_ptrs(w.dec[i].multihead_attn, layer.multihead_attn, keep)
+            _layer_ptrs(w.dec[i], layer, ("norm1", "norm2", "norm3"), keep)
+        return w, keep
+
+    def _generate_causal_mask(self, size, device):
+        return torch.triu(torch.ones(size, size, device=device), diagonal=1).bool()
+
+    def _memory_ok(self, memory, T):
+        return memory.dim() == 3 and memory.shape[1] == T and memory.shape[2] == L.TSAE_D_MODEL
+
+    def forward(self, memory, target_seq, tgt_key_padding_mask=None):
+        """Teacher forcing: memory (B,T,flow_dim), target (B,T,F) -> prediction (B,T,F)."""
+        B, T = (target_seq.shape[0], target_seq.shape[1]) if target_seq.dim() == 3 else (0, 0)
+        route = self._route_of(target_seq, T, tgt_key_padding_mask is not None, B)
+        if route == "hip" and (memory.requires_grad and torch.is_grad_enabled() or not self._memory_ok(memory, T)
+                               or memory.shape[0] != B):
+            route = "torch"
+        if route == "torch":
+            return self._forward_torch(memory, target_seq, tgt_key_padding_mask)
+        self._gpu("TimeSeriesDecoder.forward", memory, target_seq)
+        mem, tgt = L.as_f32(memory), L.as_f32(target_seq)
+        dev = tgt.device
+        with torch.cuda.device(dev):
+            h = self._handle(dev)
+            ws = self._workspace(h, B, T, dev)
+            pred = torch.empty(B, T, int(self.n_features), dtype=torch.float32, device=dev)
+            L.check(L.lib().t2s_tsae_decode(h.ptr, mem.data_ptr(), tgt.data_ptr(), pred.data_ptr(), B, T, ws.data_ptr(),
+                                            ws.numel(), L.stream_ptr(dev)), "t2s_tsae_decode")
+        return pred
+
+    def _forward_torch(self, memory, target_seq, tgt_key_padding_mask=None):
+        B, T, _ = target_seq.shape
+        emb = self.input_projection(target_seq)
+        bos = torch.zeros(B, 1, self.flow_dim, device=target_seq.device, dtype=emb.dtype)
+        tgt = self.positional_encoding(torch.cat([bos, emb[:, :-1, :]], dim=1))
+        out = self.transformer_decoder(tgt, memory, tgt_mask=self._generate_causal_mask(T, target_seq.device),
+                                       tgt_key_padding_mask=tgt_key_padding_mask)
+        return self.output_projection(out)
+
+    def generate(self, memory):
+        """Autoregressive generation: memory (B,S,flow_dim) -> series (B,S,F)."""
+        B, S = (memory.shape[0], memory.shape[1]) if memory.dim() == 3 else (0, 0)
+        if self._route_of(memory, S, False, B) == "torch" or not self._memory_ok(memory, S):
+            return self._generate_torch(memory)
+        self._gpu("TimeSeriesDecoder.generate", memory)
+        mem = L.as_f32(memory)
+        dev = mem.device
+        with torch.cuda.device(dev):
+            h = self._handle(dev)
+            ws = self._workspace(h, B, S, dev)
+            series = torch.empty(B, S, int(self.n_features), dtype=torch.float32, device=dev)
+            L.check(L.lib().t2s_tsae_generate(h.ptr, mem.data_ptr(), series.data_ptr(), B, S, ws.data_ptr(), ws.numel(),
+                                              L.stream_ptr(dev)), "t2s_tsae_generate")
+        return series
+
+    def _generate_torch(self, memory):
+        """The same generation as torch ops: the whole stack over the growing prefix at every step (no cache)."""
+        B, S = memory.size(0), memory.size(1)
+        dec_in = torch.zeros(B, 1, self.flow_dim, device=memory.device, dtype=memory.dtype)
+        steps = []
+        for _ in range(S):
+            mask = self._generate_causal_mask(dec_in.size(1), memory.device)
+            out = self.transformer_decoder(self.positional_encoding(dec_in), memory, tgt_mask=mask)
+            pred = self.output_projection(out[:, -1:, :])
+            steps.append(pred)
+            dec_in = torch.cat([dec_in, self.input_projection(pred)], dim=1)
+        return torch.cat(steps, dim=1)
+
+
+class AttentionSeq2SeqAutoencoder(BaseModel):
+    def __init__(self, args):
+        super().__init__()
+        self.n_features, self.flow_dim = args.input_dim, args.flow_dim
+        self.encoder = TimeSeriesEncoder(n_features=args.input_dim, flow_dim=args.flow_dim, num_layers=args.num_encoder_layers,
+                                         d_ff=args.d_ff, num_heads=args.num_heads)
+        self.condition_fusion = ConditionFusionModule(flow_dim=args.flow_dim)
+        self.decoder = TimeSeriesDecoder(n_features=args.input_dim, flow_dim=args.flow_dim, num_layers=args.num_decoder_layers,
+                                         d_ff=args.d_ff, num_heads=args.num_heads)
+
+    def forward(self, time_series, text_embedding, src_key_padding_mask=None, tgt_key_padding_mask=None):
+        """Encoder, text fusion, teacher-forced decoder.  The fusion block is torch ops, so the whole path is."""
+        x = self.encoder._forward_torch(time_series, src_key_padding_mask)
+        x = self.condition_fusion(x, text_embedding)
+        return self.decoder._forward_torch(x, time_series, tgt_key_padding_mask)
+
+    def forward_inference(self, time_series, text_embedding, target_length=None, src_key_padding_mask=None):
+        """Encoder, then autoregressive generation at the input's length (the text and target_length are not used)."""
+        return self.decoder.generate(memory=self.encoder(time_series, src_key_padding_mask=src_key_padding_mask))
+
+    def shared_eval(self, batch, text_embedding, optimizer, mode):  # pyright: ignore[reportIncompatibleMethodOverride]
+        """'train': one teacher-forced optimisation step (torch ops under autograd); 'val' / 'test': eval mode, no_grad,
+        encode + generate on the HIP entries.  Returns (loss, reconstruction)."""
+        if mode == "train":
+            optimizer.zero_grad()
+            recon = self.decoder(memory=self.encoder(batch), target_seq=batch)
+            loss = F.mse_loss(recon, batch)
+            loss.backward()
+            optimizer.step()
+        elif mode in ("val", "test"):
+            self.eval()
+            with torch.no_grad():
+                recon = self.forward_inference(batch, text_embedding)
+                loss = F.mse_loss(recon, batch)
+        else:
+            raise L.T2SError(f"shared_eval: mode must be 'train', 'val' or 'test' (got {mode!r})")
+        return loss, recon
+
+
+for _cls in (PositionalEncoding, AdaLN, TimeSeriesEncoder, AdaptiveLinear, ConditionFusionModule, TimeSeriesDecoder,
+             AttentionSeq2SeqAutoencoder):
+    _cls.__module__ = "model.pretrained.TSae"

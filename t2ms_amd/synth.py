@@ -224,3 +224,99 @@ def make_ts2vec_state_dict(seed: int = 2025, input_dims: int = 1, output_dims: i
         if ci != co or i == len(chans) - 1:
             sd[p + "projector.weight"], sd[p + "projector.bias"] = w(co, ci, 1), b(co)
     return sd
+
+
+def _sinusoid_table(max_len: int = 2000, d_model: int = 64) -> torch.Tensor:
+    """The (1, max_len, d_model) `pe` buffer of TSae.py's PositionalEncoding, formed in fp32 as the reference forms it."""
+    position = torch.arange(0, max_len, dtype=torch.float).unsqueeze(1)
+    div_term = torch.exp(torch.arange(0, d_model, 2, dtype=torch.float) * -(math.log(10000.0) / d_model))
+    pe = torch.zeros(max_len, d_model)
+    pe[:, 0::2] = torch.sin(position * div_term)
+    pe[:, 1::2] = torch.cos(position * div_term)
+    return pe.unsqueeze(0)
+
+
+def make_tsae_state_dict(seed: int = 2025, n_features: int = 10, d_ff: int = 128, n_enc: int = 3, n_dec: int = 3, heads: int = 8,
+                         d_model: int = 64, fusion: bool = False) -> Dict[str, torch.Tensor]:
+    """State dict of the reference's model/pretrained/TSae.py AttentionSeq2SeqAutoencoder (defaults: the bench-press `vae:`
+    block) at the reference's initialisation scale: xavier-uniform where the reference calls it (value_embedding,
+    input_projection, the attention in-projections), torch's default U(+-1/sqrt(fan_in)) for every other Linear.  Where the
+    reference starts from exact zeros / ones (attention and embedding biases, LayerNorm) the draw is 0.02 N(0,1) / 1 + 0.1 N(0,1),
+    so no term of the forward is vacuous; every layer gets its own draw.  `heads` does not change a shape.  The two `pe` buffers
+    are included; `fusion=True` adds the condition_fusion.* tensors (one of them (64, 393216)) the live paths never read."""
+    rs = np.random.RandomState(seed + 5)
+    sd: Dict[str, np.ndarray] = {}
+    assert d_model % heads == 0
+
+    def small(n):
+        return (0.02 * rs.randn(n)).astype(np.float32)
+
+    def default_linear(name, out_f, in_f):
+        a = 1.0 / math.sqrt(in_f)
+        sd[name + ".weight"] = rs.uniform(-a, a, size=(out_f, in_f)).astype(np.float32)
+        sd[name + ".bias"] = rs.uniform(-a, a, size=(out_f,)).astype(np.float32)
+
+    def norm(name, d=d_model):
+        sd[name + ".weight"] = (1.0 + 0.1 * rs.randn(d)).astype(np.float32)
+        sd[name + ".bias"] = (0.1 * rs.randn(d)).astype(np.float32)
+
+    def attention(name):
+        sd[name + ".in_proj_weight"] = _xavier(rs, 3 * d_model, d_model)
+        sd[name + ".in_proj_bias"] = small(3 * d_model)
+        a = 1.0 / math.sqrt(d_model)
+        sd[name + ".out_proj.weight"] = rs.uniform(-a, a, size=(d_model, d_model)).astype(np.float32)
+        sd[name + ".out_proj.bias"] = small(d_model)
+
+    sd["encoder.value_embedding.weight"] = _xavier(rs, d_model, n_features)
+    sd["encoder.value_embedding.bias"] = small(d_model)
+    norm("encoder.embedding_ln")
+    for i in range(n_enc):
+        p = f"encoder.transformer_encoder.layers.{i}."
+        attention(p + "self_attn")
+        default_linear(p + "linear1", d_ff, d_model)
+        default_linear(p + "linear2", d_model, d_ff)
+        norm(p + "norm1")
+        norm(p + "norm2")
+    for i in range(n_dec):
+        p = f"decoder.transformer_decoder.layers.{i}."
+        attention(p + "self_attn")
+        attention(p + "multihead_attn")
+        default_linear(p + "linear1", d_ff, d_model)
+        default_linear(p + "linear2", d_model, d_ff)
+        for n in ("norm1", "norm2", "norm3"):
+            norm(p + n)
+    default_linear("decoder.output_projection", n_features, d_model)
+    default_linear("decoder.input_projection", d_model, n_features)
+    sd["decoder.input_projection.weight"] = _xavier(rs, d_model, n_features)
+    out = {k: torch.from_numpy(v) for k, v in sd.items()}
+    out["encoder.positional_encoding.pe"] = _sinusoid_table(2000, d_model)
+    out["decoder.positional_encoding.pe"] = _sinusoid_table(2000, d_model)
+    if fusion:
+        g = torch.Generator().manual_seed(seed + 6)
+        max_in = 512 * 768
+        a = math.sqrt(6.0 / (d_model + max_in))
+        out["condition_fusion.text_projection.weight"] = torch.empty(d_model, max_in).uniform_(-a, a, generator=g)
+        out["condition_fusion.text_projection.bias"] = torch.zeros(d_model)
+        fs: Dict[str, np.ndarray] = {}
+
+        def xav(name, out_f, in_f):
+            fs[name + ".weight"] = _xavier(rs, out_f, in_f)
+            fs[name + ".bias"] = np.zeros(out_f, np.float32)
+
+        xav("condition_fusion.condition_projection", d_model, d_model)
+        xav("condition_fusion.fusion.0", 4 * d_model, 2 * d_model)
+        xav("condition_fusion.fusion.3", d_model, 4 * d_model)
+        for n in ("condition_fusion.fusion_ln", "condition_fusion.ada_ln.ln"):
+            fs[n + ".weight"], fs[n + ".bias"] = np.ones(d_model, np.float32), np.zeros(d_model, np.float32)
+        for n, o, i in (("condition_fusion.ada_ln.mlp.0", 4 * d_model, d_model), ("condition_fusion.ada_ln.mlp.2", 2 * d_model, 4 * d_model)):
+            a = 1.0 / math.sqrt(i)
+            fs[n + ".weight"] = rs.uniform(-a, a, size=(o, i)).astype(np.float32)
+            fs[n + ".bias"] = rs.uniform(-a, a, size=(o,)).astype(np.float32)
+        out.update({k: torch.from_numpy(v) for k, v in fs.items()})
+    return out
+
+
+def make_tsae_series(seed: int, batch: int, length: int, n_features: int) -> torch.Tensor:
+    """MinMax-scaled motion series stand-in in the codec's layout: U[0,1], (batch, length, n_features)."""
+    rs = np.random.RandomState((seed + 19) % (2 ** 32))
+    return torch.from_numpy(rs.uniform(0, 1, size=(batch, length, n_features)).astype(np.float32))
