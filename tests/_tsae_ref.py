@@ -60,11 +60,16 @@ def _qkv(x, sd, name, rows):
 Q, K, V = slice(0, 64), slice(64, 128), slice(128, 192)
 
 
-def encode(sd, x, heads):
-    """x (B,T,F) -> memory (B,T,64)."""
+def _table(pe, T, dt):
+    """Rows 0..T-1 of the positional table: the caller's `pe` (at least T rows of 64), or the one formed here."""
+    return sinusoid_table(T, 64, dt) if pe is None else pe[:T].to(dt)
+
+
+def encode(sd, x, heads, pe=None):
+    """x (B,T,F) -> memory (B,T,64).  `pe`: a positional table (rows >= T, 64) to use instead of sinusoid_table."""
     dt = sd["encoder.value_embedding.weight"].dtype
     x = x.to(dt)
-    h = _ln(_lin(x, sd, "encoder.value_embedding"), sd, "encoder.embedding_ln") + sinusoid_table(x.shape[1], 64, dt)
+    h = _ln(_lin(x, sd, "encoder.value_embedding"), sd, "encoder.embedding_ln") + _table(pe, x.shape[1], dt)
     for i in range(_n_layers(sd, "encoder.transformer_encoder.layers.")):
         p = f"encoder.transformer_encoder.layers.{i}."
         n = _ln(h, sd, p + "norm1")
@@ -103,22 +108,22 @@ def _memory_kv(sd, memory):
              _qkv(memory, sd, f"decoder.transformer_decoder.layers.{i}.multihead_attn", V)) for i in range(_dec_layers(sd))]
 
 
-def decode(sd, memory, target, heads):
+def decode(sd, memory, target, heads, pe=None):
     """Teacher forcing: memory (B,T,64), target (B,T,F) -> prediction (B,T,F); all rows at once (an empty cache)."""
     dt = sd["decoder.input_projection.weight"].dtype
     memory, target = memory.to(dt), target.to(dt)
     B, T, _ = target.shape
     rows = torch.cat([torch.zeros(B, 1, 64, dtype=dt), _lin(target, sd, "decoder.input_projection")[:, :-1]], dim=1)
-    rows = rows + sinusoid_table(T, 64, dt)
+    rows = rows + _table(pe, T, dt)
     return _dec_rows(sd, rows, _memory_kv(sd, memory), [None] * _dec_layers(sd), heads)
 
 
-def generate(sd, memory, heads):
+def generate(sd, memory, heads, pe=None):
     """Autoregressive generation with a key/value cache: memory (B,S,64) -> series (B,S,F); step t computes ONE new row."""
     dt = sd["decoder.input_projection.weight"].dtype
     memory = memory.to(dt)
     B, S, _ = memory.shape
-    pe = sinusoid_table(S, 64, dt)
+    pe = _table(pe, S, dt)
     mkv, cache = _memory_kv(sd, memory), [None] * _dec_layers(sd)
     row, out = torch.zeros(B, 1, 64, dtype=dt), []
     for t in range(S):

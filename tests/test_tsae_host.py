@@ -1,6 +1,9 @@
 """TSae codec, what needs no GPU: the mirror's state-dict layout, its torch-op path and the plain-tensor restatement
 (tests/_tsae_ref.py, explicit key/value cache) against the reference's recorded outputs (tests/golden/tsae.npz), the routing
-predicate condition by condition, and the tool's command line."""
+predicate condition by condition, and the tool's command line; and the inputs of the case table (tests/_tsae_cases.py) that
+tests/test_tsae_fp64.py runs on the GPU: each case is well conditioned (the fp32 restatement within a quarter of the bar of the
+fp64 one) and, at gain 4, really stresses the softmax."""
+import functools
 import os
 import subprocess
 import sys
@@ -8,6 +11,7 @@ import sys
 import pytest
 import torch
 
+import _tsae_cases as TC
 import _tsae_fixture as FX
 import _tsae_ref as R
 from t2ms_amd import _lib as L
@@ -164,3 +168,86 @@ def test_switch_is_documented():
 def test_reconstruct_tool_help_parses():
     r = subprocess.run([sys.executable, os.path.join(REPO, "tools", "tsae_reconstruct.py"), "--help"], capture_output=True, text=True)
     assert r.returncode == 0 and "--random_init" in r.stdout and "--state_dict" in r.stdout
+
+
+# ---- the case table of tests/_tsae_cases.py ---------------------------------------------------------------------------------
+GATED = TC.TABLE + (TC.MIRROR,)
+GATED_IDS = TC.IDS + ["mirror_" + TC.case_id(TC.MIRROR)]
+
+
+@functools.lru_cache(maxsize=None)
+def _restated(c, dtype):
+    """(memory, teacher-forced prediction, generation) of the restatement in `dtype`, computed once per case."""
+    sd, x = TC.state_dict_as(c, dtype), TC.series(c)
+    memory = R.encode(sd, x, c.heads)
+    return memory, R.decode(sd, memory, x, c.heads), R.generate(sd, memory, c.heads)
+
+
+def test_table_reaches_the_kernels_branch_points():
+    """What the table is for, as data: the d_ff chunkings, layer counts, feature widths and lengths the recorded fixture lacks."""
+    t = [c for c in TC.TABLE if c.gain == 4.0]
+    assert 20 <= len(TC.TABLE) <= 25 and len(set(TC.TABLE)) == len(TC.TABLE) and max(c.gain for c in GATED) == 4.0
+    assert {64, 192, 512} <= {c.d_ff for c in t} and {320, 448} & {c.d_ff for c in t}
+    assert {(6, 6), (2, 1), (1, 2)} <= {(c.n_enc, c.n_dec) for c in t}
+    assert any((c.n_enc, c.n_dec, c.heads) == (3, 3, 4) for c in t)
+    assert any((c.n_enc, c.n_dec, c.d_ff, c.n_features) == (6, 6, 512, 16) for c in t)
+    assert {1, 5} <= {c.n_features for c in t}
+    for T in (31, 32, 33, 63, 64, 127, 128, 129, 257):
+        assert any(c.T == T and c.B in (1, 3) for c in t), T
+    assert any(c.B == 5 and c.n_dec >= 3 for c in t)
+    assert any((c.T, c.B, c.heads, c.d_ff, c.n_enc, c.n_dec) == (2000, 1, 4, 192, 2, 1) for c in t)
+    assert any((c.T, c.heads, c.n_enc, c.n_dec) == (600, 8, 1, 2) for c in t)
+    assert TC.TABLE[0] == TC.BP_GAIN1 and TC.TABLE[1] == TC.BP_GAIN1._replace(gain=4.0)
+    k = FX.golden()[1]["cfgs"]["bp"]
+    assert (k["n_features"], k["d_ff"], k["n_enc"], k["n_dec"], k["heads"], k["seed"]) == TC.BP_GAIN1[:5] + (TC.BP_GAIN1.seed,)
+    assert TC.BAR == FX.golden()[1]["bar"]
+
+
+def test_gain_one_is_the_recorded_weights():
+    """At gain 1 the builder returns the recorded configuration's state dict unchanged; a gain touches q and k rows only."""
+    a, b, g = FX.state_dict("bp"), TC.state_dict(TC.BP_GAIN1), TC.state_dict(TC.TABLE[1])
+    assert a.keys() == b.keys() and all(torch.equal(a[k], b[k]) for k in a)
+    for k in a:
+        if k.endswith(".in_proj_weight"):
+            assert torch.equal(g[k][:128], a[k][:128] * 4.0) and torch.equal(g[k][128:], a[k][128:])
+        else:
+            assert torch.equal(g[k], a[k]), k
+
+
+@pytest.mark.parametrize("c", GATED, ids=GATED_IDS)
+def test_case_is_well_conditioned(c):
+    """Conditioning gate, a condition on the INPUTS (the rule of test_fixture_is_its_own_witness): the fp32 restatement is within
+    a quarter of the bar of the fp64 one for memory, teacher-forced prediction and generation.  A case that fails is replaced
+    (seed, gain, T); the bar is not moved."""
+    for name, a, b in zip(("memory", "pred", "gen"), _restated(c, torch.float32), _restated(c, torch.float64)):
+        dev, bar = float((a.double() - b).abs().max()), TC.bar(b)
+        print(f"{TC.case_id(c)} {name}: fp32 vs fp64 {dev / bar:.3f} of the bar, max|out| {float(b.abs().max()):.3f}")
+        assert bool(torch.isfinite(b).all()) and dev <= bar / 4, (name, dev, bar)
+
+
+@pytest.mark.parametrize("c", GATED, ids=GATED_IDS)
+def test_case_stresses_the_softmax(c):
+    """Stress gate, from encoder layer 0's logits: at gain 4 the per-row logit spread has median >= 8 and, for T > 64, at least
+    a quarter of the rows see the running maximum over 64-key chunks rise by more than 1 after the first chunk (the mirror's
+    T = 65 case is exempt from the second: its last chunk holds one key).  The recorded `bp` weights at gain 1 fail both --
+    the reason the table exists."""
+    spread, rising = TC.stress(c)
+    print(f"{TC.case_id(c)}: logit spread median {spread:.2f}, rows with a rising maximum {rising:.3f}")
+    if c.gain == 1.0:
+        assert c == TC.BP_GAIN1 and spread < TC.MIN_SPREAD and rising < TC.MIN_RISING, (spread, rising)
+        return
+    assert spread >= TC.MIN_SPREAD, spread
+    if c.T > 64 and c != TC.MIRROR:
+        assert rising >= TC.MIN_RISING, rising
+
+
+@pytest.mark.parametrize("c", GATED, ids=GATED_IDS)
+def test_cached_generation_is_the_causal_pass(c):
+    """generate (explicit cache, one row a step) equals decode fed generate's output (all rows at once).  In fp64 the two differ
+    by summation order alone: 1e-9 is five orders above 2^-53 times the amplification the conditioning gate allows fp32
+    (2^-24 -> a quarter of the bar) and four below the bar.  In fp32, the bar."""
+    for dtype, bound in ((torch.float64, 1e-9), (torch.float32, None)):
+        memory, _, gen = _restated(c, dtype)
+        again = R.decode(TC.state_dict_as(c, dtype), memory, gen, c.heads)
+        err = float((again - gen).abs().max())
+        assert err <= (TC.bar(gen) if bound is None else bound), (dtype, err)
