@@ -193,26 +193,38 @@ using BfPlanes = t2s_dit::BfPlanes;
 
 namespace {
 
-struct ArenaPlan {
-    size_t off = 0;
-    size_t take(size_t n) {
-        size_t o = off;
-        off += (n + 63) & ~size_t(63);
-        return o;
+// The layouts of the handle's device memory, each written once: `take(slot, n)` per piece, in order.  A Carver (t2s_arena.h)
+// measures and binds the pieces of an arena with them; create and destroy walk the workspace list with hipMalloc / hipFree.
+template <class Take>
+void carve_params(t2s_dit* h, Take&& take) {
+    take(h->conv_w, 16); take(h->conv_b, 4); take(h->patch_w, 512); take(h->patch_b, 128); take(h->pos, (size_t)h->ntok() * D);
+    take(h->ln_w, D); take(h->ln_b, D); take(h->out_w, 4 * D); take(h->out_b, 4); take(h->freqs, 64);
+    take(h->ada_b, MODROW); take(h->ada_p, (size_t)MODROW * D);
+    for (int i = 0; i < NBLK; ++i) {
+        for (int j = 0; j < NMAT; ++j) take(h->bias[i][j], MAT_N[j]);
+        for (int j = 0; j < NMAT; ++j) take(h->p32[i][j], mat_elems(j));
+        for (int j = 0; j < NMAT; ++j) take(h->p16[i][j], mat_elems(j));
     }
-};
+}
+template <class Take>
+void carve_bf_weights(BfPlanes& pl, Take&& take) {
+    for (int i = 0; i < NBLK; ++i)
+        for (int j = 0; j < NMAT; ++j) take(pl.m[i][j], mat_elems(j) * pl.np);
+}
+template <class Take>
+void workspace_bufs(t2s_dit* h, Take&& take) {   // every size follows the handle's token count
+    const size_t S = (size_t)h->max_seqs, tokD = S * h->ntok() * D;
+    take(h->h, tokD); take(h->q, tokD); take(h->k, tokD); take(h->v, tokD); take(h->ao, tokD);
+    take(h->mod, S * MODROW); take(h->h0, (S / 2 + 1) * h->ntok() * D);
+}
 
 // the planes of the row-chain weights from the handle's packed fp32 copies (bf16x3: the three-way split, bf16: its h plane)
 int pack_bf_weights(const t2s_dit* h, const BfPlanes& pl, hipStream_t st) {
-    auto pack = [&](const f32x4* P, __bf16* dst, int N, int K, int fc2) {
-        return pack_rows_xn(pl.np, reinterpret_cast<const float*>(P), reinterpret_cast<bf16x8*>(dst), N, K, fc2, st);
-    };
-    int rc;
-    for (int i = 0; i < NBLK; ++i) {
-        if ((rc = pack(h->qkv_p[i], pl.qkv[i], 3 * D, D, 0)) || (rc = pack(h->proj_p[i], pl.proj[i], D, D, 0)) ||
-            (rc = pack(h->fc1_p[i], pl.fc1[i], 2 * D, D, 0)) || (rc = pack(h->fc2_c[i], pl.fc2c[i], D, 2 * D, 1)))
-            return rc;
-    }
+    for (int i = 0; i < NBLK; ++i)
+        for (int j = 0; j < NMAT; ++j)
+            if (int rc = pack_rows_xn(pl.np, reinterpret_cast<const float*>(h->p32[i][j]), reinterpret_cast<bf16x8*>(pl.m[i][j]),
+                                      MAT_N[j], MAT_K[j], j == FC2, st))
+                return rc;
     return T2S_OK;
 }
 
@@ -282,20 +294,12 @@ int upload_weights(t2s_dit* h, const t2s_dit_weights* w, hipStream_t st) {
     cp(h->freqs, w->time_freqs, 64);
     for (int i = 0; i < NBLK; ++i) {
         const t2s_dit_block_weights& b = w->blk[i];
-        cp(h->qkv_b[i], b.qkv_b, 3 * D);
-        cp(h->proj_b[i], b.proj_b, D);
-        cp(h->fc1_b[i], b.fc1_b, 2 * D);
-        cp(h->fc2_b[i], b.fc2_b, D);
+        for (int j = 0; j < NMAT; ++j) cp(h->bias[i][j], mat_b(b, j), MAT_N[j]);
         cp(h->ada_b + i * MODW, b.ada_b, MODW);
-        pk(b.qkv_w, h->qkv_p[i], 3 * D, D, 0, 0);
-        pk(b.proj_w, h->proj_p[i], D, D, 0, 0);
-        pk(b.fc1_w, h->fc1_p[i], 2 * D, D, 0, 0);
-        pk(b.fc2_w, h->fc2_c[i], D, 2 * D, 0, 1);
+        // (the last argument is pack_weight_elem's mode: fc2 goes in chunk order)
+        for (int j = 0; j < NMAT; ++j) pk(mat_w(b, j), h->p32[i][j], MAT_N[j], MAT_K[j], 0, j == FC2 ? 1 : 0);
         pk(b.ada_w, h->ada_p, MODW, D, i * MODW, 0);
-        pk(b.qkv_w, h->qkv_p16[i], 3 * D, D, 0, 2);
-        pk(b.proj_w, h->proj_p16[i], D, D, 0, 2);
-        pk(b.fc1_w, h->fc1_p16[i], 2 * D, D, 0, 2);
-        pk(b.fc2_w, h->fc2_c16[i], D, 2 * D, 0, 3);
+        for (int j = 0; j < NMAT; ++j) pk(mat_w(b, j), h->p16[i][j], MAT_N[j], MAT_K[j], 0, j == FC2 ? 3 : 2);
     }
     static_assert(10 + 5 * NBLK <= MULTI_JOBS && 9 * NBLK <= MULTI_JOBS, "job tables too small");
     copy_multi_kernel<<<dim3(16, nc), 256, 0, st>>>(ct);
@@ -382,30 +386,30 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
             a.f_lnw = h->ln_w; a.f_lnb = h->ln_b; a.f_ow = h->out_w; a.f_ob = h->out_b;
             a.out0 = out0; a.out1 = out1; a.split = split; a.keep_x = keep_stream;
         }
-        if (blk >= 0) { a.bp = h->proj_b[blk]; a.b1 = h->fc1_b[blk]; a.b2 = h->fc2_b[blk]; }
-        if (qkv_blk >= 0) a.bq = h->qkv_b[qkv_blk];
+        if (blk >= 0) { a.bp = h->bias[blk][PROJ]; a.b1 = h->bias[blk][FC1]; a.b2 = h->bias[blk][FC2]; }
+        if (qkv_blk >= 0) a.bq = h->bias[qkv_blk][QKV];
         a.q = w_q;
+    };
+    auto set_mats = [](auto& a, const auto* set, int blk, int qkv_blk) {   // the launch's matrices from one set of the handle
+        using W = decltype(a.Wp);
+        if (blk >= 0) { a.Wp = reinterpret_cast<W>(set[blk][PROJ]); a.W1 = reinterpret_cast<W>(set[blk][FC1]); a.W2c = reinterpret_cast<W>(set[blk][FC2]); }
+        if (qkv_blk >= 0) a.Wq = reinterpret_cast<W>(set[qkv_blk][QKV]);
     };
     auto launch_rows = [&](auto do_mlp, auto do_qkv, int blk, int qkv_blk) {   // (std::bool_constant: the kernel instance)
         constexpr bool DO_MLP = decltype(do_mlp)::value, DO_QKV = decltype(do_qkv)::value;
         if (pl) {
-            auto w8 = [](const __bf16* p) { return reinterpret_cast<const bf16x8*>(p); };
             RowArgsX3 a{};
             fill_shared(a, blk, qkv_blk);
-            if (blk >= 0) { a.Wp = w8(pl->proj[blk]); a.W1 = w8(pl->fc1[blk]); a.W2c = w8(pl->fc2c[blk]); }
-            if (qkv_blk >= 0) a.Wq = w8(pl->qkv[qkv_blk]);
+            set_mats(a, pl->m, blk, qkv_blk);
             a.k3 = w_kp; a.v3 = w_vp;
             return launch_dit_rows_xn<DO_MLP, DO_QKV>(pl->np, a, st);
         }
         RowArgs a{};
         fill_shared(a, blk, qkv_blk);
-        if (blk >= 0) { a.Wp = h->proj_p[blk]; a.W1 = h->fc1_p[blk]; a.W2c = h->fc2_c[blk]; }
-        if (qkv_blk >= 0) a.Wq = h->qkv_p[qkv_blk];
+        set_mats(a, use16 ? h->p16 : h->p32, blk, qkv_blk);
         a.k = w_k; a.v = w_v;
         a.tps = ntok == NTOK ? 0 : ntok / 32;   // wide handle: the kernels that take the tiles per sequence at run time
         if (!use16) return launch_dit_rows<DO_MLP, DO_QKV>(a, st);
-        if (blk >= 0) { a.Wp = h->proj_p16[blk]; a.W1 = h->fc1_p16[blk]; a.W2c = h->fc2_c16[blk]; }
-        if (qkv_blk >= 0) a.Wq = h->qkv_p16[qkv_blk];
         return launch_dit_rows16<DO_MLP, DO_QKV>(a, st);
     };
     auto launch_attention = [&] {
@@ -483,57 +487,23 @@ int t2s_dit_create_w(const t2s_dit_weights* w, int latent_w, int max_seqs, t2s_d
     t2s_dit* h = new t2s_dit();
     h->max_seqs = max_seqs;
     h->latw = latent_w;
-    const int ntok = h->ntok();   // every size below follows the handle's token count
-    ArenaPlan p;
-    const size_t o_conv_w = p.take(16), o_conv_b = p.take(4), o_patch_w = p.take(512),
-                 o_patch_b = p.take(128), o_pos = p.take((size_t)ntok * D), o_ln_w = p.take(D),
-                 o_ln_b = p.take(D), o_out_w = p.take(4 * D), o_out_b = p.take(4),
-                 o_freqs = p.take(64), o_ada_b = p.take(MODROW), o_ada_p = p.take((size_t)MODROW * D);
-    size_t o_qkv_b[NBLK], o_proj_b[NBLK], o_fc1_b[NBLK], o_fc2_b[NBLK];
-    size_t o_qkv_p[NBLK], o_proj_p[NBLK], o_fc1_p[NBLK], o_fc2_c[NBLK];
-    size_t o_qkv_p16[NBLK], o_proj_p16[NBLK], o_fc1_p16[NBLK], o_fc2_c16[NBLK];
-    for (int i = 0; i < NBLK; ++i) {
-        o_qkv_b[i] = p.take(3 * D); o_proj_b[i] = p.take(D); o_fc1_b[i] = p.take(2 * D);
-        o_fc2_b[i] = p.take(D);
-        o_qkv_p[i] = p.take(3 * D * D); o_proj_p[i] = p.take(D * D);
-        o_fc1_p[i] = p.take(2 * D * D); o_fc2_c[i] = p.take(2 * D * D);
-        o_qkv_p16[i] = p.take(3 * D * D); o_proj_p16[i] = p.take(D * D);
-        o_fc1_p16[i] = p.take(2 * D * D); o_fc2_c16[i] = p.take(2 * D * D);
-    }
-    hipError_t e = hipMalloc(&h->arena, p.off * sizeof(float));
+    hipError_t e = carve_alloc(h->arena, [&](auto& take) { carve_params(h, take); });
     if (e != hipSuccess) {
         set_error("t2s_dit_create: hipMalloc(params) failed: %s", hipGetErrorString(e));
         delete h;
         return T2S_E_HIP;
     }
-    float* A = h->arena;
-    h->conv_w = A + o_conv_w; h->conv_b = A + o_conv_b; h->patch_w = A + o_patch_w;
-    h->patch_b = A + o_patch_b; h->pos = A + o_pos; h->ln_w = A + o_ln_w; h->ln_b = A + o_ln_b;
-    h->out_w = A + o_out_w; h->out_b = A + o_out_b; h->freqs = A + o_freqs; h->ada_b = A + o_ada_b;
-    h->ada_p = reinterpret_cast<f32x4*>(A + o_ada_p);
-    for (int i = 0; i < NBLK; ++i) {
-        h->qkv_b[i] = A + o_qkv_b[i]; h->proj_b[i] = A + o_proj_b[i];
-        h->fc1_b[i] = A + o_fc1_b[i]; h->fc2_b[i] = A + o_fc2_b[i];
-        h->qkv_p[i] = reinterpret_cast<f32x4*>(A + o_qkv_p[i]);
-        h->proj_p[i] = reinterpret_cast<f32x4*>(A + o_proj_p[i]);
-        h->fc1_p[i] = reinterpret_cast<f32x4*>(A + o_fc1_p[i]);
-        h->fc2_c[i] = reinterpret_cast<f32x4*>(A + o_fc2_c[i]);
-        h->qkv_p16[i] = reinterpret_cast<f32x4*>(A + o_qkv_p16[i]);
-        h->proj_p16[i] = reinterpret_cast<f32x4*>(A + o_proj_p16[i]);
-        h->fc1_p16[i] = reinterpret_cast<f32x4*>(A + o_fc1_p16[i]);
-        h->fc2_c16[i] = reinterpret_cast<f32x4*>(A + o_fc2_c16[i]);
-    }
-    const size_t S = (size_t)max_seqs, tokD = S * ntok * D;
-    float** bufs[] = {&h->h, &h->q, &h->k, &h->v, &h->ao, &h->mod, &h->h0};
-    const size_t sizes[] = {tokD, tokD, tokD, tokD, tokD, S * MODROW, (S / 2 + 1) * ntok * D};
-    for (int i = 0; i < 7; ++i) {
-        e = hipMalloc(bufs[i], sizes[i] * sizeof(float));
-        if (e != hipSuccess) {
-            set_error("t2s_dit_create: hipMalloc(workspace %d, %zu B) failed: %s", i,
-                      sizes[i] * sizeof(float), hipGetErrorString(e));
-            t2s_dit_destroy(h);
-            return T2S_E_HIP;
-        }
+    int n_bufs = 0;
+    workspace_bufs(h, [&](float*& buf, size_t n) {
+        if (e != hipSuccess) return;
+        buf = nullptr;
+        if ((e = hipMalloc(&buf, n * sizeof(float))) != hipSuccess)
+            set_error("t2s_dit_create: hipMalloc(workspace %d, %zu B) failed: %s", n_bufs, n * sizeof(float), hipGetErrorString(e));
+        ++n_bufs;
+    });
+    if (e != hipSuccess) {
+        t2s_dit_destroy(h);
+        return T2S_E_HIP;
     }
     int rc = attn_init();
     if (rc == T2S_OK) rc = dit_rows_init();
@@ -578,18 +548,11 @@ int alloc_bf_planes(t2s_dit* h, BfPlanes& out) {
     BfPlanes pl = out;
     if ((rc = attn_xn_init(pl.np)) || (rc = dit_rows_xn_init(pl.np))) return rc;
     const size_t bytes = (size_t)h->max_seqs * NTOK * D * pl.np * sizeof(__bf16);
-    const size_t wvals = (size_t)NBLK * (3 + 1 + 2 + 2) * D * D * pl.np;          // qkv, proj, fc1, fc2
-    if (hipMalloc(&pl.k, bytes) != hipSuccess || hipMalloc(&pl.v, bytes) != hipSuccess || hipMalloc(&pl.w, wvals * sizeof(__bf16)) != hipSuccess) {
+    if (hipMalloc(&pl.k, bytes) != hipSuccess || hipMalloc(&pl.v, bytes) != hipSuccess ||
+        carve_alloc(pl.w, [&](auto& take) { carve_bf_weights(pl, take); }) != hipSuccess) {
         rc = T2S_E_HIP;
         set_error("t2s_dit_set_math: hipMalloc(2 x %zu B + weights) failed", bytes);
     } else {
-        __bf16* p = pl.w;
-        for (int i = 0; i < NBLK; ++i) {
-            pl.qkv[i] = p; p += (size_t)3 * D * D * pl.np;
-            pl.proj[i] = p; p += (size_t)D * D * pl.np;
-            pl.fc1[i] = p; p += (size_t)2 * D * D * pl.np;
-            pl.fc2c[i] = p; p += (size_t)2 * D * D * pl.np;
-        }
         const hipError_t e = h->w_ev ? hipStreamWaitEvent(setup, h->w_ev, 0) : hipSuccess;   // the last t2s_dit_update_weights
         rc = e == hipSuccess ? pack_bf_weights(h, pl, setup) : T2S_E_HIP;
         if (rc == T2S_OK && hipStreamSynchronize(setup) != hipSuccess) rc = T2S_E_HIP;
@@ -624,9 +587,10 @@ void t2s_dit_destroy(t2s_dit* h) {
     for (const BfPlanes& pl : h->bf)
         for (__bf16* b : {pl.k, pl.v, pl.w})
             if (b) (void)hipFree(b);
-    float* bufs[] = {h->arena, h->h, h->q, h->k, h->v, h->ao, h->mod, h->h0};
-    for (float* b : bufs)
-        if (b) (void)hipFree(b);
+    if (h->arena) (void)hipFree(h->arena);
+    workspace_bufs(h, [](float*& buf, size_t) {
+        if (buf) (void)hipFree(buf);
+    });
     delete h;
 }
 

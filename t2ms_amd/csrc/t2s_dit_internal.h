@@ -4,6 +4,7 @@
 #include <mutex>
 #include <vector>
 
+#include "t2s_arena.h"
 #include "t2s_common.h"
 
 struct t2s_train_ws;   // training workspace (t2s_train.hip), created on first use
@@ -14,13 +15,13 @@ struct t2s_dit {
     int ntok() const { return 16 * latw; }
     int lat() const { return t2s::LATC * latw; }
     // parameters (device)
-    float* arena = nullptr;  // all parameters, offsets below
-    float *conv_w, *conv_b, *patch_w, *patch_b, *pos, *ln_w, *ln_b, *out_w, *out_b, *freqs;
-    float *qkv_b[t2s::NBLK], *proj_b[t2s::NBLK], *fc1_b[t2s::NBLK], *fc2_b[t2s::NBLK], *ada_b;
-    t2s::f32x4 *qkv_p[t2s::NBLK], *proj_p[t2s::NBLK], *fc1_p[t2s::NBLK], *fc2_c[t2s::NBLK], *ada_p;
-    // the same row-chain weights in the 16-token kernel's fragment order (t2s_rows16.h; small launches)
-    t2s::f32x4 *qkv_p16[t2s::NBLK], *proj_p16[t2s::NBLK], *fc1_p16[t2s::NBLK], *fc2_c16[t2s::NBLK];
-    // workspace (device), activations fragment-major
+    float* arena = nullptr;  // all parameters, laid out by carve_params (t2s_dit.hip)
+    float *conv_w, *conv_b, *patch_w, *patch_b, *pos, *ln_w, *ln_b, *out_w, *out_b, *freqs, *ada_b;
+    t2s::f32x4* ada_p;
+    t2s::BlockMats<float*> bias[t2s::NBLK];
+    t2s::BlockMats<t2s::f32x4*> p32[t2s::NBLK];   // the row-chain weights in fragment order, fc2 in chunk order (t2s_rows.h)
+    t2s::BlockMats<t2s::f32x4*> p16[t2s::NBLK];   // the same in the 16-token kernel's fragment order (t2s_rows16.h; small launches)
+    // workspace (device), activations fragment-major; one allocation each, listed by workspace_bufs (t2s_dit.hip)
     float *h = nullptr, *q = nullptr, *k = nullptr, *v = nullptr, *ao = nullptr;
     float* h0 = nullptr;         // patchified tokens of the B distinct sequences of a CFG pass (both branches share them)
     float* mod = nullptr;        // (S, MODROW) adaLN modulation of all blocks (adaln_kernel)
@@ -32,13 +33,13 @@ struct t2s_dit {
     struct BfPlanes {
         int np;
         __bf16 *k = nullptr, *v = nullptr, *w = nullptr;
-        __bf16 *qkv[t2s::NBLK], *proj[t2s::NBLK], *fc1[t2s::NBLK], *fc2c[t2s::NBLK];   // pieces of w
+        t2s::BlockMats<__bf16*> m[t2s::NBLK];   // pieces of w (fc2 in chunk order)
     };
     BfPlanes bf[2] = {{3}, {1}};   // [math - T2S_MATH_BF16X3]
     hipEvent_t w_ev = nullptr;   // recorded behind the last t2s_dit_update_weights (what a first-use pack must wait for)
-    // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     t2s_train_ws* train = nullptr;
     int train_dtype = 0;         // T2S_TRAIN_F32 / T2S_TRAIN_BF16 (t2s_dit_set_train_dtype)
+    // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;
     std::vector<int> ev_class;   // class of interval i = [ev_pool[2i], ev_pool[2i+1]]
@@ -62,6 +63,19 @@ struct TimeScope {   // records an event pair around the launches issued in its 
     }
     ~TimeScope() { if (on) (void)hipEventRecord(h->ev_pool.back(), st); }
 };
+// One launch as one timed interval of class `cls`, in a function that returns a t2s code: T2S_TIMED takes a call that returns
+// such a code, T2S_TIMED_LAUNCH a kernel<<<...>>>(...) statement.  A failure returns from the enclosing function.
+#define T2S_TIMED(h, cls, st, ...)                                                             \
+    do {                                                                                       \
+        ::t2s::TimeScope _ts(h, cls, st);                                                      \
+        if (const int _rc = (__VA_ARGS__)) return _rc;                                         \
+    } while (0)
+#define T2S_TIMED_LAUNCH(h, cls, st, ...)                                                      \
+    do {                                                                                       \
+        ::t2s::TimeScope _ts(h, cls, st);                                                      \
+        __VA_ARGS__;                                                                           \
+        T2S_LAUNCH_CHECK();                                                                    \
+    } while (0)
 
 // t2s_attn.hip
 int attn_init();

@@ -37,39 +37,37 @@ struct t2s_train_ws {
     int cap_seqs = 0;
     int dtype = 0;        // T2S_TRAIN_F32 / T2S_TRAIN_BF16 this workspace was laid out for
     int S = 0;            // sequences of the last forward
-    bool has_text = false;
-    // packed weights for training (tile-major, both orientations), refreshed by pack_train_weights
-    float* warena = nullptr;
-    f32x4 *qkv_f[NBLK], *proj_f[NBLK], *fc1_f[NBLK], *fc2_f[NBLK];   // forward:  W   (N,K)
-    f32x4 *qkv_t[NBLK], *proj_t[NBLK], *fc1_t[NBLK], *fc2_t[NBLK];   // dgrad:    W^T (K,N)
-    f32x4* out_t = nullptr;                                           // unused (final layer is VALU)
-    // raw (reference-layout) copies the VALU backward kernels read
-    float *w_out = nullptr, *w_pe = nullptr, *w_conv = nullptr, *ln_g = nullptr;
-    // saved activations
+    // ---- both arithmetics, all fp32, pieces of `act` (carve_act): the residual stream, the statistics, the conditioning and
+    // what the backward keeps in fp32
     float* act = nullptr;
-    float *x_in[NBLK + 1], *a1[NBLK], *q[NBLK], *k[NBLK], *v[NBLK], *o[NBLK], *lse[NBLK], *p[NBLK],
-        *x_mid[NBLK], *a2[NBLK], *u[NBLK], *f[NBLK];
+    float *x_in[NBLK + 1], *x_mid[NBLK], *lse[NBLK];
     float *silu_c = nullptr, *mod = nullptr, *c = nullptr, *lat = nullptr;   // (S,128) (S,3072) (S,128) (S,1920)
-    // backward temporaries
-    float *dx = nullptr, *t1 = nullptr, *t2a = nullptr, *t2b = nullptr, *t3 = nullptr, *t4 = nullptr, *dsum = nullptr,
-          *dmod = nullptr;
-    // ---- T2S_TRAIN_BF16: packed bf16 weights (forward W and dgrad W^T) and bf16 activations; the
-    // residual stream (x_in, x_mid, dx), lse, dsum, mod, dmod above stay fp32
-    __bf16* warena16 = nullptr;
-    bf16x8 *qkv_f16[NBLK], *proj_f16[NBLK], *fc1_f16[NBLK], *fc2_f16[NBLK];
-    bf16x8 *qkv_t16[NBLK], *proj_t16[NBLK], *fc1_t16[NBLK], *fc2_t16[NBLK];
-    __bf16* act16 = nullptr;
-    __bf16 *a1h[NBLK], *qh[NBLK], *kh[NBLK], *vh[NBLK], *oh[NBLK], *ph[NBLK], *a2h[NBLK], *uh[NBLK], *fh[NBLK];
-    __bf16 *t1h = nullptr, *t2h = nullptr, *t3h = nullptr, *t4h = nullptr;   // (M,128) (M,256) (M,384) (M,128)
+    float *dx = nullptr, *dsum = nullptr, *dmod = nullptr;
+    float* t1 = nullptr;           // (S,768) dense slice of dmod for the adaLN weight gradient; f32: also the block backward's (M,128) temporary
     float* wg_scratch = nullptr;   // partial weight-gradient tiles (wgrad16 stage 1 -> stage 2)
     float* colpart = nullptr;      // bf16: (M/32, 3, 128) column-sum partials of the fused LayerNorm backward (BEPI_LNBWD)
     size_t wg_scratch_floats = 0;
     int n_cu = 0;
+    // ---- what one arithmetic owns; only the sub-struct of `dtype` is carved
+    template <class T>
+    struct Branch {   // saved branch activations of every block
+        T *a1[NBLK], *q[NBLK], *k[NBLK], *v[NBLK], *o[NBLK], *p[NBLK], *a2[NBLK], *u[NBLK], *f[NBLK];
+    };
+    struct F32 : Branch<float> {    // T2S_TRAIN_F32: the activations and temporaries are further pieces of `act`
+        float* warena = nullptr;    // training packs, refreshed by every t2s_dit_train_forward (the other forward packs are the handle's)
+        f32x4* fc2_f[NBLK];         // forward: fc2 tile-major (the handle keeps it in chunk order)
+        BlockMats<f32x4*> wt[NBLK]; // dgrad:   W^T (K,N)
+        float *t2a = nullptr, *t2b = nullptr, *t3 = nullptr, *t4 = nullptr;   // (M,256) (M,256) (M,384) (M,128)
+    } f32;
+    struct BF16 : Branch<__bf16> {  // T2S_TRAIN_BF16: bf16 packs, activations and temporaries in arenas of their own
+        __bf16* warena = nullptr;   // refreshed by every t2s_dit_train_forward
+        BlockMats<bf16x8*> w[NBLK], wt[NBLK];   // forward: W (N,K); dgrad: W^T (K,N)
+        __bf16* act = nullptr;
+        __bf16 *t1 = nullptr, *t2 = nullptr, *t3 = nullptr, *t4 = nullptr;   // (M,128) (M,256) (M,384) (M,128)
+    } bf;
 };
 
 namespace {
-
-size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
 
 // W (N,K) row-major -> packed_index order of W (transpose=0) or of W^T (K,N) (transpose=1)
 __global__ void pack_any_kernel(const float* __restrict__ W, float* __restrict__ P, int N, int K, int transpose) {
@@ -682,127 +680,96 @@ __global__ __launch_bounds__(256) void final_rows_kernel(const float* __restrict
 }
 
 // ---------------------------------------------------------------- workspace management
-int ensure_ws(t2s_dit* h, int S) {
-    const int dtype = h->train_dtype;
-    if (h->train && h->train->cap_seqs >= S && h->train->dtype == dtype) return T2S_OK;
-    t2s::train_free(h);
-    t2s_train_ws* w = new t2s_train_ws();
-    // Grow with 12.5 % headroom (within the handle's capacity): the length groups of a mix-train batch fluctuate by a few
-    // per cent from step to step (train.py:60-87), and a workspace rebuilt at every new maximum costs a device-wide
-    // hipFree + a multi-GB hipMalloc each time -- seconds in a long-lived process (found in round 4: train.py's loop at
-    // 65-180 ms per 28 ms step).  Everything below is sized for `S` = the capacity.
-    {
-        const int want = (S + S / 8 + 63) / 64 * 64;
-        S = want < h->max_seqs ? want : (S > h->max_seqs ? S : h->max_seqs);
+// The layouts of the three training arenas (t2s_arena.h: written once, run to measure and to bind).
+template <class Take>
+void carve_weights(t2s_train_ws::F32& f, Take&& take) {
+    for (int i = 0; i < NBLK; ++i)
+        for (int j = 0; j < NMAT; ++j) {
+            if (j == FC2) take(f.fc2_f[i], mat_elems(j));
+            take(f.wt[i][j], mat_elems(j));
+        }
+}
+template <class Take>
+void carve_weights(t2s_train_ws::BF16& b, Take&& take) {
+    for (int i = 0; i < NBLK; ++i)
+        for (int j = 0; j < NMAT; ++j) { take(b.w[i][j], mat_elems(j)); take(b.wt[i][j], mat_elems(j)); }
+}
+template <class T, class Take>
+void carve_branch(t2s_train_ws::Branch<T>& a, int i, size_t M, Take&& take) {
+    take(a.a1[i], M * D); take(a.q[i], M * D); take(a.k[i], M * D); take(a.v[i], M * D); take(a.o[i], M * D);
+    take(a.p[i], M * D); take(a.a2[i], M * D); take(a.u[i], M * 2 * D); take(a.f[i], M * D);
+}
+// the fp32 arena: residual stream and statistics always; branch activations and temporaries only in fp32 mode
+template <class Take>
+void carve_act(t2s_train_ws* w, Take&& take) {
+    const size_t S = (size_t)w->cap_seqs, M = S * NTOK;
+    const bool bf = w->dtype == T2S_TRAIN_BF16;
+    for (int i = 0; i <= NBLK; ++i) take(w->x_in[i], M * D);
+    for (int i = 0; i < NBLK; ++i) {
+        take(w->x_mid[i], M * D);
+        take(w->lse[i], M * NH);
+        if (!bf) carve_branch(w->f32, i, M, take);
     }
-    w->cap_seqs = S;
-    w->dtype = dtype;
-    const bool bf = dtype == T2S_TRAIN_BF16;
-    auto fail = [&](const char* what, double mb) {
-        set_error("t2s train: hipMalloc(%s, %.1f MB) failed", what, mb);
-        if (w->warena) (void)hipFree(w->warena);
-        if (w->warena16) (void)hipFree(w->warena16);
-        if (w->act) (void)hipFree(w->act);
-        if (w->act16) (void)hipFree(w->act16);
-        delete w;
+    take(w->silu_c, S * D); take(w->mod, S * MODROW); take(w->c, S * D); take(w->lat, S * LAT); take(w->dx, M * D);
+    take(w->dsum, M * NH); take(w->dmod, S * MODROW);
+    take(w->t1, bf ? S * MODW : M * D);
+    take(w->wg_scratch, w->wg_scratch_floats);
+    take(w->colpart, bf ? M / 32 * 384 : 64);
+    if (!bf) { take(w->f32.t2a, M * 2 * D); take(w->f32.t2b, M * 2 * D); take(w->f32.t3, M * 3 * D); take(w->f32.t4, M * D); }
+}
+template <class Take>
+void carve_act16(t2s_train_ws* w, Take&& take) {
+    const size_t M = (size_t)w->cap_seqs * NTOK;
+    for (int i = 0; i < NBLK; ++i) carve_branch(w->bf, i, M, take);
+    take(w->bf.t1, M * D); take(w->bf.t2, M * 2 * D); take(w->bf.t3, M * 3 * D); take(w->bf.t4, M * D);
+}
+
+// everything of a workspace laid out for w->cap_seqs sequences of w->dtype; a failure leaves what it allocated to train_free
+int build_ws(t2s_train_ws* w) {
+    auto oom = [](const char* what, size_t bytes) {
+        set_error("t2s train: hipMalloc(%s, %.1f MB) failed", what, bytes / 1e6);
         return T2S_E_HIP;
     };
+    const bool bf = w->dtype == T2S_TRAIN_BF16;
+    size_t n = 0;
     // ---- packed weights (fp32 packs: fc2 tile-major + all W^T; bf16 packs: W and W^T of every linear)
-    size_t woff = 0;
-    auto wtake = [&](size_t n) { size_t o = woff; woff += r64(n); return o; };
-    size_t o_f[4][NBLK], o_t[4][NBLK];
-    const size_t wsz[4] = {3 * D * D, D * D, 2 * D * D, 2 * D * D};   // qkv, proj, fc1, fc2
-    for (int i = 0; i < NBLK; ++i)
-        for (int j = 0; j < 4; ++j) { o_f[j][i] = wtake(wsz[j]); o_t[j][i] = wtake(wsz[j]); }
     if (!bf) {
-        if (hipMalloc(&w->warena, woff * sizeof(float)) != hipSuccess) return fail("packed weights", woff * 4 / 1e6);
-        for (int i = 0; i < NBLK; ++i) {
-            w->qkv_f[i] = (f32x4*)(w->warena + o_f[0][i]); w->proj_f[i] = (f32x4*)(w->warena + o_f[1][i]);
-            w->fc1_f[i] = (f32x4*)(w->warena + o_f[2][i]); w->fc2_f[i] = (f32x4*)(w->warena + o_f[3][i]);
-            w->qkv_t[i] = (f32x4*)(w->warena + o_t[0][i]); w->proj_t[i] = (f32x4*)(w->warena + o_t[1][i]);
-            w->fc1_t[i] = (f32x4*)(w->warena + o_t[2][i]); w->fc2_t[i] = (f32x4*)(w->warena + o_t[3][i]);
-        }
+        if (carve_alloc(w->f32.warena, [&](auto& take) { carve_weights(w->f32, take); }, &n) != hipSuccess) return oom("packed weights", n * 4);
     } else {
-        if (hipMalloc(&w->warena16, woff * sizeof(__bf16)) != hipSuccess) return fail("packed bf16 weights", woff * 2 / 1e6);
-        for (int i = 0; i < NBLK; ++i) {
-            w->qkv_f16[i] = (bf16x8*)(w->warena16 + o_f[0][i]); w->proj_f16[i] = (bf16x8*)(w->warena16 + o_f[1][i]);
-            w->fc1_f16[i] = (bf16x8*)(w->warena16 + o_f[2][i]); w->fc2_f16[i] = (bf16x8*)(w->warena16 + o_f[3][i]);
-            w->qkv_t16[i] = (bf16x8*)(w->warena16 + o_t[0][i]); w->proj_t16[i] = (bf16x8*)(w->warena16 + o_t[1][i]);
-            w->fc1_t16[i] = (bf16x8*)(w->warena16 + o_t[2][i]); w->fc2_t16[i] = (bf16x8*)(w->warena16 + o_t[3][i]);
-        }
+        if (carve_alloc(w->bf.warena, [&](auto& take) { carve_weights(w->bf, take); }, &n) != hipSuccess) return oom("packed bf16 weights", n * 2);
     }
-    // ---- fp32 arena: residual stream and statistics always; branch activations only in fp32 mode
-    const size_t M = (size_t)S * NTOK;
-    size_t aoff = 0;
-    auto atake = [&](size_t n) { size_t o = aoff; aoff += r64(n); return o; };
-    size_t o_xin[NBLK + 1], o_xm[NBLK], o_lse[NBLK];
-    size_t o_a1[NBLK], o_q[NBLK], o_k[NBLK], o_v[NBLK], o_o[NBLK], o_p[NBLK], o_a2[NBLK], o_u[NBLK], o_f32[NBLK];
-    for (int i = 0; i <= NBLK; ++i) o_xin[i] = atake(M * D);
-    for (int i = 0; i < NBLK; ++i) {
-        o_xm[i] = atake(M * D);
-        o_lse[i] = atake(M * NH);
-        if (!bf) {
-            o_a1[i] = atake(M * D); o_q[i] = atake(M * D); o_k[i] = atake(M * D); o_v[i] = atake(M * D); o_o[i] = atake(M * D);
-            o_p[i] = atake(M * D); o_a2[i] = atake(M * D); o_u[i] = atake(M * 2 * D); o_f32[i] = atake(M * D);
-        }
-    }
-    const size_t o_silu = atake((size_t)S * D), o_mod = atake((size_t)S * MODROW), o_c = atake((size_t)S * D),
-                 o_lat = atake((size_t)S * LAT), o_dx = atake(M * D), o_dsum = atake(M * NH),
-                 o_dmod = atake((size_t)S * MODROW);
-    // t1 also serves the adaLN weight gradient as an (S,768) fp32 temporary in both modes
-    const size_t o_t1 = atake(bf ? (size_t)S * MODW : M * D);
-    size_t o_wgs = 0;
     {
+        const int S = w->cap_seqs;
         int dev = 0;
         hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return fail("device query", 0.0);
+        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return oom("device query", 0);
         w->n_cu = prop.multiProcessorCount;
-        w->wg_scratch_floats = wgrad16_scratch_floats((int)M, w->n_cu);
+        w->wg_scratch_floats = wgrad16_scratch_floats(S * NTOK, w->n_cu);
         int rows, gx;                                            // the adaLN linear: M = S rows, (768,128)
         wgrad16_plan(S, MODW, D, w->n_cu, &rows, &gx);
         const size_t ada = (size_t)gx * (MODW / 128) * (128 * 128 + 128);
         if (ada > w->wg_scratch_floats) w->wg_scratch_floats = ada;
-        o_wgs = atake(w->wg_scratch_floats);
     }
-    const size_t o_colpart = atake(bf ? M / 32 * 384 : 64);
-    size_t o_t2a = 0, o_t2b = 0, o_t3 = 0, o_t4 = 0;
-    if (!bf) { o_t2a = atake(M * 2 * D); o_t2b = atake(M * 2 * D); o_t3 = atake(M * 3 * D); o_t4 = atake(M * D); }
-    if (hipMalloc(&w->act, aoff * sizeof(float)) != hipSuccess) return fail("activations", aoff * 4 / 1e6);
-    float* A = w->act;
-    for (int i = 0; i <= NBLK; ++i) w->x_in[i] = A + o_xin[i];
-    for (int i = 0; i < NBLK; ++i) {
-        w->x_mid[i] = A + o_xm[i];
-        w->lse[i] = A + o_lse[i];
-        if (!bf) {
-            w->a1[i] = A + o_a1[i]; w->q[i] = A + o_q[i]; w->k[i] = A + o_k[i]; w->v[i] = A + o_v[i]; w->o[i] = A + o_o[i];
-            w->p[i] = A + o_p[i]; w->a2[i] = A + o_a2[i]; w->u[i] = A + o_u[i]; w->f[i] = A + o_f32[i];
-        }
-    }
-    w->silu_c = A + o_silu; w->mod = A + o_mod; w->c = A + o_c; w->lat = A + o_lat; w->dx = A + o_dx;
-    w->dsum = A + o_dsum; w->dmod = A + o_dmod; w->t1 = A + o_t1;
-    if (!bf) { w->t2a = A + o_t2a; w->t2b = A + o_t2b; w->t3 = A + o_t3; w->t4 = A + o_t4; }
-    w->wg_scratch = A + o_wgs;
-    w->colpart = A + o_colpart;
-    // ---- bf16 arena
-    if (bf) {
-        size_t hoff = 0;
-        auto htake = [&](size_t n) { size_t o = hoff; hoff += r64(n); return o; };
-        size_t h_a1[NBLK], h_q[NBLK], h_k[NBLK], h_v[NBLK], h_o[NBLK], h_p[NBLK], h_a2[NBLK], h_u[NBLK], h_f[NBLK];
-        for (int i = 0; i < NBLK; ++i) {
-            h_a1[i] = htake(M * D); h_q[i] = htake(M * D); h_k[i] = htake(M * D); h_v[i] = htake(M * D); h_o[i] = htake(M * D);
-            h_p[i] = htake(M * D); h_a2[i] = htake(M * D); h_u[i] = htake(M * 2 * D); h_f[i] = htake(M * D);
-        }
-        const size_t h_t1 = htake(M * D), h_t2 = htake(M * 2 * D), h_t3 = htake(M * 3 * D), h_t4 = htake(M * D);
-        if (hipMalloc(&w->act16, hoff * sizeof(__bf16)) != hipSuccess) return fail("bf16 activations", hoff * 2 / 1e6);
-        __bf16* H = w->act16;
-        for (int i = 0; i < NBLK; ++i) {
-            w->a1h[i] = H + h_a1[i]; w->qh[i] = H + h_q[i]; w->kh[i] = H + h_k[i]; w->vh[i] = H + h_v[i]; w->oh[i] = H + h_o[i];
-            w->ph[i] = H + h_p[i]; w->a2h[i] = H + h_a2[i]; w->uh[i] = H + h_u[i]; w->fh[i] = H + h_f[i];
-        }
-        w->t1h = H + h_t1; w->t2h = H + h_t2; w->t3h = H + h_t3; w->t4h = H + h_t4;
-    }
-    h->train = w;
+    if (carve_alloc(w->act, [&](auto& take) { carve_act(w, take); }, &n) != hipSuccess) return oom("activations", n * 4);
+    if (bf && carve_alloc(w->bf.act, [&](auto& take) { carve_act16(w, take); }, &n) != hipSuccess) return oom("bf16 activations", n * 2);
     return T2S_OK;
+}
+
+int ensure_ws(t2s_dit* h, int S) {
+    const int dtype = h->train_dtype;
+    if (h->train && h->train->cap_seqs >= S && h->train->dtype == dtype) return T2S_OK;
+    t2s::train_free(h);
+    t2s_train_ws* w = h->train = new t2s_train_ws();
+    // Grow with 12.5 % headroom (within the handle's capacity): the length groups of a mix-train batch fluctuate by a few
+    // per cent from step to step (train.py:60-87), and a workspace rebuilt at every new maximum costs a device-wide
+    // hipFree + a multi-GB hipMalloc each time -- seconds in a long-lived process (found in round 4: train.py's loop at
+    // 65-180 ms per 28 ms step).  Everything is sized for the capacity.
+    const int want = (S + S / 8 + 63) / 64 * 64;
+    w->cap_seqs = want < h->max_seqs ? want : (S > h->max_seqs ? S : h->max_seqs);
+    w->dtype = dtype;
+    const int rc = build_ws(w);
+    if (rc != T2S_OK) t2s::train_free(h);
+    return rc;
 }
 
 // the 32 bf16 weight packs of a training forward (4 blocks x 4 matrices x 2 orientations) in one launch: job table
@@ -873,16 +840,23 @@ int colsum(const float* Y, float* out, int M, int N, hipStream_t st) {
     return T2S_OK;
 }
 
+// ---------------------------------------------------------------- the block recipes, one per arithmetic and direction
+// (every launch is one timed interval: the class names what bench.py reports per step)
+// Declared here and defined behind the entry point each was cut from: the compiler emits a template kernel where the source
+// first asks for it, and the order of the kernels in the code object is part of what is measured.
+int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st);
+int forward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st);
+int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st);
+int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st);
+
 }  // namespace
 
 namespace t2s {
 void train_free(t2s_dit* h) {
     if (!h || !h->train) return;
     t2s_train_ws* w = h->train;
-    if (w->warena) (void)hipFree(w->warena);
-    if (w->warena16) (void)hipFree(w->warena16);
-    if (w->act) (void)hipFree(w->act);
-    if (w->act16) (void)hipFree(w->act16);
+    for (void* arena : {(void*)w->f32.warena, (void*)w->bf.warena, (void*)w->act, (void*)w->bf.act})   // (a half-built one too)
+        if (arena) (void)hipFree(arena);
     delete w;
     h->train = nullptr;
 }
@@ -912,133 +886,103 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
     t2s_train_ws* ws = h->train;
     const int S = B, M = S * NTOK;
     ws->S = S;
-    ws->has_text = text != nullptr;
     // the handle's own parameter copies / forward packs must be current: the caller refreshes them
     // with t2s_dit_update_weights; here only the training-specific packs
     const bool bf = ws->dtype == T2S_TRAIN_BF16;
-    for (int i = 0; i < NBLK; ++i) {
-        const t2s_dit_block_weights& b = w->blk[i];
-        if (!bf) {   // fc2 tile-major, all W^T
-            if ((rc = pack_any(b.qkv_w, ws->qkv_t[i], 3 * D, D, 1, st)) || (rc = pack_any(b.proj_w, ws->proj_t[i], D, D, 1, st)) ||
-                (rc = pack_any(b.fc1_w, ws->fc1_t[i], 2 * D, D, 1, st)) || (rc = pack_any(b.fc2_w, ws->fc2_f[i], D, 2 * D, 0, st)) ||
-                (rc = pack_any(b.fc2_w, ws->fc2_t[i], D, 2 * D, 1, st)))
-                return rc;
-        }
-    }
-    if (bf) {        // bf16 copies of the fp32 master weights, both orientations
+    if (!bf) {       // fc2 tile-major, all W^T
+        for (int i = 0; i < NBLK; ++i)
+            for (int j = 0; j < NMAT; ++j) {
+                const float* W = mat_w(w->blk[i], j);
+                if (j == FC2 && (rc = pack_any(W, ws->f32.fc2_f[i], MAT_N[j], MAT_K[j], 0, st))) return rc;
+                if ((rc = pack_any(W, ws->f32.wt[i][j], MAT_N[j], MAT_K[j], 1, st))) return rc;
+            }
+    } else {         // bf16 copies of the fp32 master weights, both orientations
         Pack16Table pt{};
         int np = 0;
-        auto pk = [&](const float* W, bf16x8* plain, bf16x8* transposed, int N, int K) {
-            pt.j[np++] = Pack16Job{W, reinterpret_cast<__bf16*>(plain), N, K, 0};
-            pt.j[np++] = Pack16Job{W, reinterpret_cast<__bf16*>(transposed), N, K, 1};
-        };
-        for (int i = 0; i < NBLK; ++i) {
-            const t2s_dit_block_weights& b = w->blk[i];
-            pk(b.qkv_w, ws->qkv_f16[i], ws->qkv_t16[i], 3 * D, D);
-            pk(b.proj_w, ws->proj_f16[i], ws->proj_t16[i], D, D);
-            pk(b.fc1_w, ws->fc1_f16[i], ws->fc1_t16[i], 2 * D, D);
-            pk(b.fc2_w, ws->fc2_f16[i], ws->fc2_t16[i], D, 2 * D);
-        }
-        { TimeScope ts(h, TC_TR_TAIL, st);
-        pack16_multi_kernel<<<dim3((3 * D * D + 255) / 256, np), 256, 0, st>>>(pt);
-        T2S_LAUNCH_CHECK();
-        }
+        for (int i = 0; i < NBLK; ++i)
+            for (int j = 0; j < NMAT; ++j) {
+                pt.j[np++] = Pack16Job{mat_w(w->blk[i], j), reinterpret_cast<__bf16*>(ws->bf.w[i][j]), MAT_N[j], MAT_K[j], 0};
+                pt.j[np++] = Pack16Job{mat_w(w->blk[i], j), reinterpret_cast<__bf16*>(ws->bf.wt[i][j]), MAT_N[j], MAT_K[j], 1};
+            }
+        T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, pack16_multi_kernel<<<dim3((3 * D * D + 255) / 256, np), 256, 0, st>>>(pt));
     }
     T2S_HIP_CHECK(hipMemcpyAsync(ws->lat, x, (size_t)S * LAT * sizeof(float), hipMemcpyDeviceToDevice, st));
-    { TimeScope ts(h, TC_TR_TAIL, st);
-    cond_rows_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, temb, temb_rows, text, S);
-    T2S_LAUNCH_CHECK();
-    }
-    { TimeScope ts(h, TC_TR_TAIL, st);
-    silu_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, ws->silu_c, S * D);
-    T2S_LAUNCH_CHECK();
-    }
-    { TimeScope ts(h, TC_TR_TAIL, st);
-    if ((rc = gemm<128, 3, PRO_PLAIN, EPI_BIAS>(ws->silu_c, h->ada_p, h->ada_b, ws->mod, S, MODROW, st))) return rc;
-    }
-    { TimeScope ts(h, TC_TR_TAIL, st);
-    patchify_rows_kernel<<<((S + 3) / 4 * NTOK * 32 + 255) / 256, 256, 0, st>>>(x, ws->x_in[0], S, h->conv_w, h->conv_b, h->patch_w,
-                                                                      h->patch_b, h->pos);
-    T2S_LAUNCH_CHECK();
-    }
-    for (int i = 0; i < NBLK && bf; ++i) {
+    T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, cond_rows_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, temb, temb_rows, text, S));
+    T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, silu_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, ws->silu_c, S * D));
+    T2S_TIMED(h, TC_TR_TAIL, st, gemm<128, 3, PRO_PLAIN, EPI_BIAS>(ws->silu_c, h->ada_p, h->ada_b, ws->mod, S, MODROW, st));
+    T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
+                     patchify_rows_kernel<<<((S + 3) / 4 * NTOK * 32 + 255) / 256, 256, 0, st>>>(x, ws->x_in[0], S, h->conv_w, h->conv_b,
+                                                                                                 h->patch_w, h->patch_b, h->pos));
+    if ((rc = bf ? forward_blocks_bf16(h, ws, S, st) : forward_blocks_f32(h, ws, S, st))) return rc;
+    if (bf)   // (the last block's x_mid + g2 * f is formed here)
+        T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
+                         final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
+                                                                                            out, ws->bf.f[NBLK - 1], ws->mod, (NBLK - 1) * MODW + 5 * D));
+    else
+        T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
+                         final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[NBLK], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
+                                                                                            out, nullptr, nullptr, 0));
+    return T2S_OK;
+}
+
+}  // extern "C"
+
+namespace {
+int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    t2s_train_ws::BF16& a = ws->bf;
+    const int M = S * NTOK;
+    for (int i = 0; i < NBLK; ++i) {
         const int base = i * MODW;
         // The gate / residual adds have no kernel of their own: the GEMM that consumes a residual-stream tensor forms it
         // in its prologue (x = x_prev + gate * branch), writes it out for the backward pass and LayerNorm-modulates it.
         // a1 = mod(LN1(x_in)) -> bf16; q,k,v = a1 Wqkv^T + b -> bf16 heads; for i > 0, x_in[i] = x_mid[i-1] + g2 f[i-1]
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if (i == 0)
-            rc = bgemm<128, 384, BPRO_LN, BEPI_QKV>(ws->x_in[i], ws->qkv_f16[i], h->qkv_b[i], nullptr, M, 3 * D, st, ws->mod,
-                                                   base + 0 * D, base + 1 * D, ws->a1h[i], nullptr, ws->qh[i], ws->kh[i], ws->vh[i]);
-        else
-            rc = bgemm<128, 384, BPRO_LN_RES, BEPI_QKV>(ws->x_mid[i - 1], ws->qkv_f16[i], h->qkv_b[i], nullptr, M, 3 * D, st, ws->mod,
-                                                       base + 0 * D, base + 1 * D, ws->a1h[i], nullptr, ws->qh[i], ws->kh[i], ws->vh[i],
-                                                       ws->fh[i - 1], (i - 1) * MODW + 5 * D, ws->x_in[i]);
-        if (rc) return rc;
-        }
-        { TimeScope ts(h, TC_TR_ATTN_FWD, st);
-        if ((rc = attn16_train_fwd(ws->qh[i], ws->kh[i], ws->vh[i], ws->oh[i], ws->lse[i], S * NH, st))) return rc;
-        }
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  i == 0 ? bgemm<128, 384, BPRO_LN, BEPI_QKV>(ws->x_in[i], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
+                                                              base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i])
+                         : bgemm<128, 384, BPRO_LN_RES, BEPI_QKV>(ws->x_mid[i - 1], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
+                                                                  base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i],
+                                                                  a.f[i - 1], (i - 1) * MODW + 5 * D, ws->x_in[i]));
+        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn16_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, st));
         // p = o Wp^T + b
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm<128, 128, BPRO_BF16, BEPI_BF16>(ws->oh[i], ws->proj_f16[i], h->proj_b[i], ws->ph[i], M, D, st))) return rc;
-        }
+        T2S_TIMED(h, TC_TR_GEMM, st, bgemm<128, 128, BPRO_BF16, BEPI_BF16>(a.o[i], a.w[i][PROJ], h->bias[i][PROJ], a.p[i], M, D, st));
         // x_mid = x_in + g1 * p; a2 = mod(LN2(x_mid)); u = a2 W1^T + b1
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm<128, 256, BPRO_LN_RES, BEPI_BF16>(ws->x_in[i], ws->fc1_f16[i], h->fc1_b[i], ws->uh[i], M, 2 * D, st, ws->mod,
-                                                      base + 3 * D, base + 4 * D, ws->a2h[i], nullptr, nullptr, nullptr, nullptr,
-                                                      ws->ph[i], base + 2 * D, ws->x_mid[i])))
-            return rc;
-        }
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  bgemm<128, 256, BPRO_LN_RES, BEPI_BF16>(ws->x_in[i], a.w[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
+                                                          base + 4 * D, a.a2[i], nullptr, nullptr, nullptr, nullptr, a.p[i], base + 2 * D,
+                                                          ws->x_mid[i]));
         // f = gelu(u) W2^T + b2   (gelu(u) is not saved: the fc2 weight gradient re-applies it to u)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm<256, 128, BPRO_GELU, BEPI_BF16>(ws->uh[i], ws->fc2_f16[i], h->fc2_b[i], ws->fh[i], M, D, st))) return rc;
-        }
+        T2S_TIMED(h, TC_TR_GEMM, st, bgemm<256, 128, BPRO_GELU, BEPI_BF16>(a.u[i], a.w[i][FC2], h->bias[i][FC2], a.f[i], M, D, st));
         // (the last block's x_mid + g2 * f is formed inside the final-layer kernels, forward and backward: never written)
-    }
-    for (int i = 0; i < NBLK && !bf; ++i) {
-        const int base = i * MODW;
-        // a1 = mod(LN1(x_in)); q,k,v = a1 Wqkv^T + b
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<128, 3, PRO_LNMOD, EPI_QKV>(ws->x_in[i], h->qkv_p[i], h->qkv_b[i], nullptr, M, 3 * D, st, ws->mod,
-                                                    base + 0 * D, base + 1 * D, ws->a1[i], nullptr, ws->q[i], ws->k[i], ws->v[i])))
-            return rc;
-        }
-        { TimeScope ts(h, TC_TR_ATTN_FWD, st);
-        if ((rc = attn_plain_train_fwd(ws->q[i], ws->k[i], ws->v[i], ws->o[i], ws->lse[i], S * NH, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<128, 1, PRO_PLAIN, EPI_BIAS>(ws->o[i], h->proj_p[i], h->proj_b[i], ws->p[i], M, D, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[i], ws->p[i], ws->mod, base + 2 * D, ws->x_mid[i], M);
-        T2S_LAUNCH_CHECK();
-        }
-        // a2 = mod(LN2(x_mid)); u = a2 W1^T + b1; f = gelu(u) W2^T + b2
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<128, 2, PRO_LNMOD, EPI_BIAS>(ws->x_mid[i], h->fc1_p[i], h->fc1_b[i], ws->u[i], M, 2 * D, st, ws->mod,
-                                                     base + 3 * D, base + 4 * D, ws->a2[i])))
-            return rc;
-        }
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<256, 1, PRO_GELU, EPI_BIAS>(ws->u[i], ws->fc2_f[i], h->fc2_b[i], ws->f[i], M, D, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[i], ws->f[i], ws->mod, base + 5 * D, ws->x_in[i + 1], M);
-        T2S_LAUNCH_CHECK();
-        }
-    }
-    { TimeScope ts(h, TC_TR_TAIL, st);
-    if (bf)
-        final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b, out,
-                                                                           ws->fh[NBLK - 1], ws->mod, (NBLK - 1) * MODW + 5 * D);
-    else
-        final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[NBLK], S, h->ln_w, h->ln_b, h->out_w, h->out_b, out,
-                                                                           nullptr, nullptr, 0);
-    T2S_LAUNCH_CHECK();
     }
     return T2S_OK;
 }
+
+int forward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    t2s_train_ws::F32& a = ws->f32;
+    const int M = S * NTOK;
+    for (int i = 0; i < NBLK; ++i) {
+        const int base = i * MODW;
+        // a1 = mod(LN1(x_in)); q,k,v = a1 Wqkv^T + b
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  gemm<128, 3, PRO_LNMOD, EPI_QKV>(ws->x_in[i], h->p32[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod, base + 0 * D,
+                                                   base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i]));
+        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn_plain_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, st));
+        T2S_TIMED(h, TC_TR_GEMM, st, gemm<128, 1, PRO_PLAIN, EPI_BIAS>(a.o[i], h->p32[i][PROJ], h->bias[i][PROJ], a.p[i], M, D, st));
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
+                         gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[i], a.p[i], ws->mod, base + 2 * D, ws->x_mid[i], M));
+        // a2 = mod(LN2(x_mid)); u = a2 W1^T + b1; f = gelu(u) W2^T + b2
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  gemm<128, 2, PRO_LNMOD, EPI_BIAS>(ws->x_mid[i], h->p32[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
+                                                    base + 4 * D, a.a2[i]));
+        T2S_TIMED(h, TC_TR_GEMM, st, gemm<256, 1, PRO_GELU, EPI_BIAS>(a.u[i], a.fc2_f[i], h->bias[i][FC2], a.f[i], M, D, st));
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
+                         gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[i], a.f[i], ws->mod, base + 5 * D, ws->x_in[i + 1], M));
+    }
+    return T2S_OK;
+}
+}  // namespace
+
+extern "C" {
 
 int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g, int B, void* stream) {
     t2s::reset_tile_dir();
@@ -1081,7 +1025,7 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
     if (bf) {   // + the gate backward of the last block's MLP branch: t1 = df = g2 * dx, dgate2
         const int goff = (NBLK - 1) * MODW + 5 * D;
         final_bwd_kernel<true, FUSED_ROWS><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
-                                                                      ws->fh[NBLK - 1], ws->mod, goff, ws->t1h);
+                                                                      ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1);
         T2S_LAUNCH_CHECK();
         final_gate_reduce_kernel<<<S, D, 0, st>>>(ws->wg_scratch, final_stride, ws->dmod, goff);
     } else {
@@ -1093,118 +1037,7 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
                                                                  TailDst{{g->ln_w, g->ln_b, g->out_w, g->out_b}, {D, D, 4 * D, 4}});
     T2S_LAUNCH_CHECK();
     }
-    // (Measured and dropped in round 2: the four weight gradients of a block on a side stream.  Issued as soon as their
-    // operands exist they only share the HBM bandwidth with the GEMM / LayerNorm kernels they run beside (13.42 ms per step,
-    // the same as in order); issued beside the VALU-bound attention backward they slow it by more than they take alone
-    // (attention backward 3.0 -> 4.4 ms per step, 14.1 ms per step): the attention workgroups fill the CUs.
-    // Round 3 repeated both as timing-only builds on a stream CALIBRATED to run concurrently (t2s_sampler.hip lane_streams:
-    // HIP streams that share a hardware queue serialise, which may have been the "same as in order" of round 2): without any
-    // dependency waits 10.92 vs 11.10 ms in order, issued beside the attention backward 11.08 -- the attention backward then
-    // takes 3.1-3.7 instead of 2.2 ms: it is bound by vector issue, but its 16 waves per CU leave the other kernel no slot.)
-    for (int i = NBLK - 1; i >= 0 && bf; --i) {
-        const int base = i * MODW;
-        const t2s_dit_block_grads& b = g->blk[i];
-        // ---- MLP branch: x_out = x_mid + g2 * f.  t1 = df = g2 * dx and dgate2 come from the kernel that produced dx: the
-        // next block's LN1 backward epilogue, or the final-layer backward for the last block
-        { TimeScope ts(h, TC_TR_WGRAD, st);     // dW2 = df^T gelu(u): gelu applied to the fetched u chunks (not saved)
-        if ((rc = launch_wgrad16<true>(ws->t1h, ws->uh[i], b.fc2_w, b.fc2_b, M, D, 2 * D, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st))) return rc;
-        }
-        // du = (df W2) * gelu'(u)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm<128, 256, BPRO_BF16, BEPI_GELUBWD>(ws->t1h, ws->fc2_t16[i], nullptr, ws->t2h, M, 2 * D, st, nullptr, 0, 0,
-                                                            nullptr, ws->uh[i])))
-            return rc;
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = launch_wgrad16(ws->t2h, ws->a2h[i], b.fc1_w, b.fc1_b, M, 2 * D, D, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st))) return rc;
-        }
-        // da2 = du W1, consumed in the accumulators: LN2 backward into dx merged with the attention branch's gate
-        // backward (t1 = dp = g1 * dx, dgate1) -- the epilogue of the data-gradient GEMM (BEPI_LNBWD; da2 never reaches HBM)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm_lnbwd<256>(ws, ws->t2h, ws->fc1_t16[i], ws->x_mid[i], base + 3 * D, base + 4 * D, ws->ph[i], base + 2 * D, ws->t1h, M, st)))
-            return rc;
-        }
-        // ---- attention branch: x_mid = x_in + g1 * p
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = launch_wgrad16(ws->t1h, ws->oh[i], b.proj_w, b.proj_b, M, D, D, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm<128, 128, BPRO_BF16, BEPI_BF16>(ws->t1h, ws->proj_t16[i], nullptr, ws->t4h, M, D, st))) return rc;   // do
-        }
-        { TimeScope ts(h, TC_TR_ATTN_BWD, st);
-        if ((rc = attn16_bwd(ws->qh[i], ws->kh[i], ws->vh[i], ws->oh[i], ws->t4h, ws->lse[i], ws->dsum, ws->t3h, S * NH, st)))
-            return rc;
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = launch_wgrad16(ws->t3h, ws->a1h[i], b.qkv_w, b.qkv_b, M, 3 * D, D, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st))) return rc;
-        }
-        // da1 = dqkv Wqkv with LN1 backward into dx as its epilogue, merged with the gate backward of block i-1's MLP branch
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = bgemm_lnbwd<384>(ws, ws->t3h, ws->qkv_t16[i], ws->x_in[i], base + 0 * D, base + 1 * D,
-                                   i > 0 ? ws->fh[i - 1] : (const __bf16*)nullptr, (i - 1) * MODW + 5 * D, ws->t1h, M, st)))
-            return rc;
-        }
-    }
-    for (int i = NBLK - 1; i >= 0 && !bf; --i) {
-        const int base = i * MODW;
-        const t2s_dit_block_grads& b = g->blk[i];
-        // ---- MLP branch: x_out = x_mid + g2 * f
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, ws->f[i], ws->mod, base + 5 * D, ws->t1, ws->dmod);      // t1 = df
-        T2S_LAUNCH_CHECK();
-        }
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        gelu_kernel<<<((size_t)M * 64 + 255) / 256, 256, 0, st>>>(ws->u[i], ws->t2a, (size_t)M * 64);        // t2a = gelu(u)
-        T2S_LAUNCH_CHECK();
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = wgrad(ws, ws->t1, ws->t2a, b.fc2_w, b.fc2_b, M, D, 2 * D, st))) return rc;
-        }
-        // du = (df W2) * gelu'(u)      (dgrad = row GEMM on W2^T: out 256 <- in 128)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<128, 2, PRO_PLAIN, EPI_GELUBWD>(ws->t1, ws->fc2_t[i], nullptr, ws->t2b, M, 2 * D, st, nullptr, 0, 0,
-                                                        nullptr, ws->u[i])))
-            return rc;
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = wgrad(ws, ws->t2b, ws->a2[i], b.fc1_w, b.fc1_b, M, 2 * D, D, st))) return rc;
-        }
-        // da2 = du W1 (out 128 <- in 256)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<256, 1, PRO_PLAIN, EPI_BIAS>(ws->t2b, ws->fc1_t[i], nullptr, ws->t1, M, D, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_mid[i], ws->mod, base + 3 * D, base + 4 * D, ws->dx, ws->dmod,
-                                             (const float*)nullptr, 0, (float*)nullptr);
-        T2S_LAUNCH_CHECK();
-        }
-        // ---- attention branch: x_mid = x_in + g1 * p
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, ws->p[i], ws->mod, base + 2 * D, ws->t1, ws->dmod);       // t1 = dp
-        T2S_LAUNCH_CHECK();
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = wgrad(ws, ws->t1, ws->o[i], b.proj_w, b.proj_b, M, D, D, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<128, 1, PRO_PLAIN, EPI_BIAS>(ws->t1, ws->proj_t[i], nullptr, ws->t4, M, D, st))) return rc;   // do
-        }
-        { TimeScope ts(h, TC_TR_ATTN_BWD, st);
-        if ((rc = attn_bwd(ws->q[i], ws->k[i], ws->v[i], ws->o[i], ws->t4, ws->lse[i], ws->dsum, ws->t3, S * NH, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = wgrad(ws, ws->t3, ws->a1[i], b.qkv_w, b.qkv_b, M, 3 * D, D, st))) return rc;
-        }
-        // da1 = dqkv Wqkv (out 128 <- in 384)
-        { TimeScope ts(h, TC_TR_GEMM, st);
-        if ((rc = gemm<384, 1, PRO_PLAIN, EPI_BIAS>(ws->t3, ws->qkv_t[i], nullptr, ws->t1, M, D, st))) return rc;
-        }
-        { TimeScope ts(h, TC_TR_ELEM, st);
-        ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_in[i], ws->mod, base + 0 * D, base + 1 * D, ws->dx, ws->dmod,
-                                             (const float*)nullptr, 0, (float*)nullptr);
-        T2S_LAUNCH_CHECK();
-        }
-    }
+    if ((rc = bf ? backward_blocks_bf16(h, ws, g, S, st) : backward_blocks_f32(h, ws, g, S, st))) return rc;
     // ---- patchify
     { TimeScope ts(h, TC_TR_TAIL, st);
     patchify_bwd_kernel<<<tail_wgs, 256, 0, st>>>(ws->dx, ws->lat, S, h->conv_w, h->conv_b, h->patch_w, ws->wg_scratch, M);
@@ -1218,12 +1051,95 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
         // dmod block slice is strided (row stride MODROW): copy to a dense (S,768) temp first
         T2S_HIP_CHECK(hipMemcpy2DAsync(ws->t1, MODW * sizeof(float), ws->dmod + i * MODW, MODROW * sizeof(float),
                                        MODW * sizeof(float), S, hipMemcpyDeviceToDevice, st));
-        { TimeScope ts(h, TC_TR_WGRAD, st);
-        if ((rc = wgrad(ws, ws->t1, ws->silu_c, g->blk[i].ada_w, g->blk[i].ada_b, S, MODW, D, st))) return rc;
-        }
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, ws->t1, ws->silu_c, g->blk[i].ada_w, g->blk[i].ada_b, S, MODW, D, st));
     }
     return T2S_OK;
 }
+
+}  // extern "C"
+
+namespace {
+// (Measured and dropped in round 2: the four weight gradients of a block on a side stream.  Issued as soon as their
+// operands exist they only share the HBM bandwidth with the GEMM / LayerNorm kernels they run beside (13.42 ms per step,
+// the same as in order); issued beside the VALU-bound attention backward they slow it by more than they take alone
+// (attention backward 3.0 -> 4.4 ms per step, 14.1 ms per step): the attention workgroups fill the CUs.
+// Round 3 repeated both as timing-only builds on a stream CALIBRATED to run concurrently (t2s_sampler.hip lane_streams:
+// HIP streams that share a hardware queue serialise, which may have been the "same as in order" of round 2): without any
+// dependency waits 10.92 vs 11.10 ms in order, issued beside the attention backward 11.08 -- the attention backward then
+// takes 3.1-3.7 instead of 2.2 ms: it is bound by vector issue, but its 16 waves per CU leave the other kernel no slot.)
+int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    t2s_train_ws::BF16& a = ws->bf;
+    const int M = S * NTOK;
+    auto wgrad16 = [&](auto gelu, const __bf16* dY, const __bf16* X, float* dW, float* db, int N, int K) {
+        return launch_wgrad16<decltype(gelu)::value>(dY, X, dW, db, M, N, K, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st);
+    };
+    constexpr std::true_type gelu_x{};
+    constexpr std::false_type plain{};
+    for (int i = NBLK - 1; i >= 0; --i) {
+        const int base = i * MODW;
+        const t2s_dit_block_grads& b = g->blk[i];
+        // ---- MLP branch: x_out = x_mid + g2 * f.  t1 = df = g2 * dx and dgate2 come from the kernel that produced dx: the
+        // next block's LN1 backward epilogue, or the final-layer backward for the last block
+        // dW2 = df^T gelu(u): gelu applied to the fetched u chunks (not saved)
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(gelu_x, a.t1, a.u[i], b.fc2_w, b.fc2_b, D, 2 * D));
+        // du = (df W2) * gelu'(u)
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  bgemm<128, 256, BPRO_BF16, BEPI_GELUBWD>(a.t1, a.wt[i][FC2], nullptr, a.t2, M, 2 * D, st, nullptr, 0, 0, nullptr, a.u[i]));
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(plain, a.t2, a.a2[i], b.fc1_w, b.fc1_b, 2 * D, D));
+        // da2 = du W1, consumed in the accumulators: LN2 backward into dx merged with the attention branch's gate
+        // backward (t1 = dp = g1 * dx, dgate1) -- the epilogue of the data-gradient GEMM (BEPI_LNBWD; da2 never reaches HBM)
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  bgemm_lnbwd<256>(ws, a.t2, a.wt[i][FC1], ws->x_mid[i], base + 3 * D, base + 4 * D, a.p[i], base + 2 * D, a.t1, M, st));
+        // ---- attention branch: x_mid = x_in + g1 * p
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(plain, a.t1, a.o[i], b.proj_w, b.proj_b, D, D));
+        T2S_TIMED(h, TC_TR_GEMM, st, bgemm<128, 128, BPRO_BF16, BEPI_BF16>(a.t1, a.wt[i][PROJ], nullptr, a.t4, M, D, st));   // do
+        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn16_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, st));
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(plain, a.t3, a.a1[i], b.qkv_w, b.qkv_b, 3 * D, D));
+        // da1 = dqkv Wqkv with LN1 backward into dx as its epilogue, merged with the gate backward of block i-1's MLP branch
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  bgemm_lnbwd<384>(ws, a.t3, a.wt[i][QKV], ws->x_in[i], base + 0 * D, base + 1 * D,
+                                   i > 0 ? a.f[i - 1] : (const __bf16*)nullptr, (i - 1) * MODW + 5 * D, a.t1, M, st));
+    }
+    return T2S_OK;
+}
+
+int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    t2s_train_ws::F32& a = ws->f32;
+    const int M = S * NTOK;
+    for (int i = NBLK - 1; i >= 0; --i) {
+        const int base = i * MODW;
+        const t2s_dit_block_grads& b = g->blk[i];
+        // ---- MLP branch: x_out = x_mid + g2 * f
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, a.f[i], ws->mod, base + 5 * D, ws->t1, ws->dmod));   // t1 = df
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
+                         gelu_kernel<<<((size_t)M * 64 + 255) / 256, 256, 0, st>>>(a.u[i], a.t2a, (size_t)M * 64));   // t2a = gelu(u)
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, ws->t1, a.t2a, b.fc2_w, b.fc2_b, M, D, 2 * D, st));
+        // du = (df W2) * gelu'(u)      (dgrad = row GEMM on W2^T: out 256 <- in 128)
+        T2S_TIMED(h, TC_TR_GEMM, st,
+                  gemm<128, 2, PRO_PLAIN, EPI_GELUBWD>(ws->t1, a.wt[i][FC2], nullptr, a.t2b, M, 2 * D, st, nullptr, 0, 0, nullptr, a.u[i]));
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, a.t2b, a.a2[i], b.fc1_w, b.fc1_b, M, 2 * D, D, st));
+        // da2 = du W1 (out 128 <- in 256)
+        T2S_TIMED(h, TC_TR_GEMM, st, gemm<256, 1, PRO_PLAIN, EPI_BIAS>(a.t2b, a.wt[i][FC1], nullptr, ws->t1, M, D, st));
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
+                         ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_mid[i], ws->mod, base + 3 * D, base + 4 * D, ws->dx, ws->dmod,
+                                                              (const float*)nullptr, 0, (float*)nullptr));
+        // ---- attention branch: x_mid = x_in + g1 * p
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, a.p[i], ws->mod, base + 2 * D, ws->t1, ws->dmod));   // t1 = dp
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, ws->t1, a.o[i], b.proj_w, b.proj_b, M, D, D, st));
+        T2S_TIMED(h, TC_TR_GEMM, st, gemm<128, 1, PRO_PLAIN, EPI_BIAS>(ws->t1, a.wt[i][PROJ], nullptr, a.t4, M, D, st));   // do
+        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, st));
+        T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, a.t3, a.a1[i], b.qkv_w, b.qkv_b, M, 3 * D, D, st));
+        // da1 = dqkv Wqkv (out 128 <- in 384)
+        T2S_TIMED(h, TC_TR_GEMM, st, gemm<384, 1, PRO_PLAIN, EPI_BIAS>(a.t3, a.wt[i][QKV], nullptr, ws->t1, M, D, st));
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
+                         ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_in[i], ws->mod, base + 0 * D, base + 1 * D, ws->dx, ws->dmod,
+                                                              (const float*)nullptr, 0, (float*)nullptr));
+    }
+    return T2S_OK;
+}
+}  // namespace
+
+extern "C" {
 
 int t2s_dit_train_input_grad(t2s_dit* h, float* dinput, int B, void* stream) {
     T2S_REQUIRE(h && dinput, "t2s_dit_train_input_grad: NULL argument");

@@ -11,6 +11,7 @@
 // One kernel per direction (vae_encode_kernel, vae_decode_kernel) serves the single-channel codec (vqvae.py) and the C-channel
 // motion codec (myvqvae.py); vae_interp_rows_kernel finishes a tiled encode; the two backward kernels recompute the forward
 // through the forward's own __device__ pieces (encode_stem, stage_latent, interp_linear_ac, the convolutions).
+#include "t2s_arena.h"
 #include "t2s_wgrad.h"
 
 namespace t2s {
@@ -806,8 +807,6 @@ struct t2s_vae {
 };
 
 namespace {
-size_t r64(size_t n) { return (n + 63) & ~size_t(63); }
-
 struct VaeItem { const float* src; size_t n; const float** dst; };
 
 // every tensor of *w the handle keeps a device copy of, with the VaeDev slot that points at the copy

@@ -8,7 +8,9 @@ wait that counts it; tests/test_isa_pins.py pins exactly that against a toolchai
 
     python tools/isa_report.py [stem ...]        # e.g. t2s_attn t2s_dit
     python tools/isa_report.py --bf16            # the one-plane (T2S_MATH_BF16) kernels next to their bf16x3 forms
+    python tools/isa_report.py --digest [stem | path.o ...]   # per object: SHA-256 of the code object, per kernel of its instructions
 """
+import hashlib
 import os
 import re
 import shutil
@@ -111,8 +113,36 @@ BF16_KERNELS = [("t2s_attn_x3", "attn_fwd_bf16p_kernel"), ("t2s_attn_x3", "attn_
                 ("t2s_dit", "dit_rows_bf16p_kernel"), ("t2s_dit", "dit_rows_x3_kernel")]
 
 
+def digest(obj_path, workdir):
+    """(SHA-256 of the gfx950 code object, [(kernel name, SHA-256 of its (mnemonic, operands) stream)] in code order)"""
+    co = extract_code_object(obj_path, workdir)
+    with open(co, "rb") as f:
+        whole = hashlib.sha256(f.read()).hexdigest()
+    meta, dis = kernel_metadata(co), disassemble(co)
+    kernels = [(name, hashlib.sha256("\n".join(f"{m} {o}" for _, m, o in insts).encode()).hexdigest())
+               for name, insts in dis.items() if name in meta]
+    return whole, kernels
+
+
+def print_digests(args):
+    """--digest [stem | path.o ...]: default every object of t2ms_amd/csrc.  Two builds whose tables agree run the same
+    device code: the check of a host-side change (compare the output of this tree and of the other build's objects)."""
+    csrc = os.path.join(REPO, "t2ms_amd", "csrc")
+    objs = [a if a.endswith(".o") else os.path.join(csrc, a + ".o") for a in args] or \
+        sorted(os.path.join(csrc, f) for f in os.listdir(csrc) if f.endswith(".o"))
+    for obj in objs:
+        with tempfile.TemporaryDirectory() as wd:
+            whole, kernels = digest(obj, wd)
+        print(f"{os.path.basename(obj)} {whole} {len(kernels)} kernels")
+        for name, d in kernels:
+            print(f"    {d[:16]} {name}")
+
+
 if __name__ == "__main__":
     only = None
+    if sys.argv[1:2] == ["--digest"]:
+        print_digests(sys.argv[2:])
+        sys.exit(0)
     if sys.argv[1:] == ["--bf16"]:
         stems, only = ["t2s_attn_x3", "t2s_dit"], BF16_KERNELS
     else:
