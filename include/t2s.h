@@ -632,6 +632,20 @@ int t2s_sampler_set_lanes(t2s_sampler* s, int lanes);
  * the lane's device counter, so both forms run the same kernels in the same order: bitwise the same result.  Takes effect
  * at the next t2s_sampler_run (the graphs are re-captured when the form changes). */
 int t2s_sampler_set_loop_graph(t2s_sampler* s, int whole_loop);
+/* Guidance interval: classifier-free guidance on the window [first, end) of LOOP indices only (j = 0 is the noisiest step of
+ * both backbones; `steps` is the sampler's loop length, i.e. sample_steps with a few-step solver).  A step inside the window
+ * is the step described above: the CFG pass over 2 * batch sequences and pred = u + w (c - u).  Any other step runs ONE DiT
+ * pass over the batch rows with their text and the update takes its output as pred, unchanged (no w = 1 arithmetic): half the
+ * sequences of a guided step.  Noise draws, Philox stream ids, the coefficient row, the few-step solvers' history and the
+ * loop index are those of step j either way; a row's guidance scale (t2s_sampler_set_rows) is not read on an unguided step,
+ * its seed and key row are.  The default window is (0, steps): every step guided, the kernels, launch order and graphs of a
+ * sampler that was never given a window.  Applies to the next runs.  A window that differs from the current one drops the
+ * captured hipGraphs (the whole-loop graph holds each step's kind; the one-step form keeps one graph per kind in use); the
+ * same window again keeps them.  T2S_E_INVALID, with first / end / steps in t2s_last_error and before anything is touched,
+ * unless 0 <= first <= end <= steps.  Not in the reference (Kynkaanniemi et al., NeurIPS 2024). */
+int t2s_sampler_set_guided_steps(t2s_sampler* s, int first, int end);
+/* The current window of t2s_sampler_set_guided_steps. */
+int t2s_sampler_guided_steps(const t2s_sampler* s, int* first, int* end);
 /* Move the sampler to another shard position: global index of its first series (the Philox key of row r is
  * row0 + r).  Takes effect at the next t2s_sampler_run; the captured hipGraphs are kept (the kernels read the
  * value from device memory next to the step counter).  infer.py:66 loops over batches with one sampler. */

@@ -27,6 +27,10 @@ Differences from the reference, all additive:
     run, byte for byte; `ddim` / `dpmpp2m` sample a `--total_step` DDPM checkpoint in S evaluations, `ab2` is a second-order
     step for the flow model; a non-default solver writes to `..._{total_step}_{solver}{S}/`.
 
+  * `--cfg_interval LO,HI`: guidance interval (not in the reference, quality on trained checkpoints not
+    assessed).  Classifier-free guidance on the loop steps `LO*steps <= j < HI*steps` only, the conditional pass alone (half the
+    sequences) on the others; a window short of the whole loop writes to `..._gi{j0}-{j1}/`, after the solver suffix.
+
     python infer.py --dataset_name ETTh1_24,ETTh1_48,ETTh1_96 --cfg_scale 9 --total_step 10 --run_multi True
     python infer.py --dataset_name ETTh1_96 --backbone ddpm --total_step 1000 --solver dpmpp2m --sample_steps 50
 """
@@ -51,7 +55,7 @@ from model.backbone.rectified_flow import RectifiedFlow      # noqa: E402,F401
 from model.denoiser.transformer import Transformer            # noqa: E402
 from t2ms_amd import dist as tdist                            # noqa: E402
 from t2ms_amd import synth                                    # noqa: E402
-from t2ms_amd.sampler import Sampler, np_save_outputs, resolve_solver   # noqa: E402
+from t2ms_amd.sampler import Sampler, np_save_outputs, resolve_cfg_interval, resolve_solver   # noqa: E402
 
 
 def _weight_seed(args):
@@ -176,6 +180,14 @@ def parse_cells(args):
                                          getattr(args, "eta", None), args.total_step)
     if suffix and args.denoiser == "MLP":
         raise ValueError(f"--solver {args.solver} runs in the DiT sampler (--denoiser MLP keeps the reference's loop)")
+    # --cfg_interval LO,HI: guidance on a window of the loop (every cell of the job); the loop is --sample_steps long with a
+    # few-step ddpm solver.  Absent, or the whole loop: every path as it was; else the directory gets "_gi{j0}-{j1}"
+    interval = getattr(args, "cfg_interval", None)
+    if interval is not None and args.denoiser == "MLP":
+        raise ValueError("--cfg_interval runs in the DiT sampler (--denoiser MLP keeps the reference's loop)")
+    loop_steps = args.sample_steps if (suffix and getattr(args, "sample_steps", None) is not None) else args.total_step
+    args.guide_steps, gi_suffix = resolve_cfg_interval(interval, loop_steps)
+    suffix += gi_suffix
     cells = []
     for name in names:
         for shown, cfg in cfgs:
@@ -450,7 +462,7 @@ def sample_grid(args, cells, n_runs):
     held, held_chunks, samplers = [], [], {}
     # the few-step solver of the job (parse_cells resolved it; absent = the backbone's own update, as before)
     solver_kw = dict(solver=getattr(args, "solver", None), sample_steps=getattr(args, "sample_steps", None),
-                     eta=getattr(args, "eta", None) or 0.0)
+                     eta=getattr(args, "eta", None) or 0.0, guide_steps=getattr(args, "guide_steps", None))
     mixed = 0
     t_start = time.time()
 
@@ -617,6 +629,11 @@ def build_parser():
     p.add_argument("--sample_steps", type=int, default=None,
                    help="denoiser evaluations S <= --total_step of --solver ddim / dpmpp2m (default: --total_step)")
     p.add_argument("--eta", type=float, default=None, help="--solver ddim: noise scale (0 = deterministic, the default)")
+    p.add_argument("--cfg_interval", default=None, metavar="LO,HI",
+                   help="guidance interval (DiT only): classifier-free guidance on the loop steps j with LO*steps <= j < HI*steps "
+                        "(fractions of the loop, 0 <= LO <= HI <= 1, j = 0 the noisiest step), the conditional pass alone -- half the "
+                        "sequences -- on the others; applies to every cell of the job.  No counterpart in the reference; a window "
+                        "short of the whole loop adds the suffix _gi{j0}-{j1} to the output directory")
     return p
 
 
@@ -625,6 +642,9 @@ def main(argv=None):
     args.mix_train = False
     try:
         resolve_solver(args.backbone, args.solver, args.sample_steps, args.eta, args.total_step)
+        if args.cfg_interval is not None and args.denoiser == "MLP":
+            raise ValueError("--cfg_interval runs in the DiT sampler (--denoiser MLP keeps the reference's loop)")
+        resolve_cfg_interval(args.cfg_interval, args.sample_steps or args.total_step)
     except ValueError as e:
         sys.exit(f"infer.py: {e}")
     if not torch.cuda.is_available():

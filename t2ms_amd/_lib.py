@@ -259,6 +259,8 @@ SYMBOLS = {
     "t2s_sampler_run": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP]),
     "t2s_sampler_set_lanes": (_I, [_VP, _I]),
     "t2s_sampler_set_loop_graph": (_I, [_VP, _I]),
+    "t2s_sampler_set_guided_steps": (_I, [_VP, _I, _I]),
+    "t2s_sampler_guided_steps": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "t2s_sampler_set_row0": (_I, [_VP, _U32]),
     "t2s_sampler_set_rows": (_I, [_VP, _VP, _VP, _VP, _I]),
     "t2s_philox_normal_rows": (_I, [_VP, _VP, _VP, _U32, _I, _I, _VP]),

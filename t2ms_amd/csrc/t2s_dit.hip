@@ -446,6 +446,16 @@ int dit_forward_cfg_step(t2s_dit* h, const float* x, const float* temb_table, co
                        ws_seq0, mt);
 }
 
+// The conditional branch alone (an unguided step of the sampler, t2s_sampler_set_guided_steps): ONE pass over the B rows
+// with their text -- the same kernels at half the sequences.  Same step_ptr, workspace slot and table as the CFG pass of
+// these rows: the table keeps its (B + 1) rows per step and sequence r reads row 1 + mod_row0 + r (no text-free sequence).
+int dit_forward_cond_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr, const float* text,
+                          float* out, int B, hipStream_t st, int ws_seq0, const float* mod_table, int mod_rows, int mod_row0) {
+    ModTable mt;
+    mt.base = mod_table; mt.rows = mod_rows; mt.row0 = mod_row0;
+    return run_forward(h, x, B, B, 0, temb_table, 1, step_ptr, text, out, nullptr, B, st, /*keep_stream=*/false, ws_seq0, mt);
+}
+
 // The adaLN modulation of EVERY step of a sampling run in one launch: table (steps, B + 1, MODROW), row 0 of a step = the
 // text-free branch (identical for the whole batch), row 1 + b = batch row b.  It depends on the step's time embedding and
 // the text only, never on the state, so it need not sit on the loop's critical path (10 us of a 640 us step at 32 series):
@@ -472,7 +482,8 @@ const char* t2s_last_error(void) { return t2s::g_err; }
 // 0.4: + t2s_time_embedding_freqs, t2s_dit_weights_check, t2s_mse_ws, t2s_vae_update_weights, t2s_vae_encode_backward (additions only)
 // 0.5: + t2s_mlp_pack, t2s_mlp_forward, t2s_mlp_backward (additions only)
 // 0.6: + t2s_dit_create_w, t2s_dit_latent_w, t2s_dit_weights_check_w, t2s_attn_fwd_packed_n, t2s_lms_step_n (additions only)
-const char* t2s_version(void) { return "t2s 0.6 gfx950 fp32-mfma"; }
+// 0.7: + t2s_sampler_set_guided_steps, t2s_sampler_guided_steps (additions only)
+const char* t2s_version(void) { return "t2s 0.7 gfx950 fp32-mfma"; }
 
 int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out) { return t2s_dit_create_w(w, LATW, max_seqs, out); }
 

@@ -88,6 +88,8 @@ int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, fl
 int dit_forward_cfg_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr,
                          const float* text, float* out_u, float* out_c, int B, hipStream_t st, int ws_seq0,
                          const float* mod_table, int mod_rows, int mod_row0);
+int dit_forward_cond_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr, const float* text,
+                          float* out, int B, hipStream_t st, int ws_seq0, const float* mod_table, int mod_rows, int mod_row0);
 int dit_adaln_table(t2s_dit* h, const float* temb_table, int steps, const float* text, int B, float* table, hipStream_t st);
 // t2s_sampler.hip: the library's non-blocking set-up stream and per-device run lock (t2s_sampler_create)
 hipStream_t lib_setup_stream(int dev);

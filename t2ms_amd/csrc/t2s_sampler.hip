@@ -5,7 +5,8 @@
 // One sampling step (2B-sequence DiT forward + CFG combine + sampler update) is captured once
 // into a hipGraph and replayed `steps` times; everything that changes from step to step
 // (time-embedding row, DDPM coefficients, noise stream / injected-noise slice) is looked up on
-// the device through a step counter that the last node of the graph advances.
+// the device through a step counter that the last node of the graph advances.  With a guided window short of the loop
+// (t2s_sampler_set_guided_steps) the steps outside it run the conditional pass alone: a step of a second kind, StepKind.
 #include <cmath>
 #include <cstddef>
 #include <cstring>
@@ -556,8 +557,15 @@ struct t2s_sampler {
     int whole_req = -1;           // t2s_sampler_set_loop_graph: 1 = the WHOLE loop is one graph per lane, 0 = one step, -1 = default
     int whole_cap = 0;            // what the graphs below hold
     static constexpr int MAX_LANES = 4;
-    hipGraph_t graph[MAX_LANES] = {};
-    hipGraphExec_t exec[MAX_LANES] = {};
+    // Guided window [guide_first, guide_end) in loop indices (t2s_sampler_set_guided_steps): step j inside it is the CFG step
+    // (kind STEP_GUIDED), any other step ONE conditional pass over the lane's rows whose output is pred (STEP_COND).  The
+    // default (0, steps) guides every step.
+    int guide_first = 0, guide_end = 0;
+    // graph[k][l]: whole-loop form, k = 0 holds lane l's loop (each step enqueued with its kind); one-step form, k = the
+    // step's kind -- only the kinds the window needs are captured, and the host replays the one that step j needs
+    static constexpr int KINDS = 2;
+    hipGraph_t graph[KINDS][MAX_LANES] = {};
+    hipGraphExec_t exec[KINDS][MAX_LANES] = {};
     hipStream_t side[MAX_LANES] = {};          // lanes 1 .. (index 0 unused: lane 0 runs on the caller's stream); BORROWED
                                                // from the per-device pool below, never destroyed by a sampler
     hipEvent_t ev_fork = nullptr, ev_join[MAX_LANES] = {};
@@ -687,17 +695,27 @@ hipStream_t* lane_streams() {
     return pool[dev];
 }
 
+// The two kinds of step: STEP_GUIDED = the CFG pass over 2n sequences and pred = u + w (c - u); STEP_COND = one pass over
+// the n rows with their text, whose output the update takes as pred unchanged (pred_u = out, pred_c = NULL: no w = 1
+// arithmetic; a row's guidance scale is not read).  Draws, stream ids, coefficient row, history and the advance of the loop
+// index do not depend on the kind.
+enum StepKind { STEP_GUIDED = 0, STEP_COND = 1 };
+inline StepKind step_kind(const t2s_sampler* s, int j) { return (j >= s->guide_first && j < s->guide_end) ? STEP_GUIDED : STEP_COND; }
+
 // one loop iteration of rows [r0, r0 + n) of the batch on stream st, stepping the lane's counter
 int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise, hipStream_t st, int lane, int r0,
-                 int n) {
+                 int n, StepKind kind) {
     const t2s_sample_config& c = s->cfg;
     LoopState* loop = s->step + LANE_STATES * lane;
     const size_t lat = (size_t)s->lat;   // the sampler's row length
     float* xl = x + (size_t)r0 * lat;
     float* eu = s->eps_u + (size_t)r0 * lat;
-    float* ec = s->eps_c + (size_t)r0 * lat;
-    int rc = dit_forward_cfg_step(s->dit, xl, s->temb_table, &loop->index, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
-                                  s->mod_table, c.batch + 1, r0);
+    float* ec = kind == STEP_GUIDED ? s->eps_c + (size_t)r0 * lat : nullptr;
+    int rc = kind == STEP_GUIDED
+                 ? dit_forward_cfg_step(s->dit, xl, s->temb_table, &loop->index, text + (size_t)r0 * D, eu, ec, n, st, 2 * r0,
+                                        s->mod_table, c.batch + 1, r0)
+                 : dit_forward_cond_step(s->dit, xl, s->temb_table, &loop->index, text + (size_t)r0 * D, eu, n, st, 2 * r0,
+                                         s->mod_table, c.batch + 1, r0);
     if (rc != T2S_OK) return rc;
     UpdateArgs a{};
     a.x = xl; a.pred_u = eu; a.pred_c = ec; a.noise = noise ? noise + (size_t)r0 * lat : nullptr; a.coef = s->coef;
@@ -722,14 +740,17 @@ int enqueue_step(t2s_sampler* s, float* x, const float* text, const float* noise
 inline int loop_graph_default(int steps) { return steps <= 256; }
 
 void drop_graph(t2s_sampler* s) {
-    for (int l = 0; l < t2s_sampler::MAX_LANES; ++l) {
-        if (s->exec[l]) (void)hipGraphExecDestroy(s->exec[l]);
-        if (s->graph[l]) (void)hipGraphDestroy(s->graph[l]);
-        s->exec[l] = nullptr;
-        s->graph[l] = nullptr;
-    }
+    for (int k = 0; k < t2s_sampler::KINDS; ++k)
+        for (int l = 0; l < t2s_sampler::MAX_LANES; ++l) {
+            if (s->exec[k][l]) (void)hipGraphExecDestroy(s->exec[k][l]);
+            if (s->graph[k][l]) (void)hipGraphDestroy(s->graph[k][l]);
+            s->exec[k][l] = nullptr;
+            s->graph[k][l] = nullptr;
+        }
     s->lanes_cap = 0;
 }
+
+inline bool has_graphs(const t2s_sampler* s) { return s->exec[STEP_GUIDED][0] || s->exec[STEP_COND][0]; }
 
 // lanes of this run: as asked for, or automatically EQUAL shares of whole 32-row groups: two for a batch that is a
 // multiple of 64 (and 16 + 16 for 32 series), three for 96.  Measured with the round-3 kernels (tools/strong_probe.py,
@@ -779,6 +800,7 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
     std::lock_guard<std::recursive_mutex> pool_lock(g_pool_use[cur_dev]);
     t2s_sampler* s = new t2s_sampler();
     s->dit = dit; s->vae = vae; s->cfg = *cfg; s->lat = LATC * latw;
+    s->guide_first = 0; s->guide_end = cfg->steps;     // every step guided
     const size_t lat = (size_t)s->lat;
     s->cfg.ddpm_coef = nullptr; s->cfg.t_values = nullptr;  // host pointers are not retained
     const size_t B = (size_t)cfg->batch, T = (size_t)cfg->steps;
@@ -876,6 +898,28 @@ extern "C" int t2s_sampler_set_loop_graph(t2s_sampler* s, int whole_loop) {
     return T2S_OK;
 }
 
+extern "C" int t2s_sampler_set_guided_steps(t2s_sampler* s, int first, int end) {
+    T2S_REQUIRE(s, "t2s_sampler_set_guided_steps: NULL sampler");
+    T2S_REQUIRE(0 <= first && first <= end && end <= s->cfg.steps,
+                "t2s_sampler_set_guided_steps: first=%d end=%d must satisfy 0 <= first <= end <= steps=%d", first, end, s->cfg.steps);
+    if (first == s->guide_first && end == s->guide_end) return T2S_OK;    // unchanged: the captured graphs stay
+    // the graphs hold the kinds of the old window (destroying them waits for no stream: same lock as a run's capture)
+    int cur_dev = 0;
+    std::unique_lock<std::recursive_mutex> pool_lock;
+    if (hipGetDevice(&cur_dev) == hipSuccess && cur_dev >= 0 && cur_dev < 16) pool_lock = std::unique_lock<std::recursive_mutex>(g_pool_use[cur_dev]);
+    drop_graph(s);
+    s->guide_first = first;
+    s->guide_end = end;
+    return T2S_OK;
+}
+
+extern "C" int t2s_sampler_guided_steps(const t2s_sampler* s, int* first, int* end) {
+    T2S_REQUIRE(s && first && end, "t2s_sampler_guided_steps: NULL argument");
+    *first = s->guide_first;
+    *end = s->guide_end;
+    return T2S_OK;
+}
+
 extern "C" int t2s_sampler_set_row0(t2s_sampler* s, uint32_t row0) {
     T2S_REQUIRE(s, "t2s_sampler_set_row0: NULL sampler");
     s->cfg.row0 = row0;   // uploaded next to the step counters at the start of every run: no re-capture
@@ -905,7 +949,7 @@ extern "C" int t2s_sampler_lane_pool(void) {
     return g_lane_pool_concurrent[dev];
 }
 
-extern "C" int t2s_sampler_graph_lanes(const t2s_sampler* s) { return (s && s->exec[0]) ? s->lanes_cap : 0; }
+extern "C" int t2s_sampler_graph_lanes(const t2s_sampler* s) { return (s && has_graphs(s)) ? s->lanes_cap : 0; }
 
 extern "C" void t2s_sampler_destroy(t2s_sampler* s) {
     if (!s) return;
@@ -1003,25 +1047,32 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         const char* e = getenv("T2S_SAMPLER_LOOP_GRAPH");
         whole = e ? (atoi(e) != 0) : loop_graph_default(c.steps);
     }
-    if (graph_ok && (!s->exec[0] || s->lanes_cap != lanes || s->whole_cap != whole || s->g_x != x || s->g_text != text ||
+    // (a changed guided window has dropped the graphs: t2s_sampler_set_guided_steps)
+    if (graph_ok && (!has_graphs(s) || s->lanes_cap != lanes || s->whole_cap != whole || s->g_x != x || s->g_text != text ||
                      s->g_noise != noise)) {
         drop_graph(s);
-        for (int l = 0; l < lanes; ++l) {
-            T2S_HIP_CHECK(hipStreamBeginCapture(lst[l], hipStreamCaptureModeThreadLocal));
-            rc = T2S_OK;
-            for (int j = 0; j < (whole ? c.steps : 1) && rc == T2S_OK; ++j) rc = enqueue_step(s, x, text, noise, lst[l], l, r0[l], nr[l]);
-            hipError_t e = hipStreamEndCapture(lst[l], &s->graph[l]);
-            if (rc != T2S_OK) {
-                drop_graph(s);
-                return rc;
+        // whole loop: one graph per lane (slot 0), step j enqueued with the kind of j; one step: a graph per kind that the
+        // window needs -- with the default window the guided one alone, as before there were kinds
+        const bool need[t2s_sampler::KINDS] = {s->guide_first < s->guide_end, s->guide_first > 0 || s->guide_end < c.steps};
+        for (int l = 0; l < lanes; ++l)
+            for (int k = 0; k < (whole ? 1 : t2s_sampler::KINDS); ++k) {
+                if (!whole && !need[k]) continue;
+                T2S_HIP_CHECK(hipStreamBeginCapture(lst[l], hipStreamCaptureModeThreadLocal));
+                rc = T2S_OK;
+                for (int j = 0; j < (whole ? c.steps : 1) && rc == T2S_OK; ++j)
+                    rc = enqueue_step(s, x, text, noise, lst[l], l, r0[l], nr[l], whole ? step_kind(s, j) : (StepKind)k);
+                hipError_t e = hipStreamEndCapture(lst[l], &s->graph[k][l]);
+                if (rc != T2S_OK) {
+                    drop_graph(s);
+                    return rc;
+                }
+                if (e != hipSuccess) {
+                    set_error("t2s_sampler_run: hipStreamEndCapture failed: %s", hipGetErrorString(e));
+                    drop_graph(s);
+                    return T2S_E_HIP;
+                }
+                T2S_HIP_CHECK(hipGraphInstantiate(&s->exec[k][l], s->graph[k][l], nullptr, nullptr, 0));
             }
-            if (e != hipSuccess) {
-                set_error("t2s_sampler_run: hipStreamEndCapture failed: %s", hipGetErrorString(e));
-                drop_graph(s);
-                return T2S_E_HIP;
-            }
-            T2S_HIP_CHECK(hipGraphInstantiate(&s->exec[l], s->graph[l], nullptr, nullptr, 0));
-        }
         s->lanes_cap = lanes;
         s->whole_cap = whole;
         s->g_x = x; s->g_text = text; s->g_noise = noise;
@@ -1047,12 +1098,13 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         T2S_LAUNCH_CHECK();
     }
     if (graph_ok && whole)
-        for (int l = 0; l < lanes; ++l) T2S_HIP_CHECK(hipGraphLaunch(s->exec[l], lst[l]));
+        for (int l = 0; l < lanes; ++l) T2S_HIP_CHECK(hipGraphLaunch(s->exec[0][l], lst[l]));
     for (int j = 0; j < c.steps && !(graph_ok && whole); ++j) {
+        const StepKind kind = step_kind(s, j);     // (the host's j is the lanes' device loop index: every step advances it by one)
         for (int l = 0; l < lanes; ++l) {
             if (graph_ok) {
-                T2S_HIP_CHECK(hipGraphLaunch(s->exec[l], lst[l]));
-            } else if ((rc = enqueue_step(s, x, text, noise, lst[l], l, r0[l], nr[l])) != T2S_OK) {
+                T2S_HIP_CHECK(hipGraphLaunch(s->exec[kind][l], lst[l]));
+            } else if ((rc = enqueue_step(s, x, text, noise, lst[l], l, r0[l], nr[l], kind)) != T2S_OK) {
                 return rc;
             }
         }

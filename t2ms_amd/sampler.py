@@ -11,6 +11,8 @@ from __future__ import annotations
 import ctypes as C
 import os
 import weakref
+from fractions import Fraction
+from math import ceil as _ceil
 from typing import Optional
 
 import numpy as np
@@ -176,6 +178,56 @@ def solver_tables(backbone: str, solver: str, total_step: int, sample_steps: Opt
     return torch.from_numpy(tau.astype(np.float32)), torch.from_numpy(c32)
 
 
+def _fraction(v, what: str) -> Fraction:
+    """The exact value a float, an int, a Fraction or a decimal string WRITES: Fraction(str(v)) for floats and strings, so
+    0.7 is 7/10 and not the binary 0.6999999999999999556."""
+    try:
+        if isinstance(v, bool):
+            raise ValueError
+        f = v if isinstance(v, Fraction) else Fraction(v) if isinstance(v, int) else Fraction(str(v).strip())
+    except (ValueError, ZeroDivisionError):
+        raise ValueError(f"cfg interval: {what} = {v!r} is not a number") from None
+    return f
+
+
+def guided_steps(interval, steps: int):
+    """The guided window (j0, j1) in loop indices of interval = (lo, hi), fractions of a loop of `steps` iterations with
+    0 <= lo <= hi <= 1: step j (j = 0 the noisiest) runs classifier-free guidance iff lo*steps <= j < hi*steps, i.e.
+    j0 = ceil(lo*steps), j1 = ceil(hi*steps); every other step runs the conditional pass alone (t2s_sampler_set_guided_steps).
+    Evaluated exactly in rationals from the decimal text of lo / hi (floats and command-line strings alike), never by float
+    multiplication: (0.07, 0.5) of 100 steps is (7, 50), where ceil(0.07 * 100 = 7.000000000000001) would give 8.
+    ValueError outside that range, for lo > hi or steps < 1."""
+    try:
+        lo, hi = interval
+    except (TypeError, ValueError):
+        raise ValueError(f"cfg interval must be a pair (lo, hi), got {interval!r}") from None
+    steps = int(steps)
+    if steps < 1:
+        raise ValueError(f"cfg interval: steps must be >= 1, got {steps}")
+    lo, hi = _fraction(lo, "lo"), _fraction(hi, "hi")
+    if not 0 <= lo <= hi <= 1:
+        raise ValueError(f"cfg interval must satisfy 0 <= lo <= hi <= 1, got lo = {interval[0]}, hi = {interval[1]}")
+    return _ceil(lo * steps), _ceil(hi * steps)
+
+
+def parse_cfg_interval(text: str):
+    """--cfg_interval LO,HI -> (lo, hi) as exact Fractions; ValueError for anything else."""
+    parts = str(text).split(",")
+    if len(parts) != 2:
+        raise ValueError(f"--cfg_interval takes LO,HI (two fractions of the loop, e.g. 0.2,0.8), got {text!r}")
+    return _fraction(parts[0], "lo"), _fraction(parts[1], "hi")
+
+
+def resolve_cfg_interval(text, steps: int):
+    """The drivers' --cfg_interval LO,HI against a loop of `steps` iterations -> (guided window or None, directory suffix).
+    Without the flag: (None, ""), every path as before.  With it: the window of guided_steps, and the suffix "_gi{j0}-{j1}"
+    unless the window is the whole loop (the run is then today's run and keeps today's directory)."""
+    if text is None:
+        return None, ""
+    j0, j1 = guided_steps(parse_cfg_interval(text), steps)
+    return (j0, j1), ("" if (j0, j1) == (0, int(steps)) else f"_gi{j0}-{j1}")
+
+
 _STREAMS = {}
 
 
@@ -299,7 +351,8 @@ def lms_step(x: torch.Tensor, hist: torch.Tensor, pred_u: torch.Tensor, pred_c: 
 class Sampler:
     def __init__(self, model, decoder, backbone: str, steps: int, cfg_scale: float, batch: int, length: int,
                  device, use_graph: bool = True, seed: int = 2025, row0: int = 0, lanes: int = 0, loop_graph: int = -1,
-                 math: Optional[str] = None, solver: Optional[str] = None, sample_steps: Optional[int] = None, eta: float = 0.0):
+                 math: Optional[str] = None, solver: Optional[str] = None, sample_steps: Optional[int] = None, eta: float = 0.0,
+                 guide_steps=None, cfg_interval=None):
         """lanes: 0 = automatic (equal part-batch chains on own streams: two when the batch is a multiple of 64 or 32 series, three for 96), 1 .. 4 -- see
         t2s_sampler_set_lanes; a scheduling choice only, the results are bitwise the same.
         math: "f32" | "bf16x3" | "bf16" (single-pass bf16 mixed precision: opt-in, not fp32-accurate) selects the model's matrix arithmetic (Transformer.set_math) for this sampler and everything else
@@ -308,7 +361,10 @@ class Sampler:
         the solvers existed; "ddim" / "dpmpp2m" (ddpm) and "ab2" (flowmatching) = the few-step solvers of solver_tables
         (t2s_sampler_create_lms).  `steps` stays the TRAINED schedule length (--total_step); with a ddpm solver the loop runs
         sample_steps (default: steps) denoiser evaluations and self.steps becomes that S -- the first dimension of `noise`.
-        eta: ddim's stochasticity (0 = deterministic)."""
+        eta: ddim's stochasticity (0 = deterministic).
+        guide_steps = (j0, j1) / cfg_interval = (lo, hi): the guided window (at most one of the two; None = every step) in
+        loop indices of self.steps / as fractions of the loop (guided_steps) -- classifier-free guidance on steps j0 <= j < j1,
+        the conditional pass alone on the others, which run half the sequences (set_guided_steps).  Not in the reference."""
         self.device = torch.device(device)
         if self.device.type != "cuda":
             raise L.T2SError("Sampler needs a GPU device; the HIP path has no CPU fallback")
@@ -334,6 +390,11 @@ class Sampler:
         elif sample_steps is not None or self.eta != 0.0:
             raise ValueError(f"sample_steps / eta need a few-step solver ({', '.join(SOLVERS.get(backbone, ('?',))[1:])}); "
                              f"{default_solver(backbone)!r} runs the trained schedule")
+        if guide_steps is not None and cfg_interval is not None:
+            raise ValueError("give guide_steps (loop indices) or cfg_interval (fractions of the loop), not both")
+        if cfg_interval is not None:
+            guide_steps = guided_steps(cfg_interval, self.steps)
+        self._guided = (0, self.steps) if guide_steps is None else self._check_window(*guide_steps)
         self.batch, self.length, self.seed, self.row0 = int(batch), int(length), int(seed), int(row0)
         self.use_graph = bool(use_graph)
         self.lanes = int(lanes)
@@ -382,7 +443,32 @@ class Sampler:
         self._fin = weakref.finalize(self, L.destroy_locked, "t2s_sampler_destroy", str(self.device), self.ptr)
         if self.__dict__.get("_rows") is not None:      # a re-created C sampler keeps the per-row tables
             self.set_rows(*self._rows)
+        if self._guided != (0, self.steps):             # ... and the guided window (a new C sampler guides every step)
+            L.check(L.lib().t2s_sampler_set_guided_steps(self.ptr, *self._guided), "t2s_sampler_set_guided_steps")
         self._keep = (tvals, coef)
+
+    def _check_window(self, j0, j1):
+        j0, j1 = int(j0), int(j1)
+        if not 0 <= j0 <= j1 <= self.steps:
+            raise ValueError(f"guided steps must satisfy 0 <= j0 <= j1 <= steps = {self.steps}, got ({j0}, {j1})")
+        return j0, j1
+
+    def set_guided_steps(self, j0: int, j1: int):
+        """Classifier-free guidance on loop indices j0 <= j < j1 for the NEXT runs, the conditional pass alone on the others
+        (t2s_sampler_set_guided_steps; (0, steps) = every step).  A window that differs from the current one drops the
+        captured hipGraphs; the library refuses, and changes nothing, unless 0 <= j0 <= j1 <= steps."""
+        with L.device_lock(self.device):
+            if (int(j0), int(j1)) != self._guided:
+                self.stream.synchronize()       # a graph the last run launched is not destroyed under it
+            L.check(L.lib().t2s_sampler_set_guided_steps(self.ptr, int(j0), int(j1)), "t2s_sampler_set_guided_steps")
+            self._guided = (int(j0), int(j1))
+
+    @property
+    def guided(self):
+        """The guided window (j0, j1) in loop indices, as the C sampler holds it."""
+        j0, j1 = C.c_int(), C.c_int()
+        L.check(L.lib().t2s_sampler_guided_steps(self.ptr, C.byref(j0), C.byref(j1)), "t2s_sampler_guided_steps")
+        return j0.value, j1.value
 
     def set_row0(self, row0: int):
         """Global index of this shard's first series for the NEXT run (the Philox key of row r is row0 + r);
