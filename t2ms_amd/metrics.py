@@ -23,6 +23,7 @@ import torch
 import ctypes as C
 
 from . import _lib as L
+from ._handle import HandleOwner
 
 
 def mse_wape(ori, gen, device="cuda"):
@@ -380,11 +381,11 @@ def _encode_chunks(B, T, hidden, output_dims, depth, cap=None):
     return [(r0, min(rows, B - r0)) for r0 in range(0, B, rows)]
 
 
-class TS2VecEncoder:
+class TS2VecEncoder(HandleOwner):
     """Forward of evaluate/ts2vec.py's TSEncoder (:352-399, eval mode, mask 'all_true') on the GPU from its state dict
     (keys input_fc.*, feature_extractor.net.<i>.conv{1,2}.conv.*, feature_extractor.net.<depth>.projector.*).  Series
     whose three activation planes fit the LDS of a CU run on t2s_ts2vec_encode, longer ones (up to 4096 steps) on
-    t2s_ts2vec_encode_long with a workspace this object owns."""
+    t2s_ts2vec_encode_long with a workspace this object owns (HandleOwner._workspace)."""
 
     def __init__(self, state_dict, device="cuda"):
         self.device = _gpu(device, "TS2VecEncoder")
@@ -408,7 +409,6 @@ class TS2VecEncoder:
         p = f"feature_extractor.net.{depth}.projector."
         w.proj_w, w.proj_b = sd[p + "weight"].data_ptr(), sd[p + "bias"].data_ptr()
         self._w, self._keep = w, sd
-        self._ws = None                  # workspace of the long path, grown on demand
 
     def _workspace_bytes(self, rows, T):
         need = L.lib().t2s_ts2vec_encode_workspace_bytes(C.byref(self._w), rows, T)
@@ -440,15 +440,12 @@ class TS2VecEncoder:
         chunks = _encode_chunks(B, T, self._w.hidden, cout, self._w.depth)
         need = max(self._workspace_bytes(rows, T) for _, rows in chunks)
         with torch.cuda.device(self.device):
-            if self._ws is None or self._ws.numel() < need:
-                with L.device_lock(self.device):
-                    self._ws = None
-                    self._ws = torch.empty(need, dtype=torch.uint8, device=self.device)
+            ws = self._workspace(need, self.device)          # the long path's, grown on demand
             for r0, rows in chunks:
                 L.check(L.lib().t2s_ts2vec_encode_long(
                     C.byref(self._w), xs.data_ptr() + 4 * r0 * T * cin,
                     None if rep is None else rep.data_ptr() + 4 * r0 * T * cout, full.data_ptr() + 4 * r0 * cout,
-                    rows, T, self._ws.data_ptr(), self._ws.numel(), L.stream_ptr(self.device)), "t2s_ts2vec_encode_long")
+                    rows, T, ws.data_ptr(), ws.numel(), L.stream_ptr(self.device)), "t2s_ts2vec_encode_long")
         return full if rep is None else rep
 
 

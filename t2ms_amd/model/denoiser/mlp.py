@@ -21,6 +21,7 @@ import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import _handle as H
 from ... import _lib as L
 
 WIDTH, POSITIONS, TEXT_DIM, HEADS = 64, 6, 128, 4
@@ -42,6 +43,16 @@ def _freqs_on(device):
     if f is None:
         f = _FREQS[device] = torch.pow(10000, torch.linspace(0, 1, WIDTH // 2)).to(device)
     return f
+
+
+def _layer_struct(struct, ts, keep, name=None):
+    """A t2s_mlp_weights / t2s_mlp_grads over `ts` (_hip_tensors order).  name(layer, state-dict key) titles a tensor in
+    L.dev_ptr's T2SError; without it the addresses are taken unchecked (H.fill)."""
+    s, n = struct(), len(L.MLP_LAYER_FIELDS)
+    for i in range(L.MLP_LAYERS):
+        fields = zip(L.MLP_LAYER_FIELDS, ts[n * i: n * i + n])
+        H.fill(s.layer[i], [(f, t, name(i, key)) if name else (f, t) for (f, key), t in fields], keep)
+    return s
 
 
 class TimeEmbedding(nn.Module):
@@ -146,25 +157,16 @@ class MLP(nn.Module):
     def _packed(self, device):
         """The transposed weights `t2s_mlp_forward` reads, re-packed whenever a parameter's storage or in-place version
         changed (optimizer steps, load_state_dict, .to()); never cached for parameters torch keeps no version for."""
-        from .transformer import _stamp_of
         ts = self._hip_tensors()
-        stamp = _stamp_of(ts)
-        cached = self.__dict__.get("_t2s_packed")
-        if cached is not None and stamp is not None and cached[0] == device and cached[1] == stamp:
-            return cached[2]
+        stamp = H.stamp_of(ts)
+        packed = H.cached(self, "_t2s_packed", device, stamp)
+        if packed is not None:
+            return packed
         if len(self.layers) != L.MLP_LAYERS:
             raise L.T2SError(f"t2s_mlp_forward is built for {L.MLP_LAYERS} layers, this model has {len(self.layers)}")
-        keep = []
-        w = L.MlpWeights()
-        it = iter(ts)
-        for i in range(L.MLP_LAYERS):
-            for field, key in L.MLP_LAYER_FIELDS:
-                t = next(it)
-                if t.device != device:
-                    raise L.T2SError(f"MLP parameters live on {t.device} but the input is on {device}; call model.to(device) first")
-                t = L.as_f32(t.detach())
-                keep.append(t)
-                setattr(w.layer[i], field, L.dev_ptr(t, f"layers.{i}.{key}"))
+        H.require_on(ts, device, "MLP", "; call model.to(device) first")
+        keep = []          # (alive until the pack is enqueued)
+        w = _layer_struct(L.MlpWeights, ts, keep, lambda i, key: f"layers.{i}.{key}")
         packed = torch.empty(L.MLP_PACKED_FLOATS, dtype=torch.float32, device=device)
         with torch.cuda.device(device):
             L.check(L.lib().t2s_mlp_pack(w, packed.data_ptr(), L.stream_ptr(device)), "t2s_mlp_pack")
@@ -212,15 +214,10 @@ class _MlpFn(torch.autograd.Function):
         model, dev, B = ctx.model, x.device, x.shape[0]
         packed = model._packed(dev)                                   # the forward's weights: no step happens in between
         ts = model._hip_tensors()
-        keep, w, g = [], L.MlpWeights(), L.MlpGrads()
         grads = [torch.empty_like(p, dtype=torch.float32, memory_format=torch.contiguous_format) for p in ts]
-        it, ig = iter(ts), iter(grads)
-        for i in range(L.MLP_LAYERS):
-            for field, _ in L.MLP_LAYER_FIELDS:
-                src = L.as_f32(next(it).detach())
-                keep.append(src)
-                setattr(w.layer[i], field, L.dev_ptr(src))
-                setattr(g.layer[i], field, next(ig).data_ptr())
+        keep = []
+        w = _layer_struct(L.MlpWeights, ts, keep, lambda i, key: "tensor")          # (L.dev_ptr's own title, as before)
+        g = _layer_struct(L.MlpGrads, grads, keep)                                  # fresh fp32 tensors: bare addresses
         need_dx = ctx.needs_input_grad[1]
         dx = torch.empty_like(x) if need_dx else None
         scratch = torch.empty(B * L.MLP_GRAD_PART_FLOATS, dtype=torch.float32, device=dev)

@@ -10,14 +10,13 @@ the network, and there is no CPU fallback.
 from __future__ import annotations
 
 import ctypes as C
-import itertools
 import os
 import math
-import weakref
 
 import torch
 import torch.nn as nn
 
+from ... import _handle as H
 from ... import _lib as L
 
 __all__ = ["Transformer", "Transformerlayer", "TimeEmbedding", "modulate",
@@ -140,28 +139,7 @@ def _freqs_on(device) -> torch.Tensor:
     return _FREQS[key]
 
 
-_HANDLE_IDS = itertools.count(1)
-
-
-class _DitHandle:
-    """Owns one t2s_dit (packed weights + workspace) for one module on one device.  `uid` identifies THIS handle
-    for the life of the process: a re-created handle often gets the freed one's address back, so users that cache
-    state bound to a handle (Sampler's captured hipGraph, a pending backward) compare uids, never pointers."""
-
-    def __init__(self, weights: L.DitWeights, keep, max_seqs: int, latent_w: int = LAT_H):
-        self.uid = next(_HANDLE_IDS)
-        self.ptr = C.c_void_p()
-        self.keep = keep
-        self.max_seqs = max_seqs
-        L.check(L.lib().t2s_dit_create_w(C.byref(weights), latent_w, max_seqs, C.byref(self.ptr)), "t2s_dit_create_w")
-        dev = f"cuda:{torch.cuda.current_device()}"          # created under torch.cuda.device(device)
-        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_dit_destroy", dev, self.ptr)
-
-    def close(self):
-        self._fin()
-
-
-class Transformer(nn.Module):
+class Transformer(H.HandleOwner, nn.Module):
     """Drop-in for ``model.denoiser.transformer.Transformer`` (transformer.py:128-204).  `dim` is the reference's
     ``self.H``, the latent width: this class is also the body of ``model.denoiser.mytransformer.Transformer(dim)`` (the
     motion models' denoiser, mytransformer.py:128-204 -- the same network over a (B,64,dim) latent, 16 * dim tokens)."""
@@ -220,26 +198,18 @@ class Transformer(nn.Module):
         is handed back (the reference-style loop calls the model twice per diffusion step: building 49 detached views
         and 59 ctypes fields each time cost 150 us of host time per forward, more than a small batch's kernels)."""
         ts = self._dit_tensors()
-        stamp = _stamp_of(ts)
-        cached = self.__dict__.get("_t2s_ws")
-        if cached is not None and stamp is not None and cached[0] == device and cached[3] == stamp:
-            return cached[1], cached[2], stamp
-        for t in ts:
-            if t.device != device:
-                raise L.T2SError(f"Transformer parameters live on {t.device} but the input is on {device}; "
-                                 f"call model.to(device) first")
-        keep = [L.as_f32(t.detach()) for t in ts]
-        for t in keep:
-            L.dev_ptr(t, "Transformer parameter")          # on a GPU, fp32, contiguous -- or T2SError
-        w = L.DitWeights()
+        stamp = H.stamp_of(ts)
+        cached = H.cached(self, "_t2s_wstruct", device, stamp)
+        if cached is not None:
+            return (*cached, stamp)
+        H.require_on(ts, device, "Transformer", "; call model.to(device) first")
+        w, keep, who = L.DitWeights(), [], ["Transformer parameter"] * 10          # on a GPU, fp32, contiguous -- or T2SError
         names = [n for n, _ in L.DitWeights._fields_ if n not in ("blk", "time_freqs")]
-        for n, t in zip(names, keep[:9]):
-            setattr(w, n, t.data_ptr())
+        H.fill(w, zip(names, ts[:9], who), keep)
         w.time_freqs = _freqs_on(device).data_ptr()
         bnames = [n for n, _ in L.DitBlockWeights._fields_]
         for i in range(DEPTH):
-            for n, t in zip(bnames, keep[9 + 10 * i: 19 + 10 * i]):
-                setattr(w.blk[i], n, t.data_ptr())
+            H.fill(w.blk[i], zip(bnames, ts[9 + 10 * i: 19 + 10 * i], who), keep)
         # the C ABI carries no sizes: hand over every tensor's float count in t2s_dit_weights order (time_freqs is field 9) so an
         # undersized parameter (a foreign checkpoint assigned tensor by tensor, a sliced view) is T2S_E_INVALID with the
         # state-dict key in the message -- not an out-of-bounds read in a pack kernel
@@ -248,36 +218,34 @@ class Transformer(nn.Module):
             L.check(L.lib().t2s_dit_weights_check_w(C.byref(w), self.H, (C.c_uint64 * L.DIT_N_TENSORS)(*counts), L.DIT_N_TENSORS),
                     "t2s_dit_weights_check_w")
         if all(k.data_ptr() == t.data_ptr() for k, t in zip(keep, ts)):      # fp32 contiguous parameters: no copies made
-            self.__dict__["_t2s_ws"] = (device, w, keep, stamp)
+            self.__dict__["_t2s_wstruct"] = (device, stamp, (w, keep))
         return w, keep, stamp
 
+    def _build(self, device, w, keep, cap):
+        h = H.Handle(device, "t2s_dit_create_w", "t2s_dit_destroy", C.byref(w), self.H, cap)
+        h.max_seqs, h.keep = cap, keep
+        self.__dict__.pop("_t2s_math_applied", None)          # a new handle starts in f32
+        return h
+
+    def _refresh(self, h, device, w, keep, cap):
+        L.check(L.lib().t2s_dit_update_weights(h.ptr, C.byref(w), L.stream_ptr(device)), "t2s_dit_update_weights")
+        return keep
+
     def t2s_handle(self, device, n_seqs: int, headroom: bool = False):
-        """(Re)build or refresh the packed-weight handle: weights are re-packed whenever a parameter
-        was modified in place (optimizer step, load_state_dict) or re-allocated (.to()).
+        """(Re)build or refresh the packed-weight handle (HandleOwner._owned_handle): weights are re-packed whenever a
+        parameter was modified in place (optimizer step, load_state_dict) or re-allocated (.to()); the handle is rebuilt for
+        another device or more than its max_seqs sequences, and its capacity never shrinks.
         `headroom` (the training path): when the handle has to GROW, size it 12.5 % above the request -- the length groups
         of a mix-train batch fluctuate from step to step, and every rebuild is a device-wide free + multi-GB allocation."""
         device = torch.device(device)
         w, keep, stamp = self._weights_struct(device)
         h = self.__dict__.get("_t2s_h")
-        if h is None or self.__dict__.get("_t2s_dev") != device or h.max_seqs < n_seqs:
-            # a device synchronisation, frees and allocations: under the package's per-device lock, i.e. never while another
-            # thread's sampler run has a capture open (HIP would fail this call AND invalidate that capture, _lib.device_lock)
-            with L.device_lock(device):
-                if h is not None:
-                    h.close()
-                cap = max(n_seqs, h.max_seqs if h is not None else 0)
-                if headroom:
-                    cap = max(cap, (n_seqs + n_seqs // 8 + 63) // 64 * 64)
-                torch.cuda.synchronize(device)
-                with torch.cuda.device(device):
-                    h = _DitHandle(w, keep, cap, self.H)
-            self.__dict__["_t2s_h"], self.__dict__["_t2s_dev"], self.__dict__["_t2s_stamp"] = h, device, stamp
-            self.__dict__.pop("_t2s_math_applied", None)
-        elif stamp is None or self.__dict__.get("_t2s_stamp") != stamp:
-            L.check(L.lib().t2s_dit_update_weights(h.ptr, C.byref(w), L.stream_ptr(device)),
-                    "t2s_dit_update_weights")
-            h.keep = keep
-            self.__dict__["_t2s_stamp"] = stamp
+        cap = h.max_seqs if h is not None else 0
+        if h is None or h.device != device or cap < n_seqs:
+            cap = max(n_seqs, cap)
+            if headroom:
+                cap = max(cap, (n_seqs + n_seqs // 8 + 63) // 64 * 64)
+        h = self._owned_handle(device, (device, cap), stamp, self._build, self._refresh, device, w, keep, cap)
         math = self.__dict__.get("_t2s_math", "f32")
         if self.H != LAT_H and math != "f32":          # (set_math refuses it; a pickled or hand-set attribute ends here)
             raise L.T2SError(f"Transformer(dim={self.H}) runs math 'f32' only, got {math!r}")
@@ -327,12 +295,9 @@ class Transformer(nn.Module):
         self.__dict__["_t2s_train_dtype"] = dtype
         return self
 
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        for k in ("_t2s_h", "_t2s_dev", "_t2s_stamp", "_t2s_math_applied", "_t2s_bucket", "_t2s_flat_grad", "_t2s_fwd_gen",
-                  "_t2s_ws", "_t2s_pair", "_t2s_pairing"):
-            state.pop(k, None)
-        return state
+    # (_t2s_math and _t2s_train_dtype are settings: they travel with a pickle)
+    _t2s_transient = H.HandleOwner._t2s_transient + ("_t2s_math_applied", "_t2s_bucket", "_t2s_flat_grad", "_t2s_fwd_gen",
+                                                     "_t2s_wstruct", "_t2s_pair", "_t2s_pairing")
 
     # ---------------------------------------------------------------- forward (transformer.py:158-193)
     def forward(self, input: torch.Tensor, t: torch.Tensor, text_input):
@@ -424,15 +389,7 @@ class Transformer(nn.Module):
         return out
 
     def _param_stamp(self):
-        return _stamp_of(self._dit_tensors())
-
-
-def _stamp_of(ts):
-    """(data_ptr, in-place version) per tensor, or None when torch keeps no version counter for one of them (parameters
-    created under torch.inference_mode()): nothing can then be cached against the stamp -- every call re-packs."""
-    if any(t.is_inference() for t in ts):
-        return None
-    return tuple([(t.data_ptr(), t._version) for t in ts])
+        return H.stamp_of(self._dit_tensors())
 
 
 def _tensor_key(t):

@@ -2,7 +2,7 @@
 C-channel motion codec, latent width ``flow_dim``) share.  Both families run the same kernels of csrc/t2s_vae.hip over the
 same handle; the single-channel codec is its C = 1 case.
 
-Here: the handle and its cache (_VaeHandle, _Codec), the weight and gradient lists, the HIP forwards with their autograd nodes
+Here: the handle's recipe (_Codec over _handle.HandleOwner), the weight and gradient lists, the HIP forwards with their autograd nodes
 (_EncodeFn / _DecodeFn over _vae_backward), the torch-op forwards for what the HIP backward does not cover, the coverage
 predicate (_backward_covers), the switches (_torch_forced) and the routing between the three forwards (_route).  A family
 supplies its entries (_entries), the encoder's latent width (_width) and series layout (_series), the decoder's last torch-op
@@ -14,12 +14,12 @@ from __future__ import annotations
 import contextlib
 import ctypes as C
 import os
-import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import _handle as H
 from ... import _lib as L
 
 
@@ -98,37 +98,6 @@ def _route(direction, multichannel, g, p, i, c, t):
     return "hip" if not wants else "fn" if fn else "autograd"
 
 
-class _VaeHandle:
-    def __init__(self, w: L.VaeWeights, device, channels=None):
-        """channels: None = the single-channel codec (t2s_vae_create); C = the multichannel one (t2s_vae_create_mc)."""
-        self.ptr = C.c_void_p()
-        torch.cuda.synchronize(device)
-        with torch.cuda.device(device):
-            if channels is None:
-                L.check(L.lib().t2s_vae_create(C.byref(w), C.byref(self.ptr)), "t2s_vae_create")
-            else:
-                L.check(L.lib().t2s_vae_create_mc(C.byref(w), int(channels), C.byref(self.ptr)), "t2s_vae_create_mc")
-        # what the C handle's backward row blocks hold (a mirror handle serves one direction, an encoder's or a decoder's):
-        # vae_grow_rows (t2s_vae.hip) grows them when rows > held rows or B > held series; _vae_backward repeats that condition
-        self.bwd_rows = self.bwd_series = 0
-        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_vae_destroy", str(torch.device(device)), self.ptr)
-
-    def close(self):
-        self._fin()
-
-
-def _stack_ptrs(stack, dst: L.VaeStackWeights, keep):
-    n = len(stack._layers)
-    if n > 4:
-        raise L.T2SError(f"LA-VAE: num_residual_layers={n} > 4 is not supported by the HIP codec")
-    for i, layer in enumerate(stack._layers):
-        c3 = L.as_f32(layer._block[1].weight.detach())
-        c1 = L.as_f32(layer._block[3].weight.detach())
-        keep += [c3, c1]
-        dst.conv3_w[i], dst.conv1_w[i] = c3.data_ptr(), c1.data_ptr()
-    return n
-
-
 def _vae_backward(codec, struct, B, Ln, call):
     """What _EncodeFn.backward and _DecodeFn.backward share: fresh gradient tensors for codec._grad_params(), which lists
     them in the declared field order of `struct` (a residual-stack array takes one per layer), then
@@ -153,8 +122,8 @@ def _vae_backward(codec, struct, B, Ln, call):
     return [gr if p.requires_grad else None for gr, p in zip(grads, params)]
 
 
-class _Codec(nn.Module):
-    """What Encoder and Decoder share: the handle cache (keyed on parameter storage + version) and the routing's inputs."""
+class _Codec(H.HandleOwner, nn.Module):
+    """What Encoder and Decoder share: the handle (cached against parameter storage + version) and the routing's inputs."""
 
     @property
     def channels(self):
@@ -168,13 +137,13 @@ class _Codec(nn.Module):
 
     def _stack_weights(self, w, stack, names):
         """The fields both directions fill the same way: the stack's, and `names` = ((field, tensor), ...)."""
-        keep = []
-        w.res_hidden = self._res_hidden() or 1
-        w.n_res_layers = _stack_ptrs(self._residual_stack, stack, keep)
-        for name, t in names:
-            c = L.as_f32(t.detach())
-            keep.append(c)
-            setattr(w, name, c.data_ptr())
+        keep, layers = [], self._residual_stack._layers
+        if len(layers) > 4:
+            raise L.T2SError(f"LA-VAE: num_residual_layers={len(layers)} > 4 is not supported by the HIP codec")
+        w.res_hidden, w.n_res_layers = self._res_hidden() or 1, len(layers)
+        for i, layer in enumerate(layers):
+            H.fill(stack, ((("conv3_w", i), layer._block[1].weight), (("conv1_w", i), layer._block[3].weight)), keep)
+        H.fill(w, names, keep)
         return w, keep
 
     def _entry(self, k, *args):
@@ -201,40 +170,34 @@ class _Codec(nn.Module):
     def _tensors(self):
         return [p for p in self.parameters()]
 
+    def _build(self, device):
+        """channels None: the single-channel codec (t2s_vae_create); C: the multichannel one (t2s_vae_create_mc)."""
+        w, keep = self._weights_struct()          # (the library makes its own copies: `keep` ends with this call)
+        if self.channels is None:
+            h = H.Handle(device, "t2s_vae_create", "t2s_vae_destroy", C.byref(w))
+        else:
+            h = H.Handle(device, "t2s_vae_create_mc", "t2s_vae_destroy", C.byref(w), int(self.channels))
+        # what the C handle's backward row blocks hold (a mirror handle serves one direction, an encoder's or a decoder's):
+        # vae_grow_rows (t2s_vae.hip) grows them when rows > held rows or B > held series; _vae_backward repeats that condition
+        h.bwd_rows = h.bwd_series = 0
+        return h
+
+    def _refresh(self, h, device):
+        """Same shapes, new contents (an optimizer step on a trainable encoder, load_state_dict): re-copy into the handle's own
+        buffers -- no allocation, stream-ordered (t2s_vae_update_weights)."""
+        w, keep = self._weights_struct()
+        with torch.cuda.device(device):
+            L.check(L.lib().t2s_vae_update_weights(h.ptr, C.byref(w), L.stream_ptr(device)), "t2s_vae_update_weights")
+        return keep
+
     def _handle(self, device):
+        """The t2s_vae pointer (HandleOwner._owned_handle): rebuilt for another device or other shapes, refreshed for new
+        contents."""
         device = torch.device(device)
         ts = self._tensors()
-        for t in ts:
-            if t.device != device:
-                raise L.T2SError(f"LA-VAE parameters live on {t.device} but the input is on {device}")
-        inference = any(t.is_inference() for t in ts)          # no version counters: nothing to cache against
-        stamp = None if inference else (str(device),) + tuple((t.data_ptr(), t._version) for t in ts)
-        shape = (str(device),) + tuple(tuple(t.shape) for t in ts)
-        h = self.__dict__.get("_t2s_h")
-        if h is None or self.__dict__.get("_t2s_shape") != shape:
-            with L.device_lock(device):       # frees, allocations, a stream synchronisation: not inside another thread's capture
-                if h is not None:
-                    h.close()
-                w, keep = self._weights_struct()
-                h = _VaeHandle(w, device, self.channels)
-                del keep  # the library made its own copies
-            self.__dict__["_t2s_h"], self.__dict__["_t2s_stamp"], self.__dict__["_t2s_shape"] = h, stamp, shape
-        elif stamp is None or self.__dict__.get("_t2s_stamp") != stamp:
-            # same tensors' shapes, new contents (an optimizer step on a trainable encoder, load_state_dict): re-copy into the
-            # handle's own buffers -- no allocation, stream-ordered (t2s_vae_update_weights)
-            w, keep = self._weights_struct()
-            with torch.cuda.device(device):
-                L.check(L.lib().t2s_vae_update_weights(h.ptr, C.byref(w), L.stream_ptr(device)), "t2s_vae_update_weights")
-            h.keep = keep          # the copies are stream-ordered: keep the sources alive until the next refresh
-            self.__dict__["_t2s_stamp"] = stamp
-        return h.ptr
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        state.pop("_t2s_h", None)
-        state.pop("_t2s_stamp", None)
-        state.pop("_t2s_shape", None)
-        return state
+        H.require_on(ts, device, "LA-VAE")
+        geometry = (device,) + tuple(tuple(t.shape) for t in ts)
+        return self._owned_handle(device, geometry, H.stamp_of(ts), self._build, self._refresh, device).ptr
 
 
 class Encoder(_Codec):

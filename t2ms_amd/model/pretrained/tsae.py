@@ -16,12 +16,12 @@ no throughput claim.
 import ctypes as C
 import math
 import os
-import weakref
 
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
 
+from ... import _handle as H
 from ... import _lib as L
 from .core import BaseModel
 
@@ -117,43 +117,23 @@ class ConditionFusionModule(nn.Module):
         return self.ada_ln(fused, self.condition_projection(text_cond))
 
 
-class _TsaeHandle:
-    def __init__(self, w, device):
-        self.ptr = C.c_void_p()
-        torch.cuda.synchronize(device)
-        with torch.cuda.device(device):
-            L.check(L.lib().t2s_tsae_create(C.byref(w), C.byref(self.ptr)), "t2s_tsae_create")
-        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_tsae_destroy", str(torch.device(device)), self.ptr)
-
-    def close(self):
-        self._fin()
+def _wb(prefix, module):
+    return [(prefix + "_w", module.weight), (prefix + "_b", module.bias)]
 
 
-def _attn_ptrs(dst, attn, keep):
-    for field, t in (("in_proj_w", attn.in_proj_weight), ("in_proj_b", attn.in_proj_bias),
-                     ("out_proj_w", attn.out_proj.weight), ("out_proj_b", attn.out_proj.bias)):
-        c = L.as_f32(t.detach())
-        keep.append(c)
-        setattr(dst, field, c.data_ptr())
+def _layer_ptrs(dst, layer, attns, norms, keep):
+    """One transformer layer into its struct: the attention blocks, the feed-forward pair, the norms."""
+    for a in attns:
+        attn = getattr(layer, a)
+        H.fill(getattr(dst, a), [("in_proj_w", attn.in_proj_weight), ("in_proj_b", attn.in_proj_bias),
+                                 *_wb("out_proj", attn.out_proj)], keep)
+    for n in ("linear1", "linear2") + norms:
+        H.fill(dst, _wb(n, getattr(layer, n)), keep)
 
 
-def _fill(dst, pairs, keep):
-    for field, t in pairs:
-        c = L.as_f32(t.detach())
-        keep.append(c)
-        setattr(dst, field, c.data_ptr())
-
-
-def _layer_ptrs(dst, layer, norms, keep):
-    _fill(dst, [("linear1_w", layer.linear1.weight), ("linear1_b", layer.linear1.bias), ("linear2_w", layer.linear2.weight),
-                ("linear2_b", layer.linear2.bias)], keep)
-    for n in norms:
-        _fill(dst, [(n + "_w", getattr(layer, n).weight), (n + "_b", getattr(layer, n).bias)], keep)
-
-
-class _Side(nn.Module):
+class _Side(H.HandleOwner, nn.Module):
     """What TimeSeriesEncoder and TimeSeriesDecoder share: a one-sided library handle cached against the parameters' storage and
-    version, and the module-owned workspace."""
+    version, and the module-owned workspace (both _handle.HandleOwner's)."""
 
     def _layers(self):
         raise NotImplementedError
@@ -174,47 +154,29 @@ class _Side(nn.Module):
         covered = x.dim() == 3 and self._plain() and _covered(F_, d, dff, heads, layers, T, B)
         return _route(self.training, grad, masks, covered, _torch_forced())
 
+    def _build(self, device):
+        w, keep = self._weights_struct()          # (the library packs its own copy: `keep` ends with this call)
+        return H.Handle(device, "t2s_tsae_create", "t2s_tsae_destroy", C.byref(w))
+
     def _handle(self, device):
+        """The handle object (HandleOwner._owned_handle).  The library has no refresh entry: any change rebuilds."""
         device = torch.device(device)
         ts = list(self.parameters())
-        for t in ts:
-            if t.device != device:
-                raise L.T2SError(f"TSae parameters live on {t.device} but the input is on {device}")
-        inference = any(t.is_inference() for t in ts)
-        stamp = None if inference else (str(device),) + tuple((t.data_ptr(), t._version, tuple(t.shape)) for t in ts)
-        h = self.__dict__.get("_t2s_h")
-        if h is None or stamp is None or self.__dict__.get("_t2s_stamp") != stamp:
-            with L.device_lock(device):       # frees, allocations, synchronous copies: not inside another thread's capture
-                if h is not None:
-                    h.close()
-                w, keep = self._weights_struct()
-                h = _TsaeHandle(w, device)
-                del keep                      # the library packed its own copy
-            self.__dict__["_t2s_h"], self.__dict__["_t2s_stamp"] = h, stamp
-        return h
+        H.require_on(ts, device, "TSae")
+        geometry = (device,) + tuple(tuple(t.shape) for t in ts)
+        return self._owned_handle(device, geometry, H.stamp_of(ts), self._build, None, device)
 
-    def _workspace(self, h, B, T, device):
+    def _workspace_for(self, h, B, T, device):
         need = int(L.lib().t2s_tsae_workspace_bytes(h.ptr, B, T))
         if need == 0:
             raise L.T2SError("TSae: " + L.lib().t2s_last_error().decode("utf-8", "replace"))
-        ws = self.__dict__.get("_t2s_ws")
-        if ws is None or ws.numel() < need or ws.device != torch.device(device):
-            with L.device_lock(device):
-                ws = torch.empty(need, dtype=torch.uint8, device=device)
-            self.__dict__["_t2s_ws"] = ws
-        return ws
+        return self._workspace(need, device)
 
     def _gpu(self, who, *tensors):
         for t in tensors:
             if not t.is_cuda:
                 raise L.T2SError(f"{who}: input must live on a GPU (got device {t.device}); the HIP path has no CPU fallback "
                                  f"(T2S_TSAE=torch selects the torch ops)")
-
-    def __getstate__(self):
-        state = self.__dict__.copy()
-        for k in ("_t2s_h", "_t2s_stamp", "_t2s_ws"):
-            state.pop(k, None)
-        return state
 
 
 class TimeSeriesEncoder(_Side):
@@ -237,11 +199,9 @@ class TimeSeriesEncoder(_Side):
         F_, d, dff, heads, n = self._shape()
         w, keep = L.TsaeWeights(), []
         w.n_features, w.d_model, w.d_ff, w.heads, w.n_enc, w.n_dec = F_, d, dff, heads, n, 0
-        _fill(w, [("value_embedding_w", self.value_embedding.weight), ("value_embedding_b", self.value_embedding.bias),
-                  ("embedding_ln_w", self.embedding_ln.weight), ("embedding_ln_b", self.embedding_ln.bias)], keep)
+        H.fill(w, _wb("value_embedding", self.value_embedding) + _wb("embedding_ln", self.embedding_ln), keep)
         for i, layer in enumerate(self._layers()):
-            _attn_ptrs(w.enc[i].self_attn, layer.self_attn, keep)
-            _layer_ptrs(w.enc[i], layer, ("norm1", "norm2"), keep)
+            _layer_ptrs(w.enc[i], layer, ("self_attn",), ("norm1", "norm2"), keep)
         return w, keep
 
     def forward(self, time_series, src_key_padding_mask=None):
@@ -255,7 +215,7 @@ class TimeSeriesEncoder(_Side):
         dev = x.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
-            ws = self._workspace(h, B, T, dev)
+            ws = self._workspace_for(h, B, T, dev)
             memory = torch.empty(B, T, L.TSAE_D_MODEL, dtype=torch.float32, device=dev)
             L.check(L.lib().t2s_tsae_encode(h.ptr, x.data_ptr(), memory.data_ptr(), B, T, ws.data_ptr(), ws.numel(),
                                             L.stream_ptr(dev)), "t2s_tsae_encode")
@@ -286,13 +246,9 @@ class TimeSeriesDecoder(_Side):
         F_, d, dff, heads, n = self._shape()
         w, keep = L.TsaeWeights(), []
         w.n_features, w.d_model, w.d_ff, w.heads, w.n_enc, w.n_dec = F_, d, dff, heads, 0, n
-        _fill(w, [("input_projection_w", self.input_projection.weight), ("input_projection_b", self.input_projection.bias),
-                  ("output_projection_w", self.output_projection.weight), ("output_projection_b", self.output_projection.bias)],
-              keep)
+        H.fill(w, _wb("input_projection", self.input_projection) + _wb("output_projection", self.output_projection), keep)
         for i, layer in enumerate(self._layers()):
-            _attn_ptrs(w.dec[i].self_attn, layer.self_attn, keep)
-            _attn_ptrs(w.dec[i].multihead_attn, layer.multihead_attn, keep)
-            _layer_ptrs(w.dec[i], layer, ("norm1", "norm2", "norm3"), keep)
+            _layer_ptrs(w.dec[i], layer, ("self_attn", "multihead_attn"), ("norm1", "norm2", "norm3"), keep)
         return w, keep
 
     def _generate_causal_mask(self, size, device):
@@ -315,7 +271,7 @@ class TimeSeriesDecoder(_Side):
         dev = tgt.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
-            ws = self._workspace(h, B, T, dev)
+            ws = self._workspace_for(h, B, T, dev)
             pred = torch.empty(B, T, int(self.n_features), dtype=torch.float32, device=dev)
             L.check(L.lib().t2s_tsae_decode(h.ptr, mem.data_ptr(), tgt.data_ptr(), pred.data_ptr(), B, T, ws.data_ptr(),
                                             ws.numel(), L.stream_ptr(dev)), "t2s_tsae_decode")
@@ -340,7 +296,7 @@ class TimeSeriesDecoder(_Side):
         dev = mem.device
         with torch.cuda.device(dev):
             h = self._handle(dev)
-            ws = self._workspace(h, B, S, dev)
+            ws = self._workspace_for(h, B, S, dev)
             series = torch.empty(B, S, int(self.n_features), dtype=torch.float32, device=dev)
             L.check(L.lib().t2s_tsae_generate(h.ptr, mem.data_ptr(), series.data_ptr(), B, S, ws.data_ptr(), ws.numel(),
                                               L.stream_ptr(dev)), "t2s_tsae_generate")

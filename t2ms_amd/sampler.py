@@ -10,7 +10,6 @@ from __future__ import annotations
 
 import ctypes as C
 import os
-import weakref
 from fractions import Fraction
 from math import ceil as _ceil
 from typing import Optional
@@ -19,6 +18,7 @@ import numpy as np
 import torch
 
 from . import _lib as L
+from ._handle import Handle
 from .model.backbone.DDPM import ddpm_host_tables
 
 XT_STREAM = 0xFFFFFFFF  # Philox stream id reserved for x_T
@@ -412,7 +412,8 @@ class Sampler:
 
     def _create_locked(self):
         if self.ptr is not None:
-            self._fin()
+            self._h.close()
+            self.ptr = None          # (a create that raises below leaves no freed pointer behind)
         model, decoder, backbone, use_graph = self.model, self.decoder, self.backbone, self.use_graph
         lms = self.__dict__.get("_lms")
         tvals = loop_t_values(backbone, self.steps).contiguous() if lms is None else lms[0].contiguous()
@@ -431,16 +432,11 @@ class Sampler:
             dit = model.t2s_handle(self.device, 2 * self.batch)
             self._dit_uid = model.t2s_handle_id()
             vae = decoder._handle(self.device) if decoder is not None else None
-            torch.cuda.synchronize(self.device)
-            self.ptr = C.c_void_p()
-            if lms is not None:
-                L.check(L.lib().t2s_sampler_create_lms(dit, vae, C.byref(cfg), coef.data_ptr(), C.byref(self.ptr)),
-                        "t2s_sampler_create_lms")
-            else:
-                L.check(L.lib().t2s_sampler_create(dit, vae, C.byref(cfg), C.byref(self.ptr)), "t2s_sampler_create")
+            create = ("t2s_sampler_create",) if lms is None else ("t2s_sampler_create_lms", coef.data_ptr())
+            self._h = Handle(self.device, create[0], "t2s_sampler_destroy", dit, vae, C.byref(cfg), *create[1:])
+            self.ptr = self._h.ptr
             L.check(L.lib().t2s_sampler_set_lanes(self.ptr, self.lanes), "t2s_sampler_set_lanes")
             L.check(L.lib().t2s_sampler_set_loop_graph(self.ptr, self.loop_graph), "t2s_sampler_set_loop_graph")
-        self._fin = weakref.finalize(self, L.destroy_locked, "t2s_sampler_destroy", str(self.device), self.ptr)
         if self.__dict__.get("_rows") is not None:      # a re-created C sampler keeps the per-row tables
             self.set_rows(*self._rows)
         if self._guided != (0, self.steps):             # ... and the guided window (a new C sampler guides every step)

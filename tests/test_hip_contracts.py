@@ -78,6 +78,27 @@ def test_undersized_weight_is_an_error_code_not_a_fault(dev):
         assert float((m(input=x, t=t, text_input=None).cpu() - O.dit_forward(synth.make_dit_state_dict(31337, gain=0.7), x.cpu(), t.cpu(), None)).abs().max()) < 1e-4
 
 
+def test_refused_handle_growth_leaves_no_freed_handle_behind(dev):
+    """Growing the handle frees the old one before it builds the new one (_handle.HandleOwner._owned_handle).  A build the
+    library refuses -- max_seqs > 65536, before any allocation -- must leave the model without a handle, not with the freed
+    one: the next forward builds a fresh handle and computes the same bits."""
+    m = _model(dev)
+    m.t2s_handle(dev, 4)
+    x, t = synth.make_latents(1, 2).to(dev), torch.tensor([3, 4], device=dev)
+    text = synth.make_text_embeddings(1, 2).to(dev)
+    with torch.no_grad():
+        want = m(input=x, t=t, text_input=text).clone()
+    uid = m.t2s_handle_id()
+    assert uid is not None and m.__dict__["_t2s_h"].max_seqs == 4
+    with pytest.raises(L.T2SError, match="max_seqs=70000 out of range"):
+        m.t2s_handle(dev, 70000)
+    assert m.t2s_handle_id() is None and "_t2s_h" not in m.__dict__ and "_t2s_stamp" not in m.__dict__
+    with torch.no_grad():
+        got = m(input=x, t=t, text_input=text)
+    assert torch.equal(got, want)
+    assert m.t2s_handle_id() not in (None, uid)
+
+
 def test_vae_weights_extent_is_checked_too(dev):
     """t2s_vae_create / _update_weights derive every tensor's size from the hyper-parameters in the struct: a tensor whose
     device allocation ends before that many floats is T2S_E_INVALID, not an out-of-bounds copy."""
