@@ -55,7 +55,8 @@ from model.backbone.rectified_flow import RectifiedFlow      # noqa: E402,F401
 from model.denoiser.transformer import Transformer            # noqa: E402
 from t2ms_amd import dist as tdist                            # noqa: E402
 from t2ms_amd import synth                                    # noqa: E402
-from t2ms_amd.sampler import Sampler, np_save_outputs, resolve_cfg_interval, resolve_solver   # noqa: E402
+from t2ms_amd._lib import LAT, LAT_C, LAT_W                   # noqa: E402  (a row's latent: LAT = LAT_C x LAT_W floats)
+from t2ms_amd.sampler import Sampler, default_math, np_save_outputs, resolve_cfg_interval, resolve_solver   # noqa: E402
 
 
 def _weight_seed(args):
@@ -226,31 +227,26 @@ def _constructor_draws(args):
 _DRAWS_AFTER = {}     # (random_init, denoiser, generator state before the constructors) -> state after them
 
 
-def loader_order(args, dataset_name, seed, build_models=None):
-    """-> (dataset, index batches (n_batches, B), what build_models() returned) of the test loader of `dataset_name` in a
-    run seeded with `seed`.  THE order of every run, single or grid: the parent's infer() drew it as
+def loader_order(args, dataset_name, seed):
+    """-> (dataset, index batches (n_batches, B)) of the test loader of `dataset_name` in a run seeded with `seed`.  THE
+    order of every run, single or grid, either denoiser: the parent's infer() drew it as
         torch.manual_seed(seed); loader_provider(...); _load_models(...) (the constructors' initialisation draws from the
         global CPU generator); epoch_index_batches(loader)
-    and this helper replays exactly that sequence.  With build_models (the one-run MLP path) the real models are built in
-    the constructors' place; without, the generator state the constructors leave is replayed from a cache keyed by the
-    state before them (their draws are a function of that state alone)."""
+    and this helper replays exactly that sequence; the generator state the constructors leave is replayed from a cache
+    keyed by the state before them (their draws are a function of that state alone)."""
     torch.manual_seed(seed)
     a = copy.copy(args)
     a.dataset_name, a.seed = dataset_name, seed
     dataset, loader = loader_provider(a, period="test")
-    models = None
-    if build_models is not None:
-        models = build_models()
+    key = (bool(args.random_init), args.denoiser, torch.get_rng_state().numpy().tobytes())
+    after = _DRAWS_AFTER.get(key)
+    if after is None:
+        _constructor_draws(args)
+        _DRAWS_AFTER[key] = torch.get_rng_state()
     else:
-        key = (bool(args.random_init), args.denoiser, torch.get_rng_state().numpy().tobytes())
-        after = _DRAWS_AFTER.get(key)
-        if after is None:
-            _constructor_draws(args)
-            _DRAWS_AFTER[key] = torch.get_rng_state()
-        else:
-            torch.set_rng_state(after)
+        torch.set_rng_state(after)
     batches = walk_index_batches(loader) if getattr(args, "loader_batches", False) else epoch_index_batches(loader)
-    return dataset, batches, models
+    return dataset, batches
 
 
 def grid_plan(unit_rows, loader_batch, launch_batch, world):
@@ -287,207 +283,111 @@ def row_tables(segments, unit_seeds, unit_cfgs):
     return seeds, keys, cfgs
 
 
-def infer(args):
-    """ONE run of one (dataset, cfg scale): args.dataset_name, args.cfg_scale, seeded by args.seed, into
-    args.generation_save_path_result.  The DiT path is the 1x1 grid (sample_grid); `--denoiser MLP` keeps its own loop."""
-    if args.denoiser == "DiT":
-        cell = Cell(dataset_name=args.dataset_name, cfg=float(args.cfg_scale), cfg_shown=args.cfg_scale,
-                    path=args.generation_save_path_result)
-        res = sample_grid(args, [cell], 1)
-        return res[0] if res is not None else None
-    return _infer_mlp(args)
-
-
-def _infer_mlp(args):
-    """The MLP denoiser (BASELINE configs[0] plumbing): one sampling loop per loader batch, as the reference."""
-    device = torch.device(args.device)
-    rank, local_rank, world = tdist.env_world()
-    dist = tdist.init("nccl", device)
-    # ONE seed for the whole job: it seeds the loader shuffle (every rank must walk the same batches to take ITS rows
-    # of each) and keys the Philox noise.  A per-rank time-based default would silently mis-pair series across ranks.
-    args.seed = tdist.broadcast_int(dist, args.seed)
-    backbone = {"flowmatching": "flowmatching", "ddpm": "ddpm"}.get(args.backbone)
-    if backbone is None:
-        raise ValueError("No backbone found")
-    if rank == 0:
-        print(f"Inference config::Step: {args.total_step}\t CFG Scale: {args.cfg_scale}\t "
-              f"Use Pretrained VAE: {args.usepretrainedvae}\t GPUs: {world}")
-        os.makedirs(args.generation_save_path_result, exist_ok=True)
-    # identical loader shuffle on every rank; the models are built where the constructors drew (loader_order)
-    dataset, batches, (model, vae) = loader_order(args, args.dataset_name, args.seed,
-                                                  build_models=lambda: _load_models(args, device))
-    if rank == 0:
-        print("dataset length:", batches.shape[0])
-    if batches.shape[0] == 0:
-        raise RuntimeError("the test loader produced no full batch (drop_last=True): lower --batch_size")
-    order = batches.reshape(-1)
-    n_rows, B = int(order.numel()), int(batches.shape[1])
-    (series_tab, emb_tab, _), = resident_tables(dataset)
-    x1_host = torch.as_tensor(series_tab)[order].float()              # (N, L) fp32: what `x_1.float()` gives per batch
-    L = int(x1_host.shape[1])
-    x1_dev = x1_host.to(device)
-    emb_dev = torch.as_tensor(emb_tab)[order].float().to(device)
-    plan = launch_plan(n_rows, B, 0, world)          # one sampling loop per loader batch, as the reference
-    flush_rows = int(os.environ.get("T2S_INFER_FLUSH_ROWS", str(1 << 17)))     # outputs stay in HBM this long (16 KB / row)
-
-    out = None
-    if rank == 0:
-        out = (np.empty((n_rows, L), np.float32), np.empty((n_rows, 64, 30), np.float32),
-               np.empty((n_rows, 64, 30), np.float32))
-    held, held_chunks, trace = [], [], None
-    t_start = time.time()
-
-    def flush():
-        """Collective: every rank hands over the rows it sampled since the last flush (ONE all_gather of the packed
-        (rows, L + 2 * 1920) tensor; a rank without rows joins with an empty tensor) and rank 0 files them by global row."""
-        if not held_chunks:
-            return
-        counts = [sum(tdist.shard_rows(s1 - s0, r, world)[1] - tdist.shard_rows(s1 - s0, r, world)[0]
-                      for s0, s1 in held_chunks) for r in range(world)]
-        mine = torch.cat(held, dim=0) if held else torch.empty(0, L + 2 * 1920, device=device)
-        parts = tdist.gather_ragged(dist, mine, counts, rank)
-        if rank == 0:
-            for r, part in enumerate(parts):
-                if counts[r] == 0:
-                    continue
-                dest = torch.cat([torch.arange(s0 + tdist.shard_rows(s1 - s0, r, world)[0],
-                                               s0 + tdist.shard_rows(s1 - s0, r, world)[1]) for s0, s1 in held_chunks])
-                p = part.cpu().numpy()
-                d = dest.numpy()
-                out[0][d] = p[:, :L]
-                out[1][d] = p[:, L:L + 1920].reshape(-1, 64, 30)
-                out[2][d] = p[:, L + 1920:].reshape(-1, 64, 30)
-        held.clear()
-        held_chunks.clear()
-
-    with torch.no_grad():
-        for k, (s0, s1) in enumerate(plan):
-            lo, hi = tdist.shard_rows(s1 - s0, rank, world)
-            n = hi - lo
-            if n > 0:                     # a rank without rows in this launch (fewer rows than GPUs) only joins the flush
-                x_1, embedding = x1_dev[s0 + lo:s0 + hi], emb_dev[s0 + lo:s0 + hi]
-                lat, series, z_enc = sample_mlp_config1(model, vae, backbone, x_1, embedding, args, device, s0 + lo)
-                lat = torch.nn.functional.pad(lat, (0, 30 - lat.shape[2]))      # the .npy layout is (N,64,30): zero-padded
-                held.append(torch.cat([series.reshape(n, L), lat.reshape(n, 1920), z_enc.reshape(n, 1920)], dim=1))
-            held_chunks.append((s0, s1))
-            if rank == 0:
-                print(f"Generating {k}th Batch TS...  (rows {s0}..{s1 - 1} of {n_rows}, {s1 - s0} series per launch)")
-            if sum(b - a for a, b in held_chunks) >= flush_rows:
-                flush()
-        flush()
-    tdist.barrier(dist, device)
-    loop_s = time.time() - t_start
-    args.stats = {"series": n_rows, "loop_s": loop_s, "launches": len(plan), "loader_batch": B, "gpus": world,
-                  "series_per_launch_and_gpu": (plan[0][1] - plan[0][0]) // world}
-    if rank == 0:
-        x_1, (x_t, lat_dec, lat_enc) = x1_host.numpy(), out
-        print(f"{n_rows} series in {loop_s:.2f} s ({n_rows / loop_s:.1f} series/s)")
-        np_save_outputs(args.generation_save_path_result, x_1, x_t, lat_dec, lat_enc)   # infer.py:118-123
-        if trace is not None:
-            np.save(os.path.join(args.generation_save_path_result, "x_infer_trace.npy"), trace)
-        print(f"saved {x_1.shape[0]} series to {args.generation_save_path_result}")
-    tdist.barrier(dist, device)
-    return (x_1[:, :, None], x_t[:, :, None], lat_dec, lat_enc) if rank == 0 else None
-
-
-def sample_grid(args, cells, n_runs):
-    """The DiT sampling of every (cell, run) of `cells` x `n_runs` in ONE job; every unit writes exactly the four files
-    (and `--trace`'s x_infer_trace.npy) its own one-run invocation writes.  Models and the DiT handle are built once; the
-    rows of all units are concatenated (cell-major, then run, then the run's loader order) and cut into launches of
-    `--launch_batch` per GPU (grid_plan), sharded over the ranks as one job's rows are; each launch keys its rows by
-    (unit seed, position in the unit's order, cell cfg) through Sampler.set_rows -- rows never interact and the kernels are
-    batch-invariant bit for bit, so a row comes out as in its own invocation.  Encode and decode run per length group (a
-    launch that mixes lengths decodes outside the sampler's graph: the same decode kernel).
-    -> on rank 0 [(x_1, x_t, lat_dec, lat_enc)] per unit, grid order; None elsewhere."""
-    from t2ms_amd.sampler import default_math
+# ------------------------------------------------------------------ the job: prologue, resident tables, row sink, launch loop
+def _job_prologue(args):
+    """-> (device, rank, world, dist, backbone name) of a sampling job, the process group up and the seed agreed."""
     device = torch.device(args.device)
     rank, _, world = tdist.env_world()
     dist = tdist.init("nccl", device)
     # ONE seed for the whole job: it seeds the loader shuffle (every rank must walk the same batches to take ITS rows
     # of each) and keys the Philox noise.  A per-rank time-based default would silently mis-pair series across ranks.
     args.seed = tdist.broadcast_int(dist, args.seed)
-    backbone = {"flowmatching": "flowmatching", "ddpm": "ddpm"}.get(args.backbone)
-    if backbone is None:
+    if args.backbone not in ("flowmatching", "ddpm"):
         raise ValueError("No backbone found")
-    if args.denoiser != "DiT":
-        raise ValueError("sample_grid runs the DiT sampler (--denoiser MLP keeps its own loop)")
-    units = grid_units(cells, n_runs, args.seed)
-    if rank == 0:
-        print(f"Inference config::Step: {args.total_step}\t CFG Scale: {', '.join(str(c.cfg_shown) for c in cells)}\t "
-              f"Use Pretrained VAE: {args.usepretrainedvae}\t GPUs: {world}\t cells: {len(cells)} x runs: {n_runs}")
-        for u in units:
-            os.makedirs(u.path, exist_ok=True)
-    first = copy.copy(args)
-    first.dataset_name = cells[0].dataset_name          # every cell shares the root (parse_cells): one checkpoint, one LA-VAE
-    model, vae = _load_models(first, device)
-    args.math = getattr(args, "math", None) or default_math()
-    model.set_math(args.math)
-    if rank == 0:
-        print(f"matrix arithmetic: {args.math}" + {"bf16x3": " (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)",
-                                                   "bf16": " (single-pass bf16 operands, fp32 accumulate and residual stream: NOT fp32-accurate; "
-                                                           "--math bf16x3 = fp32-accurate)"}.get(args.math, ""))
+    return device, rank, world, dist, args.backbone
 
-    # Every unit's rows in its loader order (loader_order: the parent's generator sequence per (dataset, seed)); output
-    # row i of a unit is dataset row order[i] -- the concatenation of the reference's batches (shuffle=True,
-    # drop_last=True, infer.py:66; N = floor(test / B) * B rows).  The test splits live in HBM.
-    x1_host, x1_dev, emb_dev, lens = [], [], [], []
-    B = None
+
+def _unit_tables(args, units, device):
+    """Per unit its rows in its loader order (loader_order: the parent's generator sequence per (dataset, seed)), resident:
+    x1_host (N, L) fp32, x1_dev, emb_dev, the length L and the loader batch B.  Output row i of a unit is dataset row
+    order[i] -- the concatenation of the reference's batches (shuffle=True, drop_last=True, infer.py:66; N = floor(test / B)
+    * B rows).  The test splits live in HBM."""
+    tabs = []
     for u in units:
-        dataset, batches, _ = loader_order(args, u.dataset_name, u.seed)
+        dataset, batches = loader_order(args, u.dataset_name, u.seed)
         if batches.shape[0] == 0:
             raise RuntimeError(f"{u.dataset_name}: the test loader produced no full batch (drop_last=True): lower --batch_size")
         order = batches.reshape(-1)
-        B = int(batches.shape[1])
         (series_tab, emb_tab, _), = resident_tables(dataset)
         xh = torch.as_tensor(series_tab)[order].float()              # (N, L) fp32: what `x_1.float()` gives per batch
-        x1_host.append(xh)
-        x1_dev.append(xh.to(device))
-        emb_dev.append(torch.as_tensor(emb_tab)[order].float().to(device))
-        lens.append(int(xh.shape[1]))
-    unit_rows = [int(x.shape[0]) for x in x1_host]
-    offs = np.cumsum([0] + unit_rows)
-    n_rows, Lmax = int(offs[-1]), max(lens)
-    if rank == 0:
-        print("dataset length:", ", ".join(str(n // B) for n in unit_rows[::n_runs]))
-    launch_batch = int(getattr(args, "launch_batch", 256))
-    plan = grid_plan(unit_rows, B, launch_batch, world)
-    unit_seeds, unit_cfgs = [u.seed for u in units], [u.cfg for u in units]
-    flush_rows = int(os.environ.get("T2S_INFER_FLUSH_ROWS", str(1 << 17)))     # outputs stay in HBM this long (16 KB / row)
-    width = Lmax + 2 * 1920                  # a packed row: series (zero-padded to the longest length), latent, encoding
+        tabs.append(types.SimpleNamespace(x1_host=xh, x1_dev=xh.to(device), L=int(xh.shape[1]), B=int(batches.shape[1]),
+                                          emb_dev=torch.as_tensor(emb_tab)[order].float().to(device)))
+    return tabs
 
-    out = None
-    if rank == 0:
-        out = (np.empty((n_rows, Lmax), np.float32), np.empty((n_rows, 64, 30), np.float32),
-               np.empty((n_rows, 64, 30), np.float32))
-    held, held_chunks, samplers = [], [], {}
+
+def rank_rows(held_chunks, r, world):
+    """The global rows rank `r` of `world` holds of the launches `held_chunks` [(s0, s1)], in the order it sampled them:
+    its shard_rows slice of every launch.  A function of its arguments alone, so every rank knows every rank's rows."""
+    return np.concatenate([np.arange(0)] + [s0 + np.arange(*tdist.shard_rows(s1 - s0, r, world)) for s0, s1 in held_chunks])
+
+
+class RowSink:
+    """Where the sampled rows of a job go: they stay in HBM as packed fp32 rows
+        (series zero-padded to Lmax | latent, LAT | encoding, LAT)
+    until a flush gathers them and rank 0 files them by global row into `out` = (series (N, Lmax), latent (N, LAT_C,
+    LAT_W), encoding likewise).  A flush runs at the end of the job and whenever the launches held since the last one
+    reach T2S_INFER_FLUSH_ROWS rows (default 2^17; a row is 16 KB)."""
+
+    def __init__(self, n_rows, Lmax, dist, rank, world, device):
+        self.Lmax, self.dist, self.rank, self.world, self.device = Lmax, dist, rank, world, device
+        self.flush_rows = int(os.environ.get("T2S_INFER_FLUSH_ROWS", str(1 << 17)))
+        self.out = None
+        if rank == 0:
+            self.out = (np.empty((n_rows, Lmax), np.float32), np.empty((n_rows, LAT_C, LAT_W), np.float32),
+                        np.empty((n_rows, LAT_C, LAT_W), np.float32))
+        self.held, self.held_chunks = [], []
+
+    @staticmethod
+    def pack(series, lat, z_enc):
+        n = series.shape[0]
+        return torch.cat([series, lat.reshape(n, LAT), z_enc.reshape(n, LAT)], dim=1)
+
+    def add(self, s0, s1, packed):
+        """Launch [s0, s1) is done: `packed` holds this rank's rows of it, None for a rank without rows in the launch (it
+        records the launch all the same, and joins the flush)."""
+        if packed is not None:
+            self.held.append(packed)
+        self.held_chunks.append((s0, s1))
+        if sum(b - a for a, b in self.held_chunks) >= self.flush_rows:
+            self.flush()
+
+    def flush(self):
+        """Collective: every rank hands over the rows it sampled since the last flush (ONE all_gather of the packed rows; a
+        rank without rows joins with an empty tensor) and rank 0 files them by global row."""
+        if not self.held_chunks:
+            return
+        Lmax = self.Lmax
+        dest = [rank_rows(self.held_chunks, r, self.world) for r in range(self.world)]
+        mine = torch.cat(self.held, dim=0) if self.held else torch.empty(0, Lmax + 2 * LAT, device=self.device)
+        parts = tdist.gather_ragged(self.dist, mine, [len(d) for d in dest], self.rank)
+        if self.rank == 0:
+            for d, part in zip(dest, parts):
+                if len(d) == 0:
+                    continue
+                p = part.cpu().numpy()
+                self.out[0][d] = p[:, :Lmax]
+                self.out[1][d] = p[:, Lmax:Lmax + LAT].reshape(-1, LAT_C, LAT_W)
+                self.out[2][d] = p[:, Lmax + LAT:].reshape(-1, LAT_C, LAT_W)
+        self.held.clear()
+        self.held_chunks.clear()
+
+
+def _dit_launch(args, device, backbone, model, vae, tabs, unit_seeds, unit_cfgs):
+    """-> (sample_launch, trace_rows) of the DiT: the fused Sampler on the rows of a launch, each keyed by (unit seed,
+    position in the unit's order, cell cfg) through Sampler.set_rows; encode and decode run per length group (a launch that
+    mixes lengths decodes outside the sampler's graph: the same decode kernel)."""
+    lens = [t.L for t in tabs]
+    Lmax = max(lens)
+    samplers = {}
     # the few-step solver of the job (parse_cells resolved it; absent = the backbone's own update, as before)
     solver_kw = dict(solver=getattr(args, "solver", None), sample_steps=getattr(args, "sample_steps", None),
                      eta=getattr(args, "eta", None) or 0.0, guide_steps=getattr(args, "guide_steps", None))
-    mixed = 0
-    t_start = time.time()
 
-    def flush():
-        """Collective: every rank hands over the rows it sampled since the last flush (ONE all_gather of the packed
-        (rows, Lmax + 2 * 1920) tensor; a rank without rows joins with an empty tensor) and rank 0 files them by global row."""
-        if not held_chunks:
-            return
-        counts = [sum(tdist.shard_rows(s1 - s0, r, world)[1] - tdist.shard_rows(s1 - s0, r, world)[0]
-                      for s0, s1 in held_chunks) for r in range(world)]
-        mine = torch.cat(held, dim=0) if held else torch.empty(0, width, device=device)
-        parts = tdist.gather_ragged(dist, mine, counts, rank)
-        if rank == 0:
-            for r, part in enumerate(parts):
-                if counts[r] == 0:
-                    continue
-                dest = torch.cat([torch.arange(s0 + tdist.shard_rows(s1 - s0, r, world)[0],
-                                               s0 + tdist.shard_rows(s1 - s0, r, world)[1]) for s0, s1 in held_chunks])
-                p = part.cpu().numpy()
-                d = dest.numpy()
-                out[0][d] = p[:, :Lmax]
-                out[1][d] = p[:, Lmax:Lmax + 1920].reshape(-1, 64, 30)
-                out[2][d] = p[:, Lmax + 1920:].reshape(-1, 64, 30)
-        held.clear()
-        held_chunks.clear()
+    def sampler_of(key, cfg, n, L):
+        if key not in samplers:
+            samplers[key] = Sampler(model, vae.decoder, backbone, args.total_step, cfg, n, L, device, use_graph=True,
+                                    seed=args.seed, row0=0, **solver_kw)
+        return samplers[key]
 
     def length_groups(segs):
         """{L: (row positions in the launch, the segments of that length)} in launch order."""
@@ -499,59 +399,124 @@ def sample_grid(args, cells, n_runs):
             pos += i1 - i0
         return {Lg: (torch.cat(p), s) for Lg, (p, s) in groups.items()}
 
+    def sample_launch(segs, n):
+        seeds, keys, cfgs = row_tables(segs, unit_seeds, unit_cfgs)
+        embedding = torch.cat([tabs[u].emb_dev[i0:i1] for u, i0, i1 in segs]) if len(segs) > 1 else \
+            tabs[segs[0][0]].emb_dev[segs[0][1]:segs[0][2]]
+        groups = length_groups(segs)
+        if len(groups) == 1:
+            x_1 = torch.cat([tabs[u].x1_dev[i0:i1] for u, i0, i1 in segs])
+            z_enc, _ = model.encoder(x_1.contiguous())                      # infer.py:73-74
+        else:
+            z_enc = torch.empty(n, LAT_C, LAT_W, device=device)
+            for Lg, (pos, gsegs) in groups.items():
+                z_enc[pos] = model.encoder(torch.cat([tabs[u].x1_dev[i0:i1] for u, i0, i1 in gsegs]).contiguous())[0]
+        L0 = lens[segs[0][0]]
+        sampler = sampler_of((n, L0), unit_cfgs[segs[0][0]], n, L0)
+        sampler.set_rows(seeds, keys, cfgs)       # this launch's (seed, key row, cfg) per row; the graph is kept
+        lat, series, _ = sampler.run(embedding.contiguous(), decode=len(groups) == 1)
+        ser = torch.zeros(n, Lmax, device=device)
+        if len(groups) == 1:
+            ser[:, :L0] = series.reshape(n, L0)
+        else:
+            for Lg, (pos, _) in groups.items():
+                ser[pos, :Lg] = vae.decoder(lat[pos].contiguous(), length=Lg)[0].reshape(-1, Lg)
+        return ser, lat, z_enc
+
+    def trace_rows(ui, m):
+        """The per-step decode of row 0 (infer.py:90-93) of unit `ui`, from an eager run of its first `m` rows."""
+        ts = sampler_of(("trace", m, lens[ui]), unit_cfgs[ui], m, lens[ui])
+        ts.set_rows(*row_tables([(ui, 0, m)], unit_seeds, unit_cfgs))
+        return ts.run(tabs[ui].emb_dev[:m].contiguous(), decode=True, trace=True)[2].cpu().numpy()
+
+    return sample_launch, trace_rows
+
+
+def _mlp_launch(args, device, backbone, model, vae, tabs, unit_seeds, unit_cfgs):
+    """-> (sample_launch, no trace) of the MLP denoiser (BASELINE configs[0] plumbing): sample_mlp_config1 on one loader
+    batch of one unit, keyed by the unit's seed and the rows' position in the unit, at the cell's cfg."""
+    runs = []
+    for seed, cfg in zip(unit_seeds, unit_cfgs):
+        a = copy.copy(args)
+        a.seed, a.cfg_scale = seed, cfg
+        runs.append(a)
+
+    def sample_launch(segs, n):
+        assert len(segs) == 1, "an MLP launch is one loader batch of one unit"
+        u, i0, i1 = segs[0]
+        lat, series, z_enc = sample_mlp_config1(model, vae, backbone, tabs[u].x1_dev[i0:i1], tabs[u].emb_dev[i0:i1], runs[u],
+                                                device, i0)
+        lat = torch.nn.functional.pad(lat, (0, LAT_W - lat.shape[2]))      # the .npy layout is (N,64,30): zero-padded
+        return series, lat, z_enc
+
+    return sample_launch, None
+
+
+def infer(args):
+    """ONE run of one (dataset, cfg scale): args.dataset_name, args.cfg_scale, seeded by args.seed, into
+    args.generation_save_path_result -- the 1x1 job of sample_grid, either denoiser."""
+    cell = Cell(dataset_name=args.dataset_name, cfg=float(args.cfg_scale), cfg_shown=args.cfg_scale,
+                path=args.generation_save_path_result)
+    res = sample_grid(args, [cell], 1)
+    return res[0] if res is not None else None
+
+
+def sample_grid(args, cells, n_runs):
+    """THE sampling job: every (cell, run) of `cells` x `n_runs` in one go; every unit writes exactly the four files (and
+    `--trace`'s x_infer_trace.npy) its own one-run invocation writes.  Models are built once; the rows of all units are
+    concatenated (cell-major, then run, then the run's loader order), cut into launches (grid_plan) and each launch is
+    sharded over the ranks; what differs between the denoisers is how the rows of a launch are sampled.  DiT:
+    `--launch_batch` rows per GPU across unit boundaries, the fused Sampler with per-row tables (_dit_launch) -- rows never
+    interact and the kernels are batch-invariant bit for bit, so a row comes out as in its own invocation.  MLP: one
+    launch per loader batch of one unit, as the reference (_mlp_launch).
+    -> on rank 0 [(x_1, x_t, lat_dec, lat_enc)] per unit, grid order; None elsewhere."""
+    device, rank, world, dist, backbone = _job_prologue(args)
+    dit = args.denoiser == "DiT"
+    units = grid_units(cells, n_runs, args.seed)
+    if rank == 0:
+        grid = f"\t cells: {len(cells)} x runs: {n_runs}" if dit or len(units) > 1 else ""       # one MLP run: the reference's line
+        print(f"Inference config::Step: {args.total_step}\t CFG Scale: {', '.join(str(c.cfg_shown) for c in cells)}\t "
+              f"Use Pretrained VAE: {args.usepretrainedvae}\t GPUs: {world}{grid}")
+        for u in units:
+            os.makedirs(u.path, exist_ok=True)
+    first = copy.copy(args)
+    first.dataset_name = cells[0].dataset_name          # every cell shares the root (parse_cells): one checkpoint, one LA-VAE
+    model, vae = _load_models(first, device)
+    if dit:
+        args.math = getattr(args, "math", None) or default_math()
+        model.set_math(args.math)
+        if rank == 0:
+            print(f"matrix arithmetic: {args.math}" + {"bf16x3": " (fp32-accurate split-bf16 products; --math f32 = exact f32 MFMA)",
+                                                       "bf16": " (single-pass bf16 operands, fp32 accumulate and residual stream: NOT fp32-accurate; "
+                                                               "--math bf16x3 = fp32-accurate)"}.get(args.math, ""))
+    tabs = _unit_tables(args, units, device)
+    unit_rows = [int(t.x1_host.shape[0]) for t in tabs]
+    offs = np.cumsum([0] + unit_rows)
+    n_rows, Lmax, B = int(offs[-1]), max(t.L for t in tabs), tabs[0].B
+    if rank == 0:
+        print("dataset length:", ", ".join(str(n // B) for n in unit_rows[::n_runs]))
+    launch_batch = int(getattr(args, "launch_batch", 256)) if dit else 0     # MLP: one sampling loop per loader batch
+    plan = grid_plan(unit_rows, B, launch_batch, world)
+    sample_launch, trace_rows = (_dit_launch if dit else _mlp_launch)(args, device, backbone, model, vae, tabs,
+                                                                      [u.seed for u in units], [u.cfg for u in units])
+    sink = RowSink(n_rows, Lmax, dist, rank, world, device)
+    mixed, traces = 0, {}
+    t_start = time.time()
     with torch.no_grad():
         for k, (s0, s1) in enumerate(plan):
             if len(launch_segments(unit_rows, s0, s1)) > 1:
                 mixed += 1
             lo, hi = tdist.shard_rows(s1 - s0, rank, world)
-            n = hi - lo
-            if n > 0:                     # a rank without rows in this launch (fewer rows than GPUs) only joins the flush
-                segs = launch_segments(unit_rows, s0 + lo, s0 + hi)
-                seeds, keys, cfgs = row_tables(segs, unit_seeds, unit_cfgs)
-                embedding = torch.cat([emb_dev[u][i0:i1] for u, i0, i1 in segs]) if len(segs) > 1 else \
-                    emb_dev[segs[0][0]][segs[0][1]:segs[0][2]]
-                groups = length_groups(segs)
-                if len(groups) == 1:
-                    x_1 = torch.cat([x1_dev[u][i0:i1] for u, i0, i1 in segs])
-                    z_enc, _ = model.encoder(x_1.contiguous())                      # infer.py:73-74
-                else:
-                    z_enc = torch.empty(n, 64, 30, device=device)
-                    for Lg, (pos, gsegs) in groups.items():
-                        z_enc[pos] = model.encoder(torch.cat([x1_dev[u][i0:i1] for u, i0, i1 in gsegs]).contiguous())[0]
-                L0 = lens[segs[0][0]]
-                sampler = samplers.get((n, L0))
-                if sampler is None:
-                    sampler = samplers[(n, L0)] = Sampler(model, vae.decoder, backbone, args.total_step, unit_cfgs[segs[0][0]],
-                                                          n, L0, device, use_graph=True, seed=args.seed, row0=0, **solver_kw)
-                sampler.set_rows(seeds, keys, cfgs)       # this launch's (seed, key row, cfg) per row; the graph is kept
-                lat, series, _ = sampler.run(embedding.contiguous(), decode=len(groups) == 1)
-                ser = torch.zeros(n, Lmax, device=device)
-                if len(groups) == 1:
-                    ser[:, :L0] = series.reshape(n, L0)
-                else:
-                    for Lg, (pos, _) in groups.items():
-                        ser[pos, :Lg] = vae.decoder(lat[pos].contiguous(), length=Lg)[0].reshape(-1, Lg)
-                held.append(torch.cat([ser, lat.reshape(n, 1920), z_enc.reshape(n, 1920)], dim=1))
-            held_chunks.append((s0, s1))
+            n = hi - lo                   # a rank without rows in this launch (fewer rows than GPUs) only joins the flush
+            sink.add(s0, s1, sink.pack(*sample_launch(launch_segments(unit_rows, s0 + lo, s0 + hi), n)) if n > 0 else None)
             if rank == 0:
                 print(f"Generating {k}th Batch TS...  (rows {s0}..{s1 - 1} of {n_rows}, {s1 - s0} series per launch)")
-            if sum(b - a for a, b in held_chunks) >= flush_rows:
-                flush()
-        flush()
-        traces = {}
-        if getattr(args, "trace", False) and rank == 0:
-            # the per-step decode of row 0 (infer.py:90-93), from an eager run of exactly the rows the unit's own
-            # invocation holds in its first launch on rank 0
-            for ui, u in enumerate(units):
-                first = min(B if launch_batch <= 0 else launch_batch * world, unit_rows[ui])
-                m = tdist.shard_rows(first, 0, world)[1]
-                ts = samplers.get(("trace", m, lens[ui]))
-                if ts is None:
-                    ts = samplers[("trace", m, lens[ui])] = Sampler(model, vae.decoder, backbone, args.total_step, u.cfg, m,
-                                                                    lens[ui], device, use_graph=True, seed=args.seed, row0=0,
-                                                                    **solver_kw)
-                ts.set_rows(*row_tables([(ui, 0, m)], unit_seeds, unit_cfgs))
-                traces[ui] = ts.run(emb_dev[ui][:m].contiguous(), decode=True, trace=True)[2].cpu().numpy()
+        sink.flush()
+        if getattr(args, "trace", False) and rank == 0 and trace_rows is not None:
+            # from exactly the rows the unit's own invocation holds in its first launch on rank 0
+            for ui in range(len(units)):
+                first_launch = min(B if launch_batch <= 0 else launch_batch * world, unit_rows[ui])
+                traces[ui] = trace_rows(ui, tdist.shard_rows(first_launch, 0, world)[1])
     tdist.barrier(dist, device)
     loop_s = time.time() - t_start
     args.stats = {"series": n_rows, "loop_s": loop_s, "launches": len(plan), "loader_batch": B, "gpus": world,
@@ -563,9 +528,9 @@ def sample_grid(args, cells, n_runs):
         results = []
         for ui, u in enumerate(units):
             a, b = int(offs[ui]), int(offs[ui + 1])
-            x_1 = x1_host[ui].numpy()
-            x_t = np.ascontiguousarray(out[0][a:b, :lens[ui]])
-            lat_dec, lat_enc = out[1][a:b], out[2][a:b]
+            x_1 = tabs[ui].x1_host.numpy()
+            x_t = np.ascontiguousarray(sink.out[0][a:b, :tabs[ui].L])
+            lat_dec, lat_enc = sink.out[1][a:b], sink.out[2][a:b]
             np_save_outputs(u.path, x_1, x_t, lat_dec, lat_enc)                    # infer.py:118-123
             if ui in traces:
                 np.save(os.path.join(u.path, "x_infer_trace.npy"), traces[ui])
@@ -659,21 +624,10 @@ def main(argv=None):
     root = cells[0].dataset_name.split("_")[0]
     args.checkpoint_path = os.path.join(args.save_path, "checkpoints", f"{args.backbone}_{args.denoiser}_{root}",
                                         f"model_{args.checkpoint_id}.pth")
-    args.generation_save_path = cells[0].path
     print("start generate", args.run_multi)
-    args.generation_save_path_result = args.generation_save_path
     n_runs = 11 if args.run_multi else 1                         # infer.py:148-164: 1 + 10 runs
     if len(cells) == 1:                                          # a single cell: the args of the parent's one-cell job
         args.dataset_name, args.cfg_scale = cells[0].dataset_name, cells[0].cfg_shown
-    if args.denoiser != "DiT":                                   # (one cell: parse_cells) the MLP loop, run by run
-        out = infer(args)
-        for run_index in range(n_runs - 1):
-            args.generation_save_path_result = os.path.join(args.generation_save_path, f"run_{run_index}")
-            args.seed += 1
-            out = infer(args)
-        if out is not None and not args.no_figs:
-            _save_figs(args.generation_save_path, out[0], out[1])
-        return args
     results = sample_grid(args, cells, n_runs)
     if results is not None and not args.no_figs:
         for ci, c in enumerate(cells):                           # each cell's figures from its last run, as before

@@ -9,6 +9,7 @@ import torch
 
 import infer as drv
 from datafactory.dataloader import epoch_index_batches, loader_provider
+from model.denoiser.mlp import MLP
 from model.denoiser.transformer import Transformer
 from model.pretrained.vqvae import vqvae
 from t2ms_amd import dist as tdist
@@ -70,16 +71,16 @@ def test_refused_grids(argv, tmp_path):
         drv.parse_cells(_args(["--save_path", str(tmp_path)] + argv))
 
 
-def _literal_parent_order(args, name, seed):
+def _literal_parent_order(args, name, seed, denoiser=Transformer):
     """The parent's infer() up to the order, replayed literally: manual_seed, loader_provider, the model constructors
-    of _load_models, epoch_index_batches."""
+    of _load_models (the LA-VAE's, then the denoiser's), epoch_index_batches."""
     torch.manual_seed(seed)
     a = types.SimpleNamespace(**vars(args))
     a.dataset_name, a.seed = name, seed
     _, loader = loader_provider(a, period="test")
     if args.random_init:
         vqvae(types.SimpleNamespace(block_hidden_size=128, num_residual_layers=2, res_hidden_size=256, embedding_dim=64))
-    Transformer()
+    denoiser()
     return epoch_index_batches(loader), torch.get_rng_state()
 
 
@@ -92,18 +93,17 @@ def test_loader_order_replays_the_parents_generator_sequence(random_init):
     for name in ("exchangerate_24", "ETTh1_48", "ETTh1_96"):
         for seed in range(S, S + 11):
             want, state = _literal_parent_order(args, name, seed)
-            ds, got, models = drv.loader_order(args, name, seed)
-            assert models is None and len(ds) == 13
+            ds, got = drv.loader_order(args, name, seed)
+            assert len(ds) == 13
             assert torch.equal(got, want), (name, seed)
             assert torch.equal(torch.get_rng_state(), state), (name, seed)
-    # the MLP path builds its models where the constructors drew: the same order
-    want, _ = _literal_parent_order(args, "ETTh1_24", 7)
-
-    def build():
-        drv._constructor_draws(args)
-        return "models"
-    _, got, models = drv.loader_order(args, "ETTh1_24", 7, build_models=build)
-    assert models == "models" and torch.equal(got, want)
+    # the MLP job takes the same path, its own constructor in the Transformer's place: the same order as a run that builds
+    # the MLP where the parent's did
+    mlp = _args(argv + ["--denoiser", "MLP"])
+    want, state = _literal_parent_order(mlp, "ETTh1_24", 7, denoiser=MLP)
+    for _ in range(2):                                  # the constructors' draws themselves, then their replay from the cache
+        _, got = drv.loader_order(mlp, "ETTh1_24", 7)
+        assert torch.equal(got, want) and torch.equal(torch.get_rng_state(), state)
 
 
 def _tables_1x1(n_rows, seed, cfg, B, launch_batch, world):

@@ -220,3 +220,62 @@ def test_two_rank_grid_writes_the_single_process_grids_files(tmp_path):
     for f in files:
         with open(tmp_path / "one" / f, "rb") as x, open(tmp_path / "two" / f, "rb") as y:
             assert x.read() == y.read(), f
+
+
+def _same_trees(a, b, n_files):
+    files = _tree(a)
+    assert len(files) == n_files and _tree(b) == files
+    for f in files:
+        with open(os.path.join(a, f), "rb") as x, open(os.path.join(b, f), "rb") as y:
+            assert x.read() == y.read(), f
+
+
+def test_a_flush_after_every_launch_writes_the_one_final_flushs_files(tmp_path, monkeypatch):
+    """T2S_INFER_FLUSH_ROWS=1: the sink gathers and files after every launch instead of once at the end.  The grid of
+    test_two_rank_grid_writes_the_single_process_grids_files (6 rows per unit, 3 per GPU and launch): 88 launches and
+    flushes on one process; on two ranks every launch holds 6 rows, 3 per rank, so in every flush rank 0 files two ranks'
+    rows by global row.  Both trees equal the default's (one flush at the end of the job)."""
+    import infer as drv
+    monkeypatch.chdir(tmp_path)
+    argv = ["--dataset_name", "exchangerate_24,exchangerate_48", "--cfg_scale", "5,9", "--run_multi", "True", "--backbone", "ddpm",
+            "--total_step", "2", "--batch_size", "2", "--synthetic", "7", "--launch_batch", "3", "--random_init", "--seed", "4",
+            "--no_figs"]
+    monkeypatch.delenv("T2S_INFER_FLUSH_ROWS", raising=False)
+    drv.main(argv + ["--save_path", str(tmp_path / "end")])
+    monkeypatch.setenv("T2S_INFER_FLUSH_ROWS", "1")
+    a = drv.main(argv + ["--save_path", str(tmp_path / "each")])
+    assert a.stats["series"] == 4 * 11 * 6 and a.stats["launches"] == 88
+    _same_trees(tmp_path / "end", tmp_path / "each", 4 * 11 * 4)
+    monkeypatch.delenv("T2S_INFER_FLUSH_ROWS")
+    r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr",
+                        "127.0.0.1", "--master-port", "29594", os.path.join(REPO, "infer.py")] + argv +
+                       ["--save_path", str(tmp_path / "two")], env=dict(_env(29594), T2S_INFER_FLUSH_ROWS="1"),
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, f"{r.stdout[-3000:]}\n{r.stderr[-3000:]}"
+    _same_trees(tmp_path / "end", tmp_path / "two", 4 * 11 * 4)
+
+
+def test_mlp_run_multi_in_one_job_writes_the_run_by_run_files(tmp_path, monkeypatch):
+    """`--denoiser MLP --run_multi True` as the 11 units of ONE job (models built once) against infer(args) one run at a
+    time, seed 3 + k, weights from seed 3, as the parent's main() looped."""
+    import infer as drv
+    monkeypatch.chdir(tmp_path)
+    common = ["--denoiser", "MLP", "--backbone", "ddpm", "--dataset_name", "ETTh1_24", "--total_step", "3", "--batch_size", "4",
+              "--synthetic", "9", "--random_init", "--seed", "3", "--no_figs"]
+    job = str(tmp_path / "job")
+    a = drv.main(common + ["--run_multi", "True", "--save_path", job])
+    st = a.stats
+    assert st["series"] == 11 * 8 and st["launches"] == 22 and st["loader_batch"] == 4 and st["series_per_launch_and_gpu"] == 4
+    assert (st["cells"], st["runs"], st["mixed_launches"]) == (1, 11, 0)
+    one = str(tmp_path / "one")
+    args = drv.build_parser().parse_args(common + ["--save_path", one])
+    args.mix_train = False
+    args.device = "cuda:0"
+    args.weight_seed = 3
+    args.checkpoint_path = ""
+    base = os.path.join(one, "generation", "ddpm_MLP_ETTh1_24_7_3")
+    for k in range(11):
+        args.seed = 3 + k
+        args.generation_save_path_result = base if k == 0 else os.path.join(base, f"run_{k - 1}")
+        drv.infer(args)
+    _same_trees(one, job, 11 * 4)
