@@ -972,8 +972,8 @@ typedef struct t2s_tsae_weights {
 /* Reads every tensor once (extents checked), packs the transposes and the sinusoidal table (a function of position and channel,
  * computed here) into one device buffer the handle owns; later calls copy nothing.  Covered: d_model 64, heads 4 or 8, d_ff a
  * multiple of 64 up to 512, 1..6 layers on each side, 1..16 features; anything else is T2S_E_INVALID naming the value.  n_enc 0 or
- * n_dec 0 (not both) makes a one-sided handle: that side's tensors are not read, and its entries are T2S_E_INVALID.  Create again
- * after the weights change.  Synchronous (not for use inside a stream capture). */
+ * n_dec 0 (not both) makes a one-sided handle: that side's tensors are not read, and its entries are T2S_E_INVALID.  After the
+ * weights change, create again or call t2s_tsae_update_weights.  Synchronous (not for use inside a stream capture). */
 int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out);
 void t2s_tsae_destroy(t2s_tsae* h);
 /* Rows [first, first + count) of the handle's positional table -> pe (count,64), device. */
@@ -996,6 +996,38 @@ int t2s_tsae_decode(const t2s_tsae* h, const float* memory, const float* target,
  * cross-attention K / V, one launch (a workgroup per series) runs all S steps with the self-attention K / V cached in the workspace. */
 int t2s_tsae_generate(const t2s_tsae* h, const float* memory, float* series, int B, int S, void* workspace, uint64_t workspace_bytes,
                       void* stream);
+
+/* ---- TSae training: the teacher-forced step  prediction = decoder(memory = encoder(x), target_seq = x)  in training mode ---- */
+#define T2S_TSAE_TRAIN_MAX_T 192 /* trained lengths: a whole head's K and V rows stay in LDS */
+/* Re-reads every tensor of `w` into the handle's blob on the caller's stream (one launch): no allocation, no synchronisation, the
+ * positional table is not recomputed.  The shape fields of `w` must equal the handle's; a one-sided handle reads its side only.
+ * Afterwards every entry computes what a fresh handle on the same tensors computes, bit for bit. */
+int t2s_tsae_update_weights(t2s_tsae* h, const t2s_tsae_weights* w, void* stream);
+/* Dropout of the training entries.  Nothing is stored: element e of series b at site s is KEPT iff u >= p, u the value
+ * t2s_philox_uniform defines for (seed, stream_id = s, row = b, element e), p the fp32 dropout probability; kept values are
+ * multiplied by the fp32 1 / (1 - p).  At p == 0 no Philox work is done.  The element index:
+ *   a row site of width W (64; d_ff for the FFN hidden rows):  e = t * W + c        (row t, column c)
+ *   an attention site (the softmax probabilities, not renormalised):  e = (h * T + i) * T + j   (head, query, key)
+ * The sites:
+ *   0  encoder embedding_dropout          1  encoder positional_encoding.dropout          2  decoder positional_encoding.dropout
+ *   16 + 4 i + k  encoder layer i:  k = 0 attention probabilities, 1 dropout1 (after attention), 2 dropout (FFN hidden), 3 dropout2
+ *   64 + 6 i + k  decoder layer i:  k = 0 self-attention probabilities, 1 dropout1, 2 cross-attention probabilities, 3 dropout2,
+ *                                   4 dropout (FFN hidden), 5 dropout3
+ * The training entries below need a two-sided handle, 1 <= T <= T2S_TSAE_TRAIN_MAX_T, 1 <= B <= 65535 and 0 <= p_drop < 1; they
+ * run on the caller's stream, never allocate or synchronise, keep no state outside the workspace, and refuse with T2S_E_INVALID,
+ * before any launch, anything else, a NULL pointer and a workspace smaller than t2s_tsae_train_workspace_bytes (0 and a message on
+ * a bad argument). */
+uint64_t t2s_tsae_train_workspace_bytes(const t2s_tsae* h, int B, int T);
+/* x (B,T,F) -> prediction (B,T,F), every activation the backward needs left in the workspace.  2 + 5 n_enc + 9 n_dec + 1 launches. */
+int t2s_tsae_train_forward(const t2s_tsae* h, const float* x, float* prediction, int B, int T, float p_drop, uint64_t seed,
+                           void* workspace, uint64_t workspace_bytes, void* stream);
+/* The gradients: the fields of t2s_tsae_weights, written through (the library casts the const away); the shape fields are not read. */
+typedef t2s_tsae_weights t2s_tsae_grads;
+/* d_prediction (B,T,F) -> d loss / d (every tensor that takes part), torch layouts, written (not accumulated); the sums over
+ * (series, row) run in an order that depends on (B, T, shape) only, so a step repeats bit for bit.  x, B, T, p_drop, seed and the
+ * workspace are those of the matching t2s_tsae_train_forward, the workspace untouched in between.  No gradient for x. */
+int t2s_tsae_train_backward(const t2s_tsae* h, const float* x, const float* d_prediction, const t2s_tsae_grads* g, int B, int T,
+                            float p_drop, uint64_t seed, void* workspace, uint64_t workspace_bytes, void* stream);
 
 #ifdef __cplusplus
 }

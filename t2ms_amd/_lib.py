@@ -133,6 +133,7 @@ class MlpGrads(C.Structure):            # t2s_mlp_grads: the same fields, writab
 
 TSAE_D_MODEL, TSAE_MAX_LAYERS, TSAE_MAX_T = 64, 6, 2000   # t2s.h: T2S_TSAE_D_MODEL / _MAX_LAYERS / _MAX_T
 TSAE_MAX_FEATURES, TSAE_MAX_D_FF = 16, 512                 # t2s.h: T2S_TSAE_MAX_FEATURES / _MAX_D_FF
+TSAE_TRAIN_MAX_T = 192                                     # t2s.h: T2S_TSAE_TRAIN_MAX_T
 
 
 class TsaeAttnWeights(C.Structure):
@@ -273,6 +274,10 @@ SYMBOLS = {
     "t2s_tsae_encode": (_I, [_VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
     "t2s_tsae_decode": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
     "t2s_tsae_generate": (_I, [_VP, _VP, _VP, _I, _I, _VP, _U64, _VP]),
+    "t2s_tsae_update_weights": (_I, [_VP, C.POINTER(TsaeWeights), _VP]),
+    "t2s_tsae_train_workspace_bytes": (_U64, [_VP, _I, _I]),
+    "t2s_tsae_train_forward": (_I, [_VP, _VP, _VP, _I, _I, _F, _U64, _VP, _U64, _VP]),
+    "t2s_tsae_train_backward": (_I, [_VP, _VP, _VP, C.POINTER(TsaeWeights), _I, _I, _F, _U64, _VP, _U64, _VP]),
 }
 
 _lib: Optional[C.CDLL] = None

@@ -94,6 +94,26 @@ __device__ __forceinline__ float xhalf(float v) {  // value held by lane ^ 32
     return __shfl_xor(v, 32, 64);
 }
 
+// Philox4x32-10: the library's counter-based generator (t2s_philox_*, the TSae training kernels' dropout masks)
+struct u32x4 { uint32_t x, y, z, w; };
+
+__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
+        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
+        u32x4 n;
+        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
+        n.y = (uint32_t)p1;
+        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
+        n.w = (uint32_t)p0;
+        c = n;
+        k0 += 0x9E3779B9u;
+        k1 += 0xBB67AE85u;
+    }
+    return c;
+}
+
 // Weight packing for the B operand (W is a torch Linear weight (N,K) row-major, the GEMM is
 // x @ W^T).  For n-tile nt (32 outputs) and k-group g (8 inputs) lane l owns the float4
 //   W[32*nt + (l&31)][8*g + 4*(l>>5) + 0..3]

@@ -20,26 +20,7 @@ struct t2s_vae;
 
 namespace t2s {
 
-// ---------------------------------------------------------------- Philox4x32-10 + Box-Muller
-struct u32x4 { uint32_t x, y, z, w; };
-
-__device__ __forceinline__ u32x4 philox4x32_10(u32x4 c, uint32_t k0, uint32_t k1) {
-#pragma unroll
-    for (int r = 0; r < 10; ++r) {
-        const uint64_t p0 = (uint64_t)0xD2511F53u * c.x;
-        const uint64_t p1 = (uint64_t)0xCD9E8D57u * c.z;
-        u32x4 n;
-        n.x = (uint32_t)(p1 >> 32) ^ c.y ^ k0;
-        n.y = (uint32_t)p1;
-        n.z = (uint32_t)(p0 >> 32) ^ c.w ^ k1;
-        n.w = (uint32_t)p0;
-        c = n;
-        k0 += 0x9E3779B9u;
-        k1 += 0xBB67AE85u;
-    }
-    return c;
-}
-
+// ---------------------------------------------------------------- Philox4x32-10 (t2s_common.h) + Box-Muller
 // 4 N(0,1) draws for quad `quad` of global row `row` in stream `stream_id`
 __device__ __forceinline__ f32x4 normal4(uint64_t seed, uint32_t stream_id, uint32_t row, uint32_t quad) {
     const u32x4 r = philox4x32_10(u32x4{quad, row, stream_id, 0u}, (uint32_t)seed, (uint32_t)(seed >> 32));

@@ -11,64 +11,19 @@
 // Generation is one launch of tsae_generate_kernel, one workgroup per series, all S steps inside (after one tsae_linear_kernel
 // launch that projects the memory to every layer's cross-attention K / V): the current row lives in LDS, the self-attention K / V
 // of the rows written so far in a global cache, the weights are streamed from L2.
-#include "t2s_common.h"
+// t2s_tsae_update_weights replays the create-time packing (a table of PackItems kept with the blob) in one launch of
+// tsae_pack_kernel.  The training entries are t2s_tsae_train.hip; what the two files share is t2s_tsae.h.
+#include "t2s_tsae.h"
 
-#include <math.h>
+#include <stddef.h>
 #include <string.h>
-
-#include <vector>
 
 namespace t2s {
 namespace {
 
-constexpr int TS_D = T2S_TSAE_D_MODEL;        // 64
-constexpr int TS_ML = T2S_TSAE_MAX_LAYERS;    // 6
-constexpr int TS_MAXT = T2S_TSAE_MAX_T;       // 2000
-constexpr int TS_MAXF = T2S_TSAE_MAX_FEATURES;  // 16
-constexpr int TS_MAXFF = T2S_TSAE_MAX_D_FF;   // 512
-constexpr float TS_EPS = 1e-5f;
+using namespace tsae;
 
-// Packed at create: a Linear (N,K) becomes w (K, Npad) -- consecutive outputs are consecutive floats -- and b (Npad), zero padded.
-struct Lin { const float* w; const float* b; };
-struct Norm { const float* g; const float* b; };
-struct EncLayerP { Lin qkv, out, l1, l2; Norm n1, n2; };
-struct DecLayerP { Lin qkv, out, cq, ckv, cout, l1, l2; Norm n1, n2, n3; };
-struct GenP {
-    DecLayerP L[TS_ML];
-    Lin inp, outp;
-    const float* pe;
-    int n_dec, dff, F;
-};
 struct LinBatch { Lin lin[TS_ML]; };   // blockIdx.z picks one (the cross K / V of every decoder layer in one launch)
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-// LayerNorm over the 64 channels a wave holds one per lane (biased variance, eps 1e-5)
-__device__ __forceinline__ float layer_norm_lane(float v, float g, float b) {
-    const float mean = wave_sum(v) * (1.0f / TS_D);
-    const float d = v - mean;
-    const float var = wave_sum(d * d) * (1.0f / TS_D);
-    return d * (1.0f / sqrtf(var + TS_EPS)) * g + b;
-}
-
-// One wave: acc(32 x 32) += xs(32 rows x [k0,k1), row stride ldx, LDS) . wt([k0,k1) x ldw, global)[:, n0 .. n0+31]; k1 - k0 a multiple of 16.
-__device__ __forceinline__ f32x16 tile_gemm(const float* xs, int ldx, const float* __restrict__ wt, int ldw, int n0, int k0, int k1,
-                                            f32x16 acc) {
-    const int lane = threadIdx.x & 63, j = lane & 31, half = lane >> 5;
-    const float* xp = xs + j * ldx + k0 + half;
-    const float* wp = wt + (size_t)(k0 + half) * ldw + n0 + j;
-    for (int k = k0; k < k1; k += 16) {
-#pragma unroll
-        for (int e = 0; e < 8; ++e) acc = mfma32(xp[2 * e], wp[(size_t)(2 * e) * ldw], acc);
-        xp += 16;
-        wp += 16 * (size_t)ldw;
-    }
-    return acc;
-}
 
 // rows of one series, 32 per block: wave w loads rows 8w .. 8w+7 (lane = channel), normalised if ln.g
 __device__ __forceinline__ void load_tile(float (*xs)[TS_D + 1], const float* x, int ldx, size_t row0, int t0, int T, Norm ln) {
@@ -377,27 +332,37 @@ __global__ __launch_bounds__(256) void tsae_generate_kernel(GenP P, const float*
     }
 }
 
+// One workgroup per PackItem: the create-time packing of one tensor pair, from the caller's tensors as they are now.
+__global__ __launch_bounds__(256) void tsae_pack_kernel(t2s_tsae_weights w, const PackItem* __restrict__ items, float* __restrict__ blob) {
+    const PackItem it = items[blockIdx.x];
+    const float* sw = *(const float* const*)((const char*)&w + it.w_field);
+    const float* sb = *(const float* const*)((const char*)&w + it.b_field);
+    for (int i = threadIdx.x; i < it.N * it.K; i += 256) {
+        const int n = i / it.K, k = i - n * it.K;
+        const float v = sw[(size_t)it.r0 * it.K + i];
+        blob[it.off_w + (size_t)k * it.Npad + n] = v;
+        if (it.off_t) blob[it.off_t + i] = v;
+    }
+    for (int n = threadIdx.x; n < it.N; n += 256) blob[it.off_b + n] = sb[it.r0 + n];
+}
+
 }  // namespace
 }  // namespace t2s
 
 using namespace t2s;
-
-struct t2s_tsae {
-    int F = 0, dff = 0, heads = 0, n_enc = 0, n_dec = 0;
-    float* blob = nullptr;
-    Lin emb{};
-    Norm emb_ln{};
-    EncLayerP enc[TS_ML]{};
-    GenP dec{};
-};
+using namespace t2s::tsae;
 
 namespace {
 
 // Host-side packing: tensors are read back once, transposed into one blob (offsets in floats, every item 64-float aligned).
 struct Packer {
+    const t2s_tsae_weights* W;
     std::vector<float> blob;
     std::vector<float> tmp;
+    std::vector<PackItem> items;
     int rc = T2S_OK;
+
+    uint32_t field(const float* const& p) const { return (uint32_t)((const char*)&p - (const char*)W); }
 
     size_t reserve(size_t n) {
         const size_t off = blob.size();
@@ -424,32 +389,33 @@ struct Packer {
         }
         return true;
     }
-    // rows [r0, r0 + N) of a torch Linear weight (Nall, K) and its bias -> (K, Npad) + (Npad); offsets returned as w, b
-    void lin(const float* w, const float* b, int Nall, int r0, int N, int K, int Npad, const char* name, size_t off[2]) {
-        off[0] = off[1] = 0;
+    // rows [r0, r0 + N) of a torch Linear weight (Nall, K) and its bias -> (K, Npad) + (Npad) and, if want_t, the rows as they are
+    // (N rounded up to 32, K); offsets returned as w, b, t.  w and b are MEMBERS of *W: their place in the struct goes into the item.
+    void lin(const float* const& w, const float* const& b, int Nall, int r0, int N, int K, int Npad, bool want_t, const char* name,
+             size_t off[3]) {
+        off[0] = off[1] = off[2] = 0;
         if (!fetch(w, (size_t)Nall * K, name)) return;
         off[0] = reserve((size_t)K * Npad);
         for (int n = 0; n < N; ++n)
             for (int k = 0; k < K; ++k) blob[off[0] + (size_t)k * Npad + n] = tmp[(size_t)(r0 + n) * K + k];
+        if (want_t) {
+            off[2] = reserve((size_t)((N + 31) & ~31) * K);
+            memcpy(&blob[off[2]], &tmp[(size_t)r0 * K], (size_t)N * K * sizeof(float));
+        }
         if (!fetch(b, (size_t)Nall, name)) return;
         off[1] = reserve(Npad);
         for (int n = 0; n < N; ++n) blob[off[1] + n] = tmp[r0 + n];
+        items.push_back(PackItem{field(w), field(b), r0, N, K, Npad, (uint32_t)off[0], (uint32_t)off[1], (uint32_t)off[2]});
     }
-    void norm(const float* g, const float* b, const char* name, size_t off[2]) {
-        off[0] = off[1] = 0;
-        if (!fetch(g, TS_D, name)) return;
-        off[0] = reserve(TS_D);
-        memcpy(&blob[off[0]], tmp.data(), TS_D * sizeof(float));
-        if (!fetch(b, TS_D, name)) return;
-        off[1] = reserve(TS_D);
-        memcpy(&blob[off[1]], tmp.data(), TS_D * sizeof(float));
+    void norm(const float* const& g, const float* const& b, const char* name, size_t off[3]) {
+        lin(g, b, TS_D, 0, TS_D, 1, TS_D, false, name, off);
     }
 };
 
-struct OffLayer { size_t qkv[2], out[2], cq[2], ckv[2], cout[2], l1[2], l2[2], n1[2], n2[2], n3[2]; };
+struct OffLayer { size_t qkv[3], out[3], cq[3], ckv[3], cout[3], l1[3], l2[3], n1[3], n2[3], n3[3]; };
 
-inline Lin mk_lin(const float* base, const size_t off[2]) { return Lin{base + off[0], base + off[1]}; }
-inline Norm mk_norm(const float* base, const size_t off[2]) { return Norm{base + off[0], base + off[1]}; }
+inline Lin mk_lin(const float* base, const size_t off[3]) { return Lin{base + off[0], base + off[1], off[2] ? base + off[2] : nullptr}; }
+inline Norm mk_norm(const float* base, const size_t off[3]) { return Norm{base + off[0], base + off[1]}; }
 
 // floats of workspace per (series x row): encode needs qkv + attention output, decode x + qkv + attention output + every layer's
 // cross K / V, generate every layer's cross K / V and self K / V cache
@@ -500,12 +466,6 @@ int launch_cross_kv(const t2s_tsae* h, const float* memory, float* ckv, int B, i
     return launch_linear(memory, TS_D, ckv, 128, (size_t)B * T * 128, lb, h->n_dec, Norm{nullptr, nullptr}, 128, 128, 0, B, T, s);
 }
 
-#define TS_TRY(expr)                 \
-    do {                             \
-        const int _rc = (expr);      \
-        if (_rc != T2S_OK) return _rc; \
-    } while (0)
-
 }  // namespace
 
 extern "C" int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out) {
@@ -523,41 +483,42 @@ extern "C" int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out) {
                 TS_MAXF);
     const int F = w->n_features, dff = w->d_ff;
     Packer pk;
-    size_t emb[2] = {0, 0}, emb_ln[2] = {0, 0}, inp[2] = {0, 0}, outp[2] = {0, 0};
+    pk.W = w;
+    size_t emb[3] = {0, 0, 0}, emb_ln[3] = {0, 0, 0}, inp[3] = {0, 0, 0}, outp[3] = {0, 0, 0};
     OffLayer eo[TS_ML], dol[TS_ML];
     pk.reserve(64);   // offset 0 stays unused
     if (w->n_enc) {
-        pk.lin(w->value_embedding_w, w->value_embedding_b, TS_D, 0, TS_D, F, TS_D, "encoder.value_embedding", emb);
+        pk.lin(w->value_embedding_w, w->value_embedding_b, TS_D, 0, TS_D, F, TS_D, false, "encoder.value_embedding", emb);
         pk.norm(w->embedding_ln_w, w->embedding_ln_b, "encoder.embedding_ln", emb_ln);
     }
     for (int l = 0; l < w->n_enc; ++l) {
         const t2s_tsae_enc_layer& L = w->enc[l];
-        pk.lin(L.self_attn.in_proj_w, L.self_attn.in_proj_b, 3 * TS_D, 0, 3 * TS_D, TS_D, 3 * TS_D, "encoder self_attn.in_proj", eo[l].qkv);
-        pk.lin(L.self_attn.out_proj_w, L.self_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, "encoder self_attn.out_proj", eo[l].out);
-        pk.lin(L.linear1_w, L.linear1_b, dff, 0, dff, TS_D, dff, "encoder linear1", eo[l].l1);
-        pk.lin(L.linear2_w, L.linear2_b, TS_D, 0, TS_D, dff, TS_D, "encoder linear2", eo[l].l2);
+        pk.lin(L.self_attn.in_proj_w, L.self_attn.in_proj_b, 3 * TS_D, 0, 3 * TS_D, TS_D, 3 * TS_D, true, "encoder self_attn.in_proj", eo[l].qkv);
+        pk.lin(L.self_attn.out_proj_w, L.self_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, true, "encoder self_attn.out_proj", eo[l].out);
+        pk.lin(L.linear1_w, L.linear1_b, dff, 0, dff, TS_D, dff, true, "encoder linear1", eo[l].l1);
+        pk.lin(L.linear2_w, L.linear2_b, TS_D, 0, TS_D, dff, TS_D, true, "encoder linear2", eo[l].l2);
         pk.norm(L.norm1_w, L.norm1_b, "encoder norm1", eo[l].n1);
         pk.norm(L.norm2_w, L.norm2_b, "encoder norm2", eo[l].n2);
     }
     for (int l = 0; l < w->n_dec; ++l) {
         const t2s_tsae_dec_layer& L = w->dec[l];
-        pk.lin(L.self_attn.in_proj_w, L.self_attn.in_proj_b, 3 * TS_D, 0, 3 * TS_D, TS_D, 3 * TS_D, "decoder self_attn.in_proj", dol[l].qkv);
-        pk.lin(L.self_attn.out_proj_w, L.self_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, "decoder self_attn.out_proj", dol[l].out);
-        pk.lin(L.multihead_attn.in_proj_w, L.multihead_attn.in_proj_b, 3 * TS_D, 0, TS_D, TS_D, TS_D, "decoder multihead_attn.in_proj",
+        pk.lin(L.self_attn.in_proj_w, L.self_attn.in_proj_b, 3 * TS_D, 0, 3 * TS_D, TS_D, 3 * TS_D, true, "decoder self_attn.in_proj", dol[l].qkv);
+        pk.lin(L.self_attn.out_proj_w, L.self_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, true, "decoder self_attn.out_proj", dol[l].out);
+        pk.lin(L.multihead_attn.in_proj_w, L.multihead_attn.in_proj_b, 3 * TS_D, 0, TS_D, TS_D, TS_D, true, "decoder multihead_attn.in_proj",
                dol[l].cq);
-        pk.lin(L.multihead_attn.in_proj_w, L.multihead_attn.in_proj_b, 3 * TS_D, TS_D, 2 * TS_D, TS_D, 2 * TS_D,
+        pk.lin(L.multihead_attn.in_proj_w, L.multihead_attn.in_proj_b, 3 * TS_D, TS_D, 2 * TS_D, TS_D, 2 * TS_D, true,
                "decoder multihead_attn.in_proj", dol[l].ckv);
-        pk.lin(L.multihead_attn.out_proj_w, L.multihead_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, "decoder multihead_attn.out_proj",
+        pk.lin(L.multihead_attn.out_proj_w, L.multihead_attn.out_proj_b, TS_D, 0, TS_D, TS_D, TS_D, true, "decoder multihead_attn.out_proj",
                dol[l].cout);
-        pk.lin(L.linear1_w, L.linear1_b, dff, 0, dff, TS_D, dff, "decoder linear1", dol[l].l1);
-        pk.lin(L.linear2_w, L.linear2_b, TS_D, 0, TS_D, dff, TS_D, "decoder linear2", dol[l].l2);
+        pk.lin(L.linear1_w, L.linear1_b, dff, 0, dff, TS_D, dff, true, "decoder linear1", dol[l].l1);
+        pk.lin(L.linear2_w, L.linear2_b, TS_D, 0, TS_D, dff, TS_D, true, "decoder linear2", dol[l].l2);
         pk.norm(L.norm1_w, L.norm1_b, "decoder norm1", dol[l].n1);
         pk.norm(L.norm2_w, L.norm2_b, "decoder norm2", dol[l].n2);
         pk.norm(L.norm3_w, L.norm3_b, "decoder norm3", dol[l].n3);
     }
     if (w->n_dec) {
-        pk.lin(w->input_projection_w, w->input_projection_b, TS_D, 0, TS_D, F, TS_D, "decoder.input_projection", inp);
-        pk.lin(w->output_projection_w, w->output_projection_b, F, 0, F, TS_D, 32, "decoder.output_projection", outp);
+        pk.lin(w->input_projection_w, w->input_projection_b, TS_D, 0, TS_D, F, TS_D, false, "decoder.input_projection", inp);
+        pk.lin(w->output_projection_w, w->output_projection_b, F, 0, F, TS_D, 32, true, "decoder.output_projection", outp);
     }
     if (pk.rc != T2S_OK) return pk.rc;
     // The sinusoidal table, a function of (position, channel): the divisor 10000^(-2i/64) and the angle are formed in fp32 as the
@@ -572,6 +533,9 @@ extern "C" int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out) {
             pk.blob[pe + (size_t)p * TS_D + 2 * i + 1] = (float)cos((double)ang);
         }
     }
+    // the items ride behind the table, for the device replay of this packing (t2s_tsae_update_weights)
+    const size_t items_off = pk.reserve((pk.items.size() * sizeof(PackItem) + sizeof(float) - 1) / sizeof(float));
+    memcpy(&pk.blob[items_off], pk.items.data(), pk.items.size() * sizeof(PackItem));
     t2s_tsae* h = new t2s_tsae();
     hipError_t e = hipMalloc((void**)&h->blob, pk.blob.size() * sizeof(float));
     if (e == hipSuccess) e = hipMemcpy(h->blob, pk.blob.data(), pk.blob.size() * sizeof(float), hipMemcpyHostToDevice);
@@ -595,8 +559,30 @@ extern "C" int t2s_tsae_create(const t2s_tsae_weights* w, t2s_tsae** out) {
     h->dec.inp = mk_lin(base, inp);
     h->dec.outp = mk_lin(base, outp);
     h->dec.pe = base + pe;
+    h->items = pk.items;
+    h->items_dev = (PackItem*)(h->blob + items_off);
     h->dec.n_dec = h->n_dec, h->dec.dff = dff, h->dec.F = F;
     *out = h;
+    return T2S_OK;
+}
+
+extern "C" int t2s_tsae_update_weights(t2s_tsae* h, const t2s_tsae_weights* w, void* stream) {
+    T2S_REQUIRE(h != nullptr && w != nullptr, "t2s_tsae_update_weights: NULL argument");
+    T2S_REQUIRE(w->n_features == h->F && w->d_model == TS_D && w->d_ff == h->dff && w->heads == h->heads && w->n_enc == h->n_enc &&
+                    w->n_dec == h->n_dec,
+                "t2s_tsae_update_weights: the shape (n_features=%d d_model=%d d_ff=%d heads=%d n_enc=%d n_dec=%d) is not the handle's "
+                "(%d %d %d %d %d %d): create a new handle",
+                w->n_features, w->d_model, w->d_ff, w->heads, w->n_enc, w->n_dec, h->F, TS_D, h->dff, h->heads, h->n_enc, h->n_dec);
+    for (const PackItem& it : h->items) {
+        const float* sw = *(const float* const*)((const char*)w + it.w_field);
+        const float* sb = *(const float* const*)((const char*)w + it.b_field);
+        T2S_REQUIRE(sw != nullptr && sb != nullptr, "t2s_tsae_update_weights: a tensor is NULL (pointer at byte %u / %u of t2s_tsae_weights)",
+                    it.w_field, it.b_field);
+        TS_TRY(check_device_extent(sw, (size_t)(it.r0 + it.N) * it.K * sizeof(float), "t2s_tsae_update_weights: a weight"));
+        TS_TRY(check_device_extent(sb, (size_t)(it.r0 + it.N) * sizeof(float), "t2s_tsae_update_weights: a bias"));
+    }
+    tsae_pack_kernel<<<(unsigned)h->items.size(), 256, 0, (hipStream_t)stream>>>(*w, h->items_dev, h->blob);
+    T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 

@@ -12,6 +12,12 @@ launch, key/value cached); a CPU tensor on that route is a T2SError.  Everything
 wanted (``shared_eval(..., 'train')``), masks, the text-fusion path of ``forward()``, uncovered shapes, and everything under
 ``T2S_TSAE=torch`` (read at call time) -- runs the ``_forward_torch`` methods: torch ops on the same parameters, plumbing with
 no throughput claim.
+
+Training (``shared_eval(..., 'train')``) has an opt-in HIP engine: ``T2S_TSAE_TRAIN=hip`` (read at call time; default ``torch``)
+or ``AttentionSeq2SeqAutoencoder.set_train_engine("hip")`` sends the teacher-forced step through csrc/t2s_tsae_train.hip -- one
+autograd node over the taking-part parameters, t2s_tsae_train_forward / _backward, dropout from the library's Philox rule -- when
+``_train_route`` says the call is covered (T <= 192, a GPU input that wants no gradient, every parameter trainable, one common
+dropout p, no ``T2S_TSAE=torch``); everything else runs the torch-op line as before.  The loss and the optimizer stay torch's.
 """
 import ctypes as C
 import math
@@ -37,6 +43,20 @@ def _covered(n_features, d_model, d_ff, heads, layers, T, B=1):
     return (d_model == L.TSAE_D_MODEL and heads in (4, 8) and d_ff % 64 == 0 and 64 <= d_ff <= L.TSAE_MAX_D_FF
             and 1 <= layers <= L.TSAE_MAX_LAYERS and 1 <= n_features <= L.TSAE_MAX_FEATURES and 1 <= T <= L.TSAE_MAX_T
             and 1 <= B <= 65535)
+
+
+def _train_engine_env():
+    v = os.environ.get("T2S_TSAE_TRAIN", "") or "torch"
+    if v not in ("hip", "torch"):
+        raise L.T2SError(f"T2S_TSAE_TRAIN must be 'hip' or 'torch' (got {v!r})")
+    return v
+
+
+def _train_route(engine, forced, covered, on_gpu, input_grad, params_grad, common_p, masks=False):
+    """'hip' or 'torch' for one shared_eval(..., 'train') call: the HIP node only when every condition holds."""
+    ok = (engine == "hip" and not forced and covered and on_gpu and not input_grad and params_grad and common_p is not None
+          and not masks)
+    return "hip" if ok else "torch"
 
 
 def _route(training, grad, masks, covered, forced):
@@ -159,7 +179,8 @@ class _Side(H.HandleOwner, nn.Module):
         return H.Handle(device, "t2s_tsae_create", "t2s_tsae_destroy", C.byref(w))
 
     def _handle(self, device):
-        """The handle object (HandleOwner._owned_handle).  The library has no refresh entry: any change rebuilds."""
+        """The handle object (HandleOwner._owned_handle).  Any change rebuilds: the one-sided handles serve inference; the
+        refresh entry (t2s_tsae_update_weights) is the autoencoder's training handle's."""
         device = torch.device(device)
         ts = list(self.parameters())
         H.require_on(ts, device, "TSae")
@@ -316,7 +337,66 @@ class TimeSeriesDecoder(_Side):
         return torch.cat(steps, dim=1)
 
 
-class AttentionSeq2SeqAutoencoder(BaseModel):
+def _two_sided_fields(w, enc, dec):
+    """[(struct, field, parameter)] of every tensor that takes part in the teacher-forced step, in t2s_tsae_weights order."""
+    out = [(w, f, p) for f, p in _wb("value_embedding", enc.value_embedding) + _wb("embedding_ln", enc.embedding_ln)]
+
+    def layer(dst, mod, attns, norms):
+        for a in attns:
+            attn, d = getattr(mod, a), getattr(dst, a)
+            out.extend([(d, "in_proj_w", attn.in_proj_weight), (d, "in_proj_b", attn.in_proj_bias),
+                        (d, "out_proj_w", attn.out_proj.weight), (d, "out_proj_b", attn.out_proj.bias)])
+        for n in ("linear1", "linear2") + norms:
+            out.extend((dst, f, p) for f, p in _wb(n, getattr(mod, n)))
+
+    for i, mod in enumerate(enc._layers()):
+        layer(w.enc[i], mod, ("self_attn",), ("norm1", "norm2"))
+    for i, mod in enumerate(dec._layers()):
+        layer(w.dec[i], mod, ("self_attn", "multihead_attn"), ("norm1", "norm2", "norm3"))
+    out.extend((w, f, p) for f, p in _wb("input_projection", dec.input_projection) + _wb("output_projection", dec.output_projection))
+    return out
+
+
+class _TrainStep(torch.autograd.Function):
+    """prediction = decoder(encoder(x), x) on t2s_tsae_train_forward, its backward on t2s_tsae_train_backward.  The activations
+    live in the model's workspace between the two: a backward after another forward of the same model is refused."""
+
+    @staticmethod
+    def forward(ctx, model, x, p, seed, *params):
+        dev = x.device
+        B, T, F_ = x.shape
+        with torch.cuda.device(dev):
+            h = model._train_handle(dev)
+            need = int(L.lib().t2s_tsae_train_workspace_bytes(h.ptr, B, T))
+            if need == 0:
+                raise L.T2SError("TSae: " + L.lib().t2s_last_error().decode("utf-8", "replace"))
+            ws = model._workspace(need, dev)
+            pred = torch.empty(B, T, F_, dtype=torch.float32, device=dev)
+            L.check(L.lib().t2s_tsae_train_forward(h.ptr, x.data_ptr(), pred.data_ptr(), B, T, p, seed, ws.data_ptr(), ws.numel(),
+                                                   L.stream_ptr(dev)), "t2s_tsae_train_forward")
+        model.__dict__["_t2s_train_token"] = token = model.__dict__.get("_t2s_train_token", 0) + 1
+        ctx.model, ctx.x, ctx.p, ctx.seed, ctx.h, ctx.ws, ctx.token = model, x, p, seed, h, ws, token
+        return pred
+
+    @staticmethod
+    def backward(ctx, d_pred):  # pyright: ignore[reportIncompatibleMethodOverride]
+        model, x, h, ws = ctx.model, ctx.x, ctx.h, ctx.ws
+        if model.__dict__.get("_t2s_train_token") != ctx.token or model.__dict__.get("_t2s_h") is not h:
+            raise L.T2SError("TSae: backward of a training step whose workspace a later forward of the same model has overwritten")
+        dev = x.device
+        B, T, _ = x.shape
+        d_pred = L.as_f32(d_pred)
+        g, grads = L.TsaeWeights(), []
+        for dst, field, prm in _two_sided_fields(g, model.encoder, model.decoder):
+            grads.append(torch.empty(prm.shape, dtype=torch.float32, device=dev))
+            setattr(dst, field, grads[-1].data_ptr())
+        with torch.cuda.device(dev):
+            L.check(L.lib().t2s_tsae_train_backward(h.ptr, x.data_ptr(), d_pred.data_ptr(), C.byref(g), B, T, ctx.p, ctx.seed,
+                                                    ws.data_ptr(), ws.numel(), L.stream_ptr(dev)), "t2s_tsae_train_backward")
+        return (None, None, None, None, *grads)
+
+
+class AttentionSeq2SeqAutoencoder(H.HandleOwner, BaseModel):
     def __init__(self, args):
         super().__init__()
         self.n_features, self.flow_dim = args.input_dim, args.flow_dim
@@ -336,12 +416,85 @@ class AttentionSeq2SeqAutoencoder(BaseModel):
         """Encoder, then autoregressive generation at the input's length (the text and target_length are not used)."""
         return self.decoder.generate(memory=self.encoder(time_series, src_key_padding_mask=src_key_padding_mask))
 
+    # ---- the opt-in HIP training engine ----------------------------------------------------------------------------------
+    def set_train_engine(self, engine):
+        """'hip' or 'torch' for shared_eval(..., 'train'), overriding T2S_TSAE_TRAIN; None hands the choice back to it."""
+        if engine not in ("hip", "torch", None):
+            raise L.T2SError(f"set_train_engine: 'hip', 'torch' or None (got {engine!r})")
+        self.__dict__["_t2s_train_engine"] = engine
+
+    def _train_engine(self):
+        return self.__dict__.get("_t2s_train_engine") or _train_engine_env()
+
+    def _train_params(self):
+        return [p for _, _, p in _two_sided_fields(L.TsaeWeights(), self.encoder, self.decoder)]
+
+    def _common_dropout(self):
+        """The one dropout probability of every nn.Dropout of the two sides and of their attention modules, or None."""
+        ps = set()
+        for side in (self.encoder, self.decoder):
+            for m in side.modules():
+                if isinstance(m, nn.Dropout):
+                    ps.add(float(m.p))
+                elif isinstance(m, nn.MultiheadAttention):
+                    ps.add(float(m.dropout))
+        return ps.pop() if len(ps) == 1 else None
+
+    def _train_conditions(self, batch, masks=False):
+        """What _train_route weighs for one 'train' call on `batch`, as its keyword arguments."""
+        shapes = (self.encoder._shape(), self.decoder._shape())
+        B, T = (batch.shape[0], batch.shape[1]) if batch.dim() == 3 else (0, 0)
+        covered = (batch.dim() == 3 and shapes[0][:4] == shapes[1][:4] and self.encoder._plain() and self.decoder._plain()
+                   and all(_covered(*s, T, B) for s in shapes) and T <= L.TSAE_TRAIN_MAX_T and batch.shape[2] == shapes[0][0]
+                   and self.encoder.training == self.decoder.training == self.training)
+        return dict(engine=self._train_engine(), forced=_torch_forced(), covered=covered, on_gpu=batch.is_cuda,
+                    input_grad=batch.requires_grad, params_grad=torch.is_grad_enabled() and all(p.requires_grad for p in self._train_params()),
+                    common_p=self._common_dropout(), masks=masks)
+
+    def _weights_struct(self):
+        F_, d, dff, heads, n_enc = self.encoder._shape()
+        w, keep = L.TsaeWeights(), []
+        w.n_features, w.d_model, w.d_ff, w.heads, w.n_enc, w.n_dec = F_, d, dff, heads, n_enc, self.decoder._shape()[4]
+        for dst, field, prm in _two_sided_fields(w, self.encoder, self.decoder):
+            H.fill(dst, [(field, prm)], keep)
+        return w, keep
+
+    def _build(self, device):
+        w, keep = self._weights_struct()          # (the library packs its own copy: `keep` ends with this call)
+        return H.Handle(device, "t2s_tsae_create", "t2s_tsae_destroy", C.byref(w))
+
+    def _refresh(self, h, device):
+        """The parameters moved (an optimizer step): one launch re-packs them on the caller's stream; the sources stay alive on
+        the handle until the next refresh."""
+        w, keep = self._weights_struct()
+        with torch.cuda.device(device):
+            L.check(L.lib().t2s_tsae_update_weights(h.ptr, C.byref(w), L.stream_ptr(device)), "t2s_tsae_update_weights")
+        return keep
+
+    def _train_handle(self, device):
+        """The two-sided handle (HandleOwner._owned_handle): rebuilt when a shape changes, refreshed when only versions did."""
+        device = torch.device(device)
+        ts = self._train_params()
+        H.require_on(ts, device, "TSae")
+        geometry = (device, self.encoder._shape()[3]) + tuple(tuple(t.shape) for t in ts)
+        return self._owned_handle(device, geometry, H.stamp_of(ts), self._build, self._refresh, device)
+
+    def _train_forward_hip(self, batch):
+        """One draw of torch's default CPU generator seeds the step's dropout: seed_everything governs a run, nothing synchronises."""
+        seed = int(torch.randint(0, 2 ** 63 - 1, (1,), dtype=torch.int64).item())
+        p = float(self._common_dropout()) if self.training else 0.0
+        return _TrainStep.apply(self, L.as_f32(batch.detach()), p, seed, *self._train_params())
+
     def shared_eval(self, batch, text_embedding, optimizer, mode):  # pyright: ignore[reportIncompatibleMethodOverride]
-        """'train': one teacher-forced optimisation step (torch ops under autograd); 'val' / 'test': eval mode, no_grad,
-        encode + generate on the HIP entries.  Returns (loss, reconstruction)."""
+        """'train': one teacher-forced optimisation step -- torch ops under autograd, or the HIP node where the training engine is
+        'hip' and _train_route takes it; 'val' / 'test': eval mode, no_grad, encode + generate on the HIP entries.  Returns
+        (loss, reconstruction)."""
         if mode == "train":
             optimizer.zero_grad()
-            recon = self.decoder(memory=self.encoder(batch), target_seq=batch)
+            if _train_route(**self._train_conditions(batch)) == "hip":
+                recon = self._train_forward_hip(batch)
+            else:
+                recon = self.decoder(memory=self.encoder(batch), target_seq=batch)
             loss = F.mse_loss(recon, batch)
             loss.backward()
             optimizer.step()
