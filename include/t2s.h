@@ -480,6 +480,21 @@ int t2s_vae_channels(const t2s_vae* h);            /* 0 for a handle made by t2s
 int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream);
 /* z (B,emb,latent_w) -> recon (B,channels,L) (never squeezed), after (B,emb,L/4) (may be NULL) */
 int t2s_vae_decode_mc(t2s_vae* h, const float* z, float* recon, float* after, int B, int L, int latent_w, void* stream);
+/* 0.7 additions: ragged rows -- every series of a launch has its own length, so the clips of a motion test split (each a
+ * (channels, T_i) recording) share one launch.  lengths (B) int32 and offsets (B + 1) uint64 = the prefix sums of lengths are
+ * DEVICE arrays; series b is (channels, L_b), contiguous at base + channels * offsets[b]; z is (B,emb,latent_w) as in the
+ * uniform entries.  offsets4 (B + 1) = the prefix sums of L_b / 4, `before` the packed (emb, L_b / 4) rows at
+ * emb * offsets4[b] -- required unless max_L / 4 <= 32, as the uniform entry's `before`.  max_L (host, 8 .. 2^20) sizes the
+ * grid's tile dimension for the longest row.  A row is skipped -- nothing of it read or written, its z row untouched by the
+ * encode -- when L_b == 0, when L_b is outside [8, max_L], or when its offsets do not span L_b (offsets4: L_b / 4): a kernel
+ * never leaves the span a row's own offsets give it.  Each row comes out bit for bit as from the uniform entry run on that
+ * row alone at L_b (the kernels share one per-series body).  One launch per direction (the tiled encode adds one ragged
+ * interpolation launch), no device allocation, no synchronisation: usable inside a captured graph.  T2S_E_INVALID before any
+ * launch for a NULL pointer, a handle that is not multichannel, B <= 0, max_L or latent_w out of range. */
+int t2s_vae_decode_mc_ragged(t2s_vae* h, const float* z, const int32_t* lengths, const uint64_t* offsets, float* recon, int B,
+                             int max_L, int latent_w, void* stream);
+int t2s_vae_encode_mc_ragged(t2s_vae* h, const float* x, const int32_t* lengths, const uint64_t* offsets,
+                             const uint64_t* offsets4, float* z, float* before, int B, int max_L, int latent_w, void* stream);
 
 /* Backward of Encoder.forward (vqvae.py:57-71) for the one reference configuration that TRAINS the LA-VAE encoder (train.py:31-33,
  * `usepretrainedvae` false: the encoder is grafted into the denoiser and its parameters join the optimizer).
@@ -660,6 +675,15 @@ int t2s_sampler_set_row0(t2s_sampler* s, uint32_t row0);
  * synchronous copy.  x_T is the caller's: draw it with t2s_philox_normal_rows (stream_id 0xFFFFFFFF).
  * T2S_E_INVALID when n != batch or a cfg value is not finite. */
 int t2s_sampler_set_rows(t2s_sampler* s, const uint64_t* seeds, const uint32_t* key_rows, const float* cfg, int n);
+/* 0.7 additions: per-row series lengths for a sampler with a multichannel decoder.  lengths is a HOST array of n == batch
+ * entries, each 0 (the row decodes nothing) or in [8, cfg.length] -- cfg.length is the maximum; NULL restores the uniform
+ * sampler.  With lengths set, the final decode of t2s_sampler_run is t2s_vae_decode_mc_ragged: `series` is the packed
+ * layout above (row b is (channels, L_b) at channels * sum of the lengths before it) and trace0 is (steps, channels,
+ * lengths[0]).  The loop, its graphs, lanes, solvers and guidance window are untouched: the latent of a run does not depend
+ * on the lengths.  Copied at the call; lengths and offsets reach the device at the next run, stream-ordered from the
+ * sampler's pinned buffer like the tables of t2s_sampler_set_rows.  T2S_E_INVALID, before anything is touched, without a
+ * multichannel decoder, when n != batch or a length is out of range. */
+int t2s_sampler_set_lengths(t2s_sampler* s, const int32_t* lengths, int n);
 /* Number of lanes the sampler currently holds an instantiated hipGraph for (0: the last run was eager / nothing run
  * yet).  Lets a caller (and tests/test_hip_parity.py) check that use_graph = 1 really replays a graph. */
 int t2s_sampler_graph_lanes(const t2s_sampler* s);

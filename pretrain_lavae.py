@@ -71,13 +71,17 @@ NO_MOTION_DATA = ("pretrain_lavae.py: --input_dim > 1 needs a data source: --ser
 
 def motion_groups(args):
     """The length groups of a motion run -> [float tensor (N, C, L)], one per group: the `--series_npy` arrays in the order
-    given, or `--synthetic N` rows at `--split_base_num` x 1, 2, 4."""
+    given, `--synthetic N` rows at `--split_base_num` x 1, 2, 4, or the train split of the bench-press / deadlift dataset
+    under `--dataset_root` (datafactory.motion.motion_groups: the reference's length groups and alignment)."""
     C = args.input_dim
     if args.series_npy:
         groups = [torch.from_numpy(np.asarray(np.load(path), dtype=np.float32)) for path in args.series_npy.split(",") if path]
     elif args.synthetic > 0:
         from t2ms_amd import synth
         groups = [synth.make_mseries(args.general_seed + k, args.synthetic, C, args.split_base_num * m) for k, m in enumerate((1, 2, 4))]
+    elif getattr(args, "dataset_root", ""):
+        from datafactory.motion import motion_groups as dataset_groups
+        groups = [g for g in dataset_groups(args) if g.shape[0]]
     else:
         sys.exit(NO_MOTION_DATA)
     for g in groups:
@@ -185,6 +189,26 @@ def pretrain(args):
     return losses
 
 
+def add_dataset_root(p):
+    """The third data source of a motion run (shared with pretrain_tsae.py)."""
+    p.add_argument("--dataset_root", type=str, default="", help="motion codec: train on <dataset_root>/<dataset_name> (benchpress / "
+                   "deadlift: data.json + captions), the reference's three length groups; --series_npy / --synthetic come first")
+    p.add_argument("--caption", type=str, default="", help="--dataset_root: the caption directory (default: the reference's per dataset)")
+
+
+def resolve_dataset_root(p, args):
+    """With --dataset_root in use: a motion dataset name, and the dataset's own group lengths and caption directory unless the
+    command line gave them."""
+    if not args.dataset_root or args.series_npy or args.synthetic > 0:
+        return
+    from datafactory.motion import DEFAULTS
+    if args.dataset_name not in DEFAULTS:
+        p.error(f"--dataset_root serves the motion datasets: --dataset_name {' / '.join(DEFAULTS)}, got {args.dataset_name!r}")
+    if args.split_base_num == p.get_default("split_base_num"):
+        args.split_base_num = DEFAULTS[args.dataset_name]["split_base_num"]
+    args.caption = args.caption or DEFAULTS[args.dataset_name]["caption"]
+
+
 def get_args(argv=None):
     p = argparse.ArgumentParser(description="Pre-train the LA-VAE")
     p.add_argument("--dataset_name", type=str, default="ETTh1", help="dataset served by loader_provider")
@@ -207,13 +231,16 @@ def get_args(argv=None):
     p.add_argument("--flow_dim", type=int, default=30, help="latent width of the motion codec (50 deadlift, 64 bench press)")
     p.add_argument("--series_npy", type=str, default="", help="motion codec: comma-separated .npy files, one (N,C,L) array per length group")
     p.add_argument("--split_base_num", type=int, default=36, help="motion codec: --synthetic groups are this long x 1, 2, 4")
+    add_dataset_root(p)
     args = p.parse_args(argv)
     if args.split_train:
         args.mix_train = False
     if args.input_dim < 1:
         p.error("--input_dim must be >= 1")
-    if args.input_dim > 1 and not args.series_npy and args.synthetic <= 0:
+    if args.input_dim > 1 and not args.series_npy and args.synthetic <= 0 and not args.dataset_root:
         sys.exit(NO_MOTION_DATA)
+    if args.input_dim > 1:
+        resolve_dataset_root(p, args)
     return args
 
 

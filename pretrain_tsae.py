@@ -28,7 +28,8 @@ REPO = os.path.dirname(os.path.abspath(__file__))
 if REPO not in sys.path:
     sys.path.insert(0, REPO)
 
-from pretrain_lavae import MotionLoader, motion_groups, seed_everything  # noqa: E402  (the length-group plumbing is shared)
+from pretrain_lavae import (MotionLoader, add_dataset_root, motion_groups, resolve_dataset_root,  # noqa: E402
+                            seed_everything)                            # (the length-group plumbing is shared)
 
 
 def save_dir_of(args):
@@ -118,9 +119,11 @@ def get_args(argv=None):
     p.add_argument("--series_npy", type=str, default="", help="comma-separated .npy files, one (N,C,L) array per length group")
     p.add_argument("--synthetic", type=int, default=0, help="N seeded rows per length group instead of files")
     p.add_argument("--train_engine", choices=["hip", "torch"], default=None, help="engine of the 'train' steps (default: T2S_TSAE_TRAIN)")
+    add_dataset_root(p)
     args = p.parse_args(argv)
-    if not args.series_npy and args.synthetic <= 0:
+    if not args.series_npy and args.synthetic <= 0 and not args.dataset_root:
         p.error("a data source is needed: --series_npy a.npy,b.npy,... or --synthetic N")
+    resolve_dataset_root(p, args)
     return args
 
 

@@ -254,6 +254,8 @@ SYMBOLS = {
     "t2s_vae_channels": (_I, [_VP]),
     "t2s_vae_encode_mc": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_vae_decode_mc": (_I, [_VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "t2s_vae_decode_mc_ragged": (_I, [_VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+    "t2s_vae_encode_mc_ragged": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
     "t2s_sampler_create": (_I, [_VP, _VP, C.POINTER(SampleConfig), C.POINTER(_VP)]),
     "t2s_sampler_create_lms": (_I, [_VP, _VP, C.POINTER(SampleConfig), _VP, C.POINTER(_VP)]),
     "t2s_sampler_destroy": (None, [_VP]),
@@ -264,6 +266,7 @@ SYMBOLS = {
     "t2s_sampler_guided_steps": (_I, [_VP, C.POINTER(_I), C.POINTER(_I)]),
     "t2s_sampler_set_row0": (_I, [_VP, _U32]),
     "t2s_sampler_set_rows": (_I, [_VP, _VP, _VP, _VP, _I]),
+    "t2s_sampler_set_lengths": (_I, [_VP, _VP, _I]),
     "t2s_philox_normal_rows": (_I, [_VP, _VP, _VP, _U32, _I, _I, _VP]),
     "t2s_sampler_graph_lanes": (_I, [_VP]),
     "t2s_sampler_lane_pool": (_I, []),
@@ -327,6 +330,49 @@ def as_f32(t: torch.Tensor) -> torch.Tensor:
     if t.dtype != torch.float32:
         t = t.float()
     return t.contiguous()
+
+
+def ragged_layout(lengths, max_length, what: str, batch=None):
+    """The host tables of a ragged launch (t2s_vae_*_mc_ragged, t2s_sampler_set_lengths), validated here before anything
+    reaches the library: (int32 lengths (n), uint64 offsets (n + 1) = prefix sums of the lengths, uint64 offsets4 (n + 1) =
+    prefix sums of L_b // 4).  Every length is an integer, 0 (an empty row) or in [8, max_length] (max_length None: 2**20);
+    `batch`: the row count the caller's object holds.  T2SError otherwise."""
+    import operator
+
+    import numpy as np
+    try:
+        vals = [operator.index(v) for v in lengths]
+        if any(isinstance(v, bool) for v in lengths):
+            raise TypeError
+    except TypeError:
+        raise T2SError(f"{what}: lengths must be a sequence of integers") from None
+    if not vals:
+        raise T2SError(f"{what}: lengths is empty")
+    if batch is not None and len(vals) != int(batch):
+        raise T2SError(f"{what}: {len(vals)} lengths for {int(batch)} rows")
+    top = (1 << 20) if max_length is None else int(max_length)
+    for r, v in enumerate(vals):
+        if v != 0 and not 8 <= v <= top:
+            raise T2SError(f"{what}: lengths[{r}] = {v} (0, or 8 .. {top})")
+    lens = np.asarray(vals, dtype=np.int32)
+    off = np.zeros(len(vals) + 1, dtype=np.uint64)
+    off4 = np.zeros(len(vals) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens.astype(np.uint64))
+    off4[1:] = np.cumsum((lens // 4).astype(np.uint64))
+    return lens, off, off4
+
+
+def ragged_device_tables(lens, off, off4, device):
+    """ragged_layout's tables on the device: ONE pinned staging tensor, one asynchronous copy on the current stream ->
+    (tensor to keep alive, lengths pointer, offsets pointer, offsets4 pointer)."""
+    import numpy as np
+    n = len(lens)
+    pad = np.zeros(n + (n & 1), dtype=np.int32)
+    pad[:n] = lens
+    host = np.concatenate([off, off4, pad.view(np.uint64)])
+    t = torch.from_numpy(host.view(np.int64)).pin_memory().to(device, non_blocking=True)
+    base = t.data_ptr()
+    return t, base + 16 * (n + 1), base, base + 8 * (n + 1)
 
 
 _DEVICE_LOCKS = {}

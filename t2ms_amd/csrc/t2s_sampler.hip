@@ -569,6 +569,10 @@ struct t2s_sampler {
     void* d_rows = nullptr;       // (batch) u64 seeds | (batch) u32 key rows | (batch) f32 cfg
     hipEvent_t ev_rows = nullptr;
     bool ev_rows_recorded = false;
+    // Per-row series lengths (t2s_sampler_set_lengths): the host copy `h_len` = (batch + 1) u64 offsets | (batch) i32 lengths,
+    // staged behind the row tables in the same pinned buffer and the same device buffer, uploaded the same way
+    bool ragged = false, len_dirty = false;
+    std::vector<unsigned char> h_len;
 };
 
 namespace {
@@ -576,6 +580,10 @@ inline size_t rows_bytes(int batch) { return (size_t)batch * (sizeof(uint64_t) +
 inline uint64_t* rows_seed(void* base, int batch) { (void)batch; return (uint64_t*)base; }
 inline uint32_t* rows_key(void* base, int batch) { return (uint32_t*)((uint64_t*)base + batch); }
 inline float* rows_cfg(void* base, int batch) { return (float*)(rows_key(base, batch) + batch); }
+// behind the row tables (rows_bytes is a multiple of 8)
+inline size_t len_bytes(int batch) { return (size_t)(batch + 1) * sizeof(uint64_t) + (size_t)batch * sizeof(int32_t); }
+inline uint64_t* len_offsets(void* base) { return (uint64_t*)base; }
+inline int32_t* len_lengths(void* base, int batch) { return (int32_t*)((uint64_t*)base + batch + 1); }
 }  // namespace
 
 namespace {
@@ -794,10 +802,11 @@ static int sampler_create(t2s_dit* dit, t2s_vae* vae, const t2s_sample_config* c
     alloc((void**)&s->eps_c, B * lat * sizeof(float));
     alloc((void**)&s->tvals, T * sizeof(float));
     alloc((void**)&s->step, t2s_sampler::MAX_LANES * LANE_STATES * sizeof(LoopState));   // one per lane, 64 B apart
-    alloc(&s->d_rows, rows_bytes(cfg->batch));                            // per-row tables (t2s_sampler_set_rows)
-    if (e == hipSuccess) e = hipHostMalloc(&s->h_stage, rows_bytes(cfg->batch), hipHostMallocDefault);
+    alloc(&s->d_rows, rows_bytes(cfg->batch) + len_bytes(cfg->batch));    // per-row tables (t2s_sampler_set_rows, _set_lengths)
+    if (e == hipSuccess) e = hipHostMalloc(&s->h_stage, rows_bytes(cfg->batch) + len_bytes(cfg->batch), hipHostMallocDefault);
     if (e == hipSuccess) e = hipEventCreateWithFlags(&s->ev_rows, hipEventDisableTiming);
     s->h_rows.assign(rows_bytes(cfg->batch), 0);
+    s->h_len.assign(len_bytes(cfg->batch), 0);
     // whole-run adaLN table (dit_adaln_table; 3.2 GB at 256 series x 1000 steps for ~2 % of a step): only while it is a
     // small part of what the device has FREE right now -- at most 1/8 of it and 16 GB -- so that a process holding several
     // samplers, or sharing the GPU with torch's allocator or a training job, does not run dry later for an optimisation;
@@ -924,6 +933,34 @@ extern "C" int t2s_sampler_set_rows(t2s_sampler* s, const uint64_t* seeds, const
     return T2S_OK;
 }
 
+extern "C" int t2s_sampler_set_lengths(t2s_sampler* s, const int32_t* lengths, int n) {
+    T2S_REQUIRE(s, "t2s_sampler_set_lengths: NULL sampler");
+    if (!lengths) {          // uniform again
+        s->ragged = false;
+        s->len_dirty = false;
+        return T2S_OK;
+    }
+    T2S_REQUIRE(s->vae && t2s_vae_channels(s->vae) != 0,
+                "t2s_sampler_set_lengths: per-row lengths need a multichannel decoder (t2s_vae_create_mc)");
+    const int B = s->cfg.batch;
+    T2S_REQUIRE(n == B, "t2s_sampler_set_lengths: n=%d, the sampler's batch is %d", n, B);
+    for (int r = 0; r < n; ++r)
+        T2S_REQUIRE(lengths[r] == 0 || (lengths[r] >= 8 && lengths[r] <= s->cfg.length),
+                    "t2s_sampler_set_lengths: lengths[%d]=%d (0, or 8 .. the sampler's length %d)", r, lengths[r], s->cfg.length);
+    // host work only, as t2s_sampler_set_rows: the arrays reach the device at the next run
+    void* h = s->h_len.data();
+    uint64_t off = 0;
+    for (int r = 0; r < n; ++r) {
+        len_offsets(h)[r] = off;
+        len_lengths(h, B)[r] = lengths[r];
+        off += (uint64_t)lengths[r];
+    }
+    len_offsets(h)[n] = off;
+    s->ragged = true;
+    s->len_dirty = true;
+    return T2S_OK;
+}
+
 extern "C" int t2s_sampler_lane_pool(void) {
     int dev = 0;
     if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return 0;
@@ -966,6 +1003,8 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
     T2S_REQUIRE(!trace0 || s->vae, "t2s_sampler_run: trace requested but the sampler has no VAE");
     hipStream_t st = (hipStream_t)stream;
     const t2s_sample_config& c = s->cfg;
+    const int len0 = s->ragged ? len_lengths(s->h_len.data(), c.batch)[0] : c.length;
+    T2S_REQUIRE(!trace0 || len0 != 0, "t2s_sampler_run: trace requested but row 0 has length 0 (t2s_sampler_set_lengths)");
     int rc;
     int lanes = pick_lanes(s, trace0 != nullptr);
     const bool graph_ok = c.use_graph && !trace0;
@@ -1062,13 +1101,24 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
     if (s->mod_table && (rc = dit_adaln_table(s->dit, s->temb_table, c.steps, text, c.batch, s->mod_table, st)) != T2S_OK) return rc;
     // per-row tables set since the last run: stream-ordered upload from the sampler's own pinned staging buffer (the
     // previous upload has read it once ev_rows completes), before the fork so that every lane sees them
-    if (s->rows && s->rows_dirty) {
+    // (the lengths of t2s_sampler_set_lengths ride behind them, for the decode at the end)
+    const bool up_rows = s->rows && s->rows_dirty, up_len = s->ragged && s->len_dirty;
+    if (up_rows || up_len) {
         if (s->ev_rows_recorded) T2S_HIP_CHECK(hipEventSynchronize(s->ev_rows));
-        memcpy(s->h_stage, s->h_rows.data(), s->h_rows.size());
-        T2S_HIP_CHECK(hipMemcpyAsync(s->d_rows, s->h_stage, s->h_rows.size(), hipMemcpyHostToDevice, st));
+        if (up_rows) {
+            memcpy(s->h_stage, s->h_rows.data(), s->h_rows.size());
+            T2S_HIP_CHECK(hipMemcpyAsync(s->d_rows, s->h_stage, s->h_rows.size(), hipMemcpyHostToDevice, st));
+            s->rows_dirty = false;
+        }
+        if (up_len) {
+            const size_t at = rows_bytes(c.batch);
+            memcpy((unsigned char*)s->h_stage + at, s->h_len.data(), s->h_len.size());
+            T2S_HIP_CHECK(hipMemcpyAsync((unsigned char*)s->d_rows + at, (unsigned char*)s->h_stage + at, s->h_len.size(),
+                                         hipMemcpyHostToDevice, st));
+            s->len_dirty = false;
+        }
         T2S_HIP_CHECK(hipEventRecord(s->ev_rows, st));
         s->ev_rows_recorded = true;
-        s->rows_dirty = false;
     }
     if (lanes > 1) {    // fork: the other lanes start after everything already queued on the caller's stream
         T2S_HIP_CHECK(hipEventRecord(s->ev_fork, st));
@@ -1091,15 +1141,20 @@ extern "C" int t2s_sampler_run(t2s_sampler* s, float* x, const float* text, cons
         }
         if (trace0) {
             // infer.py:90-93: decode row 0 of the first batch after every step
+            // (with per-row lengths: at row 0's own length)
             const int ch = t2s_vae_channels(s->vae);
-            if ((rc = sampler_decode(s->vae, x, trace0 + (size_t)j * (ch ? ch : 1) * c.length, 1, c.length, s->lat / LATC, st)) != T2S_OK) return rc;
+            if ((rc = sampler_decode(s->vae, x, trace0 + (size_t)j * (ch ? ch : 1) * len0, 1, len0, s->lat / LATC, st)) != T2S_OK) return rc;
         }
     }
     for (int l = 1; l < lanes; ++l) {   // join before the decode (and before anything the caller queues next)
         T2S_HIP_CHECK(hipEventRecord(s->ev_join[l], s->side[l]));
         T2S_HIP_CHECK(hipStreamWaitEvent(st, s->ev_join[l], 0));
     }
-    if (series) {
+    if (series && s->ragged) {
+        void* d_len = (unsigned char*)s->d_rows + rows_bytes(c.batch);
+        if ((rc = t2s_vae_decode_mc_ragged(s->vae, x, len_lengths(d_len, c.batch), len_offsets(d_len), series, c.batch, c.length,
+                                           s->lat / LATC, st)) != T2S_OK) return rc;
+    } else if (series) {
         if ((rc = sampler_decode(s->vae, x, series, c.batch, c.length, s->lat / LATC, st)) != T2S_OK) return rc;
     }
     if (via_own) {      // whatever the caller queues on its stream next sees the results

@@ -281,19 +281,19 @@ __device__ inline float decode_last_sample(const VaeDev& w, const float* wide, i
 // The final resampling 4 T -> L: output position t reads samples i0(t) and i0(t) + 1; a tile owns the outputs whose i0 falls in
 // its core [4 c0, 4 c1), and the one sample beyond, 4 c1, lies inside its halo window (it reads the same
 // first-transposed-convolution outputs as the core sample 4 c1 - 1).  i0 is monotone in t, so every output has exactly one owner.
-__global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w, const float* __restrict__ z,
-                                                                 float* __restrict__ recon, float* __restrict__ after,
-                                                                 int L, int W, int C) {
+// The body works on ONE series -- z (emb, W), recon (C, L), after (emb, L/4) or NULL are that series' own rows -- and one time
+// tile `ti` of it; the uniform and the ragged kernel below differ only in where a workgroup finds its rows and its L.
+__device__ __forceinline__ void vae_decode_series(const VaeDev& w, const float* __restrict__ z, float* __restrict__ recon,
+                                                  float* __restrict__ after, int L, int W, int C, int ti) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bufA = smem;                   // [<=256][LD]
     float* bufB = smem + VAE_CMAX * LD;   // [<=256][LD]
     float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][2 Tw] for the first transposed conv
-    const int b = blockIdx.x;
     const int T = L / 4, L4 = 4 * T;
-    const VaeTile tl = vae_tile(T, w.n_res + 2, blockIdx.y);
+    const VaeTile tl = vae_tile(T, w.n_res + 2, ti);
     const int Tw = tl.w1 - tl.w0;
     const int ldz = W <= VAE_TMAX ? LD : LDZ;
-    stage_latent(z + (size_t)b * w.emb * W, w.emb, W, bufB, ldz);
+    stage_latent(z, w.emb, W, bufB, ldz);
     __syncthreads();
     interp_linear_ac(bufB, w.emb, W, ldz, bufA, T, LD, tl.w0, Tw);
     __syncthreads();
@@ -301,7 +301,7 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w,
         const int nc = tl.c1 - tl.c0;
         for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
             const int c = o / nc, t = tl.c0 + (o - c * nc);
-            after[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
+            after[(size_t)c * T + t] = bufA[c * LD + (t - tl.w0)];
         }
     }
     conv1d_lds<3, 1, false, false>(bufA, w.emb, Tw, bufB, w.hidden, Tw, w.dec_conv1_w, w.dec_conv1_b, 1, LD, LD);
@@ -318,7 +318,7 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w,
         const int co = o / Ty, t = y0 + (o - co * Ty);
         const float acc = decode_last_sample(w, wide, ldw, 2 * Tw, 2 * tl.w0, C, co, t);
         if (resample) bufA[co * LDY + (t - y0)] = acc;
-        else recon[((size_t)b * C + co) * L + t] = acc;
+        else recon[(size_t)co * L + t] = acc;
     }
     if (!resample) return;
     __syncthreads();
@@ -333,30 +333,56 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w,
         const int co = o / nt, t = ta + (o - co * nt);
         const InterpTap p = interp_tap_ac(scale, t, L4);
         if (p.i0 < y0 || p.i0 >= yc) continue;
-        recon[((size_t)b * C + co) * L + t] = interp_apply(p, bufA[co * LDY + (p.i0 - y0)], bufA[co * LDY + (p.i1 - y0)]);
+        recon[(size_t)co * L + t] = interp_apply(p, bufA[co * LDY + (p.i0 - y0)], bufA[co * LDY + (p.i1 - y0)]);
     }
+}
+
+__global__ __launch_bounds__(VAE_THREADS) void vae_decode_kernel(const VaeDev w, const float* __restrict__ z,
+                                                                 float* __restrict__ recon, float* __restrict__ after,
+                                                                 int L, int W, int C) {
+    const size_t b = blockIdx.x;
+    vae_decode_series(w, z + b * w.emb * W, recon + b * C * L, after ? after + b * w.emb * (L / 4) : nullptr, L, W, C, blockIdx.y);
+}
+
+// Ragged rows: series b has its own length lengths[b] and lies packed at channels * offsets[b] (offsets = the prefix sums of
+// lengths, B + 1 entries).  A row is SKIPPED -- no read of z, no write -- unless 8 <= L_b <= max_L and offsets[b + 1] -
+// offsets[b] == L_b (so a row never leaves the span its own offsets give it; L_b == 0 is the empty row), and a workgroup whose
+// tile index is past its row's tile count (the grid is sized for max_L) returns: both before any barrier.
+__device__ inline int vae_ragged_length(const int32_t* __restrict__ lengths, const uint64_t* __restrict__ offsets, int b, int max_L) {
+    const int L = lengths[b];
+    return (L >= 8 && L <= max_L && offsets[b + 1] - offsets[b] == (uint64_t)L) ? L : 0;
+}
+
+__global__ __launch_bounds__(VAE_THREADS) void vae_decode_ragged_kernel(const VaeDev w, const float* __restrict__ z,
+                                                                        const int32_t* __restrict__ lengths,
+                                                                        const uint64_t* __restrict__ offsets,
+                                                                        float* __restrict__ recon, int max_L, int W, int C) {
+    const int b = blockIdx.x;
+    const int L = vae_ragged_length(lengths, offsets, b, max_L);
+    if (L == 0 || (int)blockIdx.y >= vae_tiles(L / 4, w.n_res + 2)) return;
+    vae_decode_series(w, z + (size_t)b * w.emb * W, recon + (size_t)C * offsets[b], nullptr, L, W, C, blockIdx.y);
 }
 
 // Encoder.forward (vqvae.py:57-71, myvqvae.py:49-61).  Receptive radius at the L/4 resolution behind conv_2: conv_3 1 + residual
 // stack n_res.  The final interpolation to W positions needs the WHOLE `before` row: fused here when the series is one tile,
 // otherwise vae_interp_rows_kernel reads the rows the tiles wrote.
-__global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w, const float* __restrict__ x,
-                                                                 float* __restrict__ z, float* __restrict__ before,
-                                                                 int L, int W, int C) {
+// One series and one time tile `ti` of it, as vae_decode_series: x (C, L), z (emb, W), before (emb, L/4) or NULL are the
+// series' own rows.
+__device__ __forceinline__ void vae_encode_series(const VaeDev& w, const float* __restrict__ x, float* __restrict__ z,
+                                                  float* __restrict__ before, int L, int W, int C, int ti) {
     extern __shared__ __attribute__((aligned(16))) float smem[];
     float* bufA = smem;
     float* bufB = smem + VAE_CMAX * LD;
     float* wide = bufB + VAE_CMAX * LD;   // [hidden/2][Tu]: conv_1 outputs at L/2-resolution positions [u0, u1)
-    const int b = blockIdx.x;
     const int T2 = L / 2, T = L / 4;
     const int half_c = w.hidden / 2;
-    const VaeTile tl = vae_tile(T, w.n_res + 1, blockIdx.y);
+    const VaeTile tl = vae_tile(T, w.n_res + 1, ti);
     const int Tw = tl.w1 - tl.w0;
     // conv_2 (k4 s2 p1) output t reads conv_1 outputs 2t-1 .. 2t+2
     const int u0 = 2 * tl.w0 - 1 > 0 ? 2 * tl.w0 - 1 : 0;
     const int u1 = 2 * (tl.w1 - 1) + 3 < T2 ? 2 * (tl.w1 - 1) + 3 : T2;
     const int Tu = u1 - u0;
-    encode_stem(w, x + (size_t)b * C * L, C, L, u0, u1, wide);
+    encode_stem(w, x, C, L, u0, u1, wide);
     __syncthreads();
     conv1d_lds<4, 2, true, false>(wide, half_c, Tu, bufA, w.hidden, Tw, w.enc_conv2_w, w.enc_conv2_b, 1, Tu, LD, u0, tl.w0);
     __syncthreads();
@@ -369,28 +395,70 @@ __global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w,
         const int nc = tl.c1 - tl.c0;
         for (int o = threadIdx.x; o < w.emb * nc; o += VAE_THREADS) {
             const int c = o / nc, t = tl.c0 + (o - c * nc);
-            before[((size_t)b * w.emb + c) * T + t] = bufA[c * LD + (t - tl.w0)];
+            before[(size_t)c * T + t] = bufA[c * LD + (t - tl.w0)];
         }
     }
-    if (gridDim.y > 1) return;            // tiled: vae_interp_rows_kernel finishes from `before`
+    if (T > VAE_TMAX) return;             // tiled: the interpolation kernel finishes from `before`
     const float scale = interp_scale_ac(T, W);
     for (int o = threadIdx.x; o < w.emb * W; o += VAE_THREADS) {
         const int c = o / W, t = o - c * W;
         const InterpTap p = interp_tap_ac(scale, t, T);
-        z[(size_t)b * w.emb * W + o] = interp_apply(p, bufA[c * LD + p.i0], bufA[c * LD + p.i1]);
+        z[o] = interp_apply(p, bufA[c * LD + p.i0], bufA[c * LD + p.i1]);
     }
 }
 
-// out (B,C,Tout) = F.interpolate(in (B,C,Tin), Tout, mode='linear', align_corners=True): the latent of a tiled encode
-__global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                                      int C, int Tin, int Tout) {
+__global__ __launch_bounds__(VAE_THREADS) void vae_encode_kernel(const VaeDev w, const float* __restrict__ x,
+                                                                 float* __restrict__ z, float* __restrict__ before,
+                                                                 int L, int W, int C) {
+    const size_t b = blockIdx.x;
+    vae_encode_series(w, x + b * C * L, z + b * w.emb * W, before ? before + b * w.emb * (L / 4) : nullptr, L, W, C, blockIdx.y);
+}
+
+// Ragged rows, as vae_decode_ragged_kernel; `before` rows are packed (emb, L_b / 4) at emb * offsets4[b] (offsets4 = the prefix
+// sums of L_b / 4), and a row whose offsets4 span is not L_b / 4 is skipped too.
+__device__ inline int vae_ragged_length4(const int32_t* __restrict__ lengths, const uint64_t* __restrict__ offsets,
+                                         const uint64_t* __restrict__ offsets4, int b, int max_L) {
+    const int L = vae_ragged_length(lengths, offsets, b, max_L);
+    return (L != 0 && offsets4[b + 1] - offsets4[b] == (uint64_t)(L / 4)) ? L : 0;
+}
+
+__global__ __launch_bounds__(VAE_THREADS) void vae_encode_ragged_kernel(const VaeDev w, const float* __restrict__ x,
+                                                                        const int32_t* __restrict__ lengths,
+                                                                        const uint64_t* __restrict__ offsets,
+                                                                        const uint64_t* __restrict__ offsets4, float* __restrict__ z,
+                                                                        float* __restrict__ before, int max_L, int W, int C) {
+    const int b = blockIdx.x;
+    const int L = vae_ragged_length4(lengths, offsets, offsets4, b, max_L);
+    if (L == 0 || (int)blockIdx.y >= vae_tiles(L / 4, w.n_res + 1)) return;
+    vae_encode_series(w, x + (size_t)C * offsets[b], z + (size_t)b * w.emb * W, before ? before + (size_t)w.emb * offsets4[b] : nullptr,
+                      L, W, C, blockIdx.y);
+}
+
+// out (C,Tout) = F.interpolate(in (C,Tin), Tout, mode='linear', align_corners=True) of one series: the latent of a tiled encode
+__device__ __forceinline__ void vae_interp_series(const float* __restrict__ src, float* __restrict__ out, int C, int Tin, int Tout) {
     const float scale = interp_scale_ac(Tin, Tout);
-    const float* src = in + (size_t)blockIdx.x * C * Tin;
     for (int o = threadIdx.x; o < C * Tout; o += VAE_THREADS) {
         const int c = o / Tout, t = o - c * Tout;
         const InterpTap p = interp_tap_ac(scale, t, Tin);
-        out[(size_t)blockIdx.x * C * Tout + o] = interp_apply(p, src[(size_t)c * Tin + p.i0], src[(size_t)c * Tin + p.i1]);
+        out[o] = interp_apply(p, src[(size_t)c * Tin + p.i0], src[(size_t)c * Tin + p.i1]);
     }
+}
+
+__global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                      int C, int Tin, int Tout) {
+    vae_interp_series(in + (size_t)blockIdx.x * C * Tin, out + (size_t)blockIdx.x * C * Tout, C, Tin, Tout);
+}
+
+// the rows of a ragged encode that ran in time tiles (L_b / 4 > 32); a one-tile row has its latent already
+__global__ __launch_bounds__(VAE_THREADS) void vae_interp_rows_ragged_kernel(const float* __restrict__ in, float* __restrict__ out,
+                                                                             const int32_t* __restrict__ lengths,
+                                                                             const uint64_t* __restrict__ offsets,
+                                                                             const uint64_t* __restrict__ offsets4, int max_L, int C,
+                                                                             int Tout) {
+    const int b = blockIdx.x;
+    const int L = vae_ragged_length4(lengths, offsets, offsets4, b, max_L);
+    if (L / 4 <= VAE_TMAX) return;
+    vae_interp_series(in + (size_t)C * offsets4[b], out + (size_t)b * C * Tout, C, L / 4, Tout);
 }
 
 // ------------------------------------------------------------------------------------------------ encoder backward
@@ -918,6 +986,10 @@ static int vae_create(const t2s_vae_weights* w, int channels, t2s_vae** out, con
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_decode_ragged_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(vae_encode_ragged_kernel),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, bytes));
         attr = true;
     }
     (void)vae_bwd_init();         // (here, outside any stream capture; a refusal is reported by the backward entries)
@@ -1031,6 +1103,42 @@ extern "C" int t2s_vae_encode(t2s_vae* h, const float* x, float* z, float* befor
 
 extern "C" int t2s_vae_encode_mc(t2s_vae* h, const float* x, float* z, float* before, int B, int L, int latent_w, void* stream) {
     return vae_encode("t2s_vae_encode_mc", true, h, x, z, before, B, L, latent_w, stream);
+}
+
+// Ragged rows (include/t2s.h): one launch over the rows' own lengths, the grid's tile dimension sized for max_L
+extern "C" int t2s_vae_decode_mc_ragged(t2s_vae* h, const float* z, const int32_t* lengths, const uint64_t* offsets, float* recon,
+                                        int B, int max_L, int latent_w, void* stream) {
+    const char* who = "t2s_vae_decode_mc_ragged";
+    T2S_REQUIRE(h && z && lengths && offsets && recon, "%s: NULL argument", who);
+    T2S_REQUIRE(h->has_decoder, "%s: handle was created without decoder weights", who);
+    int rc;
+    if ((rc = vae_fwd_check(who, h, true, B, max_L, latent_w))) return rc;
+    vae_decode_ragged_kernel<<<dim3(B, vae_tiles(max_L / 4, h->dev.n_res + 2)), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
+        h->dev, z, lengths, offsets, recon, max_L, latent_w, h->channels);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+extern "C" int t2s_vae_encode_mc_ragged(t2s_vae* h, const float* x, const int32_t* lengths, const uint64_t* offsets,
+                                        const uint64_t* offsets4, float* z, float* before, int B, int max_L, int latent_w,
+                                        void* stream) {
+    const char* who = "t2s_vae_encode_mc_ragged";
+    T2S_REQUIRE(h && x && lengths && offsets && offsets4 && z, "%s: NULL argument", who);
+    T2S_REQUIRE(h->has_encoder, "%s: handle was created without encoder weights", who);
+    int rc;
+    if ((rc = vae_fwd_check(who, h, true, B, max_L, latent_w))) return rc;
+    const int tiles = vae_tiles(max_L / 4, h->dev.n_res + 1);
+    T2S_REQUIRE(tiles == 1 || before, "%s: max_L=%d (max_L/4 > 32) runs in time tiles and needs the `before` output buffer "
+                                      "(the interpolation to the latent reads the whole row)", who, max_L);
+    vae_encode_ragged_kernel<<<dim3(B, tiles), VAE_THREADS, VAE_LDS_FLOATS * 4, (hipStream_t)stream>>>(
+        h->dev, x, lengths, offsets, offsets4, z, before, max_L, latent_w, h->channels);
+    T2S_LAUNCH_CHECK();
+    if (tiles > 1) {
+        vae_interp_rows_ragged_kernel<<<B, VAE_THREADS, 0, (hipStream_t)stream>>>(before, z, lengths, offsets, offsets4, max_L,
+                                                                                  h->dev.emb, latent_w);
+        T2S_LAUNCH_CHECK();
+    }
+    return T2S_OK;
 }
 
 // ------------------------------------------------------------------------ what the backward entries share on the host

@@ -259,6 +259,37 @@ class Encoder(_Codec):
                         L.stream_ptr(dev))
         return z, before
 
+    def encode_ragged(self, series):
+        """Clips of unequal length in ONE launch (t2s_vae_encode_mc_ragged): a list of (C, L_b) GPU tensors, each L_b >= 8 or
+        0 -> z (B,64,flow_dim).  Row b equals forward(series[b][None])[0] bit for bit; the latent of an empty clip is zero.
+        Multichannel codec only; under no_grad (inference: the ragged entries have no backward)."""
+        what = "Encoder.encode_ragged"
+        ch = self.channels
+        if ch is None:
+            raise L.T2SError(f"{what}: the single-channel codec has no ragged entries (model/pretrained/myvqvae.py has)")
+        series = list(series)
+        for b, t in enumerate(series):
+            if not isinstance(t, torch.Tensor) or t.dim() != 2 or t.shape[0] != ch:
+                raise L.T2SError(f"{what}: series[{b}] must be a ({ch},L) tensor, got "
+                                 f"{tuple(t.shape) if isinstance(t, torch.Tensor) else type(t).__name__}")
+        lens, off, off4 = L.ragged_layout([t.shape[1] for t in series], None, what)
+        if any(not t.is_cuda for t in series):
+            raise L.T2SError(f"{what}: the series must live on a GPU; the HIP path has no CPU fallback")
+        B, W, dev, max_L = len(series), self._width(), series[0].device, int(lens.max())
+        emb = self._pre_vq_conv.out_channels
+        with torch.no_grad(), torch.cuda.device(dev):
+            z = torch.zeros(B, emb, W, device=dev, dtype=torch.float32)
+            if max_L == 0:
+                return z
+            x = torch.cat([L.as_f32(t).reshape(-1) for t in series])
+            before = torch.empty(emb * int(off4[-1]), device=dev, dtype=torch.float32)
+            h = self._handle(dev)
+            keep, p_len, p_off, p_off4 = L.ragged_device_tables(lens, off, off4, dev)
+            L.check(L.lib().t2s_vae_encode_mc_ragged(h, L.dev_ptr(x, "series"), p_len, p_off, p_off4, L.dev_ptr(z), L.dev_ptr(before),
+                                                     B, max_L, W, L.stream_ptr(dev)), "t2s_vae_encode_mc_ragged")
+            keep.record_stream(torch.cuda.current_stream(dev))
+        return z
+
     def _forward_kernel(self, route, inputs):
         """The "hip" and "fn" routes."""
         return _EncodeFn.apply(self, inputs, *self._grad_params()) if route == "fn" else self._forward_hip(inputs)
@@ -334,6 +365,32 @@ class Decoder(_Codec):
             after = torch.empty(B, z.shape[1], Ln // 4, device=dev, dtype=torch.float32)
             self._entry(0, h, L.dev_ptr(z, "inputs"), L.dev_ptr(recon), L.dev_ptr(after), B, Ln, W, L.stream_ptr(dev))
         return recon, after
+
+    def decode_ragged(self, z, lengths):
+        """One launch, a length per row (t2s_vae_decode_mc_ragged): z (B,64,W), lengths = B integers, each 0 or >= 8 -> a list
+        of (C, L_b) tensors, views of one packed buffer.  Row b equals forward(z[b:b+1], L_b)[0][0] bit for bit.  Multichannel
+        codec only; under no_grad."""
+        what = "Decoder.decode_ragged"
+        ch = self.channels
+        if ch is None:
+            raise L.T2SError(f"{what}: the single-channel codec has no ragged entries (model/pretrained/myvqvae.py has)")
+        if not isinstance(z, torch.Tensor) or z.dim() != 3 or z.shape[1] != self._conv_1.in_channels:
+            raise L.T2SError(f"{what}: latent must be (B,{self._conv_1.in_channels},W), got "
+                             f"{tuple(z.shape) if isinstance(z, torch.Tensor) else type(z).__name__}")
+        lens, off, off4 = L.ragged_layout(lengths, None, what, batch=z.shape[0])
+        if not z.is_cuda:
+            raise L.T2SError(f"{what}: latent must live on a GPU; the HIP path has no CPU fallback")
+        B, W, dev, max_L = z.shape[0], z.shape[2], z.device, int(lens.max())
+        with torch.no_grad(), torch.cuda.device(dev):
+            packed = torch.empty(ch * int(off[-1]), device=dev, dtype=torch.float32)
+            if max_L != 0:
+                zc = L.as_f32(z)
+                h = self._handle(dev)
+                keep, p_len, p_off, _ = L.ragged_device_tables(lens, off, off4, dev)
+                L.check(L.lib().t2s_vae_decode_mc_ragged(h, L.dev_ptr(zc, "latent"), p_len, p_off, L.dev_ptr(packed), B, max_L, W,
+                                                         L.stream_ptr(dev)), "t2s_vae_decode_mc_ragged")
+                keep.record_stream(torch.cuda.current_stream(dev))
+        return [packed[ch * int(off[b]):ch * int(off[b + 1])].view(ch, int(lens[b])) for b in range(B)]
 
     def _forward_kernel(self, route, inputs, Ln):
         """The "hip" and "fn" routes: (recon, after) of the Ln samples the kernels write."""

@@ -5,6 +5,8 @@ Class names, constructor signatures, attribute names and state-dict keys equal t
 (myinfer.py:126-128, mytrain.py:29-30) and a whole-module pickle both load.  Under no_grad ``Encoder.forward`` and
 ``Decoder.forward`` run the single-launch HIP kernels t2s_vae_encode_mc / t2s_vae_decode_mc (csrc/t2s_vae.hip): C <= 16,
 flow_dim <= 64, hidden <= 128, res_hidden <= 256, <= 4 residual layers, embedding_dim 64.  No CPU fallback.
+``Encoder.encode_ragged`` / ``Decoder.decode_ragged`` (_lavae.py) take clips of unequal length in one launch each
+(t2s_vae_encode_mc_ragged / t2s_vae_decode_mc_ragged; inference only).
 
 With grad enabled and a parameter or the latent asking for a gradient, a covered shape (``_mc_backward_covers``: hidden 128,
 embedding_dim 64, res_hidden 128 / 256, 1..4 residual layers, 8 <= L <= 192, flow_dim <= 64, C <= 16) runs the same HIP forward

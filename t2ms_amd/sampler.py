@@ -439,6 +439,8 @@ class Sampler:
             L.check(L.lib().t2s_sampler_set_loop_graph(self.ptr, self.loop_graph), "t2s_sampler_set_loop_graph")
         if self.__dict__.get("_rows") is not None:      # a re-created C sampler keeps the per-row tables
             self.set_rows(*self._rows)
+        if self.__dict__.get("_lengths") is not None:   # ... and the per-row lengths
+            self._set_lengths_locked(self._lengths, force=True)
         if self._guided != (0, self.steps):             # ... and the guided window (a new C sampler guides every step)
             L.check(L.lib().t2s_sampler_set_guided_steps(self.ptr, *self._guided), "t2s_sampler_set_guided_steps")
         self._keep = (tvals, coef)
@@ -487,6 +489,31 @@ class Sampler:
                                              None if c is None else c.ctypes.data, n), "t2s_sampler_set_rows")
         self._rows = (s, k, c)
 
+    def check_lengths(self, lengths):
+        """Host-side validation of a run's per-row lengths, before anything reaches the library: `batch` integers, each 0 or
+        in [8, length], for a sampler with a multichannel decoder -> (int32 lengths, uint64 offsets).  T2SError otherwise."""
+        if self.channels is None:
+            raise L.T2SError("Sampler: per-row lengths need the multichannel decoder (model/pretrained/myvqvae.py); "
+                             "the single-channel codec has no ragged decode")
+        lens, off, _ = L.ragged_layout(lengths, self.length, "Sampler: lengths", batch=self.batch)
+        return lens, off
+
+    def _set_lengths_locked(self, lengths, force=False):
+        """lengths: what check_lengths returned, or None = the uniform (B,C,L) sampler again (t2s_sampler_set_lengths)."""
+        cur = self.__dict__.get("_lengths")
+        same = (cur is None) == (lengths is None) and (cur is None or np.array_equal(cur[0], lengths[0]))
+        if same and not force:
+            return
+        L.check(L.lib().t2s_sampler_set_lengths(self.ptr, None if lengths is None else lengths[0].ctypes.data,
+                                                0 if lengths is None else len(lengths[0])), "t2s_sampler_set_lengths")
+        self._lengths = lengths
+
+    def _ragged_rows(self, packed):
+        """The rows of a packed series buffer as (C, L_b) views."""
+        lens, off = self._lengths
+        ch = self.channels
+        return [packed[ch * int(off[b]):ch * int(off[b + 1])].view(ch, int(lens[b])) for b in range(self.batch)]
+
     def draw_xT(self, out: Optional[torch.Tensor] = None) -> torch.Tensor:
         """x_T ~ N(0,1) from the Philox stream (perf mode), (batch,64,W); per row as set_rows keyed it."""
         row = L.LAT_C * self.width
@@ -505,10 +532,16 @@ class Sampler:
         return out
 
     def run(self, text: torch.Tensor, x_T: Optional[torch.Tensor] = None, noise: Optional[torch.Tensor] = None,
-            decode: bool = True, trace: bool = False):
+            decode: bool = True, trace: bool = False, lengths=None):
         """Returns (latent (B,64,W), series (B,L) or None, trace (steps,L) or None); with a multichannel decoder the series
         is (B,C,L) and the trace (steps,C,L).  W is the model's latent width (30; 50 / 64 for mytransformer.Transformer).
-        ``noise`` (steps,B,64,W) injects the per-step draws (parity mode)."""
+        ``noise`` (steps,B,64,W) injects the per-step draws (parity mode).
+        ``lengths`` (multichannel decoder only): B integers, each 0 or in [8, length] -- row b is decoded at lengths[b], the
+        series is a LIST of (C, L_b) tensors (views of one packed buffer) and the trace (steps,C,lengths[0]).  The latent
+        does not depend on them.  They hold for this run and for run_inplace until a run() without them."""
+        ragged = None if lengths is None else self.check_lengths(lengths)       # host-side, before anything is uploaded
+        if ragged is not None and trace and int(ragged[0][0]) == 0:
+            raise L.T2SError("Sampler.run: trace requested but lengths[0] is 0")
         with L.device_lock(self.device):
             dev = self.device
             text = L.as_f32(text.to(dev))
@@ -532,12 +565,14 @@ class Sampler:
                     raise L.T2SError(f"Sampler.run: noise must be ({self.steps},{self.batch},64,{self.width})")
             if (decode or trace) and self.decoder is None:
                 raise L.T2SError("Sampler.run: decode requested but no decoder was given")
-            tr = torch.empty(self.steps, *self._row_shape(), device=dev, dtype=torch.float32) if trace else None
+            tr_shape = self._row_shape() if ragged is None else (self.channels, int(ragged[0][0]))
+            tr = torch.empty(self.steps, *tr_shape, device=dev, dtype=torch.float32) if trace else None
             with torch.cuda.device(dev):
                 # weights may have changed since the last run: refresh the packed copy on the caller's stream
                 self.model.t2s_handle(dev, 2 * self.batch)
                 if self.model.t2s_handle_id() != self._dit_uid:
                     self._create()  # the model re-created its handle (capacity grew / device moved): drop the graph
+                self._set_lengths_locked(ragged)
                 cur = torch.cuda.current_stream(dev)
                 self.stream.wait_stream(cur)
                 L.check(L.lib().t2s_sampler_run(self.ptr, L.dev_ptr(self._x), L.dev_ptr(self._text), L.dev_ptr(noise),
@@ -545,6 +580,9 @@ class Sampler:
                                                 self.stream.cuda_stream), "t2s_sampler_run")
                 cur.wait_stream(self.stream)
             self._last = (noise, tr)  # keep caller-provided buffers alive until the stream has consumed them
+            if ragged is not None and decode:      # the packed rows fill the front of the (B,C,length) buffer
+                packed = self._series.view(-1)[:self.channels * int(ragged[1][-1])].clone()
+                return self._x.clone(), self._ragged_rows(packed), tr
             return self._x.clone(), (self._series.clone() if decode else None), tr
 
     def _row_shape(self):
@@ -558,7 +596,8 @@ class Sampler:
 
     def run_inplace(self, decode: bool = True):
         """Benchmark entry: x_T from Philox into the persistent buffers, no output copies.
-        Requires one prior run() (buffers + text in place).  Returns (latent, series) views."""
+        Requires one prior run() (buffers + text in place).  Returns (latent, series) views; after a run() with lengths
+        the series is the list of (C, L_b) views of the packed buffer."""
         dev = self.device
         with L.device_lock(dev), torch.cuda.device(dev):
             if self.model.t2s_handle_id() != self._dit_uid:
@@ -570,6 +609,8 @@ class Sampler:
                                             L.dev_ptr(self._series) if decode else None, None,
                                             self.stream.cuda_stream), "t2s_sampler_run")
             cur.wait_stream(self.stream)
+        if self.__dict__.get("_lengths") is not None:
+            return self._x, self._ragged_rows(self._series.view(-1))
         return self._x, self._series
 
 
