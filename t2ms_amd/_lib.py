@@ -290,6 +290,14 @@ class T2SError(RuntimeError):
     pass
 
 
+# include/t2s_wide_train.h: the entries of wide-latent training (an extension header with a table of its own, resolved by
+# lib() with SYMBOLS; tests/test_wide_train_host.py compares the two as tests/test_cabi_symbols.py does for t2s.h)
+SYMBOLS_WIDE_TRAIN = {
+    "t2s_dit_set_trainable": (_I, [_VP, _I]),
+    "t2s_attn_train_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
+}
+
+
 def lib() -> C.CDLL:
     """Load libt2s_hip.so (once).  Raises if it has not been built."""
     global _lib
@@ -299,7 +307,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C t2ms_amd/csrc` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in SYMBOLS.items():
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         _lib = handle

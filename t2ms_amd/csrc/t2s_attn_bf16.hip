@@ -353,10 +353,10 @@ int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* 
     return T2S_OK;
 }
 
-int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* o_rows, float* lse, int BH,
+int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* o_rows, float* lse, int BH, int n_tok,
                          hipStream_t st);                                                       // t2s_attn_bwd.hip
 int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows, const float* do_rows,
-             const float* lse, float* dsum, float* dqkv_rows, int BH, hipStream_t st);
+             const float* lse, float* dsum, float* dqkv_rows, int BH, int n_tok, hipStream_t st);
 
 }  // namespace t2s
 
@@ -408,24 +408,27 @@ extern "C" int t2s_attn_fwd_bf16(const float* q, const float* k, const float* v,
     return rc;
 }
 
-extern "C" int t2s_attn_train(const float* q, const float* k, const float* v, const float* do_rows, float* o_rows, float* lse,
-                              float* dqkv_rows, int n_seq, int dtype, void* stream) {
+// t2s_attn_train / t2s_attn_train_n: the launchers of the training step on caller tensors, n_tok tokens per sequence
+static int attn_train_any(const char* who, const float* q, const float* k, const float* v, const float* do_rows, float* o_rows,
+                          float* lse, float* dqkv_rows, int n_seq, int n_tok, int dtype, void* stream) {
     using namespace t2s;
-    T2S_REQUIRE(q && k && v && do_rows && o_rows && lse && dqkv_rows && n_seq > 0, "t2s_attn_train: bad argument");
-    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_attn_train: unknown dtype %d", dtype);
+    T2S_REQUIRE(q && k && v && do_rows && o_rows && lse && dqkv_rows && n_seq > 0, "%s: bad argument", who);
+    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "%s: unknown dtype %d", who, dtype);
+    T2S_REQUIRE(n_tok == NTOK || n_tok == 800 || n_tok == 1024, "%s: n_tok=%d (480, 800 and 1024 tokens are built)", who, n_tok);
+    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || n_tok == NTOK, "%s: T2S_TRAIN_BF16 runs at 480 tokens only, not %d", who, n_tok);
     hipStream_t st = (hipStream_t)stream;
     const int BH = n_seq * NH;
-    const size_t n = (size_t)BH * NTOK * DH;               // elements of each of q, k, v, o, do; dqkv has 3 n
-    float* dsum = nullptr;                                 // D_i (BH, 480)
+    const size_t n = (size_t)BH * n_tok * DH;              // elements of each of q, k, v, o, do; dqkv has 3 n
+    float* dsum = nullptr;                                 // D_i (BH, n_tok)
     __bf16* buf = nullptr;                                 // bf16: q | k | v | o | do | dqkv
-    T2S_HIP_CHECK(hipMalloc(&dsum, (size_t)BH * NTOK * sizeof(float)));
+    T2S_HIP_CHECK(hipMalloc(&dsum, (size_t)BH * n_tok * sizeof(float)));
     reset_tile_dir();                                      // as at the top of a training forward
     int rc = T2S_OK;
     if (dtype == T2S_TRAIN_F32) {
-        rc = attn_plain_train_fwd(q, k, v, o_rows, lse, BH, st);
-        if (rc == T2S_OK) rc = attn_bwd(q, k, v, o_rows, do_rows, lse, dsum, dqkv_rows, BH, st);
+        rc = attn_plain_train_fwd(q, k, v, o_rows, lse, BH, n_tok, st);
+        if (rc == T2S_OK) rc = attn_bwd(q, k, v, o_rows, do_rows, lse, dsum, dqkv_rows, BH, n_tok, st);
     } else if (hipMalloc(&buf, 8 * n * sizeof(__bf16)) != hipSuccess) {
-        set_error("t2s_attn_train: out of memory for %zu bf16 values", 8 * n);
+        set_error("%s: out of memory for %zu bf16 values", who, 8 * n);
         rc = T2S_E_HIP;
     } else {
         __bf16 *qh = buf, *kh = buf + n, *vh = buf + 2 * n, *oh = buf + 3 * n, *doh = buf + 4 * n, *dh = buf + 5 * n;
@@ -442,4 +445,14 @@ extern "C" int t2s_attn_train(const float* q, const float* k, const float* v, co
     if (buf) (void)hipFree(buf);
     (void)hipFree(dsum);
     return rc;
+}
+
+extern "C" int t2s_attn_train(const float* q, const float* k, const float* v, const float* do_rows, float* o_rows, float* lse,
+                              float* dqkv_rows, int n_seq, int dtype, void* stream) {
+    return attn_train_any("t2s_attn_train", q, k, v, do_rows, o_rows, lse, dqkv_rows, n_seq, t2s::NTOK, dtype, stream);
+}
+
+extern "C" int t2s_attn_train_n(const float* q, const float* k, const float* v, const float* do_rows, float* o_rows, float* lse,
+                                float* dqkv_rows, int n_seq, int n_tok, int dtype, void* stream) {
+    return attn_train_any("t2s_attn_train_n", q, k, v, do_rows, o_rows, lse, dqkv_rows, n_seq, n_tok, dtype, stream);
 }

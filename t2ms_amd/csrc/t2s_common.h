@@ -6,6 +6,7 @@
 #include <stdarg.h>
 
 #include "../../include/t2s.h"
+#include "../../include/t2s_wide_train.h"
 
 namespace t2s {
 

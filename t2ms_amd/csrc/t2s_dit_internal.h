@@ -39,6 +39,7 @@ struct t2s_dit {
     hipEvent_t w_ev = nullptr;   // recorded behind the last t2s_dit_update_weights (what a first-use pack must wait for)
     t2s_train_ws* train = nullptr;
     int train_dtype = 0;         // T2S_TRAIN_F32 / T2S_TRAIN_BF16 (t2s_dit_set_train_dtype)
+    bool trainable = false;      // a wide handle trains only after t2s_dit_set_trainable (width 30 always does)
     // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;

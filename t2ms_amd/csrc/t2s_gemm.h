@@ -30,11 +30,12 @@ struct GemmArgs {
     int shift_off;      // column offsets inside a MODROW row
     int scale_off;
     int gate_off;
-    float* q;           // EPI_QKV destinations, each (S,4,480,32)
+    float* q;           // EPI_QKV destinations, each (S,4,tokens,32)
     float* k;
     float* v;
     float* save_A;      // optional (M,K): the prologue-transformed A rows (training saves LN-modulated inputs)
     const float* aux;   // EPI_GELUBWD: pre-activation u (M,N); out = acc * gelu'(u)
+    int ntok;           // TOK == 0 instantiations: tokens per sequence (a multiple of 32)
 };
 
 // d/du [ u * sigmoid(2 z(u)) ],  z = sqrt(2/pi) (u + 0.044715 u^3)   (GELU tanh form)
@@ -51,9 +52,11 @@ __device__ __forceinline__ float gelu_tanh(float x) {
     return x * __builtin_amdgcn_rcpf(1.0f + __expf(-2.0f * u));
 }
 
-template <int K, int NT, int PRO, int EPI>
+// TOK: tokens per sequence of the row -> sequence maps (PRO_LNMOD, EPI_QKV, EPI_GATERES); 0 = a.ntok at run time
+template <int K, int NT, int PRO, int EPI, int TOK = NTOK>
 __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmArgs a) {
     constexpr int BM = 64;
+    const int ntok = TOK ? TOK : a.ntok;
     constexpr int LDA = K + 4;
     constexpr int KG = K / 8;
     extern __shared__ __attribute__((aligned(16))) float smem[];
@@ -86,7 +89,7 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmArgs a) {
 #pragma unroll
             for (int o = 16; o >= 1; o >>= 1) ss += __shfl_xor(ss, o, 64);
             const float rstd = rsqrtf(ss * (1.0f / 128.0f) + 1e-6f);
-            const int seq = (grow < a.M ? grow : 0) / NTOK;
+            const int seq = (grow < a.M ? grow : 0) / ntok;
             const float* mrow = a.mod + (size_t)seq * MODROW;
             const f32x4 sc = *reinterpret_cast<const f32x4*>(mrow + a.scale_off + c4 * 4);
             const f32x4 sh = *reinterpret_cast<const f32x4*>(mrow + a.shift_off + c4 * 4);
@@ -180,11 +183,11 @@ __global__ __launch_bounds__(256) void gemm_rows_kernel(const GemmArgs a) {
                 } else if constexpr (EPI == EPI_GELUBWD) {
                     a.out[(size_t)grow * a.N + col] = y * gelu_tanh_grad(a.aux[(size_t)grow * a.N + col]);
                 } else if constexpr (EPI == EPI_QKV) {
-                    const int seq = grow / NTOK;
-                    const int tok = grow - seq * NTOK;
-                    qkv_base[(((size_t)seq * NH + head) * NTOK + tok) * DH + j] = y;
+                    const int seq = grow / ntok;
+                    const int tok = grow - seq * ntok;
+                    qkv_base[(((size_t)seq * NH + head) * ntok + tok) * DH + j] = y;
                 } else {  // EPI_GATERES
-                    const int seq = grow / NTOK;
+                    const int seq = grow / ntok;
                     const float gate = a.mod[(size_t)seq * MODROW + a.gate_off + col];
                     float* px = a.out + (size_t)grow * D + col;
                     *px = *px + gate * y;
@@ -204,7 +207,7 @@ inline int gemm_rows_init() {
     return T2S_OK;
 }
 
-template <int K, int NT, int PRO, int EPI>
+template <int K, int NT, int PRO, int EPI, int TOK = NTOK>
 inline int launch_gemm_rows(const GemmArgs& a, hipStream_t st) {
     constexpr int BN = 4 * NT * 32;
     if (a.N % BN != 0 || a.M <= 0) {
@@ -215,13 +218,17 @@ inline int launch_gemm_rows(const GemmArgs& a, hipStream_t st) {
     if constexpr (lds > 48 * 1024) {
         static bool attr = false;   // first call must not be under stream capture (training never is)
         if (!attr) {
-            T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_kernel<K, NT, PRO, EPI>),
+            T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(gemm_rows_kernel<K, NT, PRO, EPI, TOK>),
                                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
             attr = true;
         }
     }
     dim3 grid((a.M + 63) / 64, a.N / BN);
-    gemm_rows_kernel<K, NT, PRO, EPI><<<grid, 256, lds, st>>>(a);
+    if (TOK == 0 && (a.ntok <= 0 || a.ntok % 32 != 0)) {
+        set_error("gemm_rows: ntok=%d is not a positive multiple of 32", a.ntok);
+        return T2S_E_INVALID;
+    }
+    gemm_rows_kernel<K, NT, PRO, EPI, TOK><<<grid, 256, lds, st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

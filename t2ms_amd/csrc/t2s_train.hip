@@ -22,10 +22,10 @@
 using namespace t2s;
 
 namespace t2s {
-int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* o_rows, float* lse, int BH,
+int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* o_rows, float* lse, int BH, int n_tok,
                          hipStream_t st);
 int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows, const float* do_rows,
-             const float* lse, float* dsum, float* dqkv_rows, int BH, hipStream_t st);
+             const float* lse, float* dsum, float* dqkv_rows, int BH, int n_tok, hipStream_t st);
 int attn16_train_fwd(const __bf16* q, const __bf16* k, const __bf16* v, __bf16* o_rows, float* lse, int BH, hipStream_t st);
 int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* o_rows, const __bf16* do_rows,
                const float* lse, float* dsum, __bf16* dqkv_rows, int BH, hipStream_t st);
@@ -37,11 +37,14 @@ struct t2s_train_ws {
     int cap_seqs = 0;
     int dtype = 0;        // T2S_TRAIN_F32 / T2S_TRAIN_BF16 this workspace was laid out for
     int S = 0;            // sequences of the last forward
+    int latw = LATW;      // the handle's latent width: a sequence is ntok() = 16 W tokens, a latent lat_elems() = 64 W values
+    int ntok() const { return 16 * latw; }
+    int lat_elems() const { return LATC * latw; }
     // ---- both arithmetics, all fp32, pieces of `act` (carve_act): the residual stream, the statistics, the conditioning and
     // what the backward keeps in fp32
     float* act = nullptr;
     float *x_in[NBLK + 1], *x_mid[NBLK], *lse[NBLK];
-    float *silu_c = nullptr, *mod = nullptr, *c = nullptr, *lat = nullptr;   // (S,128) (S,3072) (S,128) (S,1920)
+    float *silu_c = nullptr, *mod = nullptr, *c = nullptr, *lat = nullptr;   // (S,128) (S,3072) (S,128) (S,64 W)
     float *dx = nullptr, *dsum = nullptr, *dmod = nullptr;
     float* t1 = nullptr;           // (S,768) dense slice of dmod for the adaLN weight gradient; f32: also the block backward's (M,128) temporary
     float* wg_scratch = nullptr;   // partial weight-gradient tiles (wgrad16 stage 1 -> stage 2)
@@ -93,15 +96,18 @@ __device__ __forceinline__ f32x4 ld4(const __bf16* p, size_t i4) { return unpack
 __device__ __forceinline__ void st4(float* p, size_t i4, f32x4 v) { reinterpret_cast<f32x4*>(p)[i4] = v; }
 __device__ __forceinline__ void st4(__bf16* p, size_t i4, f32x4 v) { reinterpret_cast<bf16x4*>(p)[i4] = pack4(v); }
 
+// Geometry of the kernels below: W = 30 bakes the latent width in (the 480-token step), W = 0 takes it from latw_rt
+// (800 / 1024 tokens).  Token n = hh * 32 + ww owns the 2x2 patch lat[2ww+j][2hh+i] at every width.
 // x_out = x_in + gate[seq] * f      (rows of 128)
-template <typename T>
+template <int W, typename T>
 __global__ __launch_bounds__(256) void gate_res_kernel(const float* __restrict__ xin, const T* __restrict__ f,
                                                        const float* __restrict__ mod, int gate_off,
-                                                       float* __restrict__ xout, int M) {
+                                                       float* __restrict__ xout, int M, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw;
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // float4 index
     if (idx >= M * 32) return;
     const int row = idx >> 5, c4 = idx & 31;
-    const int seq = row / NTOK;
+    const int seq = row / ntok;
     const f32x4 g = *reinterpret_cast<const f32x4*>(mod + (size_t)seq * MODROW + gate_off + c4 * 4);
     const f32x4 a = reinterpret_cast<const f32x4*>(xin)[idx];
     const f32x4 b = ld4(f, idx);
@@ -109,17 +115,18 @@ __global__ __launch_bounds__(256) void gate_res_kernel(const float* __restrict__
 }
 
 // one workgroup per sequence: t = gate * dx ; dgate[seq] = sum_tok dx * f
-template <typename T>
+template <int W, typename T>
 __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__ dx, const T* __restrict__ f,
                                                        const float* __restrict__ mod, int gate_off,
-                                                       T* __restrict__ t, float* __restrict__ dmod) {
+                                                       T* __restrict__ t, float* __restrict__ dmod, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw;
     __shared__ f32x4 red[8][32];
     const int seq = blockIdx.x;
     const int c4 = threadIdx.x & 31, rg = threadIdx.x >> 5;   // 8 row groups
     const f32x4 g = *reinterpret_cast<const f32x4*>(mod + (size_t)seq * MODROW + gate_off + c4 * 4);
     f32x4 acc = {0.f, 0.f, 0.f, 0.f};
-    for (int tok = rg; tok < NTOK; tok += 8) {
-        const size_t idx = ((size_t)seq * NTOK + tok) * 32 + c4;
+    for (int tok = rg; tok < ntok; tok += 8) {
+        const size_t idx = ((size_t)seq * ntok + tok) * 32 + c4;
         const f32x4 d = reinterpret_cast<const f32x4*>(dx)[idx];
         const f32x4 fv = ld4(f, idx);
         st4(t, idx, g * d);
@@ -141,12 +148,13 @@ __global__ __launch_bounds__(256) void gate_bwd_kernel(const float* __restrict__
 // and, when f_next != NULL, the gate backward of the branch that is differentiated next
 // (gate_bwd_kernel) on the dx it has just produced: t_next = gate_next * dx, dgate_next = sum_tok dx * f_next
 // -- that saves one read of the fp32 gradient stream per branch.
-template <typename T>
+template <int W, typename T>
 __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const T* __restrict__ da, const float* __restrict__ x,
                                                          const float* __restrict__ mod, int shift_off, int scale_off,
                                                          float* __restrict__ dx, float* __restrict__ dmod,
                                                          const T* __restrict__ f_next, int gate_next_off,
-                                                         T* __restrict__ t_next) {
+                                                         T* __restrict__ t_next, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw;
     __shared__ f32x4 red[3][8][32];
     const int seq = blockIdx.x;
     const int c4 = threadIdx.x & 31, rg = threadIdx.x >> 5;
@@ -154,8 +162,8 @@ __global__ __launch_bounds__(256) void ln_mod_bwd_kernel(const T* __restrict__ d
     f32x4 gn = {0.f, 0.f, 0.f, 0.f};
     if (f_next != nullptr) gn = *reinterpret_cast<const f32x4*>(mod + (size_t)seq * MODROW + gate_next_off + c4 * 4);
     f32x4 a_sh = {0.f, 0.f, 0.f, 0.f}, a_sc = {0.f, 0.f, 0.f, 0.f}, a_gt = {0.f, 0.f, 0.f, 0.f};
-    for (int tok = rg; tok < NTOK; tok += 8) {
-        const size_t idx = ((size_t)seq * NTOK + tok) * 32 + c4;
+    for (int tok = rg; tok < ntok; tok += 8) {
+        const size_t idx = ((size_t)seq * ntok + tok) * 32 + c4;
         const f32x4 xv = reinterpret_cast<const f32x4*>(x)[idx];
         const f32x4 g = ld4(da, idx);
         float s = (xv.x + xv.y) + (xv.z + xv.w);
@@ -269,18 +277,19 @@ __global__ void final_gate_reduce_kernel(const float* __restrict__ part, int str
     dmod[(size_t)seq * MODROW + gate_off + f] = (p[0] + p[stride]) + p[2 * stride];
 }
 
-// final layer backward (transformer.py:182-191): dout (S,64,30) -> dx (M,128) and grads of
+// final layer backward (transformer.py:182-191): dout (S,64,W) -> dx (M,128) and grads of
 // ln.weight, ln.bias, linear_emb_to_patch.{weight,bias}.  32 lanes per token row.
 // FUSED (bf16 training): the layer input x_mid + gate * f of the last block is formed here instead of being read back
 // (the forward never writes it), and the gate backward of that MLP branch runs on the dx just produced: t = gate * dx
 // (bf16 rows), dgate partial = sum over this workgroup's rows of dx * f in columns FINAL_COLS.. of its partial row.
 // FUSED workgroups own ROWS = 160 rows = a third of a sequence, so three consecutive partial rows make one sequence.
-template <bool FUSED, int ROWS>
+template <bool FUSED, int ROWS, int W>
 __global__ __launch_bounds__(256) void final_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout,
                                                         const float* __restrict__ lng, const float* __restrict__ lnb,
                                                         const float* __restrict__ ow, float* __restrict__ dx,
                                                         float* __restrict__ part, int M, const __bf16* __restrict__ f,
-                                                        const float* __restrict__ mod, int gate_off, __bf16* __restrict__ t) {
+                                                        const float* __restrict__ mod, int gate_off, __bf16* __restrict__ t, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw, lat = LATC * latw;
     constexpr int PCOLS = FUSED ? FINAL_COLS + D : FINAL_COLS;
     __shared__ f32x4 red[FUSED ? 7 : 6][8][32];
     __shared__ float redb[8][4];
@@ -294,7 +303,7 @@ __global__ __launch_bounds__(256) void final_bwd_kernel(const float* __restrict_
     float a_ob[4] = {0.f, 0.f, 0.f, 0.f};
     f32x4 a_gt = {0, 0, 0, 0}, gt = {0, 0, 0, 0};
     const int row0 = blockIdx.x * ROWS;
-    if constexpr (FUSED) gt = *reinterpret_cast<const f32x4*>(mod + (size_t)(row0 / NTOK) * MODROW + gate_off + c4 * 4);
+    if constexpr (FUSED) gt = *reinterpret_cast<const f32x4*>(mod + (size_t)(row0 / ntok) * MODROW + gate_off + c4 * 4);
     static_assert(ROWS % 32 == 0, "8 row groups x 4 rows in flight");
     for (int it0 = 0; it0 < ROWS / 8; it0 += 4) {      // 4 rows per 32-lane group in flight: loads first, then the chains
         f32x4 xv4[4], fv4[4];
@@ -313,12 +322,12 @@ __global__ __launch_bounds__(256) void final_bwd_kernel(const float* __restrict_
                 xv4[u] = xv4[u] + gt * fv4[u];              // the expression of gate_res_kernel
             }
             // gather d(lin)[p] from the unpatchified output gradient
-            const int seq = row / NTOK, tok = row - seq * NTOK;
+            const int seq = row / ntok, tok = row - seq * ntok;
             const int hh = tok >> 5, ww = tok & 31;
             const float keep = valid4[u] ? 1.f : 0.f;
 #pragma unroll
             for (int p = 0; p < 4; ++p)
-                dl4[u][p] = keep * dout[(size_t)seq * LAT + (2 * ww + (p & 1)) * LATW + 2 * hh + (p >> 1)];
+                dl4[u][p] = keep * dout[(size_t)seq * lat + (2 * ww + (p & 1)) * latw + 2 * hh + (p >> 1)];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -395,9 +404,11 @@ __global__ __launch_bounds__(256) void final_bwd_kernel(const float* __restrict_
 //   d conv.weight[c][ij]     = sum_rows (sum_d g[d] Wpe[d][c]) px[ij] = sum_d Wpe[d][c] G[d][ij],   d conv.bias[c] = sum_d Wpe[d][c] PB[d]
 // where G[d][ij] = sum_rows g[d] px[ij] and PB[d] = sum_rows g[d]: the row loop only accumulates G and PB (20 FMAs per
 // lane and row, no cross-lane step) and the contractions with the weights run once per workgroup.
+template <int W>
 __global__ __launch_bounds__(256) void patchify_bwd_kernel(const float* __restrict__ dtok, const float* __restrict__ lat,
                                                            int B, const float* __restrict__ cw, const float* __restrict__ cb,
-                                                           const float* __restrict__ pw, float* __restrict__ part, int M) {
+                                                           const float* __restrict__ pw, float* __restrict__ part, int M, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw, lat_n = LATC * latw;
     __shared__ f32x4 red[5][8][32];
     __shared__ float Gs[4][D], PBs[D];
     const int c4 = threadIdx.x & 31, rg = threadIdx.x >> 5;
@@ -414,13 +425,13 @@ __global__ __launch_bounds__(256) void patchify_bwd_kernel(const float* __restri
             const int row = valid ? row0 + rr : M - 1;
             g4[u] = reinterpret_cast<const f32x4*>(dtok)[(size_t)row * 32 + c4];
             if (!valid) g4[u] = g4[u] * 0.f;
-            const int seq = row / NTOK, tok = row - seq * NTOK;
+            const int seq = row / ntok, tok = row - seq * ntok;
             const int hh = tok >> 5, ww = tok & 31;
-            const float* xin = lat + (size_t)(seq % B) * LAT;
+            const float* xin = lat + (size_t)(seq % B) * lat_n;
 #pragma unroll
             for (int i = 0; i < 2; ++i)
 #pragma unroll
-                for (int jj = 0; jj < 2; ++jj) px4[u][i * 2 + jj] = xin[(2 * ww + jj) * LATW + 2 * hh + i];
+                for (int jj = 0; jj < 2; ++jj) px4[u][i * 2 + jj] = xin[(2 * ww + jj) * latw + 2 * hh + i];
         }
 #pragma unroll
         for (int u = 0; u < 4; ++u) {
@@ -535,16 +546,18 @@ __global__ void cond_rows_kernel(float* __restrict__ c, const float* __restrict_
 }
 
 // patchify, row-major output (transformer.py:166-172)
+template <int W>
 __global__ __launch_bounds__(256) void patchify_rows_kernel(const float* __restrict__ x, float* __restrict__ h, int S,
                                                             const float* __restrict__ cw, const float* __restrict__ cb,
                                                             const float* __restrict__ pw, const float* __restrict__ pb,
-                                                            const float* __restrict__ pos) {
+                                                            const float* __restrict__ pos, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw, lat = LATC * latw;
     // one thread = 4 features of token n for FOUR series: the weights, bias and position row are loaded once per thread
     // and the four 16-byte stores are independent (one series per thread ran at 2.6 TB/s of pure stores)
     constexpr int SPT = 4;
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
     const int c4 = gid & 31, rest = gid >> 5;
-    const int sg = rest / NTOK, n = rest - sg * NTOK;
+    const int sg = rest / ntok, n = rest - sg * ntok;
     if (sg * SPT >= S) return;
     const int hh = n >> 5, ww = n & 31;
     f32x4 w[4], bias, posr;
@@ -559,11 +572,11 @@ __global__ __launch_bounds__(256) void patchify_rows_kernel(const float* __restr
 #pragma unroll
     for (int u = 0; u < SPT; ++u) {
         const int s = sg * SPT + u < S ? sg * SPT + u : S - 1;
-        const float* xin = x + (size_t)s * LAT;
+        const float* xin = x + (size_t)s * lat;
 #pragma unroll
         for (int i = 0; i < 2; ++i)
 #pragma unroll
-            for (int j = 0; j < 2; ++j) px[u][i * 2 + j] = xin[(2 * ww + j) * LATW + 2 * hh + i];
+            for (int j = 0; j < 2; ++j) px[u][i * 2 + j] = xin[(2 * ww + j) * latw + 2 * hh + i];
     }
 #pragma unroll
     for (int u = 0; u < SPT; ++u) {
@@ -586,7 +599,7 @@ __global__ __launch_bounds__(256) void patchify_rows_kernel(const float* __restr
             acc += w[e].w * cv[3];
             o[e] = acc + bias[e] + posr[e];
         }
-        if (s < S) reinterpret_cast<f32x4*>(h)[((size_t)s * NTOK + n) * 32 + c4] = o;
+        if (s < S) reinterpret_cast<f32x4*>(h)[((size_t)s * ntok + n) * 32 + c4] = o;
     }
 }
 
@@ -594,11 +607,13 @@ __global__ __launch_bounds__(256) void patchify_rows_kernel(const float* __restr
 // lat[2ww+j][2hh+i]; dcv[c] = sum_d dx[tok][d] patch_w[d][c]; dlat[2ww+j][2hh+i] = sum_c conv_w[c][i][j] dcv[c].  Every latent
 // element belongs to exactly one token: plain stores.  Needed only when something upstream of the latent trains
 // (train.py:31-33 with the LA-VAE encoder un-frozen).
+template <int W>
 __global__ __launch_bounds__(256) void patchify_input_grad_kernel(const float* __restrict__ dx, float* __restrict__ dlat, int S,
-                                                                  const float* __restrict__ cw, const float* __restrict__ pw) {
+                                                                  const float* __restrict__ cw, const float* __restrict__ pw, int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw, lat = LATC * latw;
     const int gid = blockIdx.x * blockDim.x + threadIdx.x;
-    if (gid >= S * NTOK) return;
-    const int s = gid / NTOK, n = gid - s * NTOK;
+    if (gid >= S * ntok) return;
+    const int s = gid / ntok, n = gid - s * ntok;
     const int hh = n >> 5, ww = n & 31;
     const f32x4* row = reinterpret_cast<const f32x4*>(dx + (size_t)gid * D);
     float dcv[4] = {0.f, 0.f, 0.f, 0.f};
@@ -611,7 +626,7 @@ __global__ __launch_bounds__(256) void patchify_input_grad_kernel(const float* _
             dcv[0] += g[e] * w.x; dcv[1] += g[e] * w.y; dcv[2] += g[e] * w.z; dcv[3] += g[e] * w.w;
         }
     }
-    float* out = dlat + (size_t)s * LAT;
+    float* out = dlat + (size_t)s * lat;
 #pragma unroll
     for (int i = 0; i < 2; ++i)
 #pragma unroll
@@ -619,22 +634,25 @@ __global__ __launch_bounds__(256) void patchify_input_grad_kernel(const float* _
             float acc = 0.f;
 #pragma unroll
             for (int c = 0; c < 4; ++c) acc += cw[c * 4 + i * 2 + j] * dcv[c];
-            out[(2 * ww + j) * LATW + 2 * hh + i] = acc;
+            out[(2 * ww + j) * latw + 2 * hh + i] = acc;
         }
 }
 
 // final layer, row-major input (transformer.py:182-191)
 // f != NULL (bf16 training): the layer input is x_mid + gate * f of the last block, formed here (gate_res_kernel's expression)
+template <int W>
 __global__ __launch_bounds__(256) void final_rows_kernel(const float* __restrict__ h, int S, const float* __restrict__ lnw,
                                                          const float* __restrict__ lnb, const float* __restrict__ ow,
                                                          const float* __restrict__ ob, float* __restrict__ out,
-                                                         const __bf16* __restrict__ f, const float* __restrict__ mod, int gate_off) {
+                                                         const __bf16* __restrict__ f, const float* __restrict__ mod, int gate_off,
+                                                         int latw_rt) {
+    const int latw = W ? W : latw_rt, ntok = 16 * latw, lat = LATC * latw;
     // 32 lanes per token row, FOUR rows per group in flight: a row is 3 dependent butterfly reductions (mean, variance,
     // the four output dots) and one row per group left the kernel latency-bound at 2.7 TB/s
     constexpr int RPG = 4;
     const int c4 = threadIdx.x & 31;
     const int grp = (blockIdx.x * blockDim.x + threadIdx.x) >> 5;
-    const int M = S * NTOK;
+    const int M = S * ntok;
     const f32x4 gam = *reinterpret_cast<const f32x4*>(lnw + c4 * 4), bet = *reinterpret_cast<const f32x4*>(lnb + c4 * 4);
     f32x4 w[4];
 #pragma unroll
@@ -647,7 +665,7 @@ __global__ __launch_bounds__(256) void final_rows_kernel(const float* __restrict
         const int tk = tok[u] < M ? tok[u] : M - 1;
         v[u] = reinterpret_cast<const f32x4*>(h)[(size_t)tk * 32 + c4];
         if (f != nullptr) {
-            const f32x4 g = *reinterpret_cast<const f32x4*>(mod + (size_t)(tk / NTOK) * MODROW + gate_off + c4 * 4);
+            const f32x4 g = *reinterpret_cast<const f32x4*>(mod + (size_t)(tk / ntok) * MODROW + gate_off + c4 * 4);
             v[u] = v[u] + g * ld4(f, (size_t)tk * 32 + c4);
         }
     }
@@ -672,9 +690,9 @@ __global__ __launch_bounds__(256) void final_rows_kernel(const float* __restrict
             acc[p] = a + ob[p];
         }
         if (tok[u] < M && c4 < 4) {
-            const int s = tok[u] / NTOK, n = tok[u] - s * NTOK;
+            const int s = tok[u] / ntok, n = tok[u] - s * ntok;
             const int hh = n >> 5, ww = n & 31;
-            out[(size_t)s * LAT + (2 * ww + (c4 & 1)) * LATW + 2 * hh + (c4 >> 1)] = acc[c4];
+            out[(size_t)s * lat + (2 * ww + (c4 & 1)) * latw + 2 * hh + (c4 >> 1)] = acc[c4];
         }
     }
 }
@@ -702,7 +720,7 @@ void carve_branch(t2s_train_ws::Branch<T>& a, int i, size_t M, Take&& take) {
 // the fp32 arena: residual stream and statistics always; branch activations and temporaries only in fp32 mode
 template <class Take>
 void carve_act(t2s_train_ws* w, Take&& take) {
-    const size_t S = (size_t)w->cap_seqs, M = S * NTOK;
+    const size_t S = (size_t)w->cap_seqs, M = S * w->ntok(), lat_n = w->lat_elems();
     const bool bf = w->dtype == T2S_TRAIN_BF16;
     for (int i = 0; i <= NBLK; ++i) take(w->x_in[i], M * D);
     for (int i = 0; i < NBLK; ++i) {
@@ -710,7 +728,7 @@ void carve_act(t2s_train_ws* w, Take&& take) {
         take(w->lse[i], M * NH);
         if (!bf) carve_branch(w->f32, i, M, take);
     }
-    take(w->silu_c, S * D); take(w->mod, S * MODROW); take(w->c, S * D); take(w->lat, S * LAT); take(w->dx, M * D);
+    take(w->silu_c, S * D); take(w->mod, S * MODROW); take(w->c, S * D); take(w->lat, S * lat_n); take(w->dx, M * D);
     take(w->dsum, M * NH); take(w->dmod, S * MODROW);
     take(w->t1, bf ? S * MODW : M * D);
     take(w->wg_scratch, w->wg_scratch_floats);
@@ -744,7 +762,7 @@ int build_ws(t2s_train_ws* w) {
         hipDeviceProp_t prop;
         if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return oom("device query", 0);
         w->n_cu = prop.multiProcessorCount;
-        w->wg_scratch_floats = wgrad16_scratch_floats(S * NTOK, w->n_cu);
+        w->wg_scratch_floats = wgrad16_scratch_floats(S * w->ntok(), w->n_cu);
         int rows, gx;                                            // the adaLN linear: M = S rows, (768,128)
         wgrad16_plan(S, MODW, D, w->n_cu, &rows, &gx);
         const size_t ada = (size_t)gx * (MODW / 128) * (128 * 128 + 128);
@@ -767,6 +785,7 @@ int ensure_ws(t2s_dit* h, int S) {
     const int want = (S + S / 8 + 63) / 64 * 64;
     w->cap_seqs = want < h->max_seqs ? want : (S > h->max_seqs ? S : h->max_seqs);
     w->dtype = dtype;
+    w->latw = h->latw;
     const int rc = build_ws(w);
     if (rc != T2S_OK) t2s::train_free(h);
     return rc;
@@ -818,14 +837,15 @@ int bgemm_lnbwd(t2s_train_ws* ws, const __bf16* dY, const bf16x8* Wt, const floa
     return T2S_OK;
 }
 
-template <int K, int NT, int PRO, int EPI>
+template <int K, int NT, int PRO, int EPI, int TOK = NTOK>
 int gemm(const float* A, const f32x4* Wp, const float* bias, float* out, int M, int N, hipStream_t st,
          const float* mod = nullptr, int shift_off = 0, int scale_off = 0, float* save_A = nullptr,
-         const float* aux = nullptr, float* q = nullptr, float* k = nullptr, float* v = nullptr) {
+         const float* aux = nullptr, float* q = nullptr, float* k = nullptr, float* v = nullptr, int ntok = NTOK) {
     GemmArgs a{};
+    a.ntok = ntok;
     a.A = A; a.Wp = Wp; a.bias = bias; a.out = out; a.M = M; a.N = N; a.mod = mod; a.shift_off = shift_off;
     a.scale_off = scale_off; a.save_A = save_A; a.aux = aux; a.q = q; a.k = k; a.v = v;
-    return launch_gemm_rows<K, NT, PRO, EPI>(a, st);
+    return launch_gemm_rows<K, NT, PRO, EPI, TOK>(a, st);
 }
 
 // weight (and, if db != NULL, bias) gradient of a linear layer
@@ -839,6 +859,14 @@ int colsum(const float* Y, float* out, int M, int N, hipStream_t st) {
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
+
+// A statement that names a kernel template's width parameter W, once per form: W = 30 for a width-30 handle (the compile-time
+// 480-token step), W = 0 for any other (the width goes in as the kernel's last argument)
+#define T2S_BY_WIDTH(latw_, ...)                                                               \
+    do {                                                                                       \
+        if ((latw_) == LATW) { constexpr int W = LATW; __VA_ARGS__; }                          \
+        else { constexpr int W = 0; __VA_ARGS__; }                                             \
+    } while (0)
 
 // ---------------------------------------------------------------- the block recipes, one per arithmetic and direction
 // (every launch is one timed interval: the class names what bench.py reports per step)
@@ -867,9 +895,17 @@ extern "C" {
 
 int t2s_dit_set_train_dtype(t2s_dit* h, int dtype) {
     T2S_REQUIRE(h, "t2s_dit_set_train_dtype: NULL handle");
-    T2S_REQUIRE(h->latw == LATW, "t2s_dit_set_train_dtype: training runs at latent width 30 only, this handle has %d", h->latw);
+    T2S_REQUIRE(h->latw == LATW || h->trainable, "t2s_dit_set_train_dtype: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_dit_set_train_dtype: unknown dtype %d", dtype);
+    T2S_REQUIRE(h->latw == LATW || dtype == T2S_TRAIN_F32,
+                "t2s_dit_set_train_dtype: a handle of latent width %d trains in T2S_TRAIN_F32 only (T2S_TRAIN_BF16 exists at width 30)", h->latw);
     h->train_dtype = dtype;
+    return T2S_OK;
+}
+
+int t2s_dit_set_trainable(t2s_dit* h, int on) {
+    T2S_REQUIRE(h, "t2s_dit_set_trainable: NULL handle");
+    if (h->latw != LATW) h->trainable = on != 0;   // (a width-30 handle always trains)
     return T2S_OK;
 }
 
@@ -877,14 +913,16 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
                           const float* text, float* out, int B, void* stream) {
     t2s::reset_tile_dir();
     T2S_REQUIRE(h && w && x && temb && out, "t2s_dit_train_forward: NULL argument");
-    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_forward: training runs at latent width 30 only, this handle has %d", h->latw);
+    T2S_REQUIRE(h->latw == LATW || h->trainable, "t2s_dit_train_forward: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(B > 0 && B <= h->max_seqs, "t2s_dit_train_forward: B=%d exceeds max_seqs=%d", B, h->max_seqs);
     T2S_REQUIRE(temb_rows == 1 || temb_rows == B, "t2s_dit_train_forward: temb_rows=%d", temb_rows);
     hipStream_t st = (hipStream_t)stream;
     int rc = ensure_ws(h, B);
     if (rc != T2S_OK) return rc;
     t2s_train_ws* ws = h->train;
-    const int S = B, M = S * NTOK;
+    const int ntok = h->ntok();
+    const int S = B, M = S * ntok;
+    T2S_REQUIRE(ws->dtype == T2S_TRAIN_F32 || h->latw == LATW, "t2s_dit_train_forward: a handle of latent width %d trains in T2S_TRAIN_F32 only", h->latw);
     ws->S = S;
     // the handle's own parameter copies / forward packs must be current: the caller refreshes them
     // with t2s_dit_update_weights; here only the training-specific packs
@@ -906,22 +944,22 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
             }
         T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, pack16_multi_kernel<<<dim3((3 * D * D + 255) / 256, np), 256, 0, st>>>(pt));
     }
-    T2S_HIP_CHECK(hipMemcpyAsync(ws->lat, x, (size_t)S * LAT * sizeof(float), hipMemcpyDeviceToDevice, st));
+    T2S_HIP_CHECK(hipMemcpyAsync(ws->lat, x, (size_t)S * h->lat() * sizeof(float), hipMemcpyDeviceToDevice, st));
     T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, cond_rows_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, temb, temb_rows, text, S));
     T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st, silu_kernel<<<(S * D + 255) / 256, 256, 0, st>>>(ws->c, ws->silu_c, S * D));
     T2S_TIMED(h, TC_TR_TAIL, st, gemm<128, 3, PRO_PLAIN, EPI_BIAS>(ws->silu_c, h->ada_p, h->ada_b, ws->mod, S, MODROW, st));
     T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
-                     patchify_rows_kernel<<<((S + 3) / 4 * NTOK * 32 + 255) / 256, 256, 0, st>>>(x, ws->x_in[0], S, h->conv_w, h->conv_b,
-                                                                                                 h->patch_w, h->patch_b, h->pos));
+                     T2S_BY_WIDTH(h->latw, patchify_rows_kernel<W><<<((S + 3) / 4 * ntok * 32 + 255) / 256, 256, 0, st>>>(
+                                                   x, ws->x_in[0], S, h->conv_w, h->conv_b, h->patch_w, h->patch_b, h->pos, h->latw)));
     if ((rc = bf ? forward_blocks_bf16(h, ws, S, st) : forward_blocks_f32(h, ws, S, st))) return rc;
     if (bf)   // (the last block's x_mid + g2 * f is formed here)
         T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
-                         final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
-                                                                                            out, ws->bf.f[NBLK - 1], ws->mod, (NBLK - 1) * MODW + 5 * D));
+                         final_rows_kernel<LATW><<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
+                                                                                                  out, ws->bf.f[NBLK - 1], ws->mod, (NBLK - 1) * MODW + 5 * D, LATW));
     else
         T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
-                         final_rows_kernel<<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[NBLK], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
-                                                                                            out, nullptr, nullptr, 0));
+                         T2S_BY_WIDTH(h->latw, final_rows_kernel<W><<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(
+                                                   ws->x_in[NBLK], S, h->ln_w, h->ln_b, h->out_w, h->out_b, out, nullptr, nullptr, 0, h->latw)));
     return T2S_OK;
 }
 
@@ -957,28 +995,34 @@ int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
     return T2S_OK;
 }
 
-int forward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+template <int W>
+int forward_blocks_f32_w(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    constexpr int TOK = W ? 16 * W : 0;   // the GEMMs' row -> sequence maps
     t2s_train_ws::F32& a = ws->f32;
-    const int M = S * NTOK;
+    const int ntok = h->ntok();
+    const int M = S * ntok;
     for (int i = 0; i < NBLK; ++i) {
         const int base = i * MODW;
         // a1 = mod(LN1(x_in)); q,k,v = a1 Wqkv^T + b
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  gemm<128, 3, PRO_LNMOD, EPI_QKV>(ws->x_in[i], h->p32[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod, base + 0 * D,
-                                                   base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i]));
-        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn_plain_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, st));
+                  gemm<128, 3, PRO_LNMOD, EPI_QKV, TOK>(ws->x_in[i], h->p32[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod, base + 0 * D,
+                                                        base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i], ntok));
+        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn_plain_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, ntok, st));
         T2S_TIMED(h, TC_TR_GEMM, st, gemm<128, 1, PRO_PLAIN, EPI_BIAS>(a.o[i], h->p32[i][PROJ], h->bias[i][PROJ], a.p[i], M, D, st));
         T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
-                         gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[i], a.p[i], ws->mod, base + 2 * D, ws->x_mid[i], M));
+                         gate_res_kernel<W><<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_in[i], a.p[i], ws->mod, base + 2 * D, ws->x_mid[i], M, h->latw));
         // a2 = mod(LN2(x_mid)); u = a2 W1^T + b1; f = gelu(u) W2^T + b2
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  gemm<128, 2, PRO_LNMOD, EPI_BIAS>(ws->x_mid[i], h->p32[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
-                                                    base + 4 * D, a.a2[i]));
+                  gemm<128, 2, PRO_LNMOD, EPI_BIAS, TOK>(ws->x_mid[i], h->p32[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
+                                                         base + 4 * D, a.a2[i], nullptr, nullptr, nullptr, nullptr, ntok));
         T2S_TIMED(h, TC_TR_GEMM, st, gemm<256, 1, PRO_GELU, EPI_BIAS>(a.u[i], a.fc2_f[i], h->bias[i][FC2], a.f[i], M, D, st));
         T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
-                         gate_res_kernel<<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[i], a.f[i], ws->mod, base + 5 * D, ws->x_in[i + 1], M));
+                         gate_res_kernel<W><<<(M * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[i], a.f[i], ws->mod, base + 5 * D, ws->x_in[i + 1], M, h->latw));
     }
     return T2S_OK;
+}
+int forward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    return h->latw == LATW ? forward_blocks_f32_w<LATW>(h, ws, S, st) : forward_blocks_f32_w<0>(h, ws, S, st);
 }
 }  // namespace
 
@@ -987,12 +1031,12 @@ extern "C" {
 int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g, int B, void* stream) {
     t2s::reset_tile_dir();
     T2S_REQUIRE(h && dout && g, "t2s_dit_train_backward: NULL argument");
-    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_backward: training runs at latent width 30 only, this handle has %d", h->latw);
+    T2S_REQUIRE(h->latw == LATW || h->trainable, "t2s_dit_train_backward: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(h->train && h->train->S == B, "t2s_dit_train_backward: no matching t2s_dit_train_forward (B=%d)", B);
     T2S_REQUIRE(h->train->dtype == h->train_dtype, "t2s_dit_train_backward: training dtype changed since the forward");
     hipStream_t st = (hipStream_t)stream;
     t2s_train_ws* ws = h->train;
-    const int S = B, M = S * NTOK;
+    const int S = B, M = S * h->ntok();
     int rc;
     // ---- zero every gradient (the kernels accumulate with atomics)
     struct Z { float* p; size_t n; };
@@ -1024,13 +1068,13 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
     { TimeScope ts(h, TC_TR_TAIL, st);
     if (bf) {   // + the gate backward of the last block's MLP branch: t1 = df = g2 * dx, dgate2
         const int goff = (NBLK - 1) * MODW + 5 * D;
-        final_bwd_kernel<true, FUSED_ROWS><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
-                                                                      ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1);
+        final_bwd_kernel<true, FUSED_ROWS, LATW><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
+                                                                            ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1, LATW);
         T2S_LAUNCH_CHECK();
         final_gate_reduce_kernel<<<S, D, 0, st>>>(ws->wg_scratch, final_stride, ws->dmod, goff);
     } else {
-        final_bwd_kernel<false, TAIL_ROWS><<<final_wgs, 256, 0, st>>>(ws->x_in[NBLK], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
-                                                                      nullptr, nullptr, 0, nullptr);
+        T2S_BY_WIDTH(h->latw, final_bwd_kernel<false, TAIL_ROWS, W><<<final_wgs, 256, 0, st>>>(ws->x_in[NBLK], dout, h->ln_w, h->ln_b, h->out_w, ws->dx,
+                                                                                              ws->wg_scratch, M, nullptr, nullptr, 0, nullptr, h->latw));
     }
     T2S_LAUNCH_CHECK();
     tail_reduce_kernel<<<(FINAL_COLS + 31) / 32, 256, 0, st>>>(ws->wg_scratch, final_wgs, FINAL_COLS, final_stride,
@@ -1040,7 +1084,7 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
     if ((rc = bf ? backward_blocks_bf16(h, ws, g, S, st) : backward_blocks_f32(h, ws, g, S, st))) return rc;
     // ---- patchify
     { TimeScope ts(h, TC_TR_TAIL, st);
-    patchify_bwd_kernel<<<tail_wgs, 256, 0, st>>>(ws->dx, ws->lat, S, h->conv_w, h->conv_b, h->patch_w, ws->wg_scratch, M);
+    T2S_BY_WIDTH(h->latw, patchify_bwd_kernel<W><<<tail_wgs, 256, 0, st>>>(ws->dx, ws->lat, S, h->conv_w, h->conv_b, h->patch_w, ws->wg_scratch, M, h->latw));
     T2S_LAUNCH_CHECK();
     tail_reduce_kernel<<<(PATCH_COLS + 31) / 32, 256, 0, st>>>(ws->wg_scratch, tail_wgs, PATCH_COLS, PATCH_COLS,
                                                                  TailDst{{g->patch_w, g->patch_b, g->conv_w, g->conv_b}, {4 * D, D, 16, 4}});
@@ -1103,14 +1147,16 @@ int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, i
     return T2S_OK;
 }
 
-int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+template <int W>
+int backward_blocks_f32_w(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
     t2s_train_ws::F32& a = ws->f32;
-    const int M = S * NTOK;
+    const int ntok = h->ntok();
+    const int M = S * ntok;
     for (int i = NBLK - 1; i >= 0; --i) {
         const int base = i * MODW;
         const t2s_dit_block_grads& b = g->blk[i];
         // ---- MLP branch: x_out = x_mid + g2 * f
-        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, a.f[i], ws->mod, base + 5 * D, ws->t1, ws->dmod));   // t1 = df
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<W><<<S, 256, 0, st>>>(ws->dx, a.f[i], ws->mod, base + 5 * D, ws->t1, ws->dmod, h->latw));   // t1 = df
         T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
                          gelu_kernel<<<((size_t)M * 64 + 255) / 256, 256, 0, st>>>(a.u[i], a.t2a, (size_t)M * 64));   // t2a = gelu(u)
         T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, ws->t1, a.t2a, b.fc2_w, b.fc2_b, M, D, 2 * D, st));
@@ -1121,21 +1167,24 @@ int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, in
         // da2 = du W1 (out 128 <- in 256)
         T2S_TIMED(h, TC_TR_GEMM, st, gemm<256, 1, PRO_PLAIN, EPI_BIAS>(a.t2b, a.wt[i][FC1], nullptr, ws->t1, M, D, st));
         T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
-                         ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_mid[i], ws->mod, base + 3 * D, base + 4 * D, ws->dx, ws->dmod,
-                                                              (const float*)nullptr, 0, (float*)nullptr));
+                         ln_mod_bwd_kernel<W><<<S, 256, 0, st>>>(ws->t1, ws->x_mid[i], ws->mod, base + 3 * D, base + 4 * D, ws->dx, ws->dmod,
+                                                                 (const float*)nullptr, 0, (float*)nullptr, h->latw));
         // ---- attention branch: x_mid = x_in + g1 * p
-        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<<<S, 256, 0, st>>>(ws->dx, a.p[i], ws->mod, base + 2 * D, ws->t1, ws->dmod));   // t1 = dp
+        T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st, gate_bwd_kernel<W><<<S, 256, 0, st>>>(ws->dx, a.p[i], ws->mod, base + 2 * D, ws->t1, ws->dmod, h->latw));   // t1 = dp
         T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, ws->t1, a.o[i], b.proj_w, b.proj_b, M, D, D, st));
         T2S_TIMED(h, TC_TR_GEMM, st, gemm<128, 1, PRO_PLAIN, EPI_BIAS>(ws->t1, a.wt[i][PROJ], nullptr, a.t4, M, D, st));   // do
-        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, st));
+        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, ntok, st));
         T2S_TIMED(h, TC_TR_WGRAD, st, wgrad(ws, a.t3, a.a1[i], b.qkv_w, b.qkv_b, M, 3 * D, D, st));
         // da1 = dqkv Wqkv (out 128 <- in 384)
         T2S_TIMED(h, TC_TR_GEMM, st, gemm<384, 1, PRO_PLAIN, EPI_BIAS>(a.t3, a.wt[i][QKV], nullptr, ws->t1, M, D, st));
         T2S_TIMED_LAUNCH(h, TC_TR_ELEM, st,
-                         ln_mod_bwd_kernel<<<S, 256, 0, st>>>(ws->t1, ws->x_in[i], ws->mod, base + 0 * D, base + 1 * D, ws->dx, ws->dmod,
-                                                              (const float*)nullptr, 0, (float*)nullptr));
+                         ln_mod_bwd_kernel<W><<<S, 256, 0, st>>>(ws->t1, ws->x_in[i], ws->mod, base + 0 * D, base + 1 * D, ws->dx, ws->dmod,
+                                                                 (const float*)nullptr, 0, (float*)nullptr, h->latw));
     }
     return T2S_OK;
+}
+int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    return h->latw == LATW ? backward_blocks_f32_w<LATW>(h, ws, g, S, st) : backward_blocks_f32_w<0>(h, ws, g, S, st);
 }
 }  // namespace
 
@@ -1143,11 +1192,12 @@ extern "C" {
 
 int t2s_dit_train_input_grad(t2s_dit* h, float* dinput, int B, void* stream) {
     T2S_REQUIRE(h && dinput, "t2s_dit_train_input_grad: NULL argument");
-    T2S_REQUIRE(h->latw == LATW, "t2s_dit_train_input_grad: training runs at latent width 30 only, this handle has %d", h->latw);
+    T2S_REQUIRE(h->latw == LATW || h->trainable, "t2s_dit_train_input_grad: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(h->train && h->train->S == B, "t2s_dit_train_input_grad: no matching t2s_dit_train_backward (B=%d)", B);
     t2s_train_ws* ws = h->train;
     TimeScope ts(h, TC_TR_TAIL, (hipStream_t)stream);
-    patchify_input_grad_kernel<<<(B * NTOK + 255) / 256, 256, 0, (hipStream_t)stream>>>(ws->dx, dinput, B, h->conv_w, h->patch_w);
+    T2S_BY_WIDTH(h->latw, patchify_input_grad_kernel<W><<<(B * h->ntok() + 255) / 256, 256, 0, (hipStream_t)stream>>>(ws->dx, dinput, B, h->conv_w,
+                                                                                                                    h->patch_w, h->latw));
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

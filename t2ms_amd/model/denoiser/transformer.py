@@ -225,6 +225,7 @@ class Transformer(H.HandleOwner, nn.Module):
         h = H.Handle(device, "t2s_dit_create_w", "t2s_dit_destroy", C.byref(w), self.H, cap)
         h.max_seqs, h.keep = cap, keep
         self.__dict__.pop("_t2s_math_applied", None)          # a new handle starts in f32
+        h.trainable = False                                   # ... and, at a wide width, refuses to train
         return h
 
     def _refresh(self, h, device, w, keep, cap):
@@ -253,6 +254,10 @@ class Transformer(H.HandleOwner, nn.Module):
             with L.device_lock(device), torch.cuda.device(device):       # (first bf16x3 / bf16 use allocates and synchronises)
                 L.check(L.lib().t2s_dit_set_math(h.ptr, L.MATH_CODES[math]), "t2s_dit_set_math")
             self.__dict__["_t2s_math_applied"] = math
+        trainable = bool(self.__dict__.get("_t2s_trainable", False))
+        if h.trainable != trainable:                          # (kept on the handle: every rebuild starts switched off)
+            L.check(L.lib().t2s_dit_set_trainable(h.ptr, int(trainable)), "t2s_dit_set_trainable")
+            h.trainable = trainable
         return h.ptr
 
     def t2s_handle_id(self):
@@ -292,10 +297,21 @@ class Transformer(H.HandleOwner, nn.Module):
         accumulation, master weights, residual stream, statistics and gradients)."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"train dtype must be 'f32' or 'bf16', got {dtype!r}")
+        if self.H != LAT_H and dtype != "f32":
+            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents train in 'f32' only (bf16 training exists at dim 30), "
+                             f"got {dtype!r}")
         self.__dict__["_t2s_train_dtype"] = dtype
         return self
 
-    # (_t2s_math and _t2s_train_dtype are settings: they travel with a pickle)
+    def set_trainable(self, on: bool = True):
+        """Opt a WIDE model (dim 50 / 64, the motion denoisers of the reference's mytrain.py) into training: with it set,
+        forward under autograd runs the fp32 HIP training step at 16 * dim tokens (t2s_dit_set_trainable) in place of
+        refusing.  A dim-30 model always trains; the call changes nothing there.  What stays refused at the wide widths:
+        set_train_dtype("bf16") and set_math("bf16x3" / "bf16")."""
+        self.__dict__["_t2s_trainable"] = bool(on)
+        return self
+
+    # (_t2s_math, _t2s_train_dtype and _t2s_trainable are settings: they travel with a pickle)
     _t2s_transient = H.HandleOwner._t2s_transient + ("_t2s_math_applied", "_t2s_bucket", "_t2s_flat_grad", "_t2s_fwd_gen",
                                                      "_t2s_wstruct", "_t2s_pair", "_t2s_pairing")
 
@@ -306,7 +322,8 @@ class Transformer(H.HandleOwner, nn.Module):
             raise L.T2SError("Transformer.forward: input must live on a GPU; the HIP path has no CPU fallback")
         if input.dim() != 3 or input.shape[1] != LAT_W or input.shape[2] != self.H:
             raise L.T2SError(f"Transformer.forward: input must be (B,64,{self.H}), got {tuple(input.shape)}")
-        if self.H != LAT_H and torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self._dit_tensors())):
+        if (self.H != LAT_H and not self.__dict__.get("_t2s_trainable", False) and torch.is_grad_enabled()
+                and (input.requires_grad or any(p.requires_grad for p in self._dit_tensors()))):
             raise L.T2SError(f"Transformer(dim={self.H}): training runs at dim 30 only; call the wide model under torch.no_grad()")
         if torch.is_grad_enabled() and (input.requires_grad or any(p.requires_grad for p in self._dit_tensors())):
             from ...train import dit_forward_autograd

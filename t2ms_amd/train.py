@@ -14,7 +14,7 @@ import torch
 
 from . import _lib as L
 
-N_GRAD = 925592   # values that receive a gradient: DiT minus pos_embed minus unpatch.*
+N_GRAD = 925592   # values that receive a gradient: DiT minus pos_embed minus unpatch.* -- the same at every latent width
 
 
 # ---------------------------------------------------------------------------- loss
@@ -119,7 +119,7 @@ class _DitTrainFn(torch.autograd.Function):
             w, keep, _ = model._weights_struct(dev)
             dt = L.TRAIN_BF16 if model.__dict__.get("_t2s_train_dtype", "f32") == "bf16" else L.TRAIN_F32
             L.check(L.lib().t2s_dit_set_train_dtype(h, dt), "t2s_dit_set_train_dtype")
-            out = torch.empty(B, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
+            out = torch.empty(B, L.LAT_C, model.H, device=dev, dtype=torch.float32)
             L.check(L.lib().t2s_dit_train_forward(h, C.byref(w), L.dev_ptr(x, "input"), L.dev_ptr(temb), B,
                                                   L.dev_ptr(text, "text_input"), L.dev_ptr(out), B,
                                                   L.stream_ptr(dev)), "t2s_dit_train_forward")
@@ -155,7 +155,7 @@ class _DitTrainFn(torch.autograd.Function):
         grads = views[:4] + [None] + views[4:]      # pos_embed (index 4 of _dit_tensors) gets none
         dx = None
         if ctx.needs_input_grad[1]:                 # something upstream of the latent trains (un-frozen LA-VAE encoder)
-            dx = torch.empty(B, L.LAT_C, L.LAT_W, device=dev, dtype=torch.float32)
+            dx = torch.empty(B, L.LAT_C, model.H, device=dev, dtype=torch.float32)
             with torch.cuda.device(dev):
                 L.check(L.lib().t2s_dit_train_input_grad(h, L.dev_ptr(dx), B, L.stream_ptr(dev)), "t2s_dit_train_input_grad")
         return (None, dx, None, None) + tuple(grads)
