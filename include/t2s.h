@@ -100,7 +100,8 @@ int t2s_dit_create(const t2s_dit_weights* w, int max_seqs, t2s_dit** out);
  * those of t2s_dit_weights except pos_embed, which holds 16*latent_w*128 floats (an undersized one is T2S_E_INVALID naming
  * "pos_embed").  On such a handle every entry below takes and gives (S,64,latent_w) latents and (S,16*latent_w,128) token
  * streams.  A handle with latent_w != 30 runs T2S_MATH_F32, and inference only until t2s_dit_set_trainable (t2s_wide_train.h)
- * switches training on: t2s_dit_set_math(T2S_MATH_BF16X3 / _BF16) returns T2S_E_INVALID with a message, and so do t2s_dit_set_train_dtype and
+ * switches training on: t2s_dit_set_math(T2S_MATH_BF16X3 / _BF16) returns T2S_E_INVALID with a message unless
+ * t2s_dit_set_wide_math (t2s_wide_math.h) opted the handle in, and so do t2s_dit_set_train_dtype and
  * every t2s_dit_train_* entry on a handle without the switch, before any launch. */
 int t2s_dit_create_w(const t2s_dit_weights* w, int latent_w, int max_seqs, t2s_dit** out);
 /* latent width of a handle (30 for t2s_dit_create); 0 for NULL */

@@ -20,6 +20,8 @@ What differs from the reference, on purpose:
     (myevaluation.normalize + calculate_mse).  `--reconstruct` adds the codec's reconstruction of every clip (ragged encode ->
     ragged decode), `sample_<i>/x_rec.npy`, and its MSE.
   * every clip of the split is sampled (the reference stops after 11); `--max_clips N` caps it.
+  * `--math bf16x3|bf16` runs the denoiser's matrix products on the bf16 matrix cores (fp32-accurate split / single pass);
+    the default stays f32, and summary.json names the arithmetic only when it is not f32.
   * `--random_init` (seeded synthetic weights) and `--synthetic N` (N seeded clips of 30..160 samples instead of a dataset)
     let the driver run without checkpoints or data, as infer.py's flags do.
 The model shape comes from flags whose defaults are the reference's config.yaml values per dataset; `--config FILE` overrides
@@ -75,6 +77,9 @@ def get_args(argv=None):
     p.add_argument("--reconstruct", action="store_true", help="also the codec reconstruction of every clip and its MSE")
     p.add_argument("--synthetic", type=int, default=0, help="N seeded synthetic clips (30..160 samples) instead of the dataset")
     p.add_argument("--no_graph", action="store_true", help="run the loop eagerly (same bits)")
+    p.add_argument("--math", choices=["f32", "bf16x3", "bf16"], default="f32",
+                   help="matrix arithmetic of the denoiser: f32 (default), bf16x3 (fp32-accurate, bf16 matrix cores) or bf16 "
+                        "(single pass, not fp32-accurate); the latter two opt the wide model in (Transformer.set_wide_math)")
     args = p.parse_args(argv)
     if args.launch_batch < 1:
         p.error("--launch_batch must be >= 1")
@@ -102,6 +107,8 @@ def load_models(args, device):
         vae.load_state_dict(torch.load(args.pretrainedvae_path, map_location="cpu"))
         model.encoder = vae.encoder
         model.load_state_dict(torch.load(args.checkpoint_path, map_location="cpu")["model"])
+    if args.math != "f32":               # (mytrain.py has no such flag: wide training is fp32)
+        model.set_wide_math(True).set_math(args.math)
     return model.to(device).float().eval(), vae.to(device).float().eval()
 
 
@@ -181,6 +188,8 @@ def infer(args, run, device, model, vae, clips):
     summary = dict(dataset=args.dataset_name, channels=args.input_dim, features=names, backbone=args.backbone,
                    total_step=args.total_step, cfg_scale=args.cfg_scale, seed=args.general_seed + run, launch_batch=B,
                    embedding=args.embedding, mean_mse=float(np.mean([r["mse"] for r in rows])), clips=rows)
+    if sampler.math != "f32":            # (f32 runs keep the summary they have always written)
+        summary["math"] = sampler.math
     with open(os.path.join(root, "summary.json"), "w") as f:
         json.dump(summary, f, indent=1)
     print(f"run {run}: {len(rows)} clips, mean normalised MSE {summary['mean_mse']:.6f} -> {root}")

@@ -297,6 +297,13 @@ SYMBOLS_WIDE_TRAIN = {
     "t2s_attn_train_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _VP]),
 }
 
+# include/t2s_wide_math.h: bf16x3 / bf16 inference at the wide latent widths (tests/test_wide_math_host.py)
+SYMBOLS_WIDE_MATH = {
+    "t2s_dit_set_wide_math": (_I, [_VP, _I]),
+    "t2s_attn_fwd_x3_n": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
+    "t2s_attn_fwd_bf16p_n": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libt2s_hip.so (once).  Raises if it has not been built."""
@@ -307,7 +314,7 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C t2ms_amd/csrc` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()):
+        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()) + list(SYMBOLS_WIDE_MATH.items()):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         _lib = handle

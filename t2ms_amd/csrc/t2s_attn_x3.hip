@@ -13,6 +13,10 @@
 // The same body instantiated on one bf16 plane (Split1, t2s_x3.h) is the attention of the single-pass "bf16" arithmetic
 // (T2S_MATH_BF16, attn_fwd_bf16p_kernel): q, k, v^T and P^T each rounded once, 2 + 2 MFMAs per key block and query tile (128
 // cycles), a ring slot of 4 KiB.  Not fp32-accurate; the softmax reference, exponent and running sum stay fp32.
+//
+// Both plane counts also exist at 800 / 1024 tokens (attn_fwd_x3_wide_kernel / attn_fwd_bf16p_wide_kernel, the attention of a
+// wide handle after t2s_dit_set_wide_math): a body of its own further down, because a head then has 25 / 32 query tiles for the
+// workgroup's 16 slots and no light wave to issue the LDS-DMA.
 #include "t2s_dit_internal.h"
 #include "t2s_x3.h"
 
@@ -340,23 +344,235 @@ __global__ __launch_bounds__(X3_THREADS, 2) T2S_P1_KERNEL void attn_fwd_bf16p_ke
     attn_fwd_xn<Split1>(ring1, q, k1, vT1, o, BH);
 }
 
-// plain (BH,480,32) fp32 k or v -> split planes: k as the A operand with the key on the lane
+
+// ---------------------------------------------------------------- the wide form: 800 / 1024 tokens (t2s_dit_set_wide_math)
+// nkb = 25 or 32 key blocks and as many query tiles per head, against 16 tile slots of the workgroup (8 waves x 2 tiles).
+// A persistent WORK ITEM is therefore a (head, part) pair, item = 2 bh + part: part p holds the query tiles 16 p .. 16 p + 15
+// and streams ALL nkb key blocks of the head through the same 4-slot ring; a workgroup walks items blockIdx.x,
+// blockIdx.x + gridDim.x, ...  The ring protocol, the barrier per key block and the stagger are those of attn_x3_body; what
+// differs:
+//
+// Tiles.  Wave w of part p owns tiles 16 p + 2 w and 16 p + 2 w + 1 -- a fixed function of the tile index, so the two tiles
+// that share the wave-uniform re-reference branch are the same two in every launch, batch and grid (a row's bits do not depend
+// on them).  1024 tokens: two full parts.  800 tokens: part 0 is full, part 1 holds tiles 16 .. 24 -- waves 0-3 two tiles, wave
+// 4 one, waves 5-7 none.  A slot without a tile REPEATS tile nkb - 1 (same Q, same scores, so it never changes the wave's
+// branch) and stores nothing: every wave runs the same nkb barriers per item.  7 of the 32 slots of a head idle at 800 tokens.
+//
+// LDS-DMA.  Every wave owns two tiles, so there is no light wave to carry the issue: wave w issues pieces w and w + 8 of a
+// block's 2 PK (12 for bf16x3, 4 for one plane), i.e. NPW pieces per block and wave
+//     bf16x3:    waves 0-3 two (w, w + 8), waves 4-7 one (w)          one plane: waves 0-3 one (w), waves 4-7 none.
+// Waves 0-3 are the STAG = 0 instantiation and waves 4-7 the STAG = 1 one, so NPW is a compile-time value of the body.
+//
+// Counted waits, per wave (vmcnt counts a wave's own vector-memory operations, oldest first).  Barrier j must guarantee
+// that block j + 1 has landed, i.e. each issuing wave must have seen ITS pieces of block j + 1 land before it arrives.  At
+// that point the wave has issued, after those pieces, exactly its NPW pieces of block j + 2 (block j + 3 is issued behind
+// the barrier) and possibly loads / stores of its own (the Q prefetch, the O stores of the previous item).  "At most NPW
+// operations outstanding" = s_waitcnt vmcnt(NPW) therefore covers every piece of block j + 1: with nothing else in flight
+// the NPW youngest are the pieces of block j + 2, and anything else in flight is younger than block j + 1's pieces too, so
+// it only makes the wait stricter.  Before the first barrier blocks 1 and 2 are behind block 0: vmcnt(2 NPW).  A wave with
+// NPW = 0 has nothing to wait for.  The stream of blocks runs on across items (block nkb + d of an item is block d of the
+// workgroup's next item), so the count holds at item borders as well; past the last item the last block is fetched again
+// into slots nobody reads and drained by the final vmcnt(0).
+template <int STAG, class SP>
+__device__ __forceinline__ void attn_xw_body(bf16x8* ring, const f32x4* qall, const bf16x8* kall, const bf16x8* vall,
+                                             f32x4* og, int BH, int nkb, int lane, int wave) {
+    const int stride = gridDim.x;
+    const int n_items = 2 * BH;
+    constexpr int NP = planes_of<SP>::n;
+    constexpr int PK = 2 * NP;
+    constexpr int SLOT_UNITS = 2 * XN_TILE_UNITS<NP>;
+    constexpr int NPW = STAG ? (NP == 3 ? 1 : 0) : (NP == 3 ? 2 : 1);
+    static_assert(4 * (NP == 3 ? 2 : 1) + 4 * (NP == 3 ? 1 : 0) == 2 * PK, "every piece of a block has one issuing wave");
+    auto issue_block = [&](int it, int jb, int gslot) {
+        if constexpr (NPW > 0) {
+            if (jb >= nkb) { jb -= nkb; it += stride; }
+            if (it >= n_items) { it -= stride; jb = nkb - 1; }   // past the end: harmless re-fetch
+            const int bh = it >> 1;
+#pragma unroll
+            for (int i = 0; i < NPW; ++i) {
+                const int p = wave + 8 * i;                       // < 2 PK by the table above
+                const bf16x8* src = (p < PK ? kall : vall) + ((size_t)(bh * nkb + jb) * PK + (p < PK ? p : p - PK)) * 64 + lane;
+                glds16u(src, ring + (gslot & (X3_SLOTS - 1)) * SLOT_UNITS + p * 64);
+            }
+        }
+    };
+    auto wait_but = [&](int blocks) {
+        if constexpr (NPW == 2) {
+            if (blocks == 2) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
+        }
+        if constexpr (NPW == 1) {
+            if (blocks == 2) asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(1)" ::: "memory");
+        }
+    };
+    auto load_op = [&](SP (&f)[2], const bf16x8* base) {
+#pragma unroll
+        for (int s = 0; s < 2; ++s) {
+            f[s].h = base[(0 + s) * 64];
+            if constexpr (NP == 3) {
+                f[s].m = base[(2 + s) * 64];
+                f[s].l = base[(4 + s) * 64];
+            }
+        }
+    };
+    auto load_k = [&](SP (&kf)[2], int gslot) { load_op(kf, ring + (gslot & (X3_SLOTS - 1)) * SLOT_UNITS + lane); };
+    // the raw fragments of the wave's two tiles of item `it` (a void slot repeats the head's last tile)
+    auto fetch_q = [&](int it, f32x4 (&ra)[4], f32x4 (&rb)[4]) {
+        const int t0 = (it & 1) * 16 + wave * 2;
+        const int ta = t0 < nkb ? t0 : nkb - 1, tb = t0 + 1 < nkb ? t0 + 1 : nkb - 1;
+        const f32x4* qg = qall + (size_t)(it >> 1) * nkb * 256;
+#pragma unroll
+        for (int g = 0; g < 4; ++g) {
+            ra[g] = qg[(ta * 4 + g) * 64 + lane];
+            rb[g] = qg[(tb * 4 + g) * 64 + lane];
+        }
+    };
+    int it = blockIdx.x;
+    int gb = 0;
+    issue_block(it, 0, 0);
+    issue_block(it, 1, 1);
+    issue_block(it, 2, 2);
+
+    SP qa[2], qb[2];
+    f32x4 qna[4], qnb[4];
+    fetch_q(it, qna, qnb);
+    load_q(qna, qa);
+    load_q(qnb, qb);
+    wait_but(2);                                     // block 0 landed
+    __builtin_amdgcn_s_barrier();
+    SP kf[2];
+    load_k(kf, 0);
+
+#pragma unroll 1
+    for (; it < n_items; it += stride) {
+        f32x16 oa, ob;
+        TileState ta, tb;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            oa[r] = ob[r] = 0.f;
+            ta.negm[r] = tb.negm[r] = INFINITY;
+        }
+        ta.m_ref = tb.m_ref = -INFINITY;
+        ta.l_lane = tb.l_lane = 0.f;
+
+#pragma unroll 1
+        for (int jb = 0; jb < nkb; ++jb, ++gb) {
+            const bool first = jb == 0;                           // scalar
+            f32x16 sta = ta.negm, stb = tb.negm;
+            if (!first) {
+                sta = scores_from(kf, qa, ta.negm);
+                stb = scores_from(kf, qb, tb.negm);
+            }
+            if (STAG) {
+                wait_but(1);
+                __builtin_amdgcn_s_barrier();
+                issue_block(it, jb + 3, gb + 3);
+            }
+            SP vf[2];
+            load_op(vf, ring + (gb & (X3_SLOTS - 1)) * SLOT_UNITS + PK * 64 + lane);
+            float psa = 0.f, psb = 0.f;
+            bool redo = first;
+            if (!first) {
+                psa = exp_sum(sta);
+                psb = exp_sum(stb);
+                const bool stale = !(psa < SM_BIG) || !(psb < SM_BIG);
+                redo = __builtin_amdgcn_ballot_w64(stale) != 0;   // wave-uniform, rare
+            }
+            if (redo) {
+                psa = rereference(kf, qa, sta, oa, ta);
+                psb = rereference(kf, qb, stb, ob, tb);
+            }
+            ta.l_lane += psa;
+            tb.l_lane += psb;
+            const SP pa0 = splitp_acc<SP>(sta, 0), pa1 = splitp_acc<SP>(sta, 1);
+            const SP pb0 = splitp_acc<SP>(stb, 0), pb1 = splitp_acc<SP>(stb, 1);
+            if (!STAG) {
+                wait_but(1);
+                __builtin_amdgcn_s_barrier();
+                issue_block(it, jb + 3, gb + 3);
+            }
+            load_k(kf, gb + 1);
+            oa = mfma_x3(vf[0], pa0, oa);
+            oa = mfma_x3(vf[1], pa1, oa);
+            ob = mfma_x3(vf[0], pb0, ob);
+            ob = mfma_x3(vf[1], pb1, ob);
+            // prefetch the next item's Q fragments (a whole block old by the next counted wait)
+            if (jb == nkb - 4 && it + stride < n_items) fetch_q(it + stride, qna, qnb);
+        }
+        // ---- normalise and store O of this item's tiles (void slots store nothing); swap in the prefetched Q ----
+        const int bh = it >> 1, seq = bh / NH, head = bh % NH;
+        const int t0 = (it & 1) * 16 + wave * 2;
+        if (t0 < nkb) {
+            const float inv = 1.0f / pair_sum(ta.l_lane);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 w = {oa[4 * g] * inv, oa[4 * g + 1] * inv, oa[4 * g + 2] * inv, oa[4 * g + 3] * inv};
+                og[(((size_t)seq * nkb + t0) * 16 + head * 4 + g) * 64 + lane] = w;
+            }
+        }
+        if (t0 + 1 < nkb) {
+            const float inv = 1.0f / pair_sum(tb.l_lane);
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const f32x4 w = {ob[4 * g] * inv, ob[4 * g + 1] * inv, ob[4 * g + 2] * inv, ob[4 * g + 3] * inv};
+                og[(((size_t)seq * nkb + t0 + 1) * 16 + head * 4 + g) * 64 + lane] = w;
+            }
+        }
+        load_q(qna, qa);
+        load_q(qnb, qb);
+    }
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // drain the trailing (unused) DMAs
+}
+
+template <class SP>
+__device__ __forceinline__ void attn_fwd_xw(bf16x8* ring, const float* __restrict__ q, const __bf16* __restrict__ kp,
+                                            const __bf16* __restrict__ vTp, float* __restrict__ o, int BH, int nkb) {
+    const int lane = threadIdx.x & 63;
+    const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+    const f32x4* qg = reinterpret_cast<const f32x4*>(q);
+    const bf16x8* kg = reinterpret_cast<const bf16x8*>(kp);
+    const bf16x8* vg = reinterpret_cast<const bf16x8*>(vTp);
+    f32x4* og = reinterpret_cast<f32x4*>(o);
+    // the stagger of the 480-token kernel, kept: the SIMD partners w / w + 4 still run one body each
+    if (wave < 4)
+        attn_xw_body<0, SP>(ring, qg, kg, vg, og, BH, nkb, lane, wave);
+    else
+        attn_xw_body<1, SP>(ring, qg, kg, vg, og, BH, nkb, lane, wave);
+}
+
+// kp / vTp: planes (BH * nkb tiles, 2 NP pieces each); q, o: fp32 fragment-major as in t2s_attn_fwd_packed_n
+__global__ __launch_bounds__(X3_THREADS, 2) T2S_X3_KERNEL void attn_fwd_x3_wide_kernel(const float* __restrict__ q,
+                                                                         const __bf16* __restrict__ k3,
+                                                                         const __bf16* __restrict__ vT3,
+                                                                         float* __restrict__ o, int BH, int nkb) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 ring3w[];
+    attn_fwd_xw<Split3>(ring3w, q, k3, vT3, o, BH, nkb);
+}
+__global__ __launch_bounds__(X3_THREADS, 2) T2S_P1_KERNEL void attn_fwd_bf16p_wide_kernel(const float* __restrict__ q,
+                                                                            const __bf16* __restrict__ k1,
+                                                                            const __bf16* __restrict__ vT1,
+                                                                            float* __restrict__ o, int BH, int nkb) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 ring1w[];
+    attn_fwd_xw<Split1>(ring1w, q, k1, vT1, o, BH, nkb);
+}
+
+// plain (BH, 32 nkb, 32) fp32 k or v -> split planes: k as the A operand with the key on the lane
 // (transpose = 0), v as V^T with the feature on the lane (transpose = 1)
 template <int NP>
-__global__ void pack_xn_kernel(const float* __restrict__ src, bf16x8* __restrict__ dst, int BH, int transpose) {
+__global__ void pack_xn_kernel(const float* __restrict__ src, bf16x8* __restrict__ dst, int BH, int nkb, int transpose) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;   // one (bh, tile, s, lane)
-    if (idx >= BH * NKB * 2 * 64) return;
-    const int lane = idx & 63, s = (idx >> 6) & 1, tile = (idx >> 7) % NKB, bh = idx / (NKB * 128);
+    if (idx >= BH * nkb * 2 * 64) return;
+    const int ntok = 32 * nkb;
+    const int lane = idx & 63, s = (idx >> 6) & 1, tile = (idx >> 7) % nkb, bh = idx / (nkb * 128);
     const int i = lane & 31, h = lane >> 5;
     f32x8 v;
 #pragma unroll
     for (int j = 0; j < 8; ++j) {
         const int kk = 16 * s + 8 * (j >> 2) + 4 * h + (j & 3);     // permuted k order of the fragment
-        v[j] = transpose ? src[((size_t)bh * NTOK + tile * 32 + kk) * DH + i]     // V^T[d = i][key = kk]
-                         : src[((size_t)bh * NTOK + tile * 32 + i) * DH + kk];    // K[key = i][d = kk]
+        v[j] = transpose ? src[((size_t)bh * ntok + tile * 32 + kk) * DH + i]     // V^T[d = i][key = kk]
+                         : src[((size_t)bh * ntok + tile * 32 + i) * DH + kk];    // K[key = i][d = kk]
     }
     const Split3 sp = split3(v);   // (the one-plane form keeps h = rn_bf16(v))
-    bf16x8* d = dst + ((size_t)(bh * NKB + tile) * 2 * NP + s) * 64 + lane;
+    bf16x8* d = dst + ((size_t)(bh * nkb + tile) * 2 * NP + s) * 64 + lane;
     d[0] = sp.h;
     if constexpr (NP == 3) {
         d[2 * 64] = sp.m;
@@ -368,10 +584,12 @@ __global__ void pack_xn_kernel(const float* __restrict__ src, bf16x8* __restrict
 // host side: one set of helpers for both plane counts (np = 3: bf16x3, np = 1: the one-plane form)
 struct AttnXn {
     void (*kernel)(const float*, const __bf16*, const __bf16*, float*, int);
+    void (*wide)(const float*, const __bf16*, const __bf16*, float*, int, int);   // 800 / 1024 tokens
     int lds_bytes;
 };
 static AttnXn attn_xn(int np) {
-    return np == 3 ? AttnXn{attn_fwd_x3_kernel, X3_LDS_BYTES} : AttnXn{attn_fwd_bf16p_kernel, P1_LDS_BYTES};
+    return np == 3 ? AttnXn{attn_fwd_x3_kernel, attn_fwd_x3_wide_kernel, X3_LDS_BYTES}
+                   : AttnXn{attn_fwd_bf16p_kernel, attn_fwd_bf16p_wide_kernel, P1_LDS_BYTES};
 }
 
 int attn_xn_init(int np) {   // once per kernel, outside any stream capture (16 KiB of LDS needs no opt-in; a ring may grow)
@@ -379,12 +597,14 @@ int attn_xn_init(int np) {   // once per kernel, outside any stream capture (16 
     if (!done[np]) {
         T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_xn(np).kernel),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, attn_xn(np).lds_bytes));
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(attn_xn(np).wide),
+                                          hipFuncAttributeMaxDynamicSharedMemorySize, attn_xn(np).lds_bytes));
         done[np] = true;
     }
     return T2S_OK;
 }
 
-static int attn_xn_grid(int BH) {
+static int attn_xn_grid(int items) {
     static int n_cu = 0;
     if (n_cu == 0) {
         int dev = 0;
@@ -394,20 +614,28 @@ static int attn_xn_grid(int BH) {
         else
             n_cu = 256;
     }
-    return BH < n_cu ? BH : n_cu;   // one persistent workgroup per CU
+    return items < n_cu ? items : n_cu;   // one persistent workgroup per CU
 }
 
-int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st) {
+int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, int n_tok, hipStream_t st) {
     const AttnXn x = attn_xn(np);
-    x.kernel<<<attn_xn_grid(BH), X3_THREADS, x.lds_bytes, st>>>(q, k, vT, o, BH);
+    if (n_tok == NTOK) {
+        x.kernel<<<attn_xn_grid(BH), X3_THREADS, x.lds_bytes, st>>>(q, k, vT, o, BH);
+    } else {
+        if ((n_tok != 800 && n_tok != 1024) || BH <= 0 || BH > (1 << 22)) {
+            set_error("attention (%d planes): n_tok=%d must be 480, 800 or 1024 (BH=%d)", np, n_tok, BH);
+            return T2S_E_INVALID;
+        }
+        x.wide<<<attn_xn_grid(2 * BH), X3_THREADS, x.lds_bytes, st>>>(q, k, vT, o, BH, n_tok / 32);   // items = (head, part)
+    }
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
 template <int NP>
-static int pack_xn(const float* src, __bf16* dst, int BH, int transpose, hipStream_t st) {
-    const int n = BH * NKB * 2 * 64;
-    pack_xn_kernel<NP><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, transpose);
+static int pack_xn(const float* src, __bf16* dst, int BH, int nkb, int transpose, hipStream_t st) {
+    const int n = BH * nkb * 2 * 64;
+    pack_xn_kernel<NP><<<(n + 255) / 256, 256, 0, st>>>(src, reinterpret_cast<bf16x8*>(dst), BH, nkb, transpose);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -417,31 +645,34 @@ static int pack_xn(const float* src, __bf16* dst, int BH, int transpose, hipStre
 // ------------------------------------------------------------------ C ABI: stand-alone entry on plain tensors
 namespace {
 using namespace t2s;
-// q (BH,480,32) -> fp32 fragment-major [(bh*15 + tile)*4 + g][lane][e] = Q[32 tile + i][8g + 4h + e]
-__global__ void q_to_frag_kernel(const float* __restrict__ q, f32x4* __restrict__ qf, int BH) {
+// q (BH, 32 nkb, 32) -> fp32 fragment-major [(bh*nkb + tile)*4 + g][lane][e] = Q[32 tile + i][8g + 4h + e]
+__global__ void q_to_frag_kernel(const float* __restrict__ q, f32x4* __restrict__ qf, int BH, int nkb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= BH * 15 * 4 * 64) return;
-    const int lane = idx & 63, g = (idx >> 6) & 3, tile = (idx >> 8) % 15, bh = idx / (15 * 256);
-    qf[idx] = *reinterpret_cast<const f32x4*>(q + ((size_t)bh * NTOK + tile * 32 + (lane & 31)) * DH + 8 * g + 4 * (lane >> 5));
+    if (idx >= BH * nkb * 4 * 64) return;
+    const int lane = idx & 63, g = (idx >> 6) & 3, tile = (idx >> 8) % nkb, bh = idx / (nkb * 256);
+    qf[idx] = *reinterpret_cast<const f32x4*>(q + ((size_t)bh * nkb * 32 + tile * 32 + (lane & 31)) * DH + 8 * g + 4 * (lane >> 5));
 }
-// o fragment-major [((seq*15 + tile)*16 + head*4 + g)][lane][e] -> (BH,480,32)
-__global__ void o_from_frag_kernel(const f32x4* __restrict__ of, float* __restrict__ o, int BH) {
+// o fragment-major [((seq*nkb + tile)*16 + head*4 + g)][lane][e] -> (BH, 32 nkb, 32)
+__global__ void o_from_frag_kernel(const f32x4* __restrict__ of, float* __restrict__ o, int BH, int nkb) {
     const int idx = blockIdx.x * blockDim.x + threadIdx.x;
-    if (idx >= BH * 15 * 4 * 64) return;
-    const int lane = idx & 63, g = (idx >> 6) & 3, tile = (idx >> 8) % 15, bh = idx / (15 * 256);
+    if (idx >= BH * nkb * 4 * 64) return;
+    const int lane = idx & 63, g = (idx >> 6) & 3, tile = (idx >> 8) % nkb, bh = idx / (nkb * 256);
     const int seq = bh / NH, head = bh % NH;
-    *reinterpret_cast<f32x4*>(o + ((size_t)bh * NTOK + tile * 32 + (lane & 31)) * DH + 8 * g + 4 * (lane >> 5)) =
-        of[(((size_t)seq * 15 + tile) * 16 + head * 4 + g) * 64 + lane];
+    *reinterpret_cast<f32x4*>(o + ((size_t)bh * nkb * 32 + tile * 32 + (lane & 31)) * DH + 8 * g + 4 * (lane >> 5)) =
+        of[(((size_t)seq * nkb + tile) * 16 + head * 4 + g) * 64 + lane];
 }
 }  // namespace
 
 // NP = 3: bf16x3, NP = 1: the one-plane form
 template <int NP>
-static int attn_fwd_plain(const char* who, const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
+static int attn_fwd_plain(const char* who, const float* q, const float* k, const float* v, float* o, int BH, int n_tok, void* stream) {
+    T2S_REQUIRE(n_tok == 480 || n_tok == 800 || n_tok == 1024, "%s: n_tok=%d must be 480, 800 or 1024", who, n_tok);
     T2S_REQUIRE(q && k && v && o && BH > 0 && BH % NH == 0, "%s: bad argument (BH=%d must be a multiple of 4)", who, BH);
+    const int nkb = n_tok / 32;
+    T2S_REQUIRE((long long)BH * nkb * 256 <= 0x7fffffffLL, "%s: BH=%d at n_tok=%d exceeds the helpers' 32-bit index", who, BH, n_tok);
     hipStream_t st = (hipStream_t)stream;
     if (int rc = attn_xn_init(NP)) return rc;
-    const size_t n = (size_t)BH * NTOK * DH;
+    const size_t n = (size_t)BH * n_tok * DH;
     float* f32buf = nullptr;
     __bf16* planes = nullptr;
     T2S_HIP_CHECK(hipMalloc(&f32buf, 2 * n * sizeof(float)));
@@ -450,13 +681,13 @@ static int attn_fwd_plain(const char* who, const float* q, const float* k, const
         set_error("%s: hipMalloc failed", who);
         return T2S_E_HIP;
     }
-    const int nf = BH * 15 * 4 * 64;
-    q_to_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(q, reinterpret_cast<f32x4*>(f32buf), BH);
-    int rc = pack_xn<NP>(k, planes, BH, 0, st);
-    if (rc == T2S_OK) rc = pack_xn<NP>(v, planes + NP * n, BH, 1, st);
-    if (rc == T2S_OK) rc = launch_attn_xn(NP, f32buf, planes, planes + NP * n, f32buf + n, BH, st);
+    const int nf = BH * nkb * 4 * 64;
+    q_to_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(q, reinterpret_cast<f32x4*>(f32buf), BH, nkb);
+    int rc = pack_xn<NP>(k, planes, BH, nkb, 0, st);
+    if (rc == T2S_OK) rc = pack_xn<NP>(v, planes + NP * n, BH, nkb, 1, st);
+    if (rc == T2S_OK) rc = launch_attn_xn(NP, f32buf, planes, planes + NP * n, f32buf + n, BH, n_tok, st);
     if (rc == T2S_OK) {
-        o_from_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(reinterpret_cast<const f32x4*>(f32buf + n), o, BH);
+        o_from_frag_kernel<<<(nf + 255) / 256, 256, 0, st>>>(reinterpret_cast<const f32x4*>(f32buf + n), o, BH, nkb);
         if (hipGetLastError() != hipSuccess) rc = T2S_E_HIP;
     }
     (void)hipStreamSynchronize(st);
@@ -466,9 +697,18 @@ static int attn_fwd_plain(const char* who, const float* q, const float* k, const
 }
 
 extern "C" int t2s_attn_fwd_x3(const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
-    return attn_fwd_plain<3>("t2s_attn_fwd_x3", q, k, v, o, BH, stream);
+    return attn_fwd_plain<3>("t2s_attn_fwd_x3", q, k, v, o, BH, NTOK, stream);
 }
 
 extern "C" int t2s_attn_fwd_bf16p(const float* q, const float* k, const float* v, float* o, int BH, void* stream) {
-    return attn_fwd_plain<1>("t2s_attn_fwd_bf16p", q, k, v, o, BH, stream);
+    return attn_fwd_plain<1>("t2s_attn_fwd_bf16p", q, k, v, o, BH, NTOK, stream);
+}
+
+// include/t2s_wide_math.h
+extern "C" int t2s_attn_fwd_x3_n(const float* q, const float* k, const float* v, float* o, int BH, int n_tok, void* stream) {
+    return attn_fwd_plain<3>("t2s_attn_fwd_x3_n", q, k, v, o, BH, n_tok, stream);
+}
+
+extern "C" int t2s_attn_fwd_bf16p_n(const float* q, const float* k, const float* v, float* o, int BH, int n_tok, void* stream) {
+    return attn_fwd_plain<1>("t2s_attn_fwd_bf16p_n", q, k, v, o, BH, n_tok, stream);
 }

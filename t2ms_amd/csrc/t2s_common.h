@@ -7,6 +7,7 @@
 
 #include "../../include/t2s.h"
 #include "../../include/t2s_wide_train.h"
+#include "../../include/t2s_wide_math.h"
 
 namespace t2s {
 

@@ -402,6 +402,7 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
             fill_shared(a, blk, qkv_blk);
             set_mats(a, pl->m, blk, qkv_blk);
             a.k3 = w_kp; a.v3 = w_vp;
+            a.tps = ntok == NTOK ? 0 : ntok / 32;   // as below: the wide kernels
             return launch_dit_rows_xn<DO_MLP, DO_QKV>(pl->np, a, st);
         }
         RowArgs a{};
@@ -413,7 +414,7 @@ int run_forward(t2s_dit* h, const float* x, int B, int S, int uncond_rows, const
         return launch_dit_rows16<DO_MLP, DO_QKV>(a, st);
     };
     auto launch_attention = [&] {
-        return pl ? launch_attn_xn(pl->np, w_q, w_kp, w_vp, w_ao, S * NH, st) : launch_attn_packed_n(w_q, w_k, w_v, w_ao, S * NH, ntok, st);
+        return pl ? launch_attn_xn(pl->np, w_q, w_kp, w_vp, w_ao, S * NH, ntok, st) : launch_attn_packed_n(w_q, w_k, w_v, w_ao, S * NH, ntok, st);
     };
     constexpr std::true_type yes{};
     constexpr std::false_type no{};
@@ -558,7 +559,7 @@ int alloc_bf_planes(t2s_dit* h, BfPlanes& out) {
     T2S_REQUIRE(setup, "t2s_dit_set_math: no set-up stream on device %d", dev);
     BfPlanes pl = out;
     if ((rc = attn_xn_init(pl.np)) || (rc = dit_rows_xn_init(pl.np))) return rc;
-    const size_t bytes = (size_t)h->max_seqs * NTOK * D * pl.np * sizeof(__bf16);
+    const size_t bytes = (size_t)h->max_seqs * h->ntok() * D * pl.np * sizeof(__bf16);   // (the handle's token count: 480 / 800 / 1024)
     if (hipMalloc(&pl.k, bytes) != hipSuccess || hipMalloc(&pl.v, bytes) != hipSuccess ||
         carve_alloc(pl.w, [&](auto& take) { carve_bf_weights(pl, take); }) != hipSuccess) {
         rc = T2S_E_HIP;
@@ -583,11 +584,20 @@ int alloc_bf_planes(t2s_dit* h, BfPlanes& out) {
 int t2s_dit_set_math(t2s_dit* h, int math) {
     T2S_REQUIRE(h, "t2s_dit_set_math: NULL handle");
     T2S_REQUIRE(math == T2S_MATH_F32 || math == T2S_MATH_BF16X3 || math == T2S_MATH_BF16, "t2s_dit_set_math: unknown mode %d", math);
-    T2S_REQUIRE(math == T2S_MATH_F32 || h->latw == LATW, "t2s_dit_set_math: a handle of latent width %d runs T2S_MATH_F32 only (bf16x3 / bf16 exist at width 30)",
+    T2S_REQUIRE(math == T2S_MATH_F32 || h->latw == LATW || h->wide_math, "t2s_dit_set_math: a handle of latent width %d runs T2S_MATH_F32 only (bf16x3 / bf16 exist at width 30)",
                 h->latw);
     if (math != T2S_MATH_F32 && h->bf[math - T2S_MATH_BF16X3].w == nullptr)
         if (int rc = alloc_bf_planes(h, h->bf[math - T2S_MATH_BF16X3])) return rc;
     h->math = math;
+    return T2S_OK;
+}
+
+// include/t2s_wide_math.h
+int t2s_dit_set_wide_math(t2s_dit* h, int on) {
+    T2S_REQUIRE(h, "t2s_dit_set_wide_math: NULL handle");
+    if (h->latw == LATW) return T2S_OK;   // (a width-30 handle has always had the three arithmetics)
+    h->wide_math = on != 0;
+    if (!h->wide_math) h->math = T2S_MATH_F32;
     return T2S_OK;
 }
 

@@ -40,6 +40,7 @@ struct t2s_dit {
     t2s_train_ws* train = nullptr;
     int train_dtype = 0;         // T2S_TRAIN_F32 / T2S_TRAIN_BF16 (t2s_dit_set_train_dtype)
     bool trainable = false;      // a wide handle trains only after t2s_dit_set_trainable (width 30 always does)
+    bool wide_math = false;      // ... and takes T2S_MATH_BF16X3 / _BF16 only after t2s_dit_set_wide_math (t2s_wide_math.h)
     // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;
@@ -84,7 +85,7 @@ int launch_attn_packed(const float* q, const float* k, const float* vT, float* o
 int launch_attn_packed_n(const float* q, const float* k, const float* vT, float* o, int BH, int n_tok, hipStream_t st);
 // t2s_attn_x3.hip; np = 3: bf16x3, np = 1: bf16 (k / vT: np planes)
 int attn_xn_init(int np);
-int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, hipStream_t st);
+int launch_attn_xn(int np, const float* q, const __bf16* k, const __bf16* vT, float* o, int BH, int n_tok, hipStream_t st);
 // t2s_dit.hip
 int dit_forward_cfg_step(t2s_dit* h, const float* x, const float* temb_table, const int* step_ptr,
                          const float* text, float* out_u, float* out_c, int B, hipStream_t st, int ws_seq0,

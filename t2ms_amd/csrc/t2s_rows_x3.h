@@ -69,6 +69,7 @@ struct RowArgsX3 {
     const float *bp, *b1, *b2, *bq;
     float* q;          // q fragment-major fp32 (the attention scales and splits it once per head)
     __bf16 *k3, *v3;   // k, V^T split planes (t2s_x3.h); ONE plane each for the one-plane kernels
+    int tps;           // wide kernels only: 32-token tiles per sequence, 25 or 32 (latent width 2 tps: 800 / 1024 tokens); M = S * 32 * tps
 };
 
 // fp32 packed weights (packed_index order, or the fc2 chunk order of pack_weight_kernel mode 1) ->
@@ -146,7 +147,9 @@ __device__ __forceinline__ void ktile_x3(const bf16x8* wb, BOP&& bop, f32x16& ac
 }
 
 // SP = Split3 (bf16x3) or Split1 (one plane); wring3 = the kernel's dynamic LDS, [2][CHUNK_UNITS] + constants
-template <bool DO_MLP, bool DO_QKV, class SP>
+// TPS = 32-token tiles per sequence, as in t2s_rows.h: 15 (480 tokens, compile-time index arithmetic) or 0 = RowArgsX3::tps at
+// run time (the wide kernels).  The latent width is 2 TPS.  It enters the prologue's and the stores' addresses only.
+template <bool DO_MLP, bool DO_QKV, class SP, int TPS>
 __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wring3) {
     constexpr int NP = planes_of<SP>::n;
     constexpr int CHUNK_UNITS = XN_CHUNK_UNITS<NP>;
@@ -158,7 +161,9 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
     int tile = blockIdx.x * 4 + wave;             // 32-token tile of this wave
     const bool active = tile < n_tiles;           // tail waves compute on a clamped tile, store nothing
     if (!active) tile = n_tiles - 1;
-    const int seq = (tile * 32) / NTOK;           // 480 = 15*32: a tile never straddles sequences
+    const int tps = TPS ? TPS : a.tps, latw = 2 * tps;
+    const int seq = (tile * 32) / (32 * tps);     // 16 W tokens = W / 2 tiles: a tile never straddles sequences (tokens over
+                                                  // tokens, not tile / tps: the 480-token kernels keep their instructions)
     const float* __restrict__ modrow = a.mod + (size_t)seq * MODROW;
     if (a.mod_step != nullptr)      // (spelled out here: a helper without this kernel's target attribute would not inline)
         modrow = a.mod + ((size_t)(*a.mod_step) * a.mod_rows + (seq < a.mod_uncond ? 0 : 1 + a.mod_row0 + (seq - a.mod_uncond))) * MODROW;
@@ -252,7 +257,7 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 
     // residual stream of this lane's token, accumulator layout: x[nt][4g+e] = X[row][32nt+8g+4half+e]
     f32x16 x[4];
-    const int tile_src = tile - (seq - seq % a.in_seqs) * (NTOK / 32);   // same tile of sequence seq % in_seqs
+    const int tile_src = tile - (seq - seq % a.in_seqs) * tps;   // same tile of sequence seq % in_seqs
     bool generated = false;
     if constexpr (!DO_MLP) {
         if (a.p_lat != nullptr) {
@@ -261,9 +266,9 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
             for (int i = threadIdx.x; i < 512; i += 256) cb[i] = a.p_pw[i];
             *reinterpret_cast<f32x4*>(cm + 256 + (lane & 31) * 4) = *reinterpret_cast<const f32x4*>(a.p_pb + (lane & 31) * 4);
             wg_sync();
-            const int n = (tile - seq * (NTOK / 32)) * 32 + (lane & 31);
+            const int n = (tile - seq * tps) * 32 + (lane & 31);
             float cv[4];
-            patch_conv(a, seq, n, cv);
+            patch_conv(a, seq, n, cv, latw);
             const float* posrow = a.p_pos + (size_t)n * D;
 #pragma unroll
             for (int G = 0; G < 16; ++G) {
@@ -422,7 +427,7 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
     }
 
     // ---- fused final layer of the LAST block (transformer.py:182-191): affine LayerNorm (eps 1e-5),
-    // Linear 128 -> 4, unpatchify out[s][(2ww+pw)*30 + 2hh+ph] = y[ph*2+pw]; the lane pair of a token holds its
+    // Linear 128 -> 4, unpatchify out[s][(2ww+pw)*W + 2hh+ph] = y[ph*2+pw]; the lane pair of a token holds its
     // 128 features, so everything is lane-local up to one cross-half add per output
     if constexpr (DO_MLP && !DO_QKV) {
         if (a.out0 != nullptr) {
@@ -468,13 +473,14 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 #pragma unroll
             for (int p = 0; p < 4; ++p) fa[p] += xhalf(fa[p]);
             if (active) {   // lane half 0 writes patch outputs p = 0,1; half 1 writes p = 2,3
-                const int n = (tile - seq * (NTOK / 32)) * 32 + (lane & 31);
+                const int n = (tile - seq * tps) * 32 + (lane & 31);
                 const int hh = n >> 5, ww = n & 31;
-                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * LAT : a.out1 + (size_t)(seq - a.split) * LAT;
+                const int lat = LATC * latw;
+                float* dst = (seq < a.split) ? a.out0 + (size_t)seq * lat : a.out1 + (size_t)(seq - a.split) * lat;
 #pragma unroll
                 for (int q2 = 0; q2 < 2; ++q2) {
                     const int p = 2 * half + q2;
-                    dst[(2 * ww + (p & 1)) * LATW + 2 * hh + (p >> 1)] = (half ? fa[2 + q2] : fa[q2]) + a.f_ob[p];
+                    dst[(2 * ww + (p & 1)) * latw + 2 * hh + (p >> 1)] = (half ? fa[2 + q2] : fa[q2]) + a.f_ob[p];
                 }
             }
         }
@@ -488,13 +494,13 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 #pragma unroll
             for (int ks = 0; ks < 8; ++ks) xmp[ks] = splitp_acc<SP>(xm[ks >> 1], ks & 1);
         }
-        const int tile_in_seq = tile - seq * (NTOK / 32);
+        const int tile_in_seq = tile - seq * tps;
         X3_PRIO(0)
 #pragma unroll 1
         for (int t = 0; t < 12; ++t) {  // output tile t = which*4 + head
             const bf16x8* wb = wring3 + (ci & 1) * CHUNK_UNITS + lane;
             const int which = t >> 2, head = t & 3;
-            const size_t head_tile = ((size_t)seq * NH + head) * (NTOK / 32) + tile_in_seq;
+            const size_t head_tile = ((size_t)seq * NH + head) * tps + tile_in_seq;
             f32x16 acc;
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] = 0.f;
@@ -568,26 +574,43 @@ __device__ __forceinline__ void dit_rows_xn_body(const RowArgsX3 a, bf16x8* wrin
 template <bool DO_MLP, bool DO_QKV>
 __global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_kernel(const RowArgsX3 a) {
     extern __shared__ __attribute__((aligned(16))) bf16x8 wring3[];  // [2][X3_CHUNK_UNITS]
-    dit_rows_xn_body<DO_MLP, DO_QKV, Split3>(a, wring3);
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split3, NTOK / 32>(a, wring3);
 }
 
 // T2S_MATH_BF16: the one-plane instantiation (a kernel of its own, no run-time branch in the bf16x3 one)
 template <bool DO_MLP, bool DO_QKV>
 __global__ __launch_bounds__(256, 2) T2S_P1_KERNEL void dit_rows_bf16p_kernel(const RowArgsX3 a) {
     extern __shared__ __attribute__((aligned(16))) bf16x8 wring1[];  // [2][XN_CHUNK_UNITS<1>]
-    dit_rows_xn_body<DO_MLP, DO_QKV, Split1>(a, wring1);
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split1, NTOK / 32>(a, wring1);
+}
+
+// the same bodies for the wide latents (800 / 1024 tokens; t2s_dit_set_wide_math): tiles per sequence from RowArgsX3::tps
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) T2S_X3_KERNEL void dit_rows_x3_wide_kernel(const RowArgsX3 a) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 wring3w[];
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split3, 0>(a, wring3w);
+}
+template <bool DO_MLP, bool DO_QKV>
+__global__ __launch_bounds__(256, 2) T2S_P1_KERNEL void dit_rows_bf16p_wide_kernel(const RowArgsX3 a) {
+    extern __shared__ __attribute__((aligned(16))) bf16x8 wring1w[];
+    dit_rows_xn_body<DO_MLP, DO_QKV, Split1, 0>(a, wring1w);
 }
 
 // host side: one set of helpers for both plane counts (np = 3: bf16x3, np = 1: the one-plane kernels, named first: their
 // place in the code object, profiles/EXPERIMENTS.md 0.16)
 template <bool DO_MLP, bool DO_QKV>
 inline auto dit_rows_xn_kernel(int np) { return np == 1 ? dit_rows_bf16p_kernel<DO_MLP, DO_QKV> : dit_rows_x3_kernel<DO_MLP, DO_QKV>; }
+template <bool DO_MLP, bool DO_QKV>
+inline auto dit_rows_xn_wide_kernel(int np) { return np == 1 ? dit_rows_bf16p_wide_kernel<DO_MLP, DO_QKV> : dit_rows_x3_wide_kernel<DO_MLP, DO_QKV>; }
 inline int rows_xn_lds_bytes(int np) { return np == 3 ? ROWS_X3_LDS_BYTES : ROWS_P1_LDS_BYTES; }
 
-inline int dit_rows_xn_init(int np) {   // all three instances of a mode
-    const void* const kernels[3] = {reinterpret_cast<const void*>(dit_rows_xn_kernel<false, true>(np)),
+inline int dit_rows_xn_init(int np) {   // all three instances of a mode, in both forms
+    const void* const kernels[6] = {reinterpret_cast<const void*>(dit_rows_xn_kernel<false, true>(np)),
                                     reinterpret_cast<const void*>(dit_rows_xn_kernel<true, true>(np)),
-                                    reinterpret_cast<const void*>(dit_rows_xn_kernel<true, false>(np))};
+                                    reinterpret_cast<const void*>(dit_rows_xn_kernel<true, false>(np)),
+                                    reinterpret_cast<const void*>(dit_rows_xn_wide_kernel<false, true>(np)),
+                                    reinterpret_cast<const void*>(dit_rows_xn_wide_kernel<true, true>(np)),
+                                    reinterpret_cast<const void*>(dit_rows_xn_wide_kernel<true, false>(np))};
     for (const void* k : kernels)
         T2S_HIP_CHECK(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, rows_xn_lds_bytes(np)));
     return T2S_OK;
@@ -600,7 +623,14 @@ inline int launch_dit_rows_xn(int np, const RowArgsX3& a, hipStream_t st) {
         return T2S_E_INVALID;
     }
     const int tiles = a.M / 32;
-    dit_rows_xn_kernel<DO_MLP, DO_QKV>(np)<<<(tiles + 3) / 4, 256, rows_xn_lds_bytes(np), st>>>(a);
+    if (a.tps != 0 && ((a.tps != 25 && a.tps != 32) || tiles % a.tps != 0)) {
+        set_error("dit_rows_xn (%d planes): tps=%d must be 25 or 32 and divide the %d tiles", np, a.tps, tiles);
+        return T2S_E_INVALID;
+    }
+    if (a.tps != 0)
+        dit_rows_xn_wide_kernel<DO_MLP, DO_QKV>(np)<<<(tiles + 3) / 4, 256, rows_xn_lds_bytes(np), st>>>(a);
+    else
+        dit_rows_xn_kernel<DO_MLP, DO_QKV>(np)<<<(tiles + 3) / 4, 256, rows_xn_lds_bytes(np), st>>>(a);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }

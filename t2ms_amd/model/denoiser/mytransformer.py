@@ -5,7 +5,9 @@ patchified 2x2 into 16 * dim tokens, and ``pos_embed`` has 16 * dim rows.  Its d
 bench-press model dim 64 (1024).  State-dict keys, block count, width and heads are those of
 ``model.denoiser.transformer.Transformer``, which is this class at dim 30: one class body (handle management, locking,
 pairing, the no-grad forward) serves both, and ``forward`` runs the HIP kernels of libt2s_hip.so through a handle made by
-t2s_dit_create_w.  The wide widths run the f32 arithmetic and inference only.
+t2s_dit_create_w.  Out of the box the wide widths run the f32 arithmetic and inference only; ``set_trainable(True)`` opts a
+model into the fp32 training step, ``set_wide_math(True)`` into bf16x3 / bf16 inference.  Wide bf16 training
+and a ragged backward stay refused.
 """
 from __future__ import annotations
 

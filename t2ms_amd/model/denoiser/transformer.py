@@ -226,6 +226,7 @@ class Transformer(H.HandleOwner, nn.Module):
         h.max_seqs, h.keep = cap, keep
         self.__dict__.pop("_t2s_math_applied", None)          # a new handle starts in f32
         h.trainable = False                                   # ... and, at a wide width, refuses to train
+        h.wide_math = False                                   # ... and the bf16 arithmetics
         return h
 
     def _refresh(self, h, device, w, keep, cap):
@@ -248,8 +249,13 @@ class Transformer(H.HandleOwner, nn.Module):
                 cap = max(cap, (n_seqs + n_seqs // 8 + 63) // 64 * 64)
         h = self._owned_handle(device, (device, cap), stamp, self._build, self._refresh, device, w, keep, cap)
         math = self.__dict__.get("_t2s_math", "f32")
-        if self.H != LAT_H and math != "f32":          # (set_math refuses it; a pickled or hand-set attribute ends here)
+        wide_math = bool(self.__dict__.get("_t2s_wide_math", False))
+        if self.H != LAT_H and math != "f32" and not wide_math:   # (set_math refuses it; a pickled or hand-set attribute ends here)
             raise L.T2SError(f"Transformer(dim={self.H}) runs math 'f32' only, got {math!r}")
+        if h.wide_math != wide_math:                          # (kept on the handle, as `trainable` below; in front of set_math)
+            L.check(L.lib().t2s_dit_set_wide_math(h.ptr, int(wide_math)), "t2s_dit_set_wide_math")
+            h.wide_math = wide_math
+            self.__dict__.pop("_t2s_math_applied", None)      # switching off puts the handle back on f32
         if self.__dict__.get("_t2s_math_applied") != math:
             with L.device_lock(device), torch.cuda.device(device):       # (first bf16x3 / bf16 use allocates and synchronises)
                 L.check(L.lib().t2s_dit_set_math(h.ptr, L.MATH_CODES[math]), "t2s_dit_set_math")
@@ -273,9 +279,9 @@ class Transformer(H.HandleOwner, nn.Module):
         Set it before building a Sampler: a captured hipGraph keeps its kernels."""
         if math not in L.MATH_CODES:
             raise ValueError(f"math must be 'f32', 'bf16x3' or 'bf16', got {math!r}")
-        if self.H != LAT_H and math != "f32":
-            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents run math 'f32' only (bf16x3 / bf16 exist at dim 30), "
-                             f"got {math!r}")
+        if self.H != LAT_H and math != "f32" and not self.__dict__.get("_t2s_wide_math", False):
+            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents run math 'f32' only (bf16x3 / bf16 exist at dim 30, "
+                             f"and at the wide widths after set_wide_math(True)), got {math!r}")
         self.__dict__["_t2s_math"] = math
         return self
 
@@ -307,11 +313,24 @@ class Transformer(H.HandleOwner, nn.Module):
         """Opt a WIDE model (dim 50 / 64, the motion denoisers of the reference's mytrain.py) into training: with it set,
         forward under autograd runs the fp32 HIP training step at 16 * dim tokens (t2s_dit_set_trainable) in place of
         refusing.  A dim-30 model always trains; the call changes nothing there.  What stays refused at the wide widths:
-        set_train_dtype("bf16") and set_math("bf16x3" / "bf16")."""
+        set_train_dtype("bf16"), and set_math("bf16x3" / "bf16") unless set_wide_math(True) opted the model in (inference
+        only: training stays fp32)."""
         self.__dict__["_t2s_trainable"] = bool(on)
         return self
 
-    # (_t2s_math, _t2s_train_dtype and _t2s_trainable are settings: they travel with a pickle)
+    def set_wide_math(self, on: bool = True):
+        """Opt a WIDE model (dim 50 / 64) into the bf16 arithmetics of the no-grad forward and the sampler: with it set,
+        set_math("bf16x3") (fp32-accurate) and set_math("bf16") (single-pass, NOT fp32-accurate) are accepted and run the
+        wide bf16 row-chain and attention kernels at 16 * dim tokens (t2s_dit_set_wide_math).  Nothing else moves: the model
+        stays on the arithmetic it was on ("f32" unless set_math said otherwise), and so does a Sampler over it when nobody
+        chose.  on=False brings the refusal back and returns the model to "f32".  A dim-30 model has always had the three
+        arithmetics; the call changes nothing there."""
+        self.__dict__["_t2s_wide_math"] = bool(on)
+        if not on and self.H != LAT_H:
+            self.__dict__["_t2s_math"] = "f32"
+        return self
+
+    # (_t2s_math, _t2s_train_dtype, _t2s_trainable and _t2s_wide_math are settings: they travel with a pickle)
     _t2s_transient = H.HandleOwner._t2s_transient + ("_t2s_math_applied", "_t2s_bucket", "_t2s_flat_grad", "_t2s_fwd_gen",
                                                      "_t2s_wstruct", "_t2s_pair", "_t2s_pairing")
 

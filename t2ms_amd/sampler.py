@@ -372,6 +372,7 @@ class Sampler:
         # a multichannel decoder (model/pretrained/myvqvae.py Decoder: C-channel motion series) decodes to (B,C,L), any L >= 8
         self.channels = getattr(decoder, "channels", None)      # (None too without a decoder: the single-channel (B,L) layout)
         # the model's latent width (mytransformer.Transformer(dim): 50 / 64 for the motion models); the wide widths run f32
+        # unless somebody chose otherwise on a model opted in with set_wide_math(True) -- set_math below refuses it without
         self.width = int(getattr(model, "H", L.LAT_W))
         flow_dim = getattr(decoder, "flow_dim", None)      # (stamped by myvqvae.vqvae; a bare Decoder does not know it)
         if flow_dim is not None and int(flow_dim) != self.width:
