@@ -13,7 +13,8 @@ extern "C" {
 /* Opt a WIDE handle into training (the reference's mytrain.py): with on != 0, t2s_dit_set_train_dtype(T2S_TRAIN_F32),
  * t2s_dit_train_forward / _backward / _input_grad and the training classes of t2s_dit_timing_* accept it and run the fp32
  * step at 16*latent_w tokens (chunked attention kernels, run-time geometry; results repeat bit for bit from run to run).
- * T2S_TRAIN_BF16 stays T2S_E_INVALID with a message at a wide width, and there is no ragged backward.  on == 0 restores the
+ * T2S_TRAIN_BF16 stays T2S_E_INVALID with a message at a wide width (t2s_wide_train_bf16.h holds the opt-in that lifts this), and
+ * there is no ragged backward.  on == 0 restores the
  * refusals.  A width-30 handle always trains: T2S_OK, nothing changes. */
 int t2s_dit_set_trainable(t2s_dit* h, int on);
 

@@ -25,8 +25,9 @@ The reference's loop (mytrain.py:58-97), kept:
 Different on purpose: `loss_list` holds the per-epoch mean losses (the reference saves a list it never appends to); the
 reference's hard stop after epoch 4000 and its loss-curve plot are not built; `--max_steps N` ends the run after N
 optimisation steps (the epoch it stops in is checkpointed by the usual rule); `--synthetic N` serves N seeded clips per
-length group, one loader batch per `--batch_size` clips of each group, without a dataset.  The arithmetic is fp32: bf16
-training exists at latent width 30 only.
+length group, one loader batch per `--batch_size` clips of each group, without a dataset.  The arithmetic is fp32;
+`--bf16` (train.py's flag) runs the bf16 mixed-precision step instead: bf16 MFMA operands and saved activations, fp32
+accumulation, master weights, statistics and gradients.  The checkpoints are the same files either way (fp32 weights).
 """
 import argparse
 import os
@@ -68,6 +69,7 @@ def get_args(argv=None):
     # this driver's own
     p.add_argument("--synthetic", type=int, default=0, help="N seeded synthetic clips per length group instead of the dataset")
     p.add_argument("--max_steps", type=int, default=0, help="stop after this many optimisation steps (0: run all epochs)")
+    p.add_argument("--bf16", action="store_true", help="bf16 mixed-precision training step (fp32 master weights and gradients)")
     args = p.parse_args(argv)
     if args.batch_size < 1 or args.epochs < 1:
         p.error("--batch_size and --epochs must be >= 1")
@@ -99,6 +101,8 @@ def load_models(args, device):
     from t2ms_amd import synth
     vae = vqvae(args).float()
     model = Transformer(args.flow_dim).set_trainable(True)
+    if getattr(args, "bf16", False):
+        model.set_wide_train_bf16(True).set_train_dtype("bf16")
     if args.random_init:
         vae.load_state_dict(synth.make_mvae_state_dict(args.general_seed, args.input_dim, args.block_hidden_size,
                                                        args.num_residual_layers, args.res_hidden_size), strict=True)
@@ -166,6 +170,7 @@ def train(args):
         sys.exit("mytrain.py: the train split holds no full batch (lower --batch_size)")
     model, _vae = load_models(args, device)
     backbone = RectifiedFlow() if args.backbone == "flowmatching" else DDPM(args.total_step, device)
+    print(f"Training arithmetic: {'bf16 mixed precision (fp32 master weights, statistics and gradients)' if args.bf16 else 'fp32'}")
     print(f"Total learnable parameters: {sum(p.numel() for p in model.parameters() if p.requires_grad)}")
     print(f"VAE learnable parameters: {sum(p.numel() for p in model.encoder.parameters() if p.requires_grad)}")
     optimizer = T2SAdamW(model.parameters(), lr=1e-4, weight_decay=0.0)

@@ -304,6 +304,12 @@ SYMBOLS_WIDE_MATH = {
     "t2s_attn_fwd_bf16p_n": (_I, [_VP, _VP, _VP, _VP, _I, _I, _VP]),
 }
 
+# include/t2s_wide_train_bf16.h: the bf16 mixed-precision training step at the wide latent widths (tests/test_wide_train_bf16_host.py)
+SYMBOLS_WIDE_TRAIN_BF16 = {
+    "t2s_dit_set_wide_train_bf16": (_I, [_VP, _I]),
+    "t2s_attn_train_bf16_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libt2s_hip.so (once).  Raises if it has not been built."""
@@ -314,7 +320,8 @@ def lib() -> C.CDLL:
                 f"{LIB_PATH} is missing: build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                 f"or `make -C t2ms_amd/csrc` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
-        for name, (res, args) in list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()) + list(SYMBOLS_WIDE_MATH.items()):
+        for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()) + list(SYMBOLS_WIDE_MATH.items()) +
+                                  list(SYMBOLS_WIDE_TRAIN_BF16.items())):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         _lib = handle

@@ -133,7 +133,7 @@ struct BGemmArgs {
     const __bf16* res;    // BPRO_LN_RES: the branch output (M,128) whose gated residual add produces this layer's input:
     int gate_off;         //   x = A + mod[seq][gate_off + c] * res; x is written to x_out (fp32 (M,128)) and then
     float* x_out;         //   LayerNorm-modulated like BPRO_LN -- the stand-alone gate/residual kernel fused away
-    __bf16* q;            // BEPI_QKV destinations, each (S*4, 480, 32)
+    __bf16* q;            // BEPI_QKV destinations, each (S*4, tokens, 32)
     __bf16* k;
     __bf16* v;
     // BEPI_LNBWD (N = 128): the product is da = grad wrt modulate(LN(ln_x)); the epilogue is the LayerNorm + modulate
@@ -141,11 +141,12 @@ struct BGemmArgs {
     // dn = da (1 + scale), and -- when res != NULL -- the gate backward of the branch differentiated next on the dx just
     // produced: out = mod[gate_off] * dx (bf16), dgate = sum_tok dx * res.  The three per-sequence column sums
     // (dshift = sum da, dscale = sum da n, dgate) leave as one partial row per 32-token tile: colpart (M/32, 3, 128),
-    // added over the 15 tiles of a sequence, in tile order, by lnbwd_colsum_reduce_kernel.
+    // added over the 15 (25, 32) tiles of a sequence, in tile order, by lnbwd_colsum_reduce_kernel.
     const float* ln_x;
     float* dx;
     float* colpart;
     int reverse;          // tile order: 0 ascending, 1 descending
+    int tps;              // 32-token tiles per sequence, read by the run-time form only (bgemm_kernel<..., TOK = 0>: 25 or 32)
 };
 
 // Weights-stationary streaming GEMM: one persistent workgroup of 12 waves per CU keeps the whole
@@ -284,9 +285,13 @@ __device__ __forceinline__ void lnbwd_epilogue(f32x16 (&acc)[4], const float* __
     }
 }
 
-template <int K, int N, int PRO, int EPI>
+// TOK: tokens per sequence of the tile -> (sequence, token) map, as gemm_rows_kernel's: NTOK for the 480-token step, 0 for a
+// wide handle's (a.tps tiles per sequence at run time).
+template <int K, int N, int PRO, int EPI, int TOK = NTOK>
 __global__ __launch_bounds__(bg_threads(EPI)) T2S_NO_PK_F32 void bgemm_kernel(const BGemmArgs a) {
     constexpr int KS = K / 16, NT = N / 32, THREADS = bg_threads(EPI);
+    static_assert(TOK % 32 == 0, "a 32-token tile never straddles a sequence");
+    const int tps = TOK ? TOK / 32 : a.tps, ntok = tps * 32;
     static_assert((PRO != BPRO_LN && PRO != BPRO_LN_RES) || K == 128, "LayerNorm prologue is over d_model = 128");
     extern __shared__ __attribute__((aligned(16))) char wl[];
     bf16x8* wlds = reinterpret_cast<bf16x8*>(wl);
@@ -323,9 +328,9 @@ __global__ __launch_bounds__(bg_threads(EPI)) T2S_NO_PK_F32 void bgemm_kernel(co
     const int n_tiles = a.M >> 5;
     for (int tile_lin = blockIdx.x * (THREADS / 64) + wave; tile_lin < n_tiles; tile_lin += gridDim.x * (THREADS / 64)) {
         const int tile = a.reverse ? n_tiles - 1 - tile_lin : tile_lin;
-        const size_t row = (size_t)tile * 32 + i;   // a 32-token tile never straddles a sequence (480 = 15 x 32)
-        const int seq = tile / (NTOK / 32);
-        const int tok = (tile - seq * (NTOK / 32)) * 32 + i;
+        const size_t row = (size_t)tile * 32 + i;   // a 32-token tile never straddles a sequence (480 = 15 x 32, 800 = 25 x 32)
+        const int seq = tile / tps;
+        const int tok = (tile - seq * tps) * 32 + i;
 
         // ---- B operand: this lane's token, k = 16s + 8h + 0..7
         bf16x8 xf[KS];
@@ -476,7 +481,7 @@ __global__ __launch_bounds__(bg_threads(EPI)) T2S_NO_PK_F32 void bgemm_kernel(co
             if constexpr (EPI == BEPI_QKV) {
                 // one head tile: 32 tokens x 64 B, contiguous in the (bh, tok, d) tensor: two 1 KiB stores
                 __bf16* base = (nt >> 2) == 0 ? a.q : ((nt >> 2) == 1 ? a.k : a.v);
-                char* dst = reinterpret_cast<char*>(base + (((size_t)seq * NH + (nt & 3)) * NTOK + (tok - i)) * DH);
+                char* dst = reinterpret_cast<char*>(base + (((size_t)seq * NH + (nt & 3)) * ntok + (tok - i)) * DH);
 #pragma unroll
                 for (int u = 0; u < 2; ++u) {
                     const int r = 16 * u + (lane >> 2), c16 = lane & 3;
@@ -495,11 +500,15 @@ __global__ __launch_bounds__(bg_threads(EPI)) T2S_NO_PK_F32 void bgemm_kernel(co
     }
 }
 
-template <int K, int N, int PRO, int EPI>
+template <int K, int N, int PRO, int EPI, int TOK = NTOK>
 inline int launch_bgemm(const BGemmArgs& a, hipStream_t st) {
     constexpr int THREADS = bg_threads(EPI);
     if (a.M <= 0 || a.M % 32 != 0 || a.N != N) {
         set_error("bgemm: M=%d must be a positive multiple of 32 and N=%d must equal %d", a.M, a.N, N);
+        return T2S_E_INVALID;
+    }
+    if (TOK == 0 && (a.tps <= 0 || (a.M / 32) % a.tps != 0)) {   // whole sequences of whole tiles: no tile straddles two
+        set_error("bgemm: M=%d is not a whole number of sequences of %d 32-token tiles", a.M, a.tps);
         return T2S_E_INVALID;
     }
     constexpr int lds = N * K * 2 + N * 4 + (THREADS / 64) * BG_STAGE_BYTES + (EPI == BEPI_LNBWD ? (THREADS / 64) * 1024 : 0);
@@ -513,7 +522,7 @@ inline int launch_bgemm(const BGemmArgs& a, hipStream_t st) {
         n_cu = prop.multiProcessorCount;
     }
     if (!attr) {
-        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bgemm_kernel<K, N, PRO, EPI>),
+        T2S_HIP_CHECK(hipFuncSetAttribute(reinterpret_cast<const void*>(bgemm_kernel<K, N, PRO, EPI, TOK>),
                                           hipFuncAttributeMaxDynamicSharedMemorySize, lds));
         attr = true;
     }
@@ -521,20 +530,23 @@ inline int launch_bgemm(const BGemmArgs& a, hipStream_t st) {
     int grid = (tiles + per_wg - 1) / per_wg < n_cu ? (tiles + per_wg - 1) / per_wg : n_cu;
     BGemmArgs a2 = a;
     a2.reverse = next_tile_dir();
-    bgemm_kernel<K, N, PRO, EPI><<<grid, THREADS, lds, st>>>(a2);
+    bgemm_kernel<K, N, PRO, EPI, TOK><<<grid, THREADS, lds, st>>>(a2);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
 
 // colpart (M/32, 3, 128) of BEPI_LNBWD -> dmod[seq][shift_off | scale_off | gate_off + f]: the 15 tile rows of a sequence
-// added in tile order (deterministic).  grid = sequences, 384 threads (256 when there is no gate column).
+// (TPS = 0: tps_rt of them, 25 or 32) added in tile order (deterministic).  grid = sequences, 384 threads (256 when there is
+// no gate column).
+template <int TPS>
 static __global__ void lnbwd_colsum_reduce_kernel(const float* __restrict__ part, float* __restrict__ dmod, int shift_off,
-                                                  int scale_off, int gate_off) {
+                                                  int scale_off, int gate_off, int tps_rt) {
+    const int tps = TPS ? TPS : tps_rt;
     const int seq = blockIdx.x, t = threadIdx.x, q = t >> 7, f = t & 127;
-    const float* p = part + (size_t)seq * (NTOK / 32) * 384 + t;
+    const float* p = part + (size_t)seq * tps * 384 + t;
     float s = 0.f;
 #pragma unroll
-    for (int k = 0; k < NTOK / 32; ++k) s += p[k * 384];
+    for (int k = 0; k < tps; ++k) s += p[k * 384];
     dmod[(size_t)seq * MODROW + (q == 0 ? shift_off : (q == 1 ? scale_off : gate_off)) + f] = s;
 }
 

@@ -8,6 +8,7 @@
 #include "../../include/t2s.h"
 #include "../../include/t2s_wide_train.h"
 #include "../../include/t2s_wide_math.h"
+#include "../../include/t2s_wide_train_bf16.h"
 
 namespace t2s {
 

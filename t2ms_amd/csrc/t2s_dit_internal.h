@@ -41,6 +41,7 @@ struct t2s_dit {
     int train_dtype = 0;         // T2S_TRAIN_F32 / T2S_TRAIN_BF16 (t2s_dit_set_train_dtype)
     bool trainable = false;      // a wide handle trains only after t2s_dit_set_trainable (width 30 always does)
     bool wide_math = false;      // ... and takes T2S_MATH_BF16X3 / _BF16 only after t2s_dit_set_wide_math (t2s_wide_math.h)
+    bool wide_train_bf16 = false;   // ... and T2S_TRAIN_BF16 only after t2s_dit_set_wide_train_bf16 on top of `trainable` (t2s_wide_train_bf16.h)
     // optional in-situ kernel timing (HIP events on the launching stream; never under capture)
     bool timing = false;
     std::vector<hipEvent_t> ev_pool;

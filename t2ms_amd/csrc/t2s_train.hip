@@ -26,9 +26,9 @@ int attn_plain_train_fwd(const float* q, const float* k, const float* v, float* 
                          hipStream_t st);
 int attn_bwd(const float* q, const float* k, const float* v, const float* o_rows, const float* do_rows,
              const float* lse, float* dsum, float* dqkv_rows, int BH, int n_tok, hipStream_t st);
-int attn16_train_fwd(const __bf16* q, const __bf16* k, const __bf16* v, __bf16* o_rows, float* lse, int BH, hipStream_t st);
+int attn16_train_fwd(const __bf16* q, const __bf16* k, const __bf16* v, __bf16* o_rows, float* lse, int BH, int n_tok, hipStream_t st);
 int attn16_bwd(const __bf16* q, const __bf16* k, const __bf16* v, const __bf16* o_rows, const __bf16* do_rows,
-               const float* lse, float* dsum, __bf16* dqkv_rows, int BH, hipStream_t st);
+               const float* lse, float* dsum, __bf16* dqkv_rows, int BH, int n_tok, hipStream_t st);
 int f32_to_bf16(const float* src, __bf16* dst, size_t n, float scale, hipStream_t st);   // t2s_attn_bf16.hip
 }
 
@@ -270,19 +270,31 @@ __global__ __launch_bounds__(256) void tail_reduce_kernel(const float* __restric
     }
 }
 
-// dgate of the last block's MLP branch from the fused final-layer backward: three workgroup partials per sequence
-__global__ void final_gate_reduce_kernel(const float* __restrict__ part, int stride, float* __restrict__ dmod, int gate_off) {
+// dgate of the last block's MLP branch from the fused final-layer backward: the workgroup partials of a sequence, added in
+// workgroup order -- PPS = 3 of them at 480 tokens, PPS = 0: pps_rt (5 at 800, 8 at 1024; fused_rows below)
+template <int PPS>
+__global__ void final_gate_reduce_kernel(const float* __restrict__ part, int stride, float* __restrict__ dmod, int gate_off, int pps_rt) {
+    const int pps = PPS ? PPS : pps_rt;
     const int seq = blockIdx.x, f = threadIdx.x;
-    const float* p = part + (size_t)seq * 3 * stride + FINAL_COLS + f;
-    dmod[(size_t)seq * MODROW + gate_off + f] = (p[0] + p[stride]) + p[2 * stride];
+    const float* p = part + (size_t)seq * pps * stride + FINAL_COLS + f;
+    float s = p[0];
+#pragma unroll
+    for (int k = 1; k < pps; ++k) s += p[(size_t)k * stride];
+    dmod[(size_t)seq * MODROW + gate_off + f] = s;
 }
+// Rows per workgroup of the fused final-layer backward: a whole fraction of a sequence (a workgroup reads ONE gate row and
+// its dgate partial belongs to one sequence) and a multiple of 32 (final_bwd_kernel's row groups).  160 = 480 / 3 = 800 / 5;
+// 1024 is no multiple of 160: 128 = 1024 / 8.
+constexpr int fused_rows(int ntok) { return ntok % 160 == 0 ? 160 : 128; }
+static_assert(NTOK % fused_rows(NTOK) == 0 && 800 % fused_rows(800) == 0 && 1024 % fused_rows(1024) == 0, "whole workgroups per sequence");
 
 // final layer backward (transformer.py:182-191): dout (S,64,W) -> dx (M,128) and grads of
 // ln.weight, ln.bias, linear_emb_to_patch.{weight,bias}.  32 lanes per token row.
 // FUSED (bf16 training): the layer input x_mid + gate * f of the last block is formed here instead of being read back
 // (the forward never writes it), and the gate backward of that MLP branch runs on the dx just produced: t = gate * dx
 // (bf16 rows), dgate partial = sum over this workgroup's rows of dx * f in columns FINAL_COLS.. of its partial row.
-// FUSED workgroups own ROWS = 160 rows = a third of a sequence, so three consecutive partial rows make one sequence.
+// FUSED workgroups own ROWS = fused_rows(tokens) rows = a whole fraction of a sequence (160 = a third at 480 tokens), so that
+// many consecutive partial rows make one sequence.
 template <bool FUSED, int ROWS, int W>
 __global__ __launch_bounds__(256) void final_bwd_kernel(const float* __restrict__ x, const float* __restrict__ dout,
                                                         const float* __restrict__ lng, const float* __restrict__ lnb,
@@ -737,7 +749,7 @@ void carve_act(t2s_train_ws* w, Take&& take) {
 }
 template <class Take>
 void carve_act16(t2s_train_ws* w, Take&& take) {
-    const size_t M = (size_t)w->cap_seqs * NTOK;
+    const size_t M = (size_t)w->cap_seqs * w->ntok();
     for (int i = 0; i < NBLK; ++i) carve_branch(w->bf, i, M, take);
     take(w->bf.t1, M * D); take(w->bf.t2, M * 2 * D); take(w->bf.t3, M * 3 * D); take(w->bf.t4, M * D);
 }
@@ -810,29 +822,34 @@ __global__ void pack16_multi_kernel(const Pack16Table t) {
     j.P[dst] = (__bf16)j.W[idx];
 }
 
-template <int K, int N, int PRO, int EPI>
+// TOK: the tile -> (sequence, token) map of the kernels that need one (LayerNorm prologues, q / k / v heads), NTOK or 0 with
+// `ntok` at run time -- as gemm<..., TOK> below
+template <int K, int N, int PRO, int EPI, int TOK = NTOK>
 int bgemm(const void* A, const bf16x8* Wp, const float* bias, __bf16* out, int M, int n_out, hipStream_t st,
           const float* mod = nullptr, int shift_off = 0, int scale_off = 0, __bf16* save_A = nullptr,
           const __bf16* aux = nullptr, __bf16* q = nullptr, __bf16* k = nullptr, __bf16* v = nullptr,
-          const __bf16* res = nullptr, int gate_off = 0, float* x_out = nullptr) {
+          const __bf16* res = nullptr, int gate_off = 0, float* x_out = nullptr, int ntok = NTOK) {
     BGemmArgs a{};
     a.A = A; a.Wp = Wp; a.bias = bias; a.out = out; a.M = M; a.N = n_out; a.mod = mod; a.shift_off = shift_off;
     a.scale_off = scale_off; a.save_A = save_A; a.aux = aux; a.q = q; a.k = k; a.v = v;
-    a.res = res; a.gate_off = gate_off; a.x_out = x_out;
-    return launch_bgemm<K, N, PRO, EPI>(a, st);
+    a.res = res; a.gate_off = gate_off; a.x_out = x_out; a.tps = ntok / 32;
+    return launch_bgemm<K, N, PRO, EPI, TOK>(a, st);
 }
 
 // data-gradient GEMM (M,K) x W^T -> (M,128) whose epilogue is the LayerNorm + modulate backward (BEPI_LNBWD), then the
 // per-sequence column sums of its partials into dmod
-template <int K>
+template <int K, int TOK = NTOK>
 int bgemm_lnbwd(t2s_train_ws* ws, const __bf16* dY, const bf16x8* Wt, const float* ln_x, int shift_off, int scale_off,
                 const __bf16* f_next, int gate_next_off, __bf16* t_next, int M, hipStream_t st) {
+    const int ntok = ws->ntok();
     BGemmArgs a{};
     a.A = dY; a.Wp = Wt; a.M = M; a.N = D; a.mod = ws->mod; a.shift_off = shift_off; a.scale_off = scale_off;
     a.res = f_next; a.gate_off = gate_next_off; a.out = t_next; a.ln_x = ln_x; a.dx = ws->dx; a.colpart = ws->colpart;
+    a.tps = ntok / 32;
     int rc;
-    if ((rc = launch_bgemm<K, 128, BPRO_BF16, BEPI_LNBWD>(a, st))) return rc;
-    lnbwd_colsum_reduce_kernel<<<M / NTOK, f_next != nullptr ? 384 : 256, 0, st>>>(ws->colpart, ws->dmod, shift_off, scale_off, gate_next_off);
+    if ((rc = launch_bgemm<K, 128, BPRO_BF16, BEPI_LNBWD, TOK>(a, st))) return rc;
+    lnbwd_colsum_reduce_kernel<TOK / 32><<<M / ntok, f_next != nullptr ? 384 : 256, 0, st>>>(ws->colpart, ws->dmod, shift_off, scale_off, gate_next_off,
+                                                                                              ntok / 32);
     T2S_LAUNCH_CHECK();
     return T2S_OK;
 }
@@ -876,6 +893,11 @@ int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st);
 int forward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st);
 int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st);
 int backward_blocks_f32(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st);
+// The run-time (800 / 1024-token) forms of the bf16 recipes and of the fused final-layer backward are first asked for at the
+// END of this file, so that their kernels follow every kernel of the 480-token step in the code object.
+int forward_blocks_bf16_wide(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st);
+int backward_blocks_bf16_wide(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st);
+int final_bwd_fused_wide(t2s_dit* h, t2s_train_ws* ws, const float* dout, int M, int S, int goff, int final_wgs, int final_stride, hipStream_t st);
 
 }  // namespace
 
@@ -897,9 +919,18 @@ int t2s_dit_set_train_dtype(t2s_dit* h, int dtype) {
     T2S_REQUIRE(h, "t2s_dit_set_train_dtype: NULL handle");
     T2S_REQUIRE(h->latw == LATW || h->trainable, "t2s_dit_set_train_dtype: training runs at latent width 30 only, this handle has %d", h->latw);
     T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_dit_set_train_dtype: unknown dtype %d", dtype);
-    T2S_REQUIRE(h->latw == LATW || dtype == T2S_TRAIN_F32,
+    T2S_REQUIRE(h->latw == LATW || dtype == T2S_TRAIN_F32 || h->wide_train_bf16,
                 "t2s_dit_set_train_dtype: a handle of latent width %d trains in T2S_TRAIN_F32 only (T2S_TRAIN_BF16 exists at width 30)", h->latw);
     h->train_dtype = dtype;
+    return T2S_OK;
+}
+
+// include/t2s_wide_train_bf16.h
+int t2s_dit_set_wide_train_bf16(t2s_dit* h, int on) {
+    T2S_REQUIRE(h, "t2s_dit_set_wide_train_bf16: NULL handle");
+    if (h->latw == LATW) return T2S_OK;   // (a width-30 handle has always had both arithmetics)
+    h->wide_train_bf16 = on != 0;
+    if (!h->wide_train_bf16 && h->train_dtype == T2S_TRAIN_BF16) h->train_dtype = T2S_TRAIN_F32;   // (ensure_ws rebuilds on the dtype change)
     return T2S_OK;
 }
 
@@ -922,7 +953,8 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
     t2s_train_ws* ws = h->train;
     const int ntok = h->ntok();
     const int S = B, M = S * ntok;
-    T2S_REQUIRE(ws->dtype == T2S_TRAIN_F32 || h->latw == LATW, "t2s_dit_train_forward: a handle of latent width %d trains in T2S_TRAIN_F32 only", h->latw);
+    T2S_REQUIRE(ws->dtype == T2S_TRAIN_F32 || h->latw == LATW || h->wide_train_bf16,
+                "t2s_dit_train_forward: a handle of latent width %d trains in T2S_TRAIN_F32 only", h->latw);
     ws->S = S;
     // the handle's own parameter copies / forward packs must be current: the caller refreshes them
     // with t2s_dit_update_weights; here only the training-specific packs
@@ -954,8 +986,9 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
     if ((rc = bf ? forward_blocks_bf16(h, ws, S, st) : forward_blocks_f32(h, ws, S, st))) return rc;
     if (bf)   // (the last block's x_mid + g2 * f is formed here)
         T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
-                         final_rows_kernel<LATW><<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b,
-                                                                                                  out, ws->bf.f[NBLK - 1], ws->mod, (NBLK - 1) * MODW + 5 * D, LATW));
+                         T2S_BY_WIDTH(h->latw, final_rows_kernel<W><<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(
+                                                   ws->x_mid[NBLK - 1], S, h->ln_w, h->ln_b, h->out_w, h->out_b, out, ws->bf.f[NBLK - 1], ws->mod,
+                                                   (NBLK - 1) * MODW + 5 * D, h->latw)));
     else
         T2S_TIMED_LAUNCH(h, TC_TR_TAIL, st,
                          T2S_BY_WIDTH(h->latw, final_rows_kernel<W><<<((M + 3) / 4 * 32 + 255) / 256, 256, 0, st>>>(
@@ -966,33 +999,40 @@ int t2s_dit_train_forward(t2s_dit* h, const t2s_dit_weights* w, const float* x, 
 }  // extern "C"
 
 namespace {
-int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+template <int W>
+int forward_blocks_bf16_w(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    constexpr int TOK = W ? 16 * W : 0;   // the GEMMs' tile -> sequence maps
     t2s_train_ws::BF16& a = ws->bf;
-    const int M = S * NTOK;
+    const int ntok = h->ntok();
+    const int M = S * ntok;
     for (int i = 0; i < NBLK; ++i) {
         const int base = i * MODW;
         // The gate / residual adds have no kernel of their own: the GEMM that consumes a residual-stream tensor forms it
         // in its prologue (x = x_prev + gate * branch), writes it out for the backward pass and LayerNorm-modulates it.
         // a1 = mod(LN1(x_in)) -> bf16; q,k,v = a1 Wqkv^T + b -> bf16 heads; for i > 0, x_in[i] = x_mid[i-1] + g2 f[i-1]
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  i == 0 ? bgemm<128, 384, BPRO_LN, BEPI_QKV>(ws->x_in[i], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
-                                                              base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i])
-                         : bgemm<128, 384, BPRO_LN_RES, BEPI_QKV>(ws->x_mid[i - 1], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
-                                                                  base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i],
-                                                                  a.f[i - 1], (i - 1) * MODW + 5 * D, ws->x_in[i]));
-        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn16_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, st));
+                  i == 0 ? bgemm<128, 384, BPRO_LN, BEPI_QKV, TOK>(ws->x_in[i], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
+                                                                   base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i], nullptr, 0,
+                                                                   nullptr, ntok)
+                         : bgemm<128, 384, BPRO_LN_RES, BEPI_QKV, TOK>(ws->x_mid[i - 1], a.w[i][QKV], h->bias[i][QKV], nullptr, M, 3 * D, st, ws->mod,
+                                                                       base + 0 * D, base + 1 * D, a.a1[i], nullptr, a.q[i], a.k[i], a.v[i],
+                                                                       a.f[i - 1], (i - 1) * MODW + 5 * D, ws->x_in[i], ntok));
+        T2S_TIMED(h, TC_TR_ATTN_FWD, st, attn16_train_fwd(a.q[i], a.k[i], a.v[i], a.o[i], ws->lse[i], S * NH, ntok, st));
         // p = o Wp^T + b
         T2S_TIMED(h, TC_TR_GEMM, st, bgemm<128, 128, BPRO_BF16, BEPI_BF16>(a.o[i], a.w[i][PROJ], h->bias[i][PROJ], a.p[i], M, D, st));
         // x_mid = x_in + g1 * p; a2 = mod(LN2(x_mid)); u = a2 W1^T + b1
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  bgemm<128, 256, BPRO_LN_RES, BEPI_BF16>(ws->x_in[i], a.w[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
-                                                          base + 4 * D, a.a2[i], nullptr, nullptr, nullptr, nullptr, a.p[i], base + 2 * D,
-                                                          ws->x_mid[i]));
+                  bgemm<128, 256, BPRO_LN_RES, BEPI_BF16, TOK>(ws->x_in[i], a.w[i][FC1], h->bias[i][FC1], a.u[i], M, 2 * D, st, ws->mod, base + 3 * D,
+                                                               base + 4 * D, a.a2[i], nullptr, nullptr, nullptr, nullptr, a.p[i], base + 2 * D,
+                                                               ws->x_mid[i], ntok));
         // f = gelu(u) W2^T + b2   (gelu(u) is not saved: the fc2 weight gradient re-applies it to u)
         T2S_TIMED(h, TC_TR_GEMM, st, bgemm<256, 128, BPRO_GELU, BEPI_BF16>(a.u[i], a.w[i][FC2], h->bias[i][FC2], a.f[i], M, D, st));
         // (the last block's x_mid + g2 * f is formed inside the final-layer kernels, forward and backward: never written)
     }
     return T2S_OK;
+}
+int forward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) {
+    return h->latw == LATW ? forward_blocks_bf16_w<LATW>(h, ws, S, st) : forward_blocks_bf16_wide(h, ws, S, st);
 }
 
 template <int W>
@@ -1060,18 +1100,25 @@ int t2s_dit_train_backward(t2s_dit* h, const float* dout, const t2s_dit_grads* g
     }
     // ---- final layer
     const bool bf = ws->dtype == T2S_TRAIN_BF16;
+    T2S_REQUIRE(!bf || h->latw == LATW || h->wide_train_bf16,
+                "t2s_dit_train_backward: a handle of latent width %d trains in T2S_TRAIN_F32 only", h->latw);
     const int tail_wgs = (M + TAIL_ROWS - 1) / TAIL_ROWS;
-    constexpr int FUSED_ROWS = NTOK / 3;                       // 160: three workgroups per sequence
-    const int final_wgs = bf ? M / FUSED_ROWS : tail_wgs, final_stride = bf ? FINAL_COLS + D : FINAL_COLS;
+    const int ntok = h->ntok(), frows = fused_rows(ntok);      // bf16: 160 (128 at 1024 tokens) rows = a whole fraction of a sequence
+    T2S_REQUIRE(!bf || (ntok % frows == 0 && M % frows == 0), "t2s_dit_train_backward: %d tokens are no whole number of %d-row workgroups", ntok, frows);
+    const int final_wgs = bf ? M / frows : tail_wgs, final_stride = bf ? FINAL_COLS + D : FINAL_COLS;
     T2S_REQUIRE((size_t)final_wgs * final_stride <= ws->wg_scratch_floats && (size_t)tail_wgs * PATCH_COLS <= ws->wg_scratch_floats,
                 "t2s_dit_train_backward: scratch too small for the tail partials");
     { TimeScope ts(h, TC_TR_TAIL, st);
     if (bf) {   // + the gate backward of the last block's MLP branch: t1 = df = g2 * dx, dgate2
         const int goff = (NBLK - 1) * MODW + 5 * D;
-        final_bwd_kernel<true, FUSED_ROWS, LATW><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
-                                                                            ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1, LATW);
-        T2S_LAUNCH_CHECK();
-        final_gate_reduce_kernel<<<S, D, 0, st>>>(ws->wg_scratch, final_stride, ws->dmod, goff);
+        if (h->latw == LATW) {
+            final_bwd_kernel<true, fused_rows(NTOK), LATW><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx,
+                                                                                      ws->wg_scratch, M, ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1, LATW);
+            T2S_LAUNCH_CHECK();
+            final_gate_reduce_kernel<NTOK / fused_rows(NTOK)><<<S, D, 0, st>>>(ws->wg_scratch, final_stride, ws->dmod, goff, 0);
+        } else if ((rc = final_bwd_fused_wide(h, ws, dout, M, S, goff, final_wgs, final_stride, st))) {
+            return rc;
+        }
     } else {
         T2S_BY_WIDTH(h->latw, final_bwd_kernel<false, TAIL_ROWS, W><<<final_wgs, 256, 0, st>>>(ws->x_in[NBLK], dout, h->ln_w, h->ln_b, h->out_w, ws->dx,
                                                                                               ws->wg_scratch, M, nullptr, nullptr, 0, nullptr, h->latw));
@@ -1111,9 +1158,12 @@ namespace {
 // HIP streams that share a hardware queue serialise, which may have been the "same as in order" of round 2): without any
 // dependency waits 10.92 vs 11.10 ms in order, issued beside the attention backward 11.08 -- the attention backward then
 // takes 3.1-3.7 instead of 2.2 ms: it is bound by vector issue, but its 16 waves per CU leave the other kernel no slot.)
-int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+template <int W>
+int backward_blocks_bf16_w(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    constexpr int TOK = W ? 16 * W : 0;
     t2s_train_ws::BF16& a = ws->bf;
-    const int M = S * NTOK;
+    const int ntok = h->ntok();
+    const int M = S * ntok;
     auto wgrad16 = [&](auto gelu, const __bf16* dY, const __bf16* X, float* dW, float* db, int N, int K) {
         return launch_wgrad16<decltype(gelu)::value>(dY, X, dW, db, M, N, K, ws->wg_scratch, ws->wg_scratch_floats, ws->n_cu, st);
     };
@@ -1133,18 +1183,21 @@ int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, i
         // da2 = du W1, consumed in the accumulators: LN2 backward into dx merged with the attention branch's gate
         // backward (t1 = dp = g1 * dx, dgate1) -- the epilogue of the data-gradient GEMM (BEPI_LNBWD; da2 never reaches HBM)
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  bgemm_lnbwd<256>(ws, a.t2, a.wt[i][FC1], ws->x_mid[i], base + 3 * D, base + 4 * D, a.p[i], base + 2 * D, a.t1, M, st));
+                  bgemm_lnbwd<256, TOK>(ws, a.t2, a.wt[i][FC1], ws->x_mid[i], base + 3 * D, base + 4 * D, a.p[i], base + 2 * D, a.t1, M, st));
         // ---- attention branch: x_mid = x_in + g1 * p
         T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(plain, a.t1, a.o[i], b.proj_w, b.proj_b, D, D));
         T2S_TIMED(h, TC_TR_GEMM, st, bgemm<128, 128, BPRO_BF16, BEPI_BF16>(a.t1, a.wt[i][PROJ], nullptr, a.t4, M, D, st));   // do
-        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn16_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, st));
+        T2S_TIMED(h, TC_TR_ATTN_BWD, st, attn16_bwd(a.q[i], a.k[i], a.v[i], a.o[i], a.t4, ws->lse[i], ws->dsum, a.t3, S * NH, ntok, st));
         T2S_TIMED(h, TC_TR_WGRAD, st, wgrad16(plain, a.t3, a.a1[i], b.qkv_w, b.qkv_b, 3 * D, D));
         // da1 = dqkv Wqkv with LN1 backward into dx as its epilogue, merged with the gate backward of block i-1's MLP branch
         T2S_TIMED(h, TC_TR_GEMM, st,
-                  bgemm_lnbwd<384>(ws, a.t3, a.wt[i][QKV], ws->x_in[i], base + 0 * D, base + 1 * D,
+                  bgemm_lnbwd<384, TOK>(ws, a.t3, a.wt[i][QKV], ws->x_in[i], base + 0 * D, base + 1 * D,
                                    i > 0 ? a.f[i - 1] : (const __bf16*)nullptr, (i - 1) * MODW + 5 * D, a.t1, M, st));
     }
     return T2S_OK;
+}
+int backward_blocks_bf16(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    return h->latw == LATW ? backward_blocks_bf16_w<LATW>(h, ws, g, S, st) : backward_blocks_bf16_wide(h, ws, g, S, st);
 }
 
 template <int W>
@@ -1272,3 +1325,24 @@ int t2s_wgrad(const float* dY, const float* X, float* dW, float* db, int M, int 
 }
 
 }  // extern "C"
+
+// ------------------------------------------------------------------ the run-time forms of the bf16 step (see their declarations)
+namespace {
+int forward_blocks_bf16_wide(t2s_dit* h, t2s_train_ws* ws, int S, hipStream_t st) { return forward_blocks_bf16_w<0>(h, ws, S, st); }
+int backward_blocks_bf16_wide(t2s_dit* h, t2s_train_ws* ws, const t2s_dit_grads* g, int S, hipStream_t st) {
+    return backward_blocks_bf16_w<0>(h, ws, g, S, st);
+}
+int final_bwd_fused_wide(t2s_dit* h, t2s_train_ws* ws, const float* dout, int M, int S, int goff, int final_wgs, int final_stride, hipStream_t st) {
+    const int ntok = h->ntok(), frows = fused_rows(ntok);
+    if (frows == 160)
+        final_bwd_kernel<true, 160, 0><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
+                                                                  ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1, h->latw);
+    else
+        final_bwd_kernel<true, 128, 0><<<final_wgs, 256, 0, st>>>(ws->x_mid[NBLK - 1], dout, h->ln_w, h->ln_b, h->out_w, ws->dx, ws->wg_scratch, M,
+                                                                  ws->bf.f[NBLK - 1], ws->mod, goff, ws->bf.t1, h->latw);
+    T2S_LAUNCH_CHECK();
+    final_gate_reduce_kernel<0><<<S, D, 0, st>>>(ws->wg_scratch, final_stride, ws->dmod, goff, ntok / frows);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+}  // namespace

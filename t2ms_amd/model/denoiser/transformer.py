@@ -227,6 +227,7 @@ class Transformer(H.HandleOwner, nn.Module):
         self.__dict__.pop("_t2s_math_applied", None)          # a new handle starts in f32
         h.trainable = False                                   # ... and, at a wide width, refuses to train
         h.wide_math = False                                   # ... and the bf16 arithmetics
+        h.wide_train_bf16 = False                             # ... and the bf16 training step
         return h
 
     def _refresh(self, h, device, w, keep, cap):
@@ -264,6 +265,10 @@ class Transformer(H.HandleOwner, nn.Module):
         if h.trainable != trainable:                          # (kept on the handle: every rebuild starts switched off)
             L.check(L.lib().t2s_dit_set_trainable(h.ptr, int(trainable)), "t2s_dit_set_trainable")
             h.trainable = trainable
+        wide_bf16 = bool(self.__dict__.get("_t2s_wide_train_bf16", False))
+        if h.wide_train_bf16 != wide_bf16:                    # (next to `trainable`: re-applied after every rebuild)
+            L.check(L.lib().t2s_dit_set_wide_train_bf16(h.ptr, int(wide_bf16)), "t2s_dit_set_wide_train_bf16")
+            h.wide_train_bf16 = wide_bf16
         return h.ptr
 
     def t2s_handle_id(self):
@@ -303,9 +308,9 @@ class Transformer(H.HandleOwner, nn.Module):
         accumulation, master weights, residual stream, statistics and gradients)."""
         if dtype not in ("f32", "bf16"):
             raise ValueError(f"train dtype must be 'f32' or 'bf16', got {dtype!r}")
-        if self.H != LAT_H and dtype != "f32":
-            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents train in 'f32' only (bf16 training exists at dim 30), "
-                             f"got {dtype!r}")
+        if self.H != LAT_H and dtype != "f32" and not self.__dict__.get("_t2s_wide_train_bf16", False):
+            raise L.T2SError(f"Transformer(dim={self.H}): the wide latents train in 'f32' only (bf16 training exists at dim 30, "
+                             f"and at the wide widths after set_wide_train_bf16(True)), got {dtype!r}")
         self.__dict__["_t2s_train_dtype"] = dtype
         return self
 
@@ -313,8 +318,8 @@ class Transformer(H.HandleOwner, nn.Module):
         """Opt a WIDE model (dim 50 / 64, the motion denoisers of the reference's mytrain.py) into training: with it set,
         forward under autograd runs the fp32 HIP training step at 16 * dim tokens (t2s_dit_set_trainable) in place of
         refusing.  A dim-30 model always trains; the call changes nothing there.  What stays refused at the wide widths:
-        set_train_dtype("bf16"), and set_math("bf16x3" / "bf16") unless set_wide_math(True) opted the model in (inference
-        only: training stays fp32)."""
+        set_train_dtype("bf16") unless set_wide_train_bf16(True) opted the model in, and set_math("bf16x3" / "bf16") unless
+        set_wide_math(True) did (inference only: it does not move the training arithmetic)."""
         self.__dict__["_t2s_trainable"] = bool(on)
         return self
 
@@ -330,7 +335,19 @@ class Transformer(H.HandleOwner, nn.Module):
             self.__dict__["_t2s_math"] = "f32"
         return self
 
-    # (_t2s_math, _t2s_train_dtype, _t2s_trainable and _t2s_wide_math are settings: they travel with a pickle)
+    def set_wide_train_bf16(self, on: bool = True):
+        """Opt a WIDE model (dim 50 / 64) into the bf16 mixed-precision training step: with it set (and set_trainable),
+        set_train_dtype("bf16") is accepted and forward under autograd runs the bf16 HIP step at 16 * dim tokens
+        (t2s_dit_set_wide_train_bf16): bf16 MFMA operands and saved activations, fp32 accumulation, master weights, residual
+        stream, statistics and gradients -- the contract of train.py --bf16.  Nothing else moves: the model keeps training in
+        "f32" until set_train_dtype says otherwise.  on=False brings the refusal back and returns the model to "f32".  A
+        dim-30 model has always had both arithmetics; the call changes nothing there."""
+        self.__dict__["_t2s_wide_train_bf16"] = bool(on)
+        if not on and self.H != LAT_H:
+            self.__dict__["_t2s_train_dtype"] = "f32"
+        return self
+
+    # (_t2s_math, _t2s_train_dtype, _t2s_trainable, _t2s_wide_math and _t2s_wide_train_bf16 are settings: they travel with a pickle)
     _t2s_transient = H.HandleOwner._t2s_transient + ("_t2s_math_applied", "_t2s_bucket", "_t2s_flat_grad", "_t2s_fwd_gen",
                                                      "_t2s_wstruct", "_t2s_pair", "_t2s_pairing")
 
