@@ -310,6 +310,24 @@ SYMBOLS_WIDE_TRAIN_BF16 = {
     "t2s_attn_train_bf16_n": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _VP]),
 }
 
+# include/t2s_train_rows.h: one launch form of the training step's row kernels alone -- for tests / benchmarking of those
+# kernels (tests/test_train_rows.py, tests/test_train_rows_host.py); no class of this package calls it
+TRAIN_ROWS_OPS = {"QKV0": 0, "QKV1": 1, "FC1": 2, "FC2": 3, "LIN128": 4, "GELUBWD": 5, "LNBWD256": 6, "LNBWD384": 7, "FINAL_FUSED": 8,
+                  "F_QKV": 16, "F_FC1": 17, "F_FC2": 18, "F_LIN128": 19, "F_LIN256": 20, "F_LIN384": 21, "F_GELUBWD": 22,
+                  "F_GATE_RES": 23, "F_GATE_BWD": 24, "F_LN_MOD_BWD": 25, "F_GELU": 26, "F_FINAL": 27}   # T2S_ROWS_*
+
+
+class TrainRowsArgs(C.Structure):        # t2s_train_rows_args
+    _fields_ = [(n, C.c_void_p) for n in
+                ("a", "w", "bias", "mod", "res", "aux", "ln_x", "dout", "ln_w", "ln_b", "out", "save_a", "x_out", "q", "k", "v",
+                 "dx", "dmod", "g_ln_w", "g_ln_b", "g_out_w", "g_out_b")] + \
+               [(n, C.c_int) for n in ("shift_off", "scale_off", "gate_off")]
+
+
+SYMBOLS_TRAIN_ROWS = {
+    "t2s_train_rows": (_I, [_I, _I, _I, _I, _I, C.POINTER(TrainRowsArgs), _VP]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libt2s_hip.so (once).  Raises if it has not been built."""
@@ -321,7 +339,7 @@ def lib() -> C.CDLL:
                 f"or `make -C t2ms_amd/csrc` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()) + list(SYMBOLS_WIDE_MATH.items()) +
-                                  list(SYMBOLS_WIDE_TRAIN_BF16.items())):
+                                  list(SYMBOLS_WIDE_TRAIN_BF16.items()) + list(SYMBOLS_TRAIN_ROWS.items())):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         _lib = handle

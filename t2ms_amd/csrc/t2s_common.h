@@ -9,6 +9,7 @@
 #include "../../include/t2s_wide_train.h"
 #include "../../include/t2s_wide_math.h"
 #include "../../include/t2s_wide_train_bf16.h"
+#include "../../include/t2s_train_rows.h"
 
 namespace t2s {
 

@@ -1346,3 +1346,296 @@ int final_bwd_fused_wide(t2s_dit* h, t2s_train_ws* ws, const float* dout, int M,
     return T2S_OK;
 }
 }  // namespace
+
+// ------------------------------------------------------------------ include/t2s_train_rows.h: one launch form of the step alone
+// Host code only, and LAST in this file: every kernel it names is an instantiation the recipes above have already asked for, so
+// the code object keeps its kernels and their order.
+namespace t2s {
+int bf16_to_f32(const __bf16* src, float* dst, size_t n, hipStream_t st);   // t2s_attn_bf16.hip
+}
+namespace {
+struct RowsBufs {   // the entry's temporaries: freed when it returns
+    std::vector<void*> all;
+    struct Widen { const __bf16* src; float* dst; size_t n; };
+    std::vector<Widen> widen;
+    bool oom = false;
+    ~RowsBufs() { for (void* p : all) (void)hipFree(p); }
+    template <class T>
+    T* get(size_t n) {
+        void* p = nullptr;
+        if (hipMalloc(&p, n * sizeof(T)) != hipSuccess) { oom = true; return nullptr; }
+        all.push_back(p);
+        return static_cast<T*>(p);
+    }
+    // a bf16 copy of an fp32 operand (NULL stays NULL)
+    const __bf16* in16(const float* src, size_t n, hipStream_t st, int* rc) {
+        if (src == nullptr || *rc != T2S_OK) return nullptr;
+        __bf16* d = get<__bf16>(n);
+        if (d == nullptr) return nullptr;
+        *rc = f32_to_bf16(src, d, n, 1.0f, st);
+        return d;
+    }
+    // a bf16 result, widened into dst by finish()
+    __bf16* out16(float* dst, size_t n) {
+        if (dst == nullptr) return nullptr;
+        __bf16* d = get<__bf16>(n);
+        if (d != nullptr) widen.push_back({d, dst, n});
+        return d;
+    }
+    int finish(hipStream_t st) {
+        for (const Widen& w : widen)
+            if (const int rc = bf16_to_f32(w.src, w.dst, w.n, st)) return rc;
+        return T2S_OK;
+    }
+};
+
+// what a launch form needs of t2s_train_rows_args
+enum : unsigned { RA = 1, RW = 2, RMOD = 4, RRES = 8, RAUX = 16, RLNX = 32, RFIN = 64, ROUT = 128, RSAVE = 256, RXOUT = 512,
+                  RQKV = 1024, RDX = 2048, RDMOD = 4096, RSHIFT = 8192, RSCALE = 16384, RGATE = 32768 };
+struct RowsForm { int op, dtype; unsigned need; };
+constexpr RowsForm ROWS_FORMS[] = {
+    {T2S_ROWS_QKV0, T2S_TRAIN_BF16, RA | RW | RMOD | RSHIFT | RSCALE | RSAVE | RQKV},
+    {T2S_ROWS_QKV1, T2S_TRAIN_BF16, RA | RW | RMOD | RSHIFT | RSCALE | RGATE | RRES | RXOUT | RSAVE | RQKV},
+    {T2S_ROWS_FC1, T2S_TRAIN_BF16, RA | RW | RMOD | RSHIFT | RSCALE | RGATE | RRES | RXOUT | RSAVE | ROUT},
+    {T2S_ROWS_FC2, T2S_TRAIN_BF16, RA | RW | ROUT},
+    {T2S_ROWS_LIN128, T2S_TRAIN_BF16, RA | RW | ROUT},
+    {T2S_ROWS_GELUBWD, T2S_TRAIN_BF16, RA | RW | RAUX | ROUT},
+    {T2S_ROWS_LNBWD256, T2S_TRAIN_BF16, RA | RW | RLNX | RMOD | RSHIFT | RSCALE | RDX | RDMOD},
+    {T2S_ROWS_LNBWD384, T2S_TRAIN_BF16, RA | RW | RLNX | RMOD | RSHIFT | RSCALE | RDX | RDMOD},
+    {T2S_ROWS_FINAL_FUSED, T2S_TRAIN_BF16, RA | RW | RRES | RMOD | RGATE | RFIN | RDX | ROUT | RDMOD},
+    {T2S_ROWS_F_QKV, T2S_TRAIN_F32, RA | RW | RMOD | RSHIFT | RSCALE | RSAVE | RQKV},
+    {T2S_ROWS_F_FC1, T2S_TRAIN_F32, RA | RW | RMOD | RSHIFT | RSCALE | RSAVE | ROUT},
+    {T2S_ROWS_F_FC2, T2S_TRAIN_F32, RA | RW | ROUT},
+    {T2S_ROWS_F_LIN128, T2S_TRAIN_F32, RA | RW | ROUT},
+    {T2S_ROWS_F_LIN256, T2S_TRAIN_F32, RA | RW | ROUT},
+    {T2S_ROWS_F_LIN384, T2S_TRAIN_F32, RA | RW | ROUT},
+    {T2S_ROWS_F_GELUBWD, T2S_TRAIN_F32, RA | RW | RAUX | ROUT},
+    {T2S_ROWS_F_GATE_RES, T2S_TRAIN_F32, RA | RRES | RMOD | RGATE | RXOUT},
+    {T2S_ROWS_F_GATE_BWD, T2S_TRAIN_F32, RDX | RRES | RMOD | RGATE | ROUT | RDMOD},
+    {T2S_ROWS_F_LN_MOD_BWD, T2S_TRAIN_F32, RA | RLNX | RMOD | RSHIFT | RSCALE | RDX | RDMOD},
+    {T2S_ROWS_F_GELU, T2S_TRAIN_F32, RA | ROUT},
+    {T2S_ROWS_F_FINAL, T2S_TRAIN_F32, RA | RW | RFIN | RDX},
+};
+
+// weight (N,K) row-major -> the pack of its arithmetic, by the step's own packing kernels
+int rows_pack32(const float* W, int N, int K, RowsBufs& b, f32x4** P, hipStream_t st) {
+    *P = b.get<f32x4>((size_t)N * K / 4);
+    if (*P == nullptr) return T2S_OK;   // (b.oom is reported by the caller)
+    return pack_any(W, *P, N, K, 0, st);
+}
+int rows_pack16(const float* W, int N, int K, RowsBufs& b, bf16x8** P, hipStream_t st) {
+    *P = b.get<bf16x8>((size_t)N * K / 8);
+    if (*P == nullptr) return T2S_OK;
+    pack16_kernel<<<(N * K + 255) / 256, 256, 0, st>>>(W, reinterpret_cast<__bf16*>(*P), N, K, 0);
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+
+template <int TOK>
+int rows_bf16(int op, int n_tok, int n_seq, const t2s_train_rows_args& p, RowsBufs& b, hipStream_t st) {
+    const int M = n_seq * n_tok;
+    const size_t MD = (size_t)M * D;
+    int rc = T2S_OK;
+    bf16x8* Wp = nullptr;
+    const size_t hd = MD;   // elements of each of q, k, v: (n_seq * 4, n_tok, 32)
+    switch (op) {
+    case T2S_ROWS_QKV0:
+    case T2S_ROWS_QKV1: {
+        if ((rc = rows_pack16(p.w, 3 * D, D, b, &Wp, st))) return rc;
+        const __bf16* res = op == T2S_ROWS_QKV1 ? b.in16(p.res, MD, st, &rc) : nullptr;
+        __bf16 *a1 = b.out16(p.save_a, MD), *q = b.out16(p.q, hd), *k = b.out16(p.k, hd), *v = b.out16(p.v, hd);
+        if (rc != T2S_OK || b.oom) return rc;
+        return op == T2S_ROWS_QKV0
+                   ? bgemm<128, 384, BPRO_LN, BEPI_QKV, TOK>(p.a, Wp, p.bias, nullptr, M, 3 * D, st, p.mod, p.shift_off, p.scale_off, a1, nullptr, q, k, v,
+                                                             nullptr, 0, nullptr, n_tok)
+                   : bgemm<128, 384, BPRO_LN_RES, BEPI_QKV, TOK>(p.a, Wp, p.bias, nullptr, M, 3 * D, st, p.mod, p.shift_off, p.scale_off, a1, nullptr, q, k,
+                                                                 v, res, p.gate_off, p.x_out, n_tok);
+    }
+    case T2S_ROWS_FC1: {
+        if ((rc = rows_pack16(p.w, 2 * D, D, b, &Wp, st))) return rc;
+        const __bf16* res = b.in16(p.res, MD, st, &rc);
+        __bf16 *a2 = b.out16(p.save_a, MD), *u = b.out16(p.out, 2 * MD);
+        if (rc != T2S_OK || b.oom) return rc;
+        return bgemm<128, 256, BPRO_LN_RES, BEPI_BF16, TOK>(p.a, Wp, p.bias, u, M, 2 * D, st, p.mod, p.shift_off, p.scale_off, a2, nullptr, nullptr, nullptr,
+                                                            nullptr, res, p.gate_off, p.x_out, n_tok);
+    }
+    case T2S_ROWS_FC2: {
+        if ((rc = rows_pack16(p.w, D, 2 * D, b, &Wp, st))) return rc;
+        const __bf16* u = b.in16(p.a, 2 * MD, st, &rc);
+        __bf16* f = b.out16(p.out, MD);
+        if (rc != T2S_OK || b.oom) return rc;
+        return bgemm<256, 128, BPRO_GELU, BEPI_BF16>(u, Wp, p.bias, f, M, D, st);
+    }
+    case T2S_ROWS_LIN128: {
+        if ((rc = rows_pack16(p.w, D, D, b, &Wp, st))) return rc;
+        const __bf16* a = b.in16(p.a, MD, st, &rc);
+        __bf16* o = b.out16(p.out, MD);
+        if (rc != T2S_OK || b.oom) return rc;
+        return bgemm<128, 128, BPRO_BF16, BEPI_BF16>(a, Wp, p.bias, o, M, D, st);
+    }
+    case T2S_ROWS_GELUBWD: {
+        if ((rc = rows_pack16(p.w, 2 * D, D, b, &Wp, st))) return rc;
+        const __bf16* a = b.in16(p.a, MD, st, &rc);
+        const __bf16* u = b.in16(p.aux, 2 * MD, st, &rc);
+        __bf16* o = b.out16(p.out, 2 * MD);
+        if (rc != T2S_OK || b.oom) return rc;
+        return bgemm<128, 256, BPRO_BF16, BEPI_GELUBWD>(a, Wp, p.bias, o, M, 2 * D, st, nullptr, 0, 0, nullptr, u);
+    }
+    case T2S_ROWS_LNBWD256:
+    case T2S_ROWS_LNBWD384: {
+        const int K = op == T2S_ROWS_LNBWD256 ? 2 * D : 3 * D;
+        if ((rc = rows_pack16(p.w, D, K, b, &Wp, st))) return rc;
+        const __bf16* dY = b.in16(p.a, (size_t)M * K, st, &rc);
+        const __bf16* f_next = b.in16(p.res, MD, st, &rc);
+        __bf16* t_next = p.res != nullptr ? b.out16(p.out, MD) : nullptr;
+        t2s_train_ws ws;             // what bgemm_lnbwd reads of a workspace
+        ws.latw = n_tok / 16;
+        ws.mod = const_cast<float*>(p.mod);
+        ws.dx = p.dx;
+        ws.dmod = p.dmod;
+        ws.colpart = b.get<float>((size_t)M / 32 * 384);
+        if (rc != T2S_OK || b.oom) return rc;
+        return op == T2S_ROWS_LNBWD256 ? bgemm_lnbwd<256, TOK>(&ws, dY, Wp, p.ln_x, p.shift_off, p.scale_off, f_next, p.gate_off, t_next, M, st)
+                                       : bgemm_lnbwd<384, TOK>(&ws, dY, Wp, p.ln_x, p.shift_off, p.scale_off, f_next, p.gate_off, t_next, M, st);
+    }
+    default: {   // T2S_ROWS_FINAL_FUSED, as t2s_dit_train_backward launches it
+        const int frows = fused_rows(n_tok), final_wgs = M / frows, final_stride = FINAL_COLS + D;
+        const __bf16* f = b.in16(p.res, MD, st, &rc);
+        __bf16* t = b.out16(p.out, MD);
+        float* part = b.get<float>((size_t)final_wgs * final_stride);
+        if (rc != T2S_OK || b.oom) return rc;
+        if (TOK == NTOK) {
+            final_bwd_kernel<true, fused_rows(NTOK), LATW><<<final_wgs, 256, 0, st>>>(p.a, p.dout, p.ln_w, p.ln_b, p.w, p.dx, part, M, f, p.mod, p.gate_off, t, LATW);
+            T2S_LAUNCH_CHECK();
+            final_gate_reduce_kernel<NTOK / fused_rows(NTOK)><<<n_seq, D, 0, st>>>(part, final_stride, p.dmod, p.gate_off, 0);
+        } else {
+            t2s_dit hd;              // what final_bwd_fused_wide reads of a handle and a workspace
+            hd.latw = n_tok / 16;
+            hd.ln_w = const_cast<float*>(p.ln_w); hd.ln_b = const_cast<float*>(p.ln_b); hd.out_w = const_cast<float*>(p.w);
+            t2s_train_ws ws;
+            ws.latw = hd.latw;
+            ws.x_mid[NBLK - 1] = const_cast<float*>(p.a);
+            ws.dx = p.dx; ws.wg_scratch = part; ws.mod = const_cast<float*>(p.mod); ws.dmod = p.dmod;
+            ws.bf.f[NBLK - 1] = const_cast<__bf16*>(f);
+            ws.bf.t1 = t;
+            if ((rc = final_bwd_fused_wide(&hd, &ws, p.dout, M, n_seq, p.gate_off, final_wgs, final_stride, st))) return rc;
+        }
+        T2S_LAUNCH_CHECK();
+        tail_reduce_kernel<<<(FINAL_COLS + 31) / 32, 256, 0, st>>>(part, final_wgs, FINAL_COLS, final_stride,
+                                                                     TailDst{{p.g_ln_w, p.g_ln_b, p.g_out_w, p.g_out_b}, {D, D, 4 * D, 4}});
+        T2S_LAUNCH_CHECK();
+        return T2S_OK;
+    }
+    }
+}
+
+template <int W>
+int rows_f32(int op, int n_tok, int n_seq, const t2s_train_rows_args& p, RowsBufs& b, hipStream_t st) {
+    constexpr int TOK = W ? 16 * W : 0;
+    const int M = n_seq * n_tok, latw = n_tok / 16;
+    int rc = T2S_OK;
+    f32x4* Wp = nullptr;
+    switch (op) {
+    case T2S_ROWS_F_QKV:
+        if ((rc = rows_pack32(p.w, 3 * D, D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<128, 3, PRO_LNMOD, EPI_QKV, TOK>(p.a, Wp, p.bias, nullptr, M, 3 * D, st, p.mod, p.shift_off, p.scale_off, p.save_a, nullptr, p.q, p.k,
+                                                     p.v, n_tok);
+    case T2S_ROWS_F_FC1:
+        if ((rc = rows_pack32(p.w, 2 * D, D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<128, 2, PRO_LNMOD, EPI_BIAS, TOK>(p.a, Wp, p.bias, p.out, M, 2 * D, st, p.mod, p.shift_off, p.scale_off, p.save_a, nullptr, nullptr,
+                                                      nullptr, nullptr, n_tok);
+    case T2S_ROWS_F_FC2:
+        if ((rc = rows_pack32(p.w, D, 2 * D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<256, 1, PRO_GELU, EPI_BIAS>(p.a, Wp, p.bias, p.out, M, D, st);
+    case T2S_ROWS_F_LIN128:
+        if ((rc = rows_pack32(p.w, D, D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<128, 1, PRO_PLAIN, EPI_BIAS>(p.a, Wp, p.bias, p.out, M, D, st);
+    case T2S_ROWS_F_LIN256:
+        if ((rc = rows_pack32(p.w, D, 2 * D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<256, 1, PRO_PLAIN, EPI_BIAS>(p.a, Wp, p.bias, p.out, M, D, st);
+    case T2S_ROWS_F_LIN384:
+        if ((rc = rows_pack32(p.w, D, 3 * D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<384, 1, PRO_PLAIN, EPI_BIAS>(p.a, Wp, p.bias, p.out, M, D, st);
+    case T2S_ROWS_F_GELUBWD:
+        if ((rc = rows_pack32(p.w, 2 * D, D, b, &Wp, st)) || b.oom) return rc;
+        return gemm<128, 2, PRO_PLAIN, EPI_GELUBWD>(p.a, Wp, p.bias, p.out, M, 2 * D, st, nullptr, 0, 0, nullptr, p.aux);
+    case T2S_ROWS_F_GATE_RES:
+        gate_res_kernel<W><<<(M * 32 + 255) / 256, 256, 0, st>>>(p.a, p.res, p.mod, p.gate_off, p.x_out, M, latw);
+        break;
+    case T2S_ROWS_F_GATE_BWD:
+        gate_bwd_kernel<W><<<n_seq, 256, 0, st>>>(p.dx, p.res, p.mod, p.gate_off, p.out, p.dmod, latw);
+        break;
+    case T2S_ROWS_F_LN_MOD_BWD:
+        ln_mod_bwd_kernel<W><<<n_seq, 256, 0, st>>>(p.a, p.ln_x, p.mod, p.shift_off, p.scale_off, p.dx, p.dmod, (const float*)nullptr, 0, (float*)nullptr,
+                                                    latw);
+        break;
+    case T2S_ROWS_F_GELU:
+        gelu_kernel<<<((size_t)M * 64 + 255) / 256, 256, 0, st>>>(p.a, p.out, (size_t)M * 64);
+        break;
+    default: {   // T2S_ROWS_F_FINAL
+        const int final_wgs = (M + TAIL_ROWS - 1) / TAIL_ROWS;
+        float* part = b.get<float>((size_t)final_wgs * FINAL_COLS);
+        if (b.oom) return T2S_OK;
+        final_bwd_kernel<false, TAIL_ROWS, W><<<final_wgs, 256, 0, st>>>(p.a, p.dout, p.ln_w, p.ln_b, p.w, p.dx, part, M, nullptr, nullptr, 0, nullptr, latw);
+        T2S_LAUNCH_CHECK();
+        tail_reduce_kernel<<<(FINAL_COLS + 31) / 32, 256, 0, st>>>(part, final_wgs, FINAL_COLS, FINAL_COLS,
+                                                                     TailDst{{p.g_ln_w, p.g_ln_b, p.g_out_w, p.g_out_b}, {D, D, 4 * D, 4}});
+        break;
+    }
+    }
+    T2S_LAUNCH_CHECK();
+    return T2S_OK;
+}
+}  // namespace
+
+extern "C" int t2s_train_rows(int op, int dtype, int n_tok, int n_seq, int flags, const t2s_train_rows_args* args, void* stream) {
+    T2S_REQUIRE(args, "t2s_train_rows: args is NULL");
+    T2S_REQUIRE(dtype == T2S_TRAIN_F32 || dtype == T2S_TRAIN_BF16, "t2s_train_rows: unknown dtype %d", dtype);
+    const RowsForm* form = nullptr;
+    for (const RowsForm& f : ROWS_FORMS)
+        if (f.op == op) form = &f;
+    T2S_REQUIRE(form, "t2s_train_rows: unknown op %d", op);
+    T2S_REQUIRE(form->dtype == dtype, "t2s_train_rows: op %d is a %s launch form, dtype %d was asked", op,
+                form->dtype == T2S_TRAIN_BF16 ? "T2S_TRAIN_BF16" : "T2S_TRAIN_F32", dtype);
+    T2S_REQUIRE(n_tok == NTOK || n_tok == 800 || n_tok == 1024, "t2s_train_rows: n_tok=%d (480, 800 and 1024 tokens are built)", n_tok);
+    T2S_REQUIRE(n_seq > 0 && n_seq <= (1 << 20) / (n_tok / 32), "t2s_train_rows: n_seq=%d", n_seq);
+    T2S_REQUIRE((flags & ~2) == 0, "t2s_train_rows: unknown flags %d", flags);
+    const t2s_train_rows_args& p = *args;
+    const unsigned need = form->need;
+    T2S_REQUIRE(!(need & RA) || p.a, "t2s_train_rows: op %d needs a", op);
+    T2S_REQUIRE(!(need & RW) || p.w, "t2s_train_rows: op %d needs w", op);
+    T2S_REQUIRE(!(need & RMOD) || p.mod, "t2s_train_rows: op %d needs mod", op);
+    T2S_REQUIRE(!(need & RRES) || p.res, "t2s_train_rows: op %d needs res", op);
+    T2S_REQUIRE(!(need & RAUX) || p.aux, "t2s_train_rows: op %d needs aux", op);
+    T2S_REQUIRE(!(need & RLNX) || p.ln_x, "t2s_train_rows: op %d needs ln_x", op);
+    T2S_REQUIRE(!(need & RFIN) || (p.dout && p.ln_w && p.ln_b && p.g_ln_w && p.g_ln_b && p.g_out_w && p.g_out_b),
+                "t2s_train_rows: op %d needs dout, ln_w, ln_b, g_ln_w, g_ln_b, g_out_w and g_out_b", op);
+    T2S_REQUIRE(!(need & ROUT) || p.out, "t2s_train_rows: op %d needs out", op);
+    T2S_REQUIRE(!(need & RSAVE) || p.save_a, "t2s_train_rows: op %d needs save_a", op);
+    T2S_REQUIRE(!(need & RXOUT) || p.x_out, "t2s_train_rows: op %d needs x_out", op);
+    T2S_REQUIRE(!(need & RQKV) || (p.q && p.k && p.v), "t2s_train_rows: op %d needs q, k and v", op);
+    T2S_REQUIRE(!(need & RDX) || p.dx, "t2s_train_rows: op %d needs dx", op);
+    T2S_REQUIRE(!(need & RDMOD) || p.dmod, "t2s_train_rows: op %d needs dmod", op);
+    const bool lnbwd = op == T2S_ROWS_LNBWD256 || op == T2S_ROWS_LNBWD384;
+    T2S_REQUIRE(!lnbwd || !p.res || p.out, "t2s_train_rows: op %d with res (f_next) needs out (t_next)", op);
+    auto off_ok = [](int off) { return off >= 0 && off <= MODROW - D && off % 4 == 0; };
+    T2S_REQUIRE(!(need & RSHIFT) || off_ok(p.shift_off), "t2s_train_rows: shift_off=%d", p.shift_off);
+    T2S_REQUIRE(!(need & RSCALE) || off_ok(p.scale_off), "t2s_train_rows: scale_off=%d", p.scale_off);
+    T2S_REQUIRE(!((need & RGATE) || (lnbwd && p.res)) || off_ok(p.gate_off), "t2s_train_rows: gate_off=%d", p.gate_off);
+    hipStream_t st = (hipStream_t)stream;
+    RowsBufs bufs;
+    t2s::g_tile_flip = (flags & 2) ? 1u : 0u;               // the direction next_tile_dir() hands the launch (as t2s_wgrad)
+    int rc;
+    if (dtype == T2S_TRAIN_BF16) {
+        rc = n_tok == NTOK ? rows_bf16<NTOK>(op, n_tok, n_seq, p, bufs, st) : rows_bf16<0>(op, n_tok, n_seq, p, bufs, st);
+        if (rc == T2S_OK && !bufs.oom) rc = bufs.finish(st);
+    } else {
+        rc = n_tok == NTOK ? rows_f32<LATW>(op, n_tok, n_seq, p, bufs, st) : rows_f32<0>(op, n_tok, n_seq, p, bufs, st);
+    }
+    (void)hipStreamSynchronize(st);
+    if (rc == T2S_OK && bufs.oom) {
+        set_error("t2s_train_rows: out of device memory for the temporaries of op %d at n_seq=%d", op, n_seq);
+        rc = T2S_E_HIP;
+    }
+    return rc;
+}
