@@ -22,6 +22,9 @@ What differs from the reference, on purpose:
   * every clip of the split is sampled (the reference stops after 11); `--max_clips N` caps it.
   * `--math bf16x3|bf16` runs the denoiser's matrix products on the bf16 matrix cores (fp32-accurate split / single pass);
     the default stays f32, and summary.json names the arithmetic only when it is not f32.
+  * `--save_eval_files` additionally writes `run_<j>/x_t_sample_<i>.npy` and, once, `x_1_sample_<i>.npy` next to the run
+    directories: the names the reference's myevaluation.py reads (its own myinfer.py never writes them), so that it runs
+    unchanged on this output; myevaluation.py here reads either layout.
   * `--random_init` (seeded synthetic weights) and `--synthetic N` (N seeded clips of 30..160 samples instead of a dataset)
     let the driver run without checkpoints or data, as infer.py's flags do.
 The model shape comes from flags whose defaults are the reference's config.yaml values per dataset; `--config FILE` overrides
@@ -77,6 +80,8 @@ def get_args(argv=None):
     p.add_argument("--reconstruct", action="store_true", help="also the codec reconstruction of every clip and its MSE")
     p.add_argument("--synthetic", type=int, default=0, help="N seeded synthetic clips (30..160 samples) instead of the dataset")
     p.add_argument("--no_graph", action="store_true", help="run the loop eagerly (same bits)")
+    p.add_argument("--save_eval_files", action="store_true",
+                   help="also write run_<j>/x_t_sample_<i>.npy and, once, x_1_sample_<i>.npy: the names the reference's myevaluation.py reads")
     p.add_argument("--math", choices=["f32", "bf16x3", "bf16"], default="f32",
                    help="matrix arithmetic of the denoiser: f32 (default), bf16x3 (fp32-accurate, bf16 matrix cores) or bf16 "
                         "(single pass, not fp32-accurate); the latter two opt the wide model in (Transformer.set_wide_math)")
@@ -178,6 +183,10 @@ def infer(args, run, device, model, vae, clips):
         d = os.path.join(root, f"sample_{i}")
         os.makedirs(d, exist_ok=True)
         np.save(os.path.join(d, "x_t.npy"), x_t)
+        if args.save_eval_files:
+            np.save(os.path.join(root, f"x_t_sample_{i}.npy"), x_t)
+            if run == 0:
+                np.save(os.path.join(args.generation_save_path, f"x_1_sample_{i}.npy"), x_1)
         with open(os.path.join(d, "data.json"), "w") as f:
             json.dump({name: x_t[c].astype(float).tolist() for c, name in enumerate(names)}, f, indent=4)
         row = dict(index=i, subject=clip[2], text=clip[3], length=int(x_1.shape[1]), mse=clip_mse(x_1, x_t))

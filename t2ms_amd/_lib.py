@@ -24,6 +24,7 @@ DIT_N_TENSORS = 10 + 10 * N_BLOCKS   # t2s.h: T2S_DIT_N_TENSORS (pointers of t2s
 MSE_SCRATCH_FLOATS = 1024       # t2s.h: T2S_MSE_SCRATCH_FLOATS
 EVAL_MAX_LAG, EVAL_MDD_BINS = 64, 50   # t2s.h: T2S_EVAL_MAX_LAG / T2S_EVAL_MDD_BINS
 EVAL_CORR_MAX_SERIES, EVAL_MOTION_MAX_LEN = 64, 4096   # t2s.h: T2S_EVAL_CORR_MAX_SERIES / T2S_EVAL_MOTION_MAX_LEN
+EVAL_RUNS_MAX_CHANNELS = 16     # t2s_eval_runs.h: T2S_EVAL_RUNS_MAX_CHANNELS
 
 c_float_p = C.c_void_p  # device pointers travel as opaque addresses
 
@@ -328,6 +329,12 @@ SYMBOLS_TRAIN_ROWS = {
     "t2s_train_rows": (_I, [_I, _I, _I, _I, _I, C.POINTER(TrainRowsArgs), _VP]),
 }
 
+# include/t2s_eval_runs.h: myevaluation.py's scores over the packed ragged clips of a motion test split, all runs, one call
+# (metrics.motion_runs; tests/test_myeval_host.py)
+SYMBOLS_EVAL_RUNS = {
+    "t2s_eval_runs": (_I, [_VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _VP, _I, _I, _I, _I, _VP]),
+}
+
 
 def lib() -> C.CDLL:
     """Load libt2s_hip.so (once).  Raises if it has not been built."""
@@ -339,7 +346,8 @@ def lib() -> C.CDLL:
                 f"or `make -C t2ms_amd/csrc` (hipcc --offload-arch=gfx950).  There is no CPU fallback.")
         handle = C.CDLL(LIB_PATH)
         for name, (res, args) in (list(SYMBOLS.items()) + list(SYMBOLS_WIDE_TRAIN.items()) + list(SYMBOLS_WIDE_MATH.items()) +
-                                  list(SYMBOLS_WIDE_TRAIN_BF16.items()) + list(SYMBOLS_TRAIN_ROWS.items())):
+                                  list(SYMBOLS_WIDE_TRAIN_BF16.items()) + list(SYMBOLS_TRAIN_ROWS.items()) +
+                                  list(SYMBOLS_EVAL_RUNS.items())):
             fn = getattr(handle, name)  # AttributeError if the .so does not export it
             fn.restype, fn.argtypes = res, args
         _lib = handle

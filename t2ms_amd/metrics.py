@@ -4,7 +4,7 @@ the run_0..run_k repetitions `--run_multi` writes, the TS2Vec encoder forward + 
 (:127-135,238-243; evaluate/ts2vec.py:352-399), and the set-against-set measures MDD / ACD / SD / KD of
 evaluate/feature_based_measures.py (calculate_mdd :30-94, _acd :98-161, _sd :165-191, _kd :195-223), and the motion measures
 of evaluate/metrics.py for recordings of unequal length: correlational_score (:112-137), sequence_correlation (:219-266)
-and dtw_ragged (calculate_dtw(seq1, seq2), :139-170) on the kernels of csrc/t2s_eval_motion.hip.  `python -m t2ms_amd.metrics <generation dir>` prints them for a
+and dtw_ragged (calculate_dtw(seq1, seq2), :139-170) on the kernels of csrc/t2s_eval_motion.hip.  motion_runs scores the runs of a motion test split as the reference's myevaluation.py does (t2s_eval_runs, csrc/t2s_eval_runs.hip; driver myevaluation.py).  `python -m t2ms_amd.metrics <generation dir>` prints them for a
 directory holding x_1.npy and x_t.npy ({save_path}/generation/{backbone}_{denoiser}_{dataset}_{cfg}_{steps}/[run_k/])
 and the run_* sub-directories.
 
@@ -293,6 +293,78 @@ def dtw_ragged(a, b, lengths=None, device="cuda"):
                                             None if lb is None else lb.data_ptr(), per.data_ptr(), out.data_ptr(), a.shape[0],
                                             a.shape[1], b.shape[1], a.shape[2], L.stream_ptr(dev)), "t2s_eval_dtw_ragged")
     return float(out.cpu()[0]), per.cpu()
+
+
+def pack_motion_runs(x1_list, xt_runs):
+    """Host side of motion_runs: x1_list = K arrays (C, T_i), xt_runs = R lists of K arrays of the same shapes -> (x1 packed
+    fp32 (C * sum T_i,), xt packed (R, C * sum T_i), lengths int32 (K,), offsets uint64 (K + 1,), C).  Everything t2s_eval_runs
+    would refuse or skip is a T2SError here."""
+    what = "motion_runs"
+
+    def arr(v):
+        return np.ascontiguousarray(np.asarray(v.detach().cpu() if torch.is_tensor(v) else v, dtype=np.float32))
+
+    x1 = [arr(v) for v in x1_list]
+    if not x1:
+        raise L.T2SError(f"{what}: no clip")
+    if any(v.ndim != 2 for v in x1):
+        raise L.T2SError(f"{what}: every recording must be (C, T_i), got {[tuple(v.shape) for v in x1]}")
+    chans = int(x1[0].shape[0])
+    if not 1 <= chans <= L.EVAL_RUNS_MAX_CHANNELS:
+        raise L.T2SError(f"{what}: C={chans} is outside [1, {L.EVAL_RUNS_MAX_CHANNELS}]")
+    for i, v in enumerate(x1):
+        if v.shape[0] != chans:
+            raise L.T2SError(f"{what}: clip {i} has {v.shape[0]} channels, clip 0 has {chans}")
+        if not 1 <= v.shape[1] <= L.EVAL_MOTION_MAX_LEN:
+            raise L.T2SError(f"{what}: clip {i} has T={v.shape[1]}, outside [1, {L.EVAL_MOTION_MAX_LEN}]")
+    runs = [[arr(v) for v in run] for run in xt_runs]
+    if not runs:
+        raise L.T2SError(f"{what}: no run")
+    for r, run in enumerate(runs):
+        if len(run) != len(x1):
+            raise L.T2SError(f"{what}: run {r} holds {len(run)} clips, there are {len(x1)} recordings")
+        for i, v in enumerate(run):
+            if v.shape != x1[i].shape:
+                raise L.T2SError(f"{what}: run {r} clip {i} is {tuple(v.shape)}, its recording is {tuple(x1[i].shape)}")
+    lens = np.asarray([v.shape[1] for v in x1], dtype=np.int32)
+    off = np.zeros(len(x1) + 1, dtype=np.uint64)
+    off[1:] = np.cumsum(lens.astype(np.uint64))
+    p1 = np.concatenate([v.reshape(-1) for v in x1])
+    pt = np.stack([np.concatenate([v.reshape(-1) for v in run]) for run in runs])
+    return p1, pt, lens, off, chans
+
+
+def motion_runs(x1_list, xt_runs, device="cuda", detail=False):
+    """The reference's myevaluation.py for every clip of a motion test split in ONE t2s_eval_runs call: x1_list = K recordings
+    (C, T_i), xt_runs = R runs of K samples of the same shapes.  Per clip and run, on the min-max normalised channels
+    (a = the sample, b = the recording; the reference hands the samples over as `ori` and reads the channel axis as time):
+    MSE, WAPE (sum |a - b| / sum |a|, NaN when that is 0), ED (mean over t of the norm over channels) and DTW (between the C
+    points a[i, :] and b[j, :]).  -> ({"MSE", "WAPE", "ED", "DTW"} the mean over clips, per_clip (K, 4) the reference's
+    reductions over runs (mean, nanmean, mean, mean), per_run (K, R, 4)); detail=True adds (norm1, normt): the normalised
+    planes, K arrays (C, T_i) and K arrays (R, C, T_i), views of two device tensors.  One upload, three launches, one sync."""
+    p1, pt, lens, off, chans = pack_motion_runs(x1_list, xt_runs)
+    dev = _gpu(device, "motion_runs")
+    K, R = len(lens), pt.shape[0]
+    with torch.cuda.device(dev):
+        x1 = torch.from_numpy(p1).to(dev)
+        xt = torch.from_numpy(pt).to(dev)
+        keep, p_len, p_off, _ = L.ragged_device_tables(lens, off, off, dev)
+        norm1, normt = torch.empty_like(x1), torch.empty_like(xt)
+        res = torch.empty(K * R * 4 + K * 4 + 4, device=dev)          # per_run, per_clip, out: one download
+        base = res.data_ptr()
+        L.check(L.lib().t2s_eval_runs(x1.data_ptr(), xt.data_ptr(), p_len, p_off, base, base + 16 * K * R, base + 16 * K * (R + 1),
+                                      norm1.data_ptr(), normt.data_ptr(), K, R, chans, int(lens.max()), L.stream_ptr(dev)),
+                "t2s_eval_runs")
+        host = res.cpu()
+    del keep
+    per_run, per_clip, out = host[:K * R * 4].reshape(K, R, 4), host[K * R * 4:K * (R + 1) * 4].reshape(K, 4), host[K * (R + 1) * 4:]
+    summary = {name: float(out[m]) for m, name in enumerate(("MSE", "WAPE", "ED", "DTW"))}
+    if not detail:
+        return summary, per_clip, per_run
+    o = [chans * int(v) for v in off]
+    n1 = [norm1[o[i]:o[i + 1]].view(chans, int(lens[i])) for i in range(K)]
+    nt = [normt[:, o[i]:o[i + 1]].reshape(R, chans, int(lens[i])) for i in range(K)]
+    return summary, per_clip, per_run, n1, nt
 
 
 def _runs_first(ori, gens, what):
